@@ -2,7 +2,7 @@
 """Headline benchmark: SDF (value + gradient) queries/sec -- BASELINE.json configs[1] ("C2"):
 CachedSDF at 0.01 m voxels on the YCB power drill, 1M query points per GPU per step.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one batch: a single `pvamd_cached_query` C-ABI call (one kernel launch)
 over the rank's 1,048,576 resident query points, writing sdf_val [P] and sdf_grad [P,3].  Inputs are in HBM before
@@ -15,8 +15,9 @@ the RCCL all-gather in the timed step, and C5 (chamfer, 2M points -> 99,500 tria
 The LAST stdout line (rank 0) is the contract line: compact JSON, < 4 KB (tests/test_bench_launch.py asserts the size),
 built by `compact_line()` from the long record.  The long record (every leg's detail, latency percentiles, README legs) is
 written to `bench_detail.json` (--detail PATH) and to stderr, never to the contract line.  `value` / `ms_per_step` are the
-wall time of exactly the K steps asked for.  `roofline` is the dominant kernel (pvamd::cached_query_direct at 1M points), 28 B/query over
-its per-launch duration: `frac` is THIS run's (HIP events on the launch stream around a separate >= 2000-launch hipGraph of the
+wall time of one timed region of exactly the K steps asked for.  `--dump-outputs DIR` writes what the last timed step
+returned on rank 0 (sdf_val, sdf_grad) as DIR/<name>.npy; the inputs are seeded, so two builds compare output for output.
+`roofline` is the dominant kernel (pvamd::cached_query_direct at 1M points), 28 B/query over its per-launch duration: `frac` is THIS run's (HIP events on the launch stream around a separate >= 2000-launch hipGraph of the
 same call, so it does not depend on K); `frac_rocprof` is the committed rocprofv3 kernel-trace average of this command
 (profiles/rNN_kernel_stats.json), `frac_wall` the contract's own timed region.  `cpu_baseline` = the restatements on the host cores.
 """
@@ -38,7 +39,7 @@ from bench_legs import (BYTES_PER_QUERY, HBM_PEAK_GBS, LegSkipped, call_latency,
                         valu_model)
 
 KERNEL_GRAPH_LAUNCHES = 2000
-TIMED_REGIONS = 21  # timed regions of exactly K steps each; the median one is the line's `ms_per_step`
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: all .npy files together, headers included
 
 
 def parse_args():
@@ -67,6 +68,8 @@ def parse_args():
     ap.add_argument("--hang-rank", type=int, default=-1, help="test hook: this rank sleeps forever inside --fail-leg, after its gate")
     ap.add_argument("--fail-rank", type=int, default=-1, help="test hook: this rank raises while preparing --fail-leg")
     ap.add_argument("--fail-leg", default="", help="test hook: see --fail-rank")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write rank 0's outputs of the last one as DIR/<name>.npy (float32, <= 64 MB)")
     ap.add_argument("--launch-check", action="store_true",
                     help="no GPU work: start the ranks, all-reduce over gloo, print the rank count (CPU test of --gpus N)")
     return ap.parse_args()
@@ -104,6 +107,25 @@ def launch_check(args, rank, world):
     if rank == 0:
         print(json.dumps({"launch_check": True, "n_gpus": world, "ranks_seen_by_all_reduce": ranks,
                           "gpus_requested": args.gpus}))
+
+
+def dump_outputs(torch, np, directory, arrays):
+    """--dump-outputs: `arrays` ({name: [P, ...] float32 tensor}, all with the same leading P) -> DIR/<name>.npy.  When they
+    would exceed DUMP_LIMIT_BYTES together, every array keeps the same fixed, seeded sample of rows (ascending order)."""
+    os.makedirs(directory, exist_ok=True)
+    rows = next(iter(arrays.values())).shape[0]
+    row_bytes = sum(a[:1].numel() * a.element_size() for a in arrays.values())
+    keep = max(1, (DUMP_LIMIT_BYTES - 4096 * len(arrays)) // max(row_bytes, 1))
+    index = None
+    if rows > keep:
+        index = torch.randperm(rows, generator=torch.Generator().manual_seed(0))[:keep].sort().values
+    for name, a in arrays.items():
+        host = a.detach().cpu()
+        if index is not None:
+            host = host[index]
+        np.save(os.path.join(directory, name + ".npy"), host.numpy().astype(np.float32, copy=False))
+    return {"dir": directory, "arrays": sorted(arrays), "rows": rows, "rows_written": rows if index is None else keep,
+            "sample": None if index is None else "torch.randperm(rows, seed 0)[:rows_written], ascending"}
 
 
 class Timer:
@@ -450,11 +472,14 @@ def main():
             for _ in range(args.steps):
                 step()
 
-    # The contract's timed region -- barrier + synchronize | exactly K steps | synchronize + barrier, MAX over ranks -- is run
-    # TIMED_REGIONS times back to back and the MEDIAN region is reported: a single 20-step region is 0.13 ms of GPU work, and
-    # one host hiccup moved `ms_per_step` by 5 % between otherwise identical runs.
-    regions = sorted(timer(k_steps) for _ in range(TIMED_REGIONS))
-    elapsed = regions[len(regions) // 2]
+    # The contract's timed region -- barrier + synchronize | exactly K steps | synchronize + barrier, MAX over ranks -- run
+    # once: --steps is the number of timed steps.  (A 20-step region is 0.13 ms of GPU work, so one host hiccup shows in a
+    # short K; a longer K averages it out.)
+    elapsed = timer(k_steps)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # untimed: val / grad still hold the last timed step's outputs (everything after this reuses them)
+        dumped = dump_outputs(torch, np, args.dump_outputs, {"sdf_val": val, "sdf_grad": grad})
 
     # ---- the dominant kernel's per-launch duration, independent of K: events around a separate >=2000-launch graph ----
     kg_n = max(KERNEL_GRAPH_LAUNCHES, args.steps)
@@ -496,10 +521,9 @@ def main():
             "config": {"workload": f"C2: CachedSDF 0.01 m voxels (37x33x40) on YcbPowerDrill, {P} uniform points per GPU per step",
                        "points_per_gpu": P, "index_dtype": "f64" if cached._view.index_f64 else "f32",
                        "out_of_range": "BOUNDING_BOX fallback, fused",
-                       "launch": (f"one hipGraph of the K steps; median of {TIMED_REGIONS} timed regions" if graph is not None
-                                  else f"eager; median of {TIMED_REGIONS} timed regions"),
+                       "launch": ("one hipGraph of the K steps; one timed region" if graph is not None
+                                  else "eager; one timed region"),
                        "timed_region": "barrier + sync | exactly K steps | event spin + sync | barrier; max over ranks",
-                       "timed_regions": f"{TIMED_REGIONS} such regions back to back, the median one reported",
                        "gather": False, "parallelism": f"points x{world}", "ranks": world,
                        "backend": (dist.get_backend() if use_pg else None), "gpus_requested": args.gpus},
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -527,9 +551,11 @@ def main():
                                          "timing": "400 calls back to back + one synchronize; median of 200 synchronized calls"},
                          "copy_same_bytes_us": copy_ms * 1e3, "copy_same_bytes_GBs": algo / (copy_ms * 1e-3) / 1e9,
                          "copy_is": "torch d2d copy moving the same bytes, same hipGraph timing; Infinity-Cache resident, not an HBM figure",
-                         "timed_regions_ms": {"n": len(regions), "min": regions[0] * 1e3, "median": elapsed * 1e3, "max": regions[-1] * 1e3}},
+                         "timed_steps": args.steps, "timed_region_ms": elapsed * 1e3},
             "valu_model": valu_model(),
         }
+        if dumped is not None:
+            out["dump_outputs"] = dumped
 
     legs = {}
     emitted = threading.Lock()

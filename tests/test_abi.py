@@ -45,7 +45,7 @@ def test_no_library_kernels_inside_the_shared_object():
     assert "#include <rocprim" not in src
 
 
-def test_struct_layouts_match_the_header():
+def test_struct_layouts_match_the_header(tmp_path):
     """Compile a tiny C program against the header and compare sizeof/offsetof with the ctypes mirrors."""
     src = r'''
     #include <stdio.h>
@@ -57,7 +57,7 @@ def test_struct_layouts_match_the_header():
              offsetof(pvamd_grid_t, oob_mode));
       printf("%zu %zu %zu\n", sizeof(pvamd_mesh_t), offsetof(pvamd_mesh_t, F), offsetof(pvamd_mesh_t, ray_dir));
       return 0; }'''
-    exe = "/tmp/_pvamd_layout"
+    exe = str(tmp_path / "pvamd_layout")
     subprocess.run(["gcc", "-x", "c", "-", "-I", os.path.join(ROOT, "include"), "-o", exe], input=src.encode(), check=True)
     out = subprocess.run([exe], capture_output=True, check=True).stdout.decode().split()
     G, M = _lib.GridDesc, _lib.MeshDesc
@@ -66,7 +66,7 @@ def test_struct_layouts_match_the_header():
     assert [int(x) for x in out[7:]] == [ctypes.sizeof(M), M.F.offset, M.ray_dir.offset]
 
 
-def test_oracle_grid_layout_is_one_definition():
+def test_oracle_grid_layout_is_one_definition(tmp_path):
     """The checker's grid description lives in oracle/pvamd_oracle.h; the plain-C host test (tests/cabi/cabi_check.c) includes
     it and the ctypes mirror in oracle/oracle.py must agree with it (an outdated private copy in the C test once made the
     oracle read every grid after the first at the wrong stride)."""
@@ -79,7 +79,7 @@ def test_oracle_grid_layout_is_one_definition():
       printf("%zu %zu %zu %zu %zu %zu\n", sizeof(oracle_grid_t), offsetof(oracle_grid_t, dres), offsetof(oracle_grid_t, fres),
              offsetof(oracle_grid_t, shape), offsetof(oracle_grid_t, rule), offsetof(oracle_grid_t, dbb_max));
       return 0; }'''
-    exe = "/tmp/_pvamd_oracle_layout"
+    exe = str(tmp_path / "pvamd_oracle_layout")
     subprocess.run(["gcc", "-x", "c", "-", "-I", os.path.join(ROOT, "oracle"), "-o", exe], input=src.encode(), check=True)
     out = [int(x) for x in subprocess.run([exe], capture_output=True, check=True).stdout.decode().split()]
     G = orc.OracleGrid
@@ -87,7 +87,7 @@ def test_oracle_grid_layout_is_one_definition():
     assert "pvamd_oracle.h" in open(os.path.join(ROOT, "tests", "cabi", "cabi_check.c")).read()
 
 
-def test_buffer_size_macros_match_the_python_mirrors():
+def test_buffer_size_macros_match_the_python_mirrors(tmp_path):
     """The sizes the binding allocates are the header's macros (records in whole tiles, tile / group spheres, the scratch of
     the mesh entry points, the Morton-order scratch)."""
     src = r'''
@@ -100,7 +100,7 @@ def test_buffer_size_macros_match_the_python_mirrors():
                (long long)PVAMD_MESH_SCRATCH_BYTES(v[i]), (long long)PVAMD_MORTON_ORDER_SCRATCH_BYTES(v[i]));
       printf("%d %d %d %d\n", PVAMD_TRI_REC, PVAMD_TRI_TILE, PVAMD_TRI_GROUP, PVAMD_MESH_SCRATCH_GROUPS);
       return 0; }'''
-    exe = "/tmp/_pvamd_sizes"
+    exe = str(tmp_path / "pvamd_sizes")
     subprocess.run(["gcc", "-x", "c", "-", "-I", os.path.join(ROOT, "include"), "-o", exe], input=src.encode(), check=True)
     out = [[int(x) for x in line.split()] for line in subprocess.run([exe], capture_output=True, check=True).stdout.decode().splitlines()]
     for n, row in zip((0, 1, 255, 256, 257, 15728, 99500, 1 << 20, 1 << 21, (1 << 24) + 5, 67108877), out):

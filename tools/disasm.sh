@@ -3,7 +3,7 @@
 #   tools/disasm.sh composed [extra hipcc flags]  ->  /tmp/pvamd_<name>.s  + per-kernel resource usage on stdout
 set -e
 name=$1; shift
-src=/root/repo/pytorch_volumetric_amd/csrc/$name.hip
+src=$(cd "$(dirname "$0")/.." && pwd)/pytorch_volumetric_amd/csrc/$name.hip
 extra=""
 case $name in composed|mesh) extra="-fno-slp-vectorize";; esac
 cd /tmp && rm -f pvamd_$name.o pvamd_$name.o.*
