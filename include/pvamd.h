@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define PVAMD_ABI_VERSION 12
+#define PVAMD_ABI_VERSION 13
 
 #define PVAMD_E_NULL      (-1)  /* a required pointer is NULL            */
 #define PVAMD_E_SHAPE     (-2)  /* a size/shape argument is out of range */
@@ -458,6 +458,45 @@ int pvamd_pairwise_min_reduce(const void* errors, int32_t is_f64, int32_t B, int
 int pvamd_configure_chain(const pvamd_joint_t* joints, int32_t F, const float* q, int32_t A, int32_t M,
                           const float* offset_inv, int32_t S, float* sincos_out, float* scratch,
                           float* link_world_out, float* stack_out, void* stream);
+
+/* ---- Backward (vector-Jacobian products) for torch autograd (ABI 13) ----
+ * The gradient torch autograd would produce through the reference's expressions, GIVEN THE FORWARD'S DECISIONS (which leaf
+ * won the first minimum, whether the point was in range, which voxel it fell in, which axes are active in the bounding-box
+ * branch).  In range the value and gradient are a table lookup without a derivative w.r.t. the point (sdf.py:549-550);
+ * outside (BOUNDING_BOX, sdf.py:556-571) with d the signed per-axis excess over the box and n = d / |d|:
+ *   d val / dx = n,   d grad / dx = (I - n n^T) diag(active) / |d|   (active: the axes on which x lies outside the box).
+ * Upstream gradients dval / dgrad may each be NULL (= zero); outputs are OVERWRITTEN, not accumulated.  Every sum is a
+ * fixed-order reduction: two calls with the same inputs give the same bits.  Allocation-free and stream-ordered.
+ *
+ * pvamd_cached_query_backward: dpoints[i] = the VJP at points[i] (CachedSDF.__call__, BOUNDING_BOX grids only: PVAMD_E_MODE
+ *   otherwise).  points / dpoints: device [P][3].  dval: device [P] or NULL.  dgrad: device [P][3] or NULL.              */
+int pvamd_cached_query_backward(const pvamd_grid_t* grid, const float* points, int64_t P, const float* dval,
+                                const float* dgrad, float* dpoints, void* stream);
+int pvamd_cached_query_backward_f64(const pvamd_grid_t* grid, const double* points, int64_t P, const double* dval,
+                                    const double* dgrad, double* dpoints, void* stream);
+
+/* pvamd_composed_query_backward: ComposedSDF.__call__ over BOUNDING_BOX CachedSDF leaves (sdf.py:399,409,421-426).  Per pair
+ * (a, p) with s = out_leaf[a][p] (the forward's arg-min, from pvamd_composed_query / _grouped / _f64), L, t = tf[s*A+a]:
+ * x = L p + t is recomputed with the forward's fma chain, gg = L^T g.  The gradient reaches p, L and t of the winner only.
+ * grids / tf / points / out_leaf: as given to the forward.  dval: device [A][P] or NULL.  dgrad: device [A][P][3] or NULL.
+ * dpoints: device [P][3] or NULL (sum over configurations).  dtf: device [S*A][4][4] or NULL (sum over points; row 3 = 0).
+ * scratch: device, pvamd_composed_backward_scratch_bytes(S, A, P, is_f64) bytes, 16-byte aligned (the per-workgroup slab of
+ * dtf partials and, when the configurations are split over workgroups, the per-split dpoints partials).  1 <= S <= 64.  */
+int64_t pvamd_composed_backward_scratch_bytes(int32_t S, int32_t A, int64_t P, int32_t is_f64);
+int pvamd_composed_query_backward(const pvamd_grid_t* grids, int32_t S, const float* tf, int32_t A, const float* points,
+                                  int64_t P, const int32_t* out_leaf, const float* dval, const float* dgrad, float* dpoints,
+                                  float* dtf, void* scratch, void* stream);
+int pvamd_composed_query_backward_f64(const pvamd_grid_t* grids, int32_t S, const double* tf, int32_t A, const double* points,
+                                      int64_t P, const int32_t* out_leaf, const double* dval, const double* dgrad,
+                                      double* dpoints, double* dtf, void* scratch, void* stream);
+
+/* pvamd_chamfer_grid_backward: batch_chamfer_dist against a BOUNDING_BOX cached grid (chamfer.py:82-94) with upstream dsum[b]
+ * on the per-transform SUM of (scale d)^2 (the caller folds the 1 / N of the mean into it).  Needs no saved tensors: in-range
+ * pairs contribute zero and out-of-range ones depend on x = W[b] p and the box only.  W: device [B][4][4].  points: device
+ * [N][3].  dsum: device [B].  dW: device [B][4][4] or NULL.  dpoints: device [N][3] or NULL.
+ * scratch: pvamd_composed_backward_scratch_bytes(1, B, N, 0) bytes, 16-byte aligned.                                       */
+int pvamd_chamfer_grid_backward(const pvamd_grid_t* grid, const float* W, int32_t B, const float* points, int64_t N,
+                                float scale, const float* dsum, float* dW, float* dpoints, void* scratch, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,245 @@
+"""torch.autograd through the cached, composed, robot and grid-chamfer queries.
+
+The reference is plain PyTorch, so its outputs carry an autograd graph wherever its arithmetic is torch ops on the inputs
+(sdf.py:399,409,421-426,556-571; model_to_sdf.py:82-115; chamfer.py:82-95).  The Functions here give the same gradient,
+given the forward's own decisions (winning leaf, range flag, voxel, active box axes), with HIP kernels for the backward
+(csrc/backward.hip).  The callers (CachedSDF.__call__, ComposedSDF.__call__, RobotSDF.set_joint_configuration,
+chamfer_partial_sums) route here only when grad mode is on and an input requires grad; otherwise nothing changes.
+
+Double backward is not supported: every backward is once_differentiable, so create_graph=True raises.
+"""
+import ctypes
+import math
+
+import torch
+from torch.autograd.function import once_differentiable
+
+from pytorch_volumetric_amd import _lib
+from pytorch_volumetric_amd import transforms as tf
+
+MAX_LEAVES = 64  # pvamd_composed_query_backward: 1 <= S <= 64
+
+
+def _scratch(S, A, P, f64, dev):
+    n = int(_lib.load().pvamd_composed_backward_scratch_bytes(S, A, P, 1 if f64 else 0))
+    return torch.empty((max(n, 16),), dtype=torch.uint8, device=dev)
+
+
+def _upstream(t, dev, dtype, shape):
+    """An incoming gradient as the kernels take it (None stays None: set_materialize_grads(False))."""
+    if t is None:
+        return None
+    return t.detach().reshape(shape).to(device=dev, dtype=dtype).contiguous()
+
+
+# ---------------------------------------------------------------- CachedSDF.__call__ (sdf.py:535-571)
+class CachedQuery(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, cached, points):
+        ctx.set_materialize_grads(False)
+        val, grad = cached(points)  # grad mode is off in here: the usual path, same kernels, same bits
+        flat, _, _, _ = _lib.as_query_points(points, cached._packed.device, keep_f64=True)
+        ctx.cached, ctx.flat = cached, flat
+        ctx.pshape, ctx.pdtype, ctx.pdevice = points.shape, points.dtype, points.device
+        return val, grad
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dval, dgrad):
+        flat, cached = ctx.flat, ctx.cached
+        P, dev, dt = flat.shape[0], flat.device, flat.dtype
+        dv = _upstream(dval, dev, dt, (P,))
+        dg = _upstream(dgrad, dev, dt, (P, 3))
+        out = torch.empty((P, 3), dtype=dt, device=dev)
+        lib = _lib.load()
+        entry = lib.pvamd_cached_query_backward_f64 if dt == torch.float64 else lib.pvamd_cached_query_backward
+        desc = cached._grid_desc()
+        with _lib.on_device(dev):
+            _lib.check(entry(ctypes.byref(desc), _lib.ptr(flat), P, _lib.ptr(dv), _lib.ptr(dg), _lib.ptr(out), _lib.stream_ptr()),
+                       "pvamd_cached_query_backward")
+        return None, out.reshape(ctx.pshape).to(device=ctx.pdevice, dtype=ctx.pdtype)
+
+
+def cached_query(cached, points):
+    return CachedQuery.apply(cached, points)
+
+
+# ---------------------------------------------------------------- ComposedSDF.__call__ (sdf.py:392-433)
+class ComposedQuery(torch.autograd.Function):
+    """Forward: pvamd_composed_query (or _f64) with out_leaf -- the one dispatch pinned for a grad-requiring call (every
+    dispatch gives the same bits; the bucketed one cannot emit leaf ids).  Saved: the points, the detached stack, the leaf id
+    per pair."""
+
+    @staticmethod
+    def forward(ctx, composed, points, tfm):
+        ctx.set_materialize_grads(False)
+        S = len(composed.sdfs)
+        A = math.prod(composed.tsf_batch) if composed.tsf_batch is not None else 1
+        dev = composed._owner_device()
+        lib = _lib.load()
+        f64 = points.dtype == torch.float64
+        if f64:
+            flat = points.detach().reshape(-1, 3).to(device=dev, dtype=torch.float64).contiguous()
+            tfd = tfm.detach().to(device=dev, dtype=torch.float64).contiguous()
+            dtype = torch.float64
+        else:
+            flat, _, dtype, _ = _lib.as_query_points(points, dev)
+            tfd = composed._tf_device(dev)
+        P = flat.shape[0]
+        val = torch.empty((A, P), dtype=flat.dtype, device=dev)
+        grad = torch.empty((A, P, 3), dtype=flat.dtype, device=dev)
+        leaf = torch.empty((A, P), dtype=torch.int32, device=dev)
+        if P > 0:
+            with _lib.on_device(dev):
+                grids = composed._leaf_grids(dev)
+                if f64:
+                    _lib.check(lib.pvamd_composed_query_f64(_lib.ptr(grids), S, _lib.ptr(tfd), A, _lib.ptr(flat), P, _lib.ptr(val),
+                                                            _lib.ptr(grad), _lib.ptr(leaf), _lib.stream_ptr()),
+                               "pvamd_composed_query_f64")
+                else:
+                    _lib.check(lib.pvamd_composed_query(_lib.ptr(grids), S, _lib.ptr(tfd), A, _lib.ptr(flat), P, _lib.ptr(val),
+                                                        _lib.ptr(grad), _lib.ptr(leaf), composed._direct_flags(), _lib.stream_ptr()),
+                               "pvamd_composed_query")
+        ctx.composed, ctx.flat, ctx.tfd, ctx.leaf, ctx.grids = composed, flat, tfd, leaf, composed._leaf_grids(dev)
+        ctx.S, ctx.A = S, A
+        ctx.pshape, ctx.pdtype, ctx.pdevice = points.shape, points.dtype, points.device
+        ctx.tdtype, ctx.tdevice = tfm.dtype, tfm.device
+        pts_shape = points.shape
+        if composed.tsf_batch is not None:
+            val = val.reshape(*composed.tsf_batch, *pts_shape[:-1])
+            grad = grad.reshape(*composed.tsf_batch, *pts_shape[:-1], 3)
+        else:
+            val, grad = val.reshape(-1), grad.reshape(-1, 3)
+        out_device = composed.sdfs[0].device  # leaves return on their own device (sdf.py:546)
+        return val.to(device=out_device, dtype=dtype), grad.to(device=out_device, dtype=dtype)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dval, dgrad):
+        need_p, need_tf = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        flat, tfd, S, A = ctx.flat, ctx.tfd, ctx.S, ctx.A
+        P, dev, dt = flat.shape[0], flat.device, flat.dtype
+        dv = _upstream(dval, dev, dt, (A, P))
+        dg = _upstream(dgrad, dev, dt, (A, P, 3))
+        dpoints = torch.empty((P, 3), dtype=dt, device=dev) if need_p else None
+        dtf = torch.empty((S * A, 4, 4), dtype=dt, device=dev) if need_tf else None
+        lib = _lib.load()
+        f64 = dt == torch.float64
+        entry = lib.pvamd_composed_query_backward_f64 if f64 else lib.pvamd_composed_query_backward
+        with _lib.on_device(dev):
+            scratch = _scratch(S, A, P, f64, dev)
+            _lib.check(entry(_lib.ptr(ctx.grids), S, _lib.ptr(tfd), A, _lib.ptr(flat), P, _lib.ptr(ctx.leaf), _lib.ptr(dv), _lib.ptr(dg),
+                             _lib.ptr(dpoints), _lib.ptr(dtf), _lib.ptr(scratch), _lib.stream_ptr()),
+                       "pvamd_composed_query_backward")
+        gp = dpoints.reshape(ctx.pshape).to(device=ctx.pdevice, dtype=ctx.pdtype) if need_p else None
+        gt = dtf.to(device=ctx.tdevice, dtype=ctx.tdtype) if need_tf else None
+        return None, gp, gt
+
+
+def composed_query(composed, points):
+    if len(composed.sdfs) > MAX_LEAVES:
+        raise _lib.PvamdError(f"gradients through a composition need at most {MAX_LEAVES} leaves, this one has {len(composed.sdfs)}")
+    if not torch.is_tensor(points):
+        points = torch.as_tensor(points)
+    return ComposedQuery.apply(composed, points, composed._tf_matrix)
+
+
+# ---------------------------------------------------------------- RobotSDF.set_joint_configuration (model_to_sdf.py:82-115)
+class ChainConfigure(torch.autograd.Function):
+    """Forward: the one-launch HIP configure (pvamd_configure_chain), q (A, M) -> the (S*A, 4, 4) obj->leaf stack.  Backward:
+    the VJP of the same statements in float64 torch (forward kinematics, rigid inverse, offset compose) -- A x joints of
+    work, not a hot path."""
+
+    @staticmethod
+    def forward(ctx, robot, q, configure):
+        ctx.set_materialize_grads(False)
+        ctx.robot = robot
+        ctx.save_for_backward(q)
+        return configure(q.detach())
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dstack):
+        (q,) = ctx.saved_tensors
+        if dstack is None:
+            return None, None, None
+        with torch.enable_grad():
+            q64 = q.detach().to(dtype=torch.float64).requires_grad_()
+            stack64 = ctx.robot._stack_torch(q64)
+            (dq,) = torch.autograd.grad(stack64, q64, dstack.to(device=stack64.device, dtype=torch.float64))
+        return None, dq.to(device=q.device, dtype=q.dtype), None
+
+
+class TransformStack(torch.autograd.Function):
+    """pvamd_transform_stack (stack[s*A+a] = offset_inv[s] @ rigid_inverse(link_world[s*A+a])) for a foreign chain whose
+    forward kinematics is torch: the VJP of the same contraction in float64 torch."""
+
+    @staticmethod
+    def forward(ctx, offset_inv, link_world, contract):
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(offset_inv, link_world)
+        return contract(link_world.detach())
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dstack):
+        offset_inv, link_world = ctx.saved_tensors
+        if dstack is None:
+            return None, None, None
+        S = offset_inv.shape[0]
+        A = link_world.shape[0] // S
+        with torch.enable_grad():
+            lw = link_world.detach().to(dtype=torch.float64).requires_grad_()
+            off = offset_inv.detach().to(device=lw.device, dtype=torch.float64).repeat_interleave(A, dim=0)
+            stack64 = off @ tf.rigid_inverse(lw)
+            (dlw,) = torch.autograd.grad(stack64, lw, dstack.to(device=lw.device, dtype=torch.float64))
+        return None, dlw.to(dtype=link_world.dtype), None
+
+
+# ---------------------------------------------------------------- batch_chamfer_dist against a cached grid (chamfer.py:82-94)
+class GridChamfer(torch.autograd.Function):
+    """Per-transform sums of (scale d)^2 over the points (float64), differentiable w.r.t. the world->object matrices and the
+    points.  The backward needs no saved tensors beyond the inputs: in-range pairs contribute zero."""
+
+    @staticmethod
+    def forward(ctx, cached, W, points, scale):
+        ctx.set_materialize_grads(False)
+        dev = _lib.require_gpu()
+        lib = _lib.load()
+        pts = torch.as_tensor(points).detach().reshape(-1, 3).to(device=dev, dtype=torch.float32).contiguous()
+        Wd = W.detach().to(device=dev, dtype=torch.float32).contiguous()
+        B, N = Wd.shape[0], pts.shape[0]
+        sums = torch.empty((B,), dtype=torch.float64, device=dev)
+        desc = cached._grid_desc()
+        with _lib.on_device(dev):
+            _lib.check(lib.pvamd_chamfer_grid(ctypes.byref(desc), _lib.ptr(Wd), B, _lib.ptr(pts), N, float(scale), _lib.ptr(sums),
+                                              _lib.stream_ptr()), "pvamd_chamfer_grid")
+        ctx.cached, ctx.Wd, ctx.pts, ctx.scale = cached, Wd, pts, float(scale)
+        ctx.wdtype, ctx.wdevice = W.dtype, W.device
+        ctx.pshape, ctx.pdtype, ctx.pdevice = points.shape, points.dtype, points.device
+        return sums
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dsums):
+        need_w, need_p = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        if dsums is None:
+            return None, None, None, None
+        Wd, pts = ctx.Wd, ctx.pts
+        B, N, dev = Wd.shape[0], pts.shape[0], pts.device
+        dsum = dsums.detach().reshape(B).to(device=dev, dtype=torch.float32).contiguous()
+        dW = torch.empty((B, 4, 4), dtype=torch.float32, device=dev) if need_w else None
+        dp = torch.empty((N, 3), dtype=torch.float32, device=dev) if need_p else None
+        desc = ctx.cached._grid_desc()
+        with _lib.on_device(dev):
+            scratch = _scratch(1, B, N, False, dev)
+            _lib.check(_lib.load().pvamd_chamfer_grid_backward(ctypes.byref(desc), _lib.ptr(Wd), B, _lib.ptr(pts), N, ctx.scale,
+                                                               _lib.ptr(dsum), _lib.ptr(dW), _lib.ptr(dp), _lib.ptr(scratch),
+                                                               _lib.stream_ptr()), "pvamd_chamfer_grid_backward")
+        gw = dW.to(device=ctx.wdevice, dtype=ctx.wdtype) if need_w else None
+        gp = dp.reshape(ctx.pshape).to(device=ctx.pdevice, dtype=ctx.pdtype) if need_p else None
+        return None, gw, gp, None
+
+
+def grid_chamfer_sums(cached, W, points, scale):
+    return GridChamfer.apply(cached, W, points, scale)

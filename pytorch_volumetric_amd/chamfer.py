@@ -79,6 +79,10 @@ def chamfer_partial_sums(W, points, obj_factory, obj_sdf, scale):
 
     fused_grid = isinstance(obj_sdf, CachedSDF) and obj_sdf._dim == 3 and \
         obj_sdf.out_of_bounds_strategy == OutOfBoundsStrategy.BOUNDING_BOX
+    if fused_grid and torch.is_grad_enabled() and (W.requires_grad or getattr(points, "requires_grad", False)):
+        # differentiable w.r.t. the transforms and the points (autograd.GridChamfer): the same kernel, a HIP backward
+        from pytorch_volumetric_amd import autograd
+        return autograd.grid_chamfer_sums(obj_sdf, W, points, scale), N
     with _lib.on_device(dev):
         if fused_grid:
             desc = obj_sdf._grid_desc()

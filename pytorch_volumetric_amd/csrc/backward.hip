@@ -1,0 +1,425 @@
+// Backward (vector-Jacobian products) of the cached, composed and grid-chamfer queries: what torch autograd computes
+// through the reference's expressions (sdf.py:399,409,421-426,556-571; chamfer.py:82-94), given the forward's decisions.
+//
+// Per (configuration a, point p) with winning leaf s (out_leaf of the forward), M = tf[s*A+a], L = M[:3,:3]:
+//   x  = L p + t                                 recomputed with the forward's own fma chain (affine_row), so the range
+//                                                test, the active axes and the voxel index agree with the forward bit for bit
+//   in range:  g = the grid record's gradient    no derivative w.r.t. x (sdf.py:549-550: a table lookup)
+//   outside :  d = signed excess over the surface box, n = d / |d|, active_i = d_i != 0
+//              dx_i = active_i ? dv n_i + (dg_i - n_i (n . dg)) / |d| : 0     (d val / dx = n, d n / dx = (I - n n^T) D / |d|)
+//   gg = L^T g (the forward's rotation back)  =>  dg = L dgg,   dL[r][j] += g_r dgg_j
+//   dp = L^T dx,   dL[r][j] += dx_r p_j,   dt_r = dx_r
+// Every sum is a fixed-order reduction (no float atomics): dpoints over configurations in registers (configuration order) and,
+// when the configurations are split over workgroups, over the splits in split order; dtf over the points of a workgroup by
+// wave butterflies + per-wave LDS slots, then over the workgroups' slab rows in chunk order.  Results are bitwise
+// reproducible from run to run (float atomics would make the sums depend on arrival order).
+#include "common.h"
+#include "grid_lookup.h"
+
+namespace pvamd {
+
+constexpr int kBwdBlock = 256;                     // four waves
+constexpr int kBwdK = 4;                           // points per lane
+constexpr int kBwdChunk = kBwdBlock * kBwdK;       // points per workgroup
+constexpr int kBwdMaxLeaves = 64;                  // per-wave LDS slots (and the presence mask) hold up to 64 leaves
+constexpr int kBwdTargetBlocks = 2048;             // configurations are split over workgroups until about this many exist
+
+// ---- the leaf-frame statements per precision (the forward's own: composed.hip / cached.hip, grid_lookup.h) ----
+template <typename T> struct LeafOps;
+
+template <> struct LeafOps<float> {
+    static PVAMD_DEV void xform(const float* M, const float p[3], float x[3]) {
+        x[0] = affine_row(M[0], M[1], M[2], M[3], p[0], p[1], p[2]);
+        x[1] = affine_row(M[4], M[5], M[6], M[7], p[0], p[1], p[2]);
+        x[2] = affine_row(M[8], M[9], M[10], M[11], p[0], p[1], p[2]);
+    }
+    static PVAMD_DEV bool inside(const pvamd_grid_t& g, const float x[3]) { return in_range(g, x[0], x[1], x[2]); }
+    static PVAMD_DEV void record_grad(const pvamd_grid_t& g, const float x[3], float gr[3]) {
+        int flat;
+        if (g.index_f64) voxel_flat<true>(g, x[0], x[1], x[2], flat);
+        else voxel_flat<false>(g, x[0], x[1], x[2], flat);
+        const float4 r = load_record(g.vox, flat);
+        gr[0] = r.y; gr[1] = r.z; gr[2] = r.w;
+    }
+    static PVAMD_DEV float box(const pvamd_grid_t& g, const float x[3], float t[3]) {
+        return bounding_box_vector(g, x[0], x[1], x[2], t);
+    }
+    static PVAMD_DEV float div(float a, float b) { return div_rn(a, b); }
+};
+
+template <> struct LeafOps<double> {
+    static PVAMD_DEV void xform(const double* M, const double p[3], double x[3]) {
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+            x[r] = __builtin_fma(M[4 * r + 2], p[2], __builtin_fma(M[4 * r + 1], p[1], M[4 * r] * p[0])) + M[4 * r + 3];
+    }
+    static PVAMD_DEV bool inside(const pvamd_grid_t& g, const double x[3]) {
+        long long key[3];
+        return voxel_key_f64(g, x, key);
+    }
+    static PVAMD_DEV void record_grad(const pvamd_grid_t& g, const double x[3], double gr[3]) {
+        long long key[3];
+        voxel_key_f64(g, x, key);
+        const float4 r = load_record(g.vox, clamped_flat(g, key));
+        gr[0] = (double)r.y; gr[1] = (double)r.z; gr[2] = (double)r.w;
+    }
+    static PVAMD_DEV double box(const pvamd_grid_t& g, const double x[3], double t[3]) {
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            double lo = g.dbb_min[d] - x[d];
+            const bool lo_active = lo > 0.0;
+            lo = lo_active ? lo : 0.0;
+            double hi = x[d] - g.dbb_max[d];
+            hi = (hi > 0.0) ? hi : 0.0;
+            const double s = lo + hi;
+            t[d] = lo_active ? -s : s;
+        }
+        return __builtin_sqrt(__builtin_fma(t[2], t[2], __builtin_fma(t[1], t[1], t[0] * t[0])));
+    }
+    static PVAMD_DEV double div(double a, double b) { return a / b; }
+};
+
+// dx of the bounding-box branch at a point x outside the range: dv n + (I - n n^T) dg / |d| on the active axes.
+// Returns |d| (the value) for callers that need it.
+template <typename T>
+PVAMD_DEV T box_backward(const pvamd_grid_t& g, const T x[3], T dv, const T dg[3], bool has_g, T n[3], T dx[3]) {
+    T t[3];
+    const T nrm = LeafOps<T>::box(g, x, t);
+#pragma unroll
+    for (int d = 0; d < 3; ++d) n[d] = LeafOps<T>::div(t[d], nrm);
+    T dot = 0;
+    if (has_g) dot = n[0] * dg[0] + n[1] * dg[1] + n[2] * dg[2];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        T v = dv * n[d];
+        if (has_g) v += LeafOps<T>::div(dg[d] - n[d] * dot, nrm);
+        dx[d] = (t[d] != T(0)) ? v : T(0);
+    }
+    return nrm;
+}
+
+// ---- CachedSDF.__call__ backward: one point per lane, no reduction ----
+template <typename T, bool HAS_V, bool HAS_G>
+__global__ __launch_bounds__(256) void cached_backward_kernel(const pvamd_grid_t g, const T* __restrict__ pts, int64_t P,
+                                                              const T* __restrict__ dval, const T* __restrict__ dgrad,
+                                                              T* __restrict__ dpts) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += stride) {
+        const T x[3] = {pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]};
+        T dx[3] = {0, 0, 0};
+        if (!LeafOps<T>::inside(g, x)) {
+            const T dv = HAS_V ? dval[i] : T(0);
+            T dg[3] = {0, 0, 0};
+            if (HAS_G) { dg[0] = dgrad[3 * i]; dg[1] = dgrad[3 * i + 1]; dg[2] = dgrad[3 * i + 2]; }
+            T n[3];
+            box_backward<T>(g, x, dv, dg, HAS_G, n, dx);
+        }
+        dpts[3 * i] = dx[0];
+        dpts[3 * i + 1] = dx[1];
+        dpts[3 * i + 2] = dx[2];
+    }
+}
+
+template <typename T>
+PVAMD_DEV T wave_sum(T v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;  // a butterfly: every lane holds the same bits (float addition is commutative)
+}
+
+// ---- ComposedSDF.__call__ / grid chamfer backward ----
+// Workgroup (chunk, split): points [chunk * kBwdChunk, +kBwdChunk) x configurations [split * aper, +aper).  Each lane keeps the
+// dpoints of its kBwdK points in registers over the configurations; per configuration the 12 dtf partials of every
+// (configuration, leaf) are reduced wave by wave (one butterfly per leaf present in the wave) into a per-wave LDS slot, the
+// four waves' slots are added in wave order and leave as one slab row [chunk][s*A + a][12] (every row written, zeros for
+// absent leaves: the slab needs no clearing).
+// CHAMFER: one leaf (the grid g0), tf = the B world->object matrices, dv = dsum[a] * d(scale v)^2/dv = dsum[a] 2 scale^2 v.
+template <typename T, bool HAS_V, bool HAS_G, bool WANT_TF, bool CHAMFER>
+__global__ __launch_bounds__(kBwdBlock) void composed_backward_kernel(
+    const pvamd_grid_t* __restrict__ grids, const pvamd_grid_t g0, int S, const T* __restrict__ tf, int A,
+    const T* __restrict__ pts, int64_t P, const int32_t* __restrict__ leaf, const T* __restrict__ dval,
+    const T* __restrict__ dgrad, T scale, int aper, T* __restrict__ dp_out, T* __restrict__ slab) {
+    __shared__ T part[kBwdBlock / 64][kBwdMaxLeaves][12];
+    __shared__ uint64_t present[kBwdBlock / 64];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t chunk = blockIdx.x;
+    const int split = blockIdx.y;
+    const int a0 = split * aper;
+    const int a1 = (a0 + aper) < A ? (a0 + aper) : A;
+
+    T p[kBwdK][3], dp[kBwdK][3];
+    int64_t idx[kBwdK];
+    bool live[kBwdK];
+#pragma unroll
+    for (int k = 0; k < kBwdK; ++k) {
+        idx[k] = chunk * kBwdChunk + (int64_t)k * kBwdBlock + threadIdx.x;
+        live[k] = idx[k] < P;
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            p[k][d] = live[k] ? pts[3 * idx[k] + d] : T(0);
+            dp[k][d] = T(0);
+        }
+    }
+
+    for (int a = a0; a < a1; ++a) {
+        if (WANT_TF && lane == 0) present[wave] = 0;
+#pragma unroll
+        for (int k = 0; k < kBwdK; ++k) {
+            int s = -1;
+            T c[12] = {};
+            if (live[k]) {
+                const int64_t o = (int64_t)a * P + idx[k];
+                s = CHAMFER ? 0 : leaf[o];
+                if (s < 0 || s >= S) s = -1;  // a malformed leaf id contributes nothing (and is never dereferenced)
+                if (s >= 0) {
+                    const pvamd_grid_t& g = CHAMFER ? g0 : grids[s];
+                    const T* M = tf + 16 * ((int64_t)s * A + a);
+                    T dgg[3] = {0, 0, 0}, dg[3] = {0, 0, 0};
+                    if (HAS_G) {
+                        dgg[0] = dgrad[3 * o]; dgg[1] = dgrad[3 * o + 1]; dgg[2] = dgrad[3 * o + 2];
+#pragma unroll
+                        for (int r = 0; r < 3; ++r) dg[r] = M[4 * r] * dgg[0] + M[4 * r + 1] * dgg[1] + M[4 * r + 2] * dgg[2];
+                    }
+                    T x[3], gr[3] = {0, 0, 0}, dx[3] = {0, 0, 0};
+                    LeafOps<T>::xform(M, p[k], x);
+                    if (LeafOps<T>::inside(g, x)) {
+                        if (HAS_G) LeafOps<T>::record_grad(g, x, gr);
+                        else s = -1;  // value-only upstream: an in-range winner contributes nothing
+                    } else if (CHAMFER) {
+                        T t[3];
+                        const T nrm = LeafOps<T>::box(g, x, t);
+                        const T dv = dval[a] * (T(2) * scale) * (scale * nrm);
+#pragma unroll
+                        for (int d = 0; d < 3; ++d) dx[d] = (t[d] != T(0)) ? dv * LeafOps<T>::div(t[d], nrm) : T(0);
+                    } else {
+                        const T dv = HAS_V ? dval[o] : T(0);
+                        box_backward<T>(g, x, dv, dg, HAS_G, gr, dx);
+                    }
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) dp[k][j] += M[j] * dx[0] + M[4 + j] * dx[1] + M[8 + j] * dx[2];
+                    if (WANT_TF) {
+#pragma unroll
+                        for (int r = 0; r < 3; ++r) {
+#pragma unroll
+                            for (int j = 0; j < 3; ++j) c[4 * r + j] = dx[r] * p[k][j] + gr[r] * dgg[j];
+                            c[4 * r + 3] = dx[r];
+                        }
+                    }
+                }
+            }
+            if (WANT_TF) {
+                uint64_t todo = __builtin_amdgcn_ballot_w64(s >= 0);
+                while (todo) {  // wave-uniform: one butterfly per leaf that wins somewhere in the wave
+                    const int first = __builtin_ctzll(todo);
+                    const int sl = __builtin_amdgcn_readlane(s, first);
+                    const bool mine = s == sl;
+                    todo &= ~__builtin_amdgcn_ballot_w64(mine);
+                    const bool seen = (present[wave] >> sl) & 1ull;
+#pragma unroll
+                    for (int j = 0; j < 12; ++j) {
+                        const T v = wave_sum<T>(mine ? c[j] : T(0));
+                        if (lane == 0) part[wave][sl][j] = seen ? part[wave][sl][j] + v : v;
+                    }
+                    if (lane == 0) present[wave] |= 1ull << sl;
+                    PVAMD_WAVE_SYNC();
+                }
+            }
+        }
+        if (WANT_TF) {
+            __syncthreads();
+            for (int e = threadIdx.x; e < S * 12; e += kBwdBlock) {
+                const int s = e / 12, j = e - 12 * (e / 12);
+                T v = T(0);
+#pragma unroll
+                for (int w = 0; w < kBwdBlock / 64; ++w)
+                    if ((present[w] >> s) & 1ull) v += part[w][s][j];
+                slab[(chunk * ((int64_t)S * A) + (int64_t)s * A + a) * 12 + j] = v;
+            }
+            __syncthreads();
+        }
+    }
+    if (dp_out) {
+        T* out = dp_out + (int64_t)split * P * 3;
+#pragma unroll
+        for (int k = 0; k < kBwdK; ++k)
+            if (live[k]) {
+                out[3 * idx[k]] = dp[k][0];
+                out[3 * idx[k] + 1] = dp[k][1];
+                out[3 * idx[k] + 2] = dp[k][2];
+            }
+    }
+}
+
+// dtf[sa][r][c] = sum over chunks, in chunk order, of slab[chunk][sa][4r + c] (row 3: zeros)
+template <typename T>
+__global__ __launch_bounds__(256) void reduce_tf_kernel(const T* __restrict__ slab, int64_t nchunks, int64_t SA, T* __restrict__ dtf) {
+    const int64_t n = SA * 16;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += stride) {
+        const int64_t sa = e >> 4;
+        const int rc = (int)(e & 15);
+        T v = T(0);
+        if (rc < 12)
+            for (int64_t ch = 0; ch < nchunks; ++ch) v += slab[(ch * SA + sa) * 12 + rc];
+        dtf[e] = v;
+    }
+}
+
+// dpoints[i] = sum over splits, in split order, of part[split][i]
+template <typename T>
+__global__ __launch_bounds__(256) void reduce_splits_kernel(const T* __restrict__ part, int nsplit, int64_t n, T* __restrict__ out) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        T v = T(0);
+        for (int sp = 0; sp < nsplit; ++sp) v += part[(int64_t)sp * n + i];
+        out[i] = v;
+    }
+}
+
+struct BwdPlan {
+    int64_t nchunks;
+    int nsplit, aper;
+    int64_t slab_elems;   // [nchunks][S*A][12]
+    int64_t split_elems;  // [nsplit][P][3] when nsplit > 1, else 0
+};
+
+static BwdPlan bwd_plan(int S, int A, int64_t P) {
+    BwdPlan b;
+    b.nchunks = (P + kBwdChunk - 1) / kBwdChunk;
+    if (b.nchunks < 1) b.nchunks = 1;
+    int64_t want = (kBwdTargetBlocks + b.nchunks - 1) / b.nchunks;
+    if (want > A) want = A;
+    if (want < 1) want = 1;
+    b.aper = (int)((A + want - 1) / want);
+    b.nsplit = (A + b.aper - 1) / b.aper;
+    b.slab_elems = b.nchunks * (int64_t)S * A * 12;
+    b.split_elems = b.nsplit > 1 ? (int64_t)b.nsplit * P * 3 : 0;
+    return b;
+}
+
+static int64_t bwd_scratch_bytes(int S, int A, int64_t P, size_t elem) {
+    const BwdPlan b = bwd_plan(S, A, P);
+    const int64_t slab = ((b.slab_elems * (int64_t)elem + 255) / 256) * 256;
+    return slab + b.split_elems * (int64_t)elem;
+}
+
+template <typename T, bool HAS_V, bool HAS_G, bool CHAMFER>
+static void launch_composed_backward(const BwdPlan& b, hipStream_t st, const pvamd_grid_t* grids, const pvamd_grid_t& g0, int S,
+                                     const T* tf, int A, const T* pts, int64_t P, const int32_t* leaf, const T* dval,
+                                     const T* dgrad, T scale, T* dp_out, T* slab, bool want_tf) {
+    const dim3 grid((unsigned)b.nchunks, (unsigned)b.nsplit);
+    if (want_tf)
+        hipLaunchKernelGGL((composed_backward_kernel<T, HAS_V, HAS_G, true, CHAMFER>), grid, dim3(kBwdBlock), 0, st, grids, g0, S, tf,
+                           A, pts, P, leaf, dval, dgrad, scale, b.aper, dp_out, slab);
+    else
+        hipLaunchKernelGGL((composed_backward_kernel<T, HAS_V, HAS_G, false, CHAMFER>), grid, dim3(kBwdBlock), 0, st, grids, g0, S, tf,
+                           A, pts, P, leaf, dval, dgrad, scale, b.aper, dp_out, slab);
+}
+
+template <typename T>
+static int composed_backward(const pvamd_grid_t* grids, const pvamd_grid_t* g0, int32_t S, const T* tf, int32_t A, const T* points,
+                             int64_t P, const int32_t* leaf, const T* dval, const T* dgrad, T scale, T* dpoints, T* dtf,
+                             void* scratch, void* stream, bool chamfer) {
+    if (S < 1 || S > kBwdMaxLeaves || A < 1 || P < 0) return PVAMD_E_SHAPE;
+    if (!dpoints && !dtf) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t SA = (int64_t)S * A;
+    if (P == 0 || (!dval && !dgrad)) {  // nothing flows back: zeros
+        if (dtf && hipMemsetAsync(dtf, 0, (size_t)SA * 16 * sizeof(T), st) != hipSuccess) return (int)hipGetLastError();
+        if (dpoints && P > 0 && hipMemsetAsync(dpoints, 0, (size_t)P * 3 * sizeof(T), st) != hipSuccess) return (int)hipGetLastError();
+        return (int)hipGetLastError();
+    }
+    if (!tf || !points || (!chamfer && (!grids || !leaf))) return PVAMD_E_NULL;
+    if (!scratch && (dtf || bwd_plan(S, A, P).nsplit > 1)) return PVAMD_E_NULL;
+    if (!aligned_to(tf, sizeof(T)) || !aligned_to(points, sizeof(T)) || (scratch && !aligned_to(scratch, 16)) ||
+        (dpoints && !aligned_to(dpoints, sizeof(T))) || (dtf && !aligned_to(dtf, sizeof(T))))
+        return PVAMD_E_ALIGN;
+    const BwdPlan b = bwd_plan(S, A, P);
+    if (b.nchunks > 0x7fffffff) return PVAMD_E_SHAPE;
+    T* slab = (T*)scratch;
+    T* split_part = scratch ? (T*)((char*)scratch + ((b.slab_elems * (int64_t)sizeof(T) + 255) / 256) * 256) : nullptr;
+    T* dp_out = dpoints ? (b.nsplit > 1 ? split_part : dpoints) : nullptr;
+    const pvamd_grid_t gz = chamfer ? *g0 : pvamd_grid_t{};
+    if (chamfer)
+        launch_composed_backward<T, true, false, true>(b, st, nullptr, gz, 1, tf, A, points, P, nullptr, dval, nullptr, scale,
+                                                       dp_out, slab, dtf != nullptr);
+    else if (dval && dgrad)
+        launch_composed_backward<T, true, true, false>(b, st, grids, gz, S, tf, A, points, P, leaf, dval, dgrad, scale, dp_out,
+                                                       slab, dtf != nullptr);
+    else if (dval)
+        launch_composed_backward<T, true, false, false>(b, st, grids, gz, S, tf, A, points, P, leaf, dval, nullptr, scale, dp_out,
+                                                        slab, dtf != nullptr);
+    else
+        launch_composed_backward<T, false, true, false>(b, st, grids, gz, S, tf, A, points, P, leaf, nullptr, dgrad, scale, dp_out,
+                                                        slab, dtf != nullptr);
+    if (dtf)
+        hipLaunchKernelGGL(reduce_tf_kernel<T>, dim3(stream_grid(SA * 16, 256)), dim3(256), 0, st, slab, b.nchunks, SA, dtf);
+    if (dpoints && b.nsplit > 1)
+        hipLaunchKernelGGL(reduce_splits_kernel<T>, dim3(stream_grid(P * 3, 256)), dim3(256), 0, st, split_part, b.nsplit, P * 3,
+                           dpoints);
+    return (int)hipGetLastError();
+}
+
+template <typename T>
+static int cached_backward(const pvamd_grid_t* grid, const T* points, int64_t P, const T* dval, const T* dgrad, T* dpoints,
+                           void* stream) {
+    if (!grid || !dpoints) return PVAMD_E_NULL;
+    if (P < 0) return PVAMD_E_SHAPE;
+    if (int e = check_grid(*grid)) return e;
+    if (grid->oob_mode != PVAMD_OOB_BOUNDING_BOX) return PVAMD_E_MODE;
+    if (P == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    if (!dval && !dgrad) {
+        if (hipMemsetAsync(dpoints, 0, (size_t)P * 3 * sizeof(T), st) != hipSuccess) return (int)hipGetLastError();
+        return 0;
+    }
+    if (!points) return PVAMD_E_NULL;
+    const dim3 grd(stream_grid(P, 256));
+    if (dval && dgrad) hipLaunchKernelGGL((cached_backward_kernel<T, true, true>), grd, dim3(256), 0, st, *grid, points, P, dval, dgrad, dpoints);
+    else if (dval) hipLaunchKernelGGL((cached_backward_kernel<T, true, false>), grd, dim3(256), 0, st, *grid, points, P, dval, dgrad, dpoints);
+    else hipLaunchKernelGGL((cached_backward_kernel<T, false, true>), grd, dim3(256), 0, st, *grid, points, P, dval, dgrad, dpoints);
+    return (int)hipGetLastError();
+}
+
+}  // namespace pvamd
+
+using namespace pvamd;
+
+extern "C" int pvamd_cached_query_backward(const pvamd_grid_t* grid, const float* points, int64_t P, const float* dval,
+                                           const float* dgrad, float* dpoints, void* stream) {
+    return cached_backward<float>(grid, points, P, dval, dgrad, dpoints, stream);
+}
+
+extern "C" int pvamd_cached_query_backward_f64(const pvamd_grid_t* grid, const double* points, int64_t P, const double* dval,
+                                               const double* dgrad, double* dpoints, void* stream) {
+    return cached_backward<double>(grid, points, P, dval, dgrad, dpoints, stream);
+}
+
+extern "C" int64_t pvamd_composed_backward_scratch_bytes(int32_t S, int32_t A, int64_t P, int32_t is_f64) {
+    if (S < 1 || A < 1 || P < 0) return 0;
+    return bwd_scratch_bytes(S, A, P, is_f64 ? sizeof(double) : sizeof(float));
+}
+
+extern "C" int pvamd_composed_query_backward(const pvamd_grid_t* grids, int32_t S, const float* tf, int32_t A, const float* points,
+                                             int64_t P, const int32_t* out_leaf, const float* dval, const float* dgrad,
+                                             float* dpoints, float* dtf, void* scratch, void* stream) {
+    return composed_backward<float>(grids, nullptr, S, tf, A, points, P, out_leaf, dval, dgrad, 0.f, dpoints, dtf, scratch, stream,
+                                    false);
+}
+
+extern "C" int pvamd_composed_query_backward_f64(const pvamd_grid_t* grids, int32_t S, const double* tf, int32_t A,
+                                                 const double* points, int64_t P, const int32_t* out_leaf, const double* dval,
+                                                 const double* dgrad, double* dpoints, double* dtf, void* scratch, void* stream) {
+    return composed_backward<double>(grids, nullptr, S, tf, A, points, P, out_leaf, dval, dgrad, 0.0, dpoints, dtf, scratch,
+                                     stream, false);
+}
+
+extern "C" int pvamd_chamfer_grid_backward(const pvamd_grid_t* grid, const float* W, int32_t B, const float* points, int64_t N,
+                                           float scale, const float* dsum, float* dW, float* dpoints, void* scratch,
+                                           void* stream) {
+    if (!grid) return PVAMD_E_NULL;
+    if (int e = check_grid(*grid)) return e;
+    if (grid->oob_mode != PVAMD_OOB_BOUNDING_BOX) return PVAMD_E_MODE;
+    return composed_backward<float>(nullptr, grid, 1, W, B, points, N, nullptr, dsum, nullptr, scale, dpoints, dW, scratch, stream,
+                                    true);
+}

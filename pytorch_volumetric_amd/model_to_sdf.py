@@ -99,27 +99,45 @@ class RobotSDF(sdf.ObjectFrameSDF):
         lib = _lib.load()
         dev = _lib.require_gpu()
         offset_inv = self._offset_inv_dev(dev)
+        # gradients to q (autograd.py): the same launches inside a Function whose backward is the VJP of the same statements
+        want_grad = joint_config.requires_grad and torch.is_grad_enabled()
         with _lib.on_device(dev):
             if hasattr(self.chain, "joint_table"):
                 # ONE launch (pvamd_configure_chain): sin / cos + frame walk + offset^-1 o world^-1 on the f32 MFMA.  Joint values
                 # that already sit on this GPU as float32 (A, M) are used where they are; anything else is one H2D copy.
                 A = 1 if joint_config.dim() == 1 else joint_config.shape[0]
-                if joint_config.is_cuda and joint_config.dtype is torch.float32 and joint_config.device == dev and \
-                        joint_config.is_contiguous():
-                    q = joint_config
+
+                def configure(jc):
+                    if jc.is_cuda and jc.dtype is torch.float32 and jc.device == dev and jc.is_contiguous():
+                        q = jc
+                    else:
+                        q = jc.reshape(A, M).to(device=dev, dtype=torch.float32).contiguous()
+                    return self._configure(lib, dev, q, A, M, S, offset_inv)
+
+                if want_grad:
+                    from pytorch_volumetric_amd import autograd
+                    stack = autograd.ChainConfigure.apply(self, joint_config.reshape(A, M), configure)
                 else:
-                    q = joint_config.reshape(A, M).to(device=dev, dtype=torch.float32).contiguous()
-                stack = self._configure(lib, dev, q, A, M, S, offset_inv)
+                    stack = configure(joint_config)
             else:
                 # a foreign chain object (e.g. pytorch_kinematics.Chain): use its own forward kinematics
                 fk = self.chain.forward_kinematics(joint_config, end_only=False)
                 link_world = torch.cat([tf.as_matrix(fk[name]) for name in self.sdf_to_link_name])  # leaf-major
                 A = link_world.shape[0] // S
                 link_world_d = link_world.to(device=dev, dtype=torch.float32).contiguous()
-                # object_to_link[s*A+a] = offset[s]^-1 @ world_T_link[s,a]^-1 on the matrix cores
-                stack = torch.empty_like(link_world_d)
-                _lib.check(lib.pvamd_transform_stack(_lib.ptr(offset_inv), _lib.ptr(link_world_d), S, A,
-                                                     _lib.ptr(stack), _lib.stream_ptr()), "pvamd_transform_stack")
+
+                def contract(lw):
+                    # object_to_link[s*A+a] = offset[s]^-1 @ world_T_link[s,a]^-1 on the matrix cores
+                    out = torch.empty_like(lw)
+                    _lib.check(lib.pvamd_transform_stack(_lib.ptr(offset_inv), _lib.ptr(lw), S, A,
+                                                         _lib.ptr(out), _lib.stream_ptr()), "pvamd_transform_stack")
+                    return out
+
+                if link_world_d.requires_grad and torch.is_grad_enabled():
+                    from pytorch_volumetric_amd import autograd
+                    stack = autograd.TransformStack.apply(offset_inv, link_world_d, contract)
+                else:
+                    stack = contract(link_world_d)
         self._stack, self._stack_obj = stack, None  # the Transform3d is built when object_to_link_frames is read
         if self.sdf is not None:
             self.sdf.set_transforms(stack, batch_dim=self.configuration_batch, known_rigid=True)
@@ -213,6 +231,19 @@ class RobotSDF(sdf.ObjectFrameSDF):
                 self.sdf.set_transforms(hit[1], batch_dim=(A,), known_rigid=True)
             self.sdf.invalidate_transforms()  # this stack is re-written in place: drop everything derived from its old contents
             self.sdf.query_into(points, out_val, out_grad)
+
+    def _stack_torch(self, q):
+        """The (S*A, 4, 4) obj->leaf stack of joint values q (A, M) in torch, in q's dtype on q's device: forward kinematics,
+        rigid inverse, offset compose (model_to_sdf.py:94-113) -- what ChainConfigure differentiates (autograd.py)."""
+        key = (q.dtype, str(q.device))
+        cached = self.__dict__.get("_chain_torch")
+        if cached is None or cached[0] != key:
+            cached = self._chain_torch = (key, self.chain.to(dtype=q.dtype, device=q.device))
+        fk = cached[1].forward_kinematics(q, end_only=False)
+        link_world = torch.cat([tf.as_matrix(fk[name]) for name in self.sdf_to_link_name])  # leaf-major
+        A = q.shape[0]
+        off = tf.rigid_inverse(self.offset_transforms.get_matrix().to(device=q.device, dtype=q.dtype))
+        return off.repeat_interleave(A, dim=0) @ tf.rigid_inverse(link_world)
 
     def _offset_inv_dev(self, dev):
         if getattr(self, "_offset_inv_cache", None) is None or self._offset_inv_cache.device != dev:

@@ -602,6 +602,11 @@ class CachedSDF(ObjectFrameSDF):
     def __call__(self, points_in_object_frame):
         """sdf.py:535-591"""
         p = points_in_object_frame
+        # gradients (autograd.py): only when grad mode is on and the points require grad -- one attribute read otherwise
+        if getattr(p, "requires_grad", False) and torch.is_grad_enabled() and self._dim == 3 and \
+                self.out_of_bounds_strategy == OutOfBoundsStrategy.BOUNDING_BOX:
+            from pytorch_volumetric_amd import autograd
+            return autograd.cached_query(self, p)
         # the common call of a planner's inner loop -- float32 points already contiguous on the grid's GPU -- skips every
         # conversion below: two allocations in the final shapes and one C-ABI call (~7.5 us instead of ~18 us of host time per
         # call, 5.1 us through query_into; the kernel itself takes 5.2 us for a million points, 2.4 us for 15,251)
@@ -777,6 +782,7 @@ class ComposedSDF(ObjectFrameSDF):
     def obj_frame_to_link_frame(self, value):
         self._tf_obj = value
         self._tf_matrix = None if value is None else tf.as_matrix(value)
+        self._tf_grad = self._tf_matrix is not None and self._tf_matrix.requires_grad
 
     def ith_transform_slice(self, i):
         if self.tsf_batch is None:
@@ -790,6 +796,7 @@ class ComposedSDF(ObjectFrameSDF):
         if tsf is None:
             self.obj_frame_to_link_frame, self.link_frame_to_obj_frame = None, []
             self.tsf_batch, self._tf_dev, self._tf_dev64, self._rigid = batch_dim, None, None, True
+            self._tf_grad = False
             return
         m = tf.as_matrix(tsf)
         S, S_tsf = len(self.sdfs), m.shape[0]
@@ -805,6 +812,9 @@ class ComposedSDF(ObjectFrameSDF):
         self._tf_volatile = False
         self.tsf_batch, self._tf_dev, self._tf_dev64 = batch_dim, None, None
         self._tf_obj, self._tf_matrix = (tsf if hasattr(tsf, "get_matrix") else None), m
+        # a differentiable stack (RobotSDF under a q that requires grad, poses being optimised): __call__ routes through
+        # autograd.ComposedQuery; the kernels always read its detached storage (_tf_device)
+        self._tf_grad = m.requires_grad
         # The reference inverts with a general matrix inverse (sdf.py:380).  Rigid stacks (every RobotSDF stack, and
         # what the fused kernel's leaf-culling spheres and R^T gradient rotation assume) use the exact R^T form;
         # anything else -- scale, shear, a drifted rotation -- takes the general inverse and the unfused path, whose
@@ -946,7 +956,7 @@ class ComposedSDF(ObjectFrameSDF):
 
     def _tf_device(self, dev):
         if self._tf_dev is None or self._tf_dev.device != dev:
-            self._tf_dev = self._tf_matrix.to(device=dev, dtype=torch.float32).contiguous()
+            self._tf_dev = self._tf_matrix.detach().to(device=dev, dtype=torch.float32).contiguous()
         return self._tf_dev
 
     def _call_plan(self):
@@ -977,6 +987,10 @@ class ComposedSDF(ObjectFrameSDF):
         """sdf.py:392-433.  Returns (A..., B..., N) / (A..., B..., N, 3) with a transform batch, and -- like the
         reference -- FLAT (P,) / (P, 3) without one."""
         p = points_in_object_frame
+        # gradients (autograd.py): a flag stored by set_transforms and one attribute read of the points in front of the fast paths
+        if (self._tf_grad or getattr(p, "requires_grad", False)) and torch.is_grad_enabled() and self._fusable():
+            from pytorch_volumetric_amd import autograd
+            return autograd.composed_query(self, p)
         plan = self._call_plan()
         # float32 points already contiguous on the leaves' GPU, fused leaves, rigid transforms, no sort wanted: two
         # allocations in the final shapes around one C-ABI call (RobotSDF.__call__ in a planner's loop)
@@ -1147,7 +1161,7 @@ class ComposedSDF(ObjectFrameSDF):
         P = flat.shape[0]
         tf64 = self.__dict__.get("_tf_dev64")
         if tf64 is None or tf64.device != dev:
-            tf64 = self._tf_dev64 = self._tf_matrix.to(device=dev, dtype=torch.float64).contiguous()
+            tf64 = self._tf_dev64 = self._tf_matrix.detach().to(device=dev, dtype=torch.float64).contiguous()
         val = torch.empty((A, P), dtype=torch.float64, device=dev)
         grad = torch.empty((A, P, 3), dtype=torch.float64, device=dev)
         with _lib.on_device(dev):
