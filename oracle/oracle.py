@@ -205,6 +205,21 @@ def transform_points(tf, pts):
     return out
 
 
+def transform_pairs(tf, A, pts, leaf):
+    """x[a][p] = tf[leaf[a][p]*A + a] p with the composed kernels' fma chain: the leaf-frame point of each pair in the leaf
+    `leaf` names.  tf: [S*A,4,4] leaf-major; leaf: [A,P] (every entry in 0..S-1).  float64 tf / pts: the float64 statement."""
+    leaf = np.ascontiguousarray(leaf, dtype=np.int32).reshape(A, -1)
+    f64 = np.asarray(pts).dtype == np.float64
+    cast = _f64 if f64 else _f32
+    tf, pts = cast(tf).reshape(-1, 16), cast(pts).reshape(-1, 3)
+    P = len(pts)
+    assert leaf.shape == (A, P) and (P == 0 or (leaf.min() >= 0 and (leaf.max() + 1) * A <= len(tf)))
+    out = np.empty((A, P, 3), np.float64 if f64 else np.float32)
+    fn = load().oracle_transform_pairs_f64 if f64 else load().oracle_transform_pairs
+    fn(_p(tf), ctypes.c_int32(A), _p(pts), ctypes.c_int64(P), _p(leaf), _p(out))
+    return out
+
+
 def compose_merge(tf, leaf_val, leaf_grad, s, best_val, best_grad, best_leaf=None):
     """Fold leaf s into the running first minimum in place (sdf.py:409,421); s == 0 initialises."""
     tf = _f32(tf).reshape(-1, 16)

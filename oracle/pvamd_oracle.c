@@ -272,6 +272,30 @@ void oracle_transform_points(const float* tf, int32_t A, const float* pts, int64
         for (int64_t i = 0; i < P; ++i) affine_apply(tf + 16 * (int64_t)a, pts + 3 * i, out + 3 * ((int64_t)a * P + i));
 }
 
+/* The leaf-frame point of every (configuration, point) pair in ONE given leaf per pair: x[a][i] = tf[leaf[a][i]*A + a] p[i]
+ * (leaf-major stack, as oracle_composed_query reads it).  What the backward recomputes for the winning leaf. */
+void oracle_transform_pairs(const float* tf, int32_t A, const float* pts, int64_t P, const int32_t* leaf, float* out) {
+#pragma omp parallel for schedule(static) collapse(2)
+    for (int32_t a = 0; a < A; ++a)
+        for (int64_t i = 0; i < P; ++i) {
+            const int64_t o = (int64_t)a * P + i;
+            affine_apply(tf + 16 * ((int64_t)leaf[o] * A + a), pts + 3 * i, out + 3 * o);
+        }
+}
+
+/* the same in float64 (the statement of oracle_composed_query_f64) */
+void oracle_transform_pairs_f64(const double* tf, int32_t A, const double* pts, int64_t P, const int32_t* leaf, double* out) {
+#pragma omp parallel for schedule(static) collapse(2)
+    for (int32_t a = 0; a < A; ++a)
+        for (int64_t i = 0; i < P; ++i) {
+            const int64_t o = (int64_t)a * P + i;
+            const double* M = tf + 16 * ((int64_t)leaf[o] * A + a);
+            const double* p = pts + 3 * i;
+            for (int r = 0; r < 3; ++r)
+                out[3 * o + r] = fma(M[4 * r + 2], p[2], fma(M[4 * r + 1], p[1], M[4 * r] * p[0])) + M[4 * r + 3];
+        }
+}
+
 void oracle_compose_merge(const float* tf, int32_t A, int64_t P, const float* leaf_val, const float* leaf_grad, int32_t s,
                           int32_t first, float* best_val, float* best_grad, int32_t* best_leaf) {
     for (int32_t a = 0; a < A; ++a) {

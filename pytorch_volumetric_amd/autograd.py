@@ -25,6 +25,10 @@ def _scratch(S, A, P, f64, dev):
     return torch.empty((max(n, 16),), dtype=torch.uint8, device=dev)
 
 
+def _shares_storage(a, b):
+    return a.untyped_storage().data_ptr() == b.untyped_storage().data_ptr()
+
+
 def _upstream(t, dev, dtype, shape):
     """An incoming gradient as the kernels take it (None stays None: set_materialize_grads(False))."""
     if t is None:
@@ -39,6 +43,11 @@ class CachedQuery(torch.autograd.Function):
         ctx.set_materialize_grads(False)
         val, grad = cached(points)  # grad mode is off in here: the usual path, same kernels, same bits
         flat, _, _, _ = _lib.as_query_points(points, cached._packed.device, keep_f64=True)
+        if torch.is_tensor(points) and _shares_storage(flat, points):
+            # float32 points already contiguous on the device come back as the caller's own storage: an in-place write
+            # before backward would move the point the gradient is taken at (the reference's CachedSDF saves nothing and
+            # differentiates at the values its forward saw)
+            flat = flat.clone()
         ctx.cached, ctx.flat = cached, flat
         ctx.pshape, ctx.pdtype, ctx.pdevice = points.shape, points.dtype, points.device
         return val, grad
@@ -68,7 +77,7 @@ def cached_query(cached, points):
 class ComposedQuery(torch.autograd.Function):
     """Forward: pvamd_composed_query (or _f64) with out_leaf -- the one dispatch pinned for a grad-requiring call (every
     dispatch gives the same bits; the bucketed one cannot emit leaf ids).  Saved: the points, the detached stack, the leaf id
-    per pair."""
+    per pair, and the inputs themselves for torch's in-place check."""
 
     @staticmethod
     def forward(ctx, composed, points, tfm):
@@ -101,6 +110,9 @@ class ComposedQuery(torch.autograd.Function):
                                                         _lib.ptr(grad), _lib.ptr(leaf), composed._direct_flags(), _lib.stream_ptr()),
                                "pvamd_composed_query")
         ctx.composed, ctx.flat, ctx.tfd, ctx.leaf, ctx.grids = composed, flat, tfd, leaf, composed._leaf_grids(dev)
+        # flat / tfd may alias the inputs (float32 contiguous device tensors are used where they are): saving the inputs lets
+        # torch raise on an in-place write between forward and backward, as it does for the reference's matmul (sdf.py:399)
+        ctx.save_for_backward(points, tfm)
         ctx.S, ctx.A = S, A
         ctx.pshape, ctx.pdtype, ctx.pdevice = points.shape, points.dtype, points.device
         ctx.tdtype, ctx.tdevice = tfm.dtype, tfm.device
@@ -117,6 +129,7 @@ class ComposedQuery(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, dval, dgrad):
         need_p, need_tf = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        ctx.saved_tensors  # the version check of the inputs flat / tfd may alias
         flat, tfd, S, A = ctx.flat, ctx.tfd, ctx.S, ctx.A
         P, dev, dt = flat.shape[0], flat.device, flat.dtype
         dv = _upstream(dval, dev, dt, (A, P))
@@ -199,7 +212,7 @@ class TransformStack(torch.autograd.Function):
 # ---------------------------------------------------------------- batch_chamfer_dist against a cached grid (chamfer.py:82-94)
 class GridChamfer(torch.autograd.Function):
     """Per-transform sums of (scale d)^2 over the points (float64), differentiable w.r.t. the world->object matrices and the
-    points.  The backward needs no saved tensors beyond the inputs: in-range pairs contribute zero."""
+    points.  The backward needs nothing beyond the inputs: in-range pairs contribute zero."""
 
     @staticmethod
     def forward(ctx, cached, W, points, scale):
@@ -215,6 +228,9 @@ class GridChamfer(torch.autograd.Function):
             _lib.check(lib.pvamd_chamfer_grid(ctypes.byref(desc), _lib.ptr(Wd), B, _lib.ptr(pts), N, float(scale), _lib.ptr(sums),
                                               _lib.stream_ptr()), "pvamd_chamfer_grid")
         ctx.cached, ctx.Wd, ctx.pts, ctx.scale = cached, Wd, pts, float(scale)
+        # Wd / pts may alias W / points: torch's version check then raises on an in-place write before backward, as it does for
+        # the reference's matmul (chamfer.py:82)
+        ctx.save_for_backward(W, points if torch.is_tensor(points) else None)
         ctx.wdtype, ctx.wdevice = W.dtype, W.device
         ctx.pshape, ctx.pdtype, ctx.pdevice = points.shape, points.dtype, points.device
         return sums
@@ -225,6 +241,7 @@ class GridChamfer(torch.autograd.Function):
         need_w, need_p = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
         if dsums is None:
             return None, None, None, None
+        ctx.saved_tensors  # the version check of the inputs Wd / pts may alias
         Wd, pts = ctx.Wd, ctx.pts
         B, N, dev = Wd.shape[0], pts.shape[0], pts.device
         dsum = dsums.detach().reshape(B).to(device=dev, dtype=torch.float32).contiguous()

@@ -198,10 +198,12 @@ __global__ __launch_bounds__(kBwdBlock) void composed_backward_kernel(
 #pragma unroll
                     for (int j = 0; j < 3; ++j) dp[k][j] += M[j] * dx[0] + M[4 + j] * dx[1] + M[8 + j] * dx[2];
                     if (WANT_TF) {
+                        // without a gradient upstream gr[r] * dgg[j] is no term at all: out of range but inside the box
+                        // (|d| = 0) gr is 0 / 0, and NaN * 0 would reach dtf where torch gives 0
 #pragma unroll
                         for (int r = 0; r < 3; ++r) {
 #pragma unroll
-                            for (int j = 0; j < 3; ++j) c[4 * r + j] = dx[r] * p[k][j] + gr[r] * dgg[j];
+                            for (int j = 0; j < 3; ++j) c[4 * r + j] = HAS_G ? dx[r] * p[k][j] + gr[r] * dgg[j] : dx[r] * p[k][j];
                             c[4 * r + 3] = dx[r];
                         }
                     }

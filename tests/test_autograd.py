@@ -91,3 +91,108 @@ def test_transform_stack_backward_matches_autograd_on_cpu():
     with pytest.raises(RuntimeError):
         (d,) = torch.autograd.grad(autograd.TransformStack.apply(off, lw, contract), lw, up, create_graph=True)
         d.sum().backward()
+
+
+# ---------------------------------------------------------------- the decision-conditioned float64 VJP (oracle/conditioned_vjp.py)
+def _ellipsoid_grid(center, radii, lo, hi, shape, dtype=torch.float64):
+    """An oracle grid (reference layout) filled with the analytic ellipsoid, and the same grid as a float64 CachedOpForOp
+    whose box is the one queries of `dtype` see (sdf.py:556-557 casts self.bb to the query dtype)."""
+    import numpy as np
+    from oracle import oracle
+    from oracle.torch_opforop import CachedOpForOp
+    from tests.helpers import AnalyticEllipsoidSDF
+    lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
+    axes = [torch.linspace(lo[d], hi[d], shape[d], dtype=torch.float64) for d in range(3)]
+    pts = torch.stack(torch.meshgrid(*axes, indexing="ij"), dim=-1).reshape(-1, 3)
+    bb = np.stack((lo + 0.1 * (hi - lo), hi - 0.15 * (hi - lo)), axis=1)
+    val, grad = AnalyticEllipsoidSDF(center, radii, bb)(pts)
+    val, grad = val.float().reshape(shape).numpy(), grad.float().numpy()
+    og = oracle.Grid(val, grad, lo, hi, bb, oob_mode=1, index_f64=True)
+    ref = CachedOpForOp(torch.from_numpy(val).double(), torch.from_numpy(grad).double(), torch.from_numpy(lo),
+                        torch.from_numpy(hi), torch.from_numpy(og_bb(og)).to(dtype).double())
+    return og, ref
+
+
+def og_bb(og):
+    import numpy as np
+    return np.stack((np.array(og.c.dbb_min[:]), np.array(og.c.dbb_max[:])), axis=1)
+
+
+def _away_from_boundaries(og, x, tol=1e-4):
+    """(…,) bool: x (float64, leaf frame) is at least tol from the range faces, the surface-box faces and the half-voxel planes."""
+    lo, hi = torch.tensor(og.c.dmin[:]), torch.tensor(og.c.dmax[:])
+    bb = torch.from_numpy(og_bb(og))
+    res = torch.tensor(og.c.dres[:])
+    ok = ((x - lo).abs() > tol).all(-1) & ((x - hi).abs() > tol).all(-1)
+    ok &= ((x - bb[:, 0]).abs() > tol).all(-1) & ((x - bb[:, 1]).abs() > tol).all(-1)
+    q = (x - lo) / res
+    inside = ((lo <= x) & (x <= hi)).all(-1)
+    return ok & (~inside | ((q - torch.floor(q) - 0.5).abs() * res > tol).all(-1))
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
+def test_conditioned_vjp_matches_opforop_autograd_cached(dtype):
+    """Away from every boundary, the reference equals float64 autograd through the reference's own expressions."""
+    from oracle import conditioned_vjp as cv
+    og, ref = _ellipsoid_grid([0.01, -0.02, 0.0], [0.08, 0.05, 0.06], [-0.12, -0.1, -0.11], [0.1, 0.11, 0.09], (12, 15, 11),
+                              dtype)
+    g = torch.Generator().manual_seed(0)
+    pts = (torch.rand(4000, 3, generator=g, dtype=torch.float64) * 0.4 - 0.2).to(dtype)
+    pts = pts[_away_from_boundaries(og, pts.double())]
+    out = ~((torch.tensor(og.c.dmin[:]) <= pts.double()) & (pts.double() <= torch.tensor(og.c.dmax[:]))).all(-1)
+    assert int(out.sum()) > 500 and int((~out).sum()) > 300
+    wv = torch.randn(pts.shape[0], generator=g, dtype=torch.float64)
+    wg = torch.randn(pts.shape[0], 3, generator=g, dtype=torch.float64)
+    r = cv.cached_vjp(og, pts.numpy(), wv, wg)
+    p64 = pts.double().requires_grad_()
+    v, gr = ref(p64)
+    ((v * wv).sum() + (gr * wg).sum()).backward()
+    assert torch.equal(r["oob"], out)
+    assert torch.allclose(r["dpoints"], p64.grad, rtol=1e-12, atol=1e-12 * float(p64.grad.abs().max()))
+    assert bool((r["dpoints_mag"] >= r["dpoints"].abs() * (1 - 1e-12)).all())
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
+def test_conditioned_vjp_matches_opforop_autograd_composed(dtype):
+    """Five distinct leaves, three configurations: dpoints and the translation column as they are, the rotation block through
+    its skew projection R^T dR - (R^T dR)^T (ComposedOpForOp inverts with inverse(), the kernels with the transpose: they agree
+    on the rigid manifold only)."""
+    from oracle import conditioned_vjp as cv
+    from oracle.torch_opforop import ComposedOpForOp
+    from workloads import random_rigid
+    S, A = 5, 3
+    leaves = [_ellipsoid_grid([0.01 * s, 0.0, -0.01 * s], [0.05 + 0.01 * s, 0.04, 0.06 - 0.005 * s],
+                              [-0.1 - 0.01 * s, -0.09, -0.1], [0.1, 0.09 + 0.01 * s, 0.1], (9 + s, 10, 11 - s), dtype)
+              for s in range(S)]
+    m = random_rigid(S * A, seed=3, trans=0.15).double()
+    m[:, :3, :3] = torch.linalg.qr(m[:, :3, :3])[0] * torch.linalg.qr(m[:, :3, :3])[1].diagonal(dim1=-2, dim2=-1).sign()[:, None, :]
+    m = m.to(dtype)
+    g = torch.Generator().manual_seed(1)
+    pts = (torch.rand(3000, 3, generator=g, dtype=torch.float64) * 0.5 - 0.25).to(dtype)
+    # keep the points whose every leaf-frame point is away from every boundary, and whose winner is decided by > 1e-4
+    x = pts.double().unsqueeze(0) @ m.double()[:, :3, :3].transpose(-1, -2) + m.double()[:, None, :3, 3]
+    x = x.reshape(S, A, -1, 3)
+    keep = torch.stack([_away_from_boundaries(og, x[s]) for s, (og, _) in enumerate(leaves)]).all(0).all(0)
+    vals = torch.stack([ref(x[s])[0] for s, (_, ref) in enumerate(leaves)]).sort(0).values
+    keep &= ((vals[1] - vals[0]) > 1e-4).all(0)
+    pts = pts[keep].contiguous()
+    assert pts.shape[0] > 800
+    P = pts.shape[0]
+    wv = torch.randn(A, P, generator=g, dtype=torch.float64)
+    wg = torch.randn(A, P, 3, generator=g, dtype=torch.float64)
+    r = cv.composed_vjp([og for og, _ in leaves], m.numpy(), A, pts.numpy(), wv, wg)
+    assert len(set(r["leaf"].reshape(-1).tolist())) == S
+    m64 = m.double().requires_grad_()
+    p64 = pts.double().requires_grad_()
+    rv, rg = ComposedOpForOp([ref for _, ref in leaves], m64, batch=A)(p64)
+    ((rv * wv).sum() + (rg * wg).sum()).backward()
+    tol = 1e-12 if dtype == torch.float64 else 1e-5  # float32 matrices: inverse() and the transpose differ by ~1e-7
+    assert torch.allclose(r["dpoints"], p64.grad, rtol=tol, atol=tol * float(p64.grad.abs().max()))
+    dm, dm_ref = r["dtf"], m64.grad
+    scale = float(dm_ref[:, :3, :].abs().max())
+    assert torch.allclose(dm[:, :3, 3], dm_ref[:, :3, 3], rtol=tol, atol=tol * scale)
+    R = m64.detach()[:, :3, :3]
+    skew = lambda d: (R.transpose(-1, -2) @ d[:, :3, :3]) - (R.transpose(-1, -2) @ d[:, :3, :3]).transpose(-1, -2)
+    assert torch.allclose(skew(dm), skew(dm_ref), rtol=tol, atol=tol * scale)
+    assert torch.equal(dm[:, 3], torch.zeros_like(dm[:, 3]))
+    assert bool((r["dtf_mag"] >= dm.abs() * (1 - 1e-9)).all()) and bool((r["dpoints_mag"] >= r["dpoints"].abs() * (1 - 1e-9)).all())

@@ -202,6 +202,15 @@ def test_composed_float32_matches_float64_restatement_c3_size(cached):
     scale = dm_ref[:, :3, :].abs().max()
     assert torch.allclose(dm[:, :3, 3], dm_ref[:, :3, 3], atol=2e-3 * scale)
     assert torch.allclose(skew(dm), skew(dm_ref), atol=2e-3 * scale)
+    # and all 12 entries of every matrix (row 3 exactly zero) against the decision-conditioned float64 VJP, whose transpose
+    # form is the contract for raw matrix entries: a worst-case rounding bound (tests/test_autograd_edges_gpu.py)
+    from oracle import conditioned_vjp as cv
+    r = cv.composed_vjp([H.oracle_grid_from_cached(cached)] * S, m.cpu().numpy(), A, pts.cpu().numpy(), wv.cpu(), wg.cpu())
+    assert torch.equal(mm.grad[:, 3], torch.zeros_like(mm.grad[:, 3]))
+    ok, worst, _ = cv.within_bound(mm.grad, r["dtf"], r["dtf_mag"], 2.0 ** -24, -(-P // 1024) + 14, c=4.0)
+    assert ok, worst
+    ok, worst, _ = cv.within_bound(p32.grad, r["dpoints"], r["dpoints_mag"], 2.0 ** -24, A, c=4.0)
+    assert ok, worst
 
 
 def test_composed_backward_is_reproducible(cached):
