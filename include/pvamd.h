@@ -498,6 +498,50 @@ int pvamd_composed_query_backward_f64(const pvamd_grid_t* grids, int32_t S, cons
 int pvamd_chamfer_grid_backward(const pvamd_grid_t* grid, const float* W, int32_t B, const float* points, int64_t N,
                                 float scale, const float* dsum, float* dW, float* dpoints, void* scratch, void* stream);
 
+/* ---- Interpolated queries (CachedSDF / ComposedSDF with interpolation="trilinear"; opt-in, nearest-voxel stays the default) ----
+ * The same descriptors (pvamd_grid_t is unchanged): the entry point chooses the mode.  T is the query dtype: float32 points use
+ * fmin / fres and float32 arithmetic whatever index_f64 says, float64 points dmin / dres.  R[i][j][k] is the record
+ * (val, gx, gy, gz), n_d = shape[d].
+ *  1. The range decision is the nearest mode's, bit for bit (vlo / vhi under the grid's rule; voxel_key_f64 for float64).  Points
+ *     that fail it take the out-of-range branch, and their val / grad are IDENTICAL to the nearest mode's (BOUNDING_BOX: the
+ *     distance to the surface box; LOOKUP_GT_SDF: zeros and out_oob = 1, the caller fills in the ground truth).
+ *  2. Per axis d: s = (x_d - min_d) / res_d (IEEE subtraction, then IEEE division); c = s < 0 ? 0 : (s > n_d - 1 ? n_d - 1 : s),
+ *     clamped_d = (c != s) (under PVAMD_RULE_VALID_ON_INDEX valid points reach half a voxel beyond the end centres: the value
+ *     is held constant there); i_d = min(floor(c), n_d - 2); f_d = c - i_d (exact).
+ *  3. lerp(a, b, f) = fma(f, b - a, a).  Per channel q: e_ab = lerp(R[i+a][j+b][k][q], R[i+a][j+b][k+1][q], f_z) for (a, b) in
+ *     (0,0), (0,1), (1,0), (1,1); y_a = lerp(e_a0, e_a1, f_y); out_q = lerp(y_0, y_1, f_x).
+ *  4. The returned gradient is the interpolated stored gradient, not renormalised (norm <= 1 up to rounding); it is NOT
+ *     d val / dx, which the backward computes exactly.
+ *  5. Backward: torch autograd through these expressions given the forward's decisions (range, cell, clamped axes, winning
+ *     leaf): d lerp / d f = b - a, d f_d / d x_d = 1 / res_d (upstream / res_d), 0 on a clamped axis; out of range the
+ *     BOUNDING_BOX VJP of pvamd_cached_query_backward.
+ *  6. Composed: the nearest kernels' leaf transform (affine_row in float32, the fma chain of pvamd_composed_query_f64 in
+ *     float64), the same first-minimum comparison over leaves, the winner's gradient rotated back with the same statements.
+ *
+ * pvamd_cached_query_interp / _f64: as pvamd_cached_query / _f64 (same arguments, out_oob optional).
+ * pvamd_composed_query_interp / _f64: as pvamd_composed_query / _f64 without flags; out_leaf (the arg-min leaf, what the backward
+ *   needs) optional.  Every leaf BOUNDING_BOX, transforms rigid.
+ * pvamd_cached_query_interp_backward / _f64, pvamd_composed_query_interp_backward / _f64: as pvamd_cached_query_backward /
+ *   pvamd_composed_query_backward (same arguments, scratch sizes, fixed-order reductions) for the interpolated forward.       */
+int pvamd_cached_query_interp(const pvamd_grid_t* grid, const float* points, int64_t P, float* out_val, float* out_grad,
+                              uint8_t* out_oob, void* stream);
+int pvamd_cached_query_interp_f64(const pvamd_grid_t* grid, const double* points, int64_t P, double* out_val, double* out_grad,
+                                  uint8_t* out_oob, void* stream);
+int pvamd_composed_query_interp(const pvamd_grid_t* grids, int32_t S, const float* tf, int32_t A, const float* points, int64_t P,
+                                float* out_val, float* out_grad, int32_t* out_leaf, void* stream);
+int pvamd_composed_query_interp_f64(const pvamd_grid_t* grids, int32_t S, const double* tf, int32_t A, const double* points,
+                                    int64_t P, double* out_val, double* out_grad, int32_t* out_leaf, void* stream);
+int pvamd_cached_query_interp_backward(const pvamd_grid_t* grid, const float* points, int64_t P, const float* dval,
+                                       const float* dgrad, float* dpoints, void* stream);
+int pvamd_cached_query_interp_backward_f64(const pvamd_grid_t* grid, const double* points, int64_t P, const double* dval,
+                                           const double* dgrad, double* dpoints, void* stream);
+int pvamd_composed_query_interp_backward(const pvamd_grid_t* grids, int32_t S, const float* tf, int32_t A, const float* points,
+                                         int64_t P, const int32_t* out_leaf, const float* dval, const float* dgrad, float* dpoints,
+                                         float* dtf, void* scratch, void* stream);
+int pvamd_composed_query_interp_backward_f64(const pvamd_grid_t* grids, int32_t S, const double* tf, int32_t A,
+                                             const double* points, int64_t P, const int32_t* out_leaf, const double* dval,
+                                             const double* dgrad, double* dpoints, double* dtf, void* scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

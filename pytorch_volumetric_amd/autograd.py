@@ -50,6 +50,7 @@ class CachedQuery(torch.autograd.Function):
             flat = flat.clone()
         ctx.cached, ctx.flat = cached, flat
         ctx.pshape, ctx.pdtype, ctx.pdevice = points.shape, points.dtype, points.device
+        ctx.backward_entry = "pvamd_cached_query_backward"
         return val, grad
 
     @staticmethod
@@ -61,16 +62,31 @@ class CachedQuery(torch.autograd.Function):
         dg = _upstream(dgrad, dev, dt, (P, 3))
         out = torch.empty((P, 3), dtype=dt, device=dev)
         lib = _lib.load()
-        entry = lib.pvamd_cached_query_backward_f64 if dt == torch.float64 else lib.pvamd_cached_query_backward
+        entry = getattr(lib, ctx.backward_entry + "_f64" if dt == torch.float64 else ctx.backward_entry)
         desc = cached._grid_desc()
         with _lib.on_device(dev):
             _lib.check(entry(ctypes.byref(desc), _lib.ptr(flat), P, _lib.ptr(dv), _lib.ptr(dg), _lib.ptr(out), _lib.stream_ptr()),
-                       "pvamd_cached_query_backward")
+                       ctx.backward_entry)
         return None, out.reshape(ctx.pshape).to(device=ctx.pdevice, dtype=ctx.pdtype)
 
 
 def cached_query(cached, points):
     return CachedQuery.apply(cached, points)
+
+
+class CachedInterpQuery(CachedQuery):
+    """CachedSDF.__call__ with interpolation="trilinear": the forward is the cache's own (pvamd_cached_query_interp), the backward
+    pvamd_cached_query_interp_backward -- in range the exact derivative of the interpolated value and gradient w.r.t. the point."""
+
+    @staticmethod
+    def forward(ctx, cached, points):
+        out = CachedQuery.forward(ctx, cached, points)
+        ctx.backward_entry = "pvamd_cached_query_interp_backward"
+        return out
+
+
+def cached_interp_query(cached, points):
+    return CachedInterpQuery.apply(cached, points)
 
 
 # ---------------------------------------------------------------- ComposedSDF.__call__ (sdf.py:392-433)
@@ -114,6 +130,7 @@ class ComposedQuery(torch.autograd.Function):
         # torch raise on an in-place write between forward and backward, as it does for the reference's matmul (sdf.py:399)
         ctx.save_for_backward(points, tfm)
         ctx.S, ctx.A = S, A
+        ctx.backward_entry = "pvamd_composed_query_backward"
         ctx.pshape, ctx.pdtype, ctx.pdevice = points.shape, points.dtype, points.device
         ctx.tdtype, ctx.tdevice = tfm.dtype, tfm.device
         pts_shape = points.shape
@@ -138,12 +155,12 @@ class ComposedQuery(torch.autograd.Function):
         dtf = torch.empty((S * A, 4, 4), dtype=dt, device=dev) if need_tf else None
         lib = _lib.load()
         f64 = dt == torch.float64
-        entry = lib.pvamd_composed_query_backward_f64 if f64 else lib.pvamd_composed_query_backward
+        entry = getattr(lib, ctx.backward_entry + "_f64" if f64 else ctx.backward_entry)
         with _lib.on_device(dev):
             scratch = _scratch(S, A, P, f64, dev)
             _lib.check(entry(_lib.ptr(ctx.grids), S, _lib.ptr(tfd), A, _lib.ptr(flat), P, _lib.ptr(ctx.leaf), _lib.ptr(dv), _lib.ptr(dg),
                              _lib.ptr(dpoints), _lib.ptr(dtf), _lib.ptr(scratch), _lib.stream_ptr()),
-                       "pvamd_composed_query_backward")
+                       ctx.backward_entry)
         gp = dpoints.reshape(ctx.pshape).to(device=ctx.pdevice, dtype=ctx.pdtype) if need_p else None
         gt = dtf.to(device=ctx.tdevice, dtype=ctx.tdtype) if need_tf else None
         return None, gp, gt
@@ -155,6 +172,33 @@ def composed_query(composed, points):
     if not torch.is_tensor(points):
         points = torch.as_tensor(points)
     return ComposedQuery.apply(composed, points, composed._tf_matrix)
+
+
+class ComposedInterpQuery(ComposedQuery):
+    """ComposedSDF.__call__ over trilinear leaves: forward pvamd_composed_query_interp (or _f64) with out_leaf, backward
+    pvamd_composed_query_interp_backward -- the same saved state, reductions and conventions as ComposedQuery."""
+
+    @staticmethod
+    def forward(ctx, composed, points, tfm):
+        ctx.set_materialize_grads(False)
+        dev = composed._owner_device()
+        val, grad, leaf, flat, tfd = composed._interp_forward(points, want_leaf=True)
+        ctx.composed, ctx.flat, ctx.tfd, ctx.leaf, ctx.grids = composed, flat, tfd, leaf, composed._leaf_grids(dev)
+        # flat / tfd may alias the inputs: saving them lets torch raise on an in-place write between forward and backward
+        ctx.save_for_backward(points, tfm)
+        ctx.S, ctx.A = len(composed.sdfs), (math.prod(composed.tsf_batch) if composed.tsf_batch is not None else 1)
+        ctx.backward_entry = "pvamd_composed_query_interp_backward"
+        ctx.pshape, ctx.pdtype, ctx.pdevice = points.shape, points.dtype, points.device
+        ctx.tdtype, ctx.tdevice = tfm.dtype, tfm.device
+        return val, grad
+
+
+def composed_interp_query(composed, points):
+    if len(composed.sdfs) > MAX_LEAVES:
+        raise _lib.PvamdError(f"gradients through a composition need at most {MAX_LEAVES} leaves, this one has {len(composed.sdfs)}")
+    if not torch.is_tensor(points):
+        points = torch.as_tensor(points)
+    return ComposedInterpQuery.apply(composed, points, composed._tf_matrix)
 
 
 # ---------------------------------------------------------------- RobotSDF.set_joint_configuration (model_to_sdf.py:82-115)

@@ -78,7 +78,16 @@ def chamfer_partial_sums(W, points, obj_factory, obj_sdf, scale):
         return sums.zero_(), 0
 
     fused_grid = isinstance(obj_sdf, CachedSDF) and obj_sdf._dim == 3 and \
-        obj_sdf.out_of_bounds_strategy == OutOfBoundsStrategy.BOUNDING_BOX
+        obj_sdf.out_of_bounds_strategy == OutOfBoundsStrategy.BOUNDING_BOX and obj_sdf.interpolation == "nearest"
+    if isinstance(obj_sdf, CachedSDF) and obj_sdf.interpolation != "nearest" and torch.is_grad_enabled() and \
+            (W.requires_grad or getattr(points, "requires_grad", False)):
+        # a trilinear grid (no fused chamfer kernel): the arbitrary-SDF branch below with the graph kept -- transform in torch,
+        # query through the cache's autograd Function (autograd.CachedInterpQuery), reduce in torch
+        Wg = W.to(device=dev, dtype=torch.float32)
+        pg = torch.as_tensor(points).reshape(-1, 3).to(device=dev, dtype=torch.float32)
+        x = pg.unsqueeze(0) @ Wg[:, :3, :3].transpose(-1, -2) + Wg[:, None, :3, 3]
+        d, _ = obj_sdf(x)
+        return ((float(scale) * d.to(device=dev, dtype=torch.float32)) ** 2).double().sum(dim=-1), N
     if fused_grid and torch.is_grad_enabled() and (W.requires_grad or getattr(points, "requires_grad", False)):
         # differentiable w.r.t. the transforms and the points (autograd.GridChamfer): the same kernel, a HIP backward
         from pytorch_volumetric_amd import autograd

@@ -15,6 +15,7 @@
 // reproducible from run to run (float atomics would make the sums depend on arrival order).
 #include "common.h"
 #include "grid_lookup.h"
+#include "interp.h"
 
 namespace pvamd {
 
@@ -98,8 +99,32 @@ PVAMD_DEV T box_backward(const pvamd_grid_t& g, const T x[3], T dv, const T dg[3
     return nrm;
 }
 
+// The interpolated leaf (interpolation="trilinear", interp.h) in range: the interpolated record and the VJP of its four channels
+// w.r.t. x through the fractions -- d f_d / d x_d = 1 / res_d (torch's div backward: upstream / res_d), 0 on a clamped axis.
+// gr = the interpolated gradient (what the forward rotated back), dx = the point's VJP.
+template <typename T> struct InterpOps {
+    static PVAMD_DEV T res(const pvamd_grid_t& g, int d) {
+        if constexpr (sizeof(T) == 8) return g.dres[d];
+        else return g.fres[d];
+    }
+    static PVAMD_DEV void leaf(const pvamd_grid_t& g, const T x[3], T dv, const T dg[3], bool has_g, T gr[3], T dx[3]) {
+        InterpCell<T> c;
+        interp_cell<T>(g, x, c);
+        float4 r[8];
+        interp_gather(g, c.base, r);
+        T o[4];
+        interp_combine<T>(r, c.f, o);
+        gr[0] = o[1]; gr[1] = o[2]; gr[2] = o[3];
+        const T u[4] = {dv, dg[0], dg[1], dg[2]};
+        T df[3];
+        interp_fraction_vjp<T>(r, c.f, u, has_g, df);
+#pragma unroll
+        for (int d = 0; d < 3; ++d) dx[d] = c.cl[d] ? T(0) : LeafOps<T>::div(df[d], res(g, d));
+    }
+};
+
 // ---- CachedSDF.__call__ backward: one point per lane, no reduction ----
-template <typename T, bool HAS_V, bool HAS_G>
+template <typename T, bool HAS_V, bool HAS_G, bool INTERP>
 __global__ __launch_bounds__(256) void cached_backward_kernel(const pvamd_grid_t g, const T* __restrict__ pts, int64_t P,
                                                               const T* __restrict__ dval, const T* __restrict__ dgrad,
                                                               T* __restrict__ dpts) {
@@ -107,12 +132,14 @@ __global__ __launch_bounds__(256) void cached_backward_kernel(const pvamd_grid_t
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += stride) {
         const T x[3] = {pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]};
         T dx[3] = {0, 0, 0};
-        if (!LeafOps<T>::inside(g, x)) {
+        const bool inside = LeafOps<T>::inside(g, x);
+        if (!inside || INTERP) {
             const T dv = HAS_V ? dval[i] : T(0);
             T dg[3] = {0, 0, 0};
             if (HAS_G) { dg[0] = dgrad[3 * i]; dg[1] = dgrad[3 * i + 1]; dg[2] = dgrad[3 * i + 2]; }
             T n[3];
-            box_backward<T>(g, x, dv, dg, HAS_G, n, dx);
+            if (inside) InterpOps<T>::leaf(g, x, dv, dg, HAS_G, n, dx);
+            else box_backward<T>(g, x, dv, dg, HAS_G, n, dx);
         }
         dpts[3 * i] = dx[0];
         dpts[3 * i + 1] = dx[1];
@@ -134,7 +161,7 @@ PVAMD_DEV T wave_sum(T v) {
 // four waves' slots are added in wave order and leave as one slab row [chunk][s*A + a][12] (every row written, zeros for
 // absent leaves: the slab needs no clearing).
 // CHAMFER: one leaf (the grid g0), tf = the B world->object matrices, dv = dsum[a] * d(scale v)^2/dv = dsum[a] 2 scale^2 v.
-template <typename T, bool HAS_V, bool HAS_G, bool WANT_TF, bool CHAMFER>
+template <typename T, bool HAS_V, bool HAS_G, bool WANT_TF, bool CHAMFER, bool INTERP>
 __global__ __launch_bounds__(kBwdBlock) void composed_backward_kernel(
     const pvamd_grid_t* __restrict__ grids, const pvamd_grid_t g0, int S, const T* __restrict__ tf, int A,
     const T* __restrict__ pts, int64_t P, const int32_t* __restrict__ leaf, const T* __restrict__ dval,
@@ -183,7 +210,8 @@ __global__ __launch_bounds__(kBwdBlock) void composed_backward_kernel(
                     T x[3], gr[3] = {0, 0, 0}, dx[3] = {0, 0, 0};
                     LeafOps<T>::xform(M, p[k], x);
                     if (LeafOps<T>::inside(g, x)) {
-                        if (HAS_G) LeafOps<T>::record_grad(g, x, gr);
+                        if constexpr (INTERP) InterpOps<T>::leaf(g, x, HAS_V ? dval[o] : T(0), dg, HAS_G, gr, dx);
+                        else if (HAS_G) LeafOps<T>::record_grad(g, x, gr);
                         else s = -1;  // value-only upstream: an in-range winner contributes nothing
                     } else if (CHAMFER) {
                         T t[3];
@@ -305,20 +333,20 @@ static int64_t bwd_scratch_bytes(int S, int A, int64_t P, size_t elem) {
     return slab + b.split_elems * (int64_t)elem;
 }
 
-template <typename T, bool HAS_V, bool HAS_G, bool CHAMFER>
+template <typename T, bool HAS_V, bool HAS_G, bool CHAMFER, bool INTERP>
 static void launch_composed_backward(const BwdPlan& b, hipStream_t st, const pvamd_grid_t* grids, const pvamd_grid_t& g0, int S,
                                      const T* tf, int A, const T* pts, int64_t P, const int32_t* leaf, const T* dval,
                                      const T* dgrad, T scale, T* dp_out, T* slab, bool want_tf) {
     const dim3 grid((unsigned)b.nchunks, (unsigned)b.nsplit);
     if (want_tf)
-        hipLaunchKernelGGL((composed_backward_kernel<T, HAS_V, HAS_G, true, CHAMFER>), grid, dim3(kBwdBlock), 0, st, grids, g0, S, tf,
+        hipLaunchKernelGGL((composed_backward_kernel<T, HAS_V, HAS_G, true, CHAMFER, INTERP>), grid, dim3(kBwdBlock), 0, st, grids, g0, S, tf,
                            A, pts, P, leaf, dval, dgrad, scale, b.aper, dp_out, slab);
     else
-        hipLaunchKernelGGL((composed_backward_kernel<T, HAS_V, HAS_G, false, CHAMFER>), grid, dim3(kBwdBlock), 0, st, grids, g0, S, tf,
+        hipLaunchKernelGGL((composed_backward_kernel<T, HAS_V, HAS_G, false, CHAMFER, INTERP>), grid, dim3(kBwdBlock), 0, st, grids, g0, S, tf,
                            A, pts, P, leaf, dval, dgrad, scale, b.aper, dp_out, slab);
 }
 
-template <typename T>
+template <typename T, bool INTERP = false>
 static int composed_backward(const pvamd_grid_t* grids, const pvamd_grid_t* g0, int32_t S, const T* tf, int32_t A, const T* points,
                              int64_t P, const int32_t* leaf, const T* dval, const T* dgrad, T scale, T* dpoints, T* dtf,
                              void* scratch, void* stream, bool chamfer) {
@@ -343,16 +371,16 @@ static int composed_backward(const pvamd_grid_t* grids, const pvamd_grid_t* g0, 
     T* dp_out = dpoints ? (b.nsplit > 1 ? split_part : dpoints) : nullptr;
     const pvamd_grid_t gz = chamfer ? *g0 : pvamd_grid_t{};
     if (chamfer)
-        launch_composed_backward<T, true, false, true>(b, st, nullptr, gz, 1, tf, A, points, P, nullptr, dval, nullptr, scale,
+        launch_composed_backward<T, true, false, true, false>(b, st, nullptr, gz, 1, tf, A, points, P, nullptr, dval, nullptr, scale,
                                                        dp_out, slab, dtf != nullptr);
     else if (dval && dgrad)
-        launch_composed_backward<T, true, true, false>(b, st, grids, gz, S, tf, A, points, P, leaf, dval, dgrad, scale, dp_out,
+        launch_composed_backward<T, true, true, false, INTERP>(b, st, grids, gz, S, tf, A, points, P, leaf, dval, dgrad, scale, dp_out,
                                                        slab, dtf != nullptr);
     else if (dval)
-        launch_composed_backward<T, true, false, false>(b, st, grids, gz, S, tf, A, points, P, leaf, dval, nullptr, scale, dp_out,
+        launch_composed_backward<T, true, false, false, INTERP>(b, st, grids, gz, S, tf, A, points, P, leaf, dval, nullptr, scale, dp_out,
                                                         slab, dtf != nullptr);
     else
-        launch_composed_backward<T, false, true, false>(b, st, grids, gz, S, tf, A, points, P, leaf, nullptr, dgrad, scale, dp_out,
+        launch_composed_backward<T, false, true, false, INTERP>(b, st, grids, gz, S, tf, A, points, P, leaf, nullptr, dgrad, scale, dp_out,
                                                         slab, dtf != nullptr);
     if (dtf)
         hipLaunchKernelGGL(reduce_tf_kernel<T>, dim3(stream_grid(SA * 16, 256)), dim3(256), 0, st, slab, b.nchunks, SA, dtf);
@@ -362,7 +390,7 @@ static int composed_backward(const pvamd_grid_t* grids, const pvamd_grid_t* g0, 
     return (int)hipGetLastError();
 }
 
-template <typename T>
+template <typename T, bool INTERP = false>
 static int cached_backward(const pvamd_grid_t* grid, const T* points, int64_t P, const T* dval, const T* dgrad, T* dpoints,
                            void* stream) {
     if (!grid || !dpoints) return PVAMD_E_NULL;
@@ -377,9 +405,9 @@ static int cached_backward(const pvamd_grid_t* grid, const T* points, int64_t P,
     }
     if (!points) return PVAMD_E_NULL;
     const dim3 grd(stream_grid(P, 256));
-    if (dval && dgrad) hipLaunchKernelGGL((cached_backward_kernel<T, true, true>), grd, dim3(256), 0, st, *grid, points, P, dval, dgrad, dpoints);
-    else if (dval) hipLaunchKernelGGL((cached_backward_kernel<T, true, false>), grd, dim3(256), 0, st, *grid, points, P, dval, dgrad, dpoints);
-    else hipLaunchKernelGGL((cached_backward_kernel<T, false, true>), grd, dim3(256), 0, st, *grid, points, P, dval, dgrad, dpoints);
+    if (dval && dgrad) hipLaunchKernelGGL((cached_backward_kernel<T, true, true, INTERP>), grd, dim3(256), 0, st, *grid, points, P, dval, dgrad, dpoints);
+    else if (dval) hipLaunchKernelGGL((cached_backward_kernel<T, true, false, INTERP>), grd, dim3(256), 0, st, *grid, points, P, dval, dgrad, dpoints);
+    else hipLaunchKernelGGL((cached_backward_kernel<T, false, true, INTERP>), grd, dim3(256), 0, st, *grid, points, P, dval, dgrad, dpoints);
     return (int)hipGetLastError();
 }
 
@@ -424,4 +452,30 @@ extern "C" int pvamd_chamfer_grid_backward(const pvamd_grid_t* grid, const float
     if (grid->oob_mode != PVAMD_OOB_BOUNDING_BOX) return PVAMD_E_MODE;
     return composed_backward<float>(nullptr, grid, 1, W, B, points, N, nullptr, dsum, nullptr, scale, dpoints, dW, scratch, stream,
                                     true);
+}
+
+// ---- the interpolated leaf (interpolation="trilinear"): the same kernels, reductions and argument checks ----
+extern "C" int pvamd_cached_query_interp_backward(const pvamd_grid_t* grid, const float* points, int64_t P, const float* dval,
+                                                  const float* dgrad, float* dpoints, void* stream) {
+    return cached_backward<float, true>(grid, points, P, dval, dgrad, dpoints, stream);
+}
+
+extern "C" int pvamd_cached_query_interp_backward_f64(const pvamd_grid_t* grid, const double* points, int64_t P, const double* dval,
+                                                      const double* dgrad, double* dpoints, void* stream) {
+    return cached_backward<double, true>(grid, points, P, dval, dgrad, dpoints, stream);
+}
+
+extern "C" int pvamd_composed_query_interp_backward(const pvamd_grid_t* grids, int32_t S, const float* tf, int32_t A,
+                                                    const float* points, int64_t P, const int32_t* out_leaf, const float* dval,
+                                                    const float* dgrad, float* dpoints, float* dtf, void* scratch, void* stream) {
+    return composed_backward<float, true>(grids, nullptr, S, tf, A, points, P, out_leaf, dval, dgrad, 0.f, dpoints, dtf, scratch,
+                                          stream, false);
+}
+
+extern "C" int pvamd_composed_query_interp_backward_f64(const pvamd_grid_t* grids, int32_t S, const double* tf, int32_t A,
+                                                        const double* points, int64_t P, const int32_t* out_leaf,
+                                                        const double* dval, const double* dgrad, double* dpoints, double* dtf,
+                                                        void* scratch, void* stream) {
+    return composed_backward<double, true>(grids, nullptr, S, tf, A, points, P, out_leaf, dval, dgrad, 0.0, dpoints, dtf, scratch,
+                                           stream, false);
 }

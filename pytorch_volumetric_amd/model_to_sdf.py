@@ -208,6 +208,7 @@ class RobotSDF(sdf.ObjectFrameSDF):
         allocation after the first call with this batch size: capturable in a hipGraph (model_to_sdf.py:82-125 as two
         or three kernels).  Needs a kinematics.Chain (on-device FK) and BOUNDING_BOX CachedSDF leaves; afterwards the object is
         configured exactly as by set_joint_configuration(joint_config)."""
+        sdf._require_nearest(self.sdf, "configure_and_query_into")
         if not hasattr(self.chain, "joint_table"):
             raise ValueError("configure_and_query_into needs the on-device forward kinematics (pytorch_volumetric_amd.kinematics.Chain)")
         M, S = len(self.joint_names), len(self.sdf_to_link_name)

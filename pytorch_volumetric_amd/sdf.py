@@ -401,6 +401,28 @@ class VoxelView:
         return self._index(points, want_valid=True)[2]
 
 
+INTERPOLATIONS = ("nearest", "trilinear")
+
+
+def _check_interpolation(value, dim):
+    if value not in INTERPOLATIONS:
+        raise ValueError(f"interpolation must be one of {INTERPOLATIONS}, got {value!r}")
+    if value == "trilinear" and dim != 3:
+        raise ValueError(f'interpolation="trilinear" needs a 3-D cache, this one is {dim}-dimensional (bilinear planar caches '
+                         "are not supported)")
+
+
+def _require_nearest(sdf, what):
+    """Entry points with nearest-voxel kernels only: a trilinear cache (or a composition over one) raises rather than being
+    answered with nearest-voxel bits."""
+    leaves = getattr(sdf, "sdfs", None)
+    for s in (leaves if leaves is not None else [sdf]):
+        mode = getattr(s, "interpolation", "nearest")
+        if mode != "nearest":
+            raise ValueError(f'{what} supports interpolation="nearest" only; this {"composition has a leaf" if leaves is not None else "cache"} '
+                             f'with interpolation="{mode}" (use __call__)')
+
+
 class CachedSDF(ObjectFrameSDF):
     """SDF by nearest-voxel lookup in a precomputed (value, gradient) grid (sdf.py:441-614).
 
@@ -410,7 +432,7 @@ class CachedSDF(ObjectFrameSDF):
     def __init__(self, object_name, resolution, range_per_dim, gt_sdf: ObjectFrameSDF,
                  out_of_bounds_strategy=OutOfBoundsStrategy.BOUNDING_BOX,
                  device="cpu", clean_cache=False,
-                 debug_check_sdf=False, cache_path="sdf_cache.pkl"):
+                 debug_check_sdf=False, cache_path="sdf_cache.pkl", interpolation="nearest"):
         """
         :param object_name: readable name; combined with resolution and range into the cache key
         :param resolution: side length of each voxel
@@ -421,7 +443,12 @@ class CachedSDF(ObjectFrameSDF):
         :param clean_cache: ignore an existing cache entry and recompute
         :param debug_check_sdf: verify the cache against gt_sdf after building / on every query
         :param cache_path: torch.save'd dict {name: (val[nx,ny,nz], grad[n,3])}, same format as the reference
+        :param interpolation: "nearest" (the reference's nearest-voxel lookup, the default) or "trilinear" (opt-in, 3-D caches
+            only: continuous value and gradient in range, differentiable w.r.t. the points; see README "Interpolated queries").
+            A query-time choice: the cache and its key do not depend on it.
         """
+        _check_interpolation(interpolation, len(range_per_dim))
+        self.interpolation = interpolation
         self.device = device
         self.out_of_bounds_strategy = out_of_bounds_strategy
         self.gt_sdf = gt_sdf
@@ -537,9 +564,11 @@ class CachedSDF(ObjectFrameSDF):
                                              _lib.ptr(scratch), _lib.stream_ptr()), "pvamd_cache_build")
         return packed
 
-    _PLAN_ATTRS = frozenset(("device", "out_of_bounds_strategy", "debug_check_sdf", "_packed", "bb"))
+    _PLAN_ATTRS = frozenset(("device", "out_of_bounds_strategy", "debug_check_sdf", "_packed", "bb", "interpolation"))
 
     def __setattr__(self, name, value):
+        if name == "interpolation":
+            _check_interpolation(value, self.__dict__.get("_dim", 3))
         if name in CachedSDF._PLAN_ATTRS:
             _lib.EPOCH[0] += 1  # call plans (this object's and those of compositions over it) are rebuilt on next use
             if name in ("bb", "_packed"):
@@ -558,7 +587,7 @@ class CachedSDF(ObjectFrameSDF):
         between two allocations.  None when this object cannot take it."""
         dev = self._packed.device
         ok = self._dim == 3 and self.out_of_bounds_strategy == OutOfBoundsStrategy.BOUNDING_BOX and \
-            not self.debug_check_sdf and _lib.same_gpu(self.device, dev)
+            not self.debug_check_sdf and self.interpolation == "nearest" and _lib.same_gpu(self.device, dev)
         plan = None
         if ok:
             desc = self._grid_desc()
@@ -606,6 +635,8 @@ class CachedSDF(ObjectFrameSDF):
         if getattr(p, "requires_grad", False) and torch.is_grad_enabled() and self._dim == 3 and \
                 self.out_of_bounds_strategy == OutOfBoundsStrategy.BOUNDING_BOX:
             from pytorch_volumetric_amd import autograd
+            if self.interpolation == "trilinear":
+                return autograd.cached_interp_query(self, p)
             return autograd.cached_query(self, p)
         # the common call of a planner's inner loop -- float32 points already contiguous on the grid's GPU -- skips every
         # conversion below: two allocations in the final shapes and one C-ABI call (~7.5 us instead of ~18 us of host time per
@@ -640,10 +671,11 @@ class CachedSDF(ObjectFrameSDF):
         lookup_gt = self.out_of_bounds_strategy == OutOfBoundsStrategy.LOOKUP_GT_SDF
         oob = torch.empty((P,), dtype=torch.uint8, device=dev) if lookup_gt else None
         desc = self._grid_desc()
-        entry = lib.pvamd_cached_query_f64 if flat.dtype == torch.float64 else lib.pvamd_cached_query
+        name = "pvamd_cached_query" if self.interpolation == "nearest" else "pvamd_cached_query_interp"
+        entry = getattr(lib, name + "_f64" if flat.dtype == torch.float64 else name)
         with _lib.on_device(dev):
             _lib.check(entry(ctypes.byref(desc), _lib.ptr(flat), P, _lib.ptr(val), _lib.ptr(grad),
-                             _lib.ptr(oob), _lib.stream_ptr()), "pvamd_cached_query")
+                             _lib.ptr(oob), _lib.stream_ptr()), name)
         if lookup_gt:
             idx = oob.nonzero().squeeze(-1)  # sdf.py:552-554: ground truth on the out-of-range subset only
             if idx.numel() > 0:
@@ -681,6 +713,7 @@ class CachedSDF(ObjectFrameSDF):
                     if rc != 0:
                         _lib.check(rc, "pvamd_cached_query")
                     return
+        _require_nearest(self, "query_into")
         if self.out_of_bounds_strategy != OutOfBoundsStrategy.BOUNDING_BOX:
             raise ValueError("query_into needs the fused BOUNDING_BOX strategy")
         if not (points.is_cuda and points.dtype == torch.float32 and points.is_contiguous()):
@@ -699,9 +732,20 @@ class CachedSDF(ObjectFrameSDF):
                        "pvamd_cached_query")
 
     def outside_surface(self, points_in_object_frame, surface_level=0):
-        """sdf.py:593-602"""
+        """sdf.py:593-602 (trilinear caches: the interpolated value > surface_level in range, True out of range)"""
         lib = _lib.load()
         flat, lead, _, _ = _lib.as_query_points(self._lift(points_in_object_frame), self._packed.device, keep_f64=True)
+        if self.interpolation == "trilinear":
+            P = flat.shape[0]
+            val = torch.empty((P,), dtype=flat.dtype, device=flat.device)
+            grad = torch.empty((P, 3), dtype=flat.dtype, device=flat.device)
+            oob = torch.empty((P,), dtype=torch.uint8, device=flat.device)
+            desc = self._grid_desc()
+            entry = lib.pvamd_cached_query_interp_f64 if flat.dtype == torch.float64 else lib.pvamd_cached_query_interp
+            with _lib.on_device(flat.device):
+                _lib.check(entry(ctypes.byref(desc), _lib.ptr(flat), P, _lib.ptr(val), _lib.ptr(grad), _lib.ptr(oob),
+                                 _lib.stream_ptr()), "pvamd_cached_query_interp")
+            return ((oob != 0) | (val > surface_level)).reshape(*lead).to(device=self.device)
         out = torch.empty((flat.shape[0],), dtype=torch.uint8, device=flat.device)
         desc = self._grid_desc()
         entry = lib.pvamd_cached_outside_f64 if flat.dtype == torch.float64 else lib.pvamd_cached_outside
@@ -872,8 +916,15 @@ class ComposedSDF(ObjectFrameSDF):
     # ---- fused path ----
     def _fusable(self):
         return len(self.sdfs) > 0 and getattr(self, "_rigid", True) and all(
-            isinstance(s, CachedSDF) and s._dim == 3 and s.out_of_bounds_strategy == OutOfBoundsStrategy.BOUNDING_BOX
-            for s in self.sdfs)
+            isinstance(s, CachedSDF) and s._dim == 3 and s.out_of_bounds_strategy == OutOfBoundsStrategy.BOUNDING_BOX and
+            s.interpolation == "nearest" for s in self.sdfs)
+
+    def _interp_fusable(self):
+        """Every leaf a 3-D BOUNDING_BOX CachedSDF with interpolation="trilinear", rigid transforms: the trilinear fused kernel
+        (pvamd_composed_query_interp).  Compositions that mix nearest and trilinear leaves take the generic path."""
+        return len(self.sdfs) > 0 and getattr(self, "_rigid", True) and all(
+            isinstance(s, CachedSDF) and s._dim == 3 and s.out_of_bounds_strategy == OutOfBoundsStrategy.BOUNDING_BOX and
+            s.interpolation == "trilinear" for s in self.sdfs)
 
     bucket_points = "auto"  # True / False / "auto": sort the query points spatially before the fused kernel (see __call__)
     group_points = "auto"   # True / False / "auto": regroup the points spatially inside chunks (pvamd_composed_query_grouped)
@@ -970,7 +1021,8 @@ class ComposedSDF(ObjectFrameSDF):
             return cached[1]
         plan = None
         if len(sdfs) > 0 and all(isinstance(s, CachedSDF) and s._dim == 3 and
-                                 s.out_of_bounds_strategy == OutOfBoundsStrategy.BOUNDING_BOX for s in sdfs):
+                                 s.out_of_bounds_strategy == OutOfBoundsStrategy.BOUNDING_BOX and
+                                 s.interpolation == "nearest" for s in sdfs):
             devs = {s._packed.device for s in sdfs}
             if len(devs) == 1:
                 dev = next(iter(devs))
@@ -1034,6 +1086,12 @@ class ComposedSDF(ObjectFrameSDF):
                 if rc != 0:
                     _lib.check(rc, "pvamd_composed_query")
                 return val, grad
+        if self._interp_fusable():
+            if (self._tf_grad or getattr(p, "requires_grad", False)) and torch.is_grad_enabled():
+                from pytorch_volumetric_amd import autograd
+                return autograd.composed_interp_query(self, p)
+            val, grad, _, _, _ = self._interp_forward(p if torch.is_tensor(p) else torch.as_tensor(p), want_leaf=False)
+            return val, grad
         S = len(self.sdfs)
         A = math.prod(self.tsf_batch) if self.tsf_batch is not None else 1
         if not torch.is_tensor(points_in_object_frame):
@@ -1086,6 +1144,42 @@ class ComposedSDF(ObjectFrameSDF):
             val, grad = val.reshape(-1), grad.reshape(-1, 3)
         return val.to(device=out_device, dtype=dtype), grad.to(device=out_device, dtype=dtype)
 
+    def _interp_forward(self, points, want_leaf):
+        """The trilinear fused query (pvamd_composed_query_interp / _f64): float64 points with the float64 widening of the stack,
+        anything else in float32.  Returns (val, grad) in the caller's shapes on the leaves' device, and the (A, P) leaf ids
+        (want_leaf), the flat points and the stack the kernel read (what the backward needs)."""
+        S = len(self.sdfs)
+        A = math.prod(self.tsf_batch) if self.tsf_batch is not None else 1
+        dev = self._owner_device()
+        f64 = points.dtype == torch.float64
+        if f64:
+            flat = points.detach().reshape(-1, 3).to(device=dev, dtype=torch.float64).contiguous()
+            tfd = self.__dict__.get("_tf_dev64")
+            if tfd is None or tfd.device != dev:
+                tfd = self._tf_dev64 = self._tf_matrix.detach().to(device=dev, dtype=torch.float64).contiguous()
+            dtype = torch.float64
+        else:
+            flat, _, dtype, _ = _lib.as_query_points(points, dev)
+            tfd = self._tf_device(dev)
+        P = flat.shape[0]
+        val = torch.empty((A, P), dtype=flat.dtype, device=dev)
+        grad = torch.empty((A, P, 3), dtype=flat.dtype, device=dev)
+        leaf = torch.empty((A, P), dtype=torch.int32, device=dev) if want_leaf else None
+        if P > 0:
+            lib = _lib.load()
+            name = "pvamd_composed_query_interp_f64" if f64 else "pvamd_composed_query_interp"
+            with _lib.on_device(dev):
+                grids = self._leaf_grids(dev)
+                _lib.check(getattr(lib, name)(_lib.ptr(grids), S, _lib.ptr(tfd), A, _lib.ptr(flat), P, _lib.ptr(val), _lib.ptr(grad),
+                                              _lib.ptr(leaf), _lib.stream_ptr()), name)
+        if self.tsf_batch is not None:
+            val = val.reshape(*self.tsf_batch, *points.shape[:-1])
+            grad = grad.reshape(*self.tsf_batch, *points.shape[:-1], 3)
+        else:
+            val, grad = val.reshape(-1), grad.reshape(-1, 3)
+        out_device = self.sdfs[0].device  # leaves return on their own device (sdf.py:546)
+        return val.to(device=out_device, dtype=dtype), grad.to(device=out_device, dtype=dtype), leaf, flat, tfd
+
     # ---- prepared point sets: a planner that queries the SAME points under many configurations, step after step ----
     def prepare_points(self, points_in_object_frame):
         """Sort a point set along the Hilbert curve ONCE and keep the order: a handle for query_prepared().  The drop-in call
@@ -1093,6 +1187,7 @@ class ComposedSDF(ObjectFrameSDF):
         re-queried per joint configuration, README.md:150-200); a planner that re-uses its query points -- a fixed workspace
         grid, a fixed set of collision spheres -- pays the sort here and, with order="sorted", nothing per call.
         `points_in_object_frame`: [...] x N x 3, any float dtype / device (computed in float32 on the leaves' GPU)."""
+        _require_nearest(self, "prepare_points")
         if not self._fusable():
             raise ValueError("prepare_points needs every leaf to be a CachedSDF with the BOUNDING_BOX strategy")
         if not torch.is_tensor(points_in_object_frame):
@@ -1117,6 +1212,7 @@ class ComposedSDF(ObjectFrameSDF):
         index): no sort and no un-permute pass -- the kernel's own output order.  Same bits, permuted."""
         if order not in ("caller", "sorted"):
             raise ValueError('order must be "caller" or "sorted"')
+        _require_nearest(self, "query_prepared")
         if not self._fusable():
             raise ValueError("query_prepared needs every leaf to be a CachedSDF with the BOUNDING_BOX strategy")
         S = len(self.sdfs)
@@ -1181,6 +1277,7 @@ class ComposedSDF(ObjectFrameSDF):
         """Fused query that leaves one (val, gx, gy, gz) record per (configuration, point): (A, P, 4) fp32 for contiguous
         fp32 (P, 3) GPU points, P a multiple of 256.  What a query sharded over GPUs gathers (one buffer instead of two,
         unpacked straight into the final layout: dist.ShardedSDF); same bits as __call__."""
+        _require_nearest(self, "query_packed")
         if not self._fusable():
             raise ValueError("query_packed needs every leaf to be a CachedSDF with the BOUNDING_BOX strategy")
         A = math.prod(self.tsf_batch) if self.tsf_batch is not None else 1
@@ -1211,6 +1308,7 @@ class ComposedSDF(ObjectFrameSDF):
         """The fused query for configurations [first, first + count) of the flattened batch only (indices past the last
         configuration repeat it): fp32 (count, P) / (count, P, 3) on the leaves' GPU.  What a query sharded over
         configurations runs on each rank (dist.ShardedSDF(shard="configs")); same bits as the rows of __call__."""
+        _require_nearest(self, "query_configs")
         if not self._fusable() or self.tsf_batch is None:
             raise ValueError("query_configs needs BOUNDING_BOX CachedSDF leaves and a configuration batch")
         S, A = len(self.sdfs), math.prod(self.tsf_batch)
@@ -1247,6 +1345,7 @@ class ComposedSDF(ObjectFrameSDF):
         the caller's fp32 (A,P) / (A,P,3) buffers (A = number of configurations, 1 without a transform batch).  Needs
         every leaf to be a BOUNDING_BOX CachedSDF.  One C-ABI call, one kernel launch on the current stream (two of each where
         the chunk-grouped kernel pays: `group_points`)."""
+        _require_nearest(self, "query_into")
         if not self._fusable():
             raise ValueError("query_into needs every leaf to be a CachedSDF with the BOUNDING_BOX strategy")
         A = math.prod(self.tsf_batch) if self.tsf_batch is not None else 1

@@ -38,6 +38,9 @@ def warm_up(device=None, freeze_gc=True):
         mesh(many)                                            # mesh.hip (main launch), sort.hip (counting sort)
         cached = pv.CachedSDF("warm_up", 0.02, obj.bounding_box(padding=0.06), mesh, device=dev, cache_path=None)  # cache build
         cached(few); cached(many); cached.outside_surface(few); cached(few.double())                                 # cached.hip
+        cached.interpolation = "trilinear"
+        cached(few)                                           # interp.hip
+        cached.interpolation = "nearest"
         rot = tf.Transform3d(matrix=torch.eye(4).repeat(6, 1, 1))
         comp = pv.ComposedSDF([cached, cached], rot)
         comp.set_transforms(rot, batch_dim=(3,))
