@@ -9,7 +9,6 @@ chamfer_partial_sums) route here only when grad mode is on and an input requires
 Double backward is not supported: every backward is once_differentiable, so create_graph=True raises.
 """
 import ctypes
-import math
 
 import torch
 from torch.autograd.function import once_differentiable
@@ -18,6 +17,8 @@ from pytorch_volumetric_amd import _lib
 from pytorch_volumetric_amd import transforms as tf
 
 MAX_LEAVES = 64  # pvamd_composed_query_backward: 1 <= S <= 64
+# the backward entry point ("cached" / "composed") of each leaf mode; "_f64" is appended for float64
+_BACKWARD = {"nearest": "pvamd_{}_query_backward", "trilinear": "pvamd_{}_query_interp_backward"}
 
 
 def _scratch(S, A, P, f64, dev):
@@ -50,7 +51,8 @@ class CachedQuery(torch.autograd.Function):
             flat = flat.clone()
         ctx.cached, ctx.flat = cached, flat
         ctx.pshape, ctx.pdtype, ctx.pdevice = points.shape, points.dtype, points.device
-        ctx.backward_entry = "pvamd_cached_query_backward"
+        # interpolation="trilinear": in range the exact derivative of the interpolated value and gradient w.r.t. the point
+        ctx.backward_entry = _BACKWARD[cached.interpolation].format("cached")
         return val, grad
 
     @staticmethod
@@ -74,73 +76,26 @@ def cached_query(cached, points):
     return CachedQuery.apply(cached, points)
 
 
-class CachedInterpQuery(CachedQuery):
-    """CachedSDF.__call__ with interpolation="trilinear": the forward is the cache's own (pvamd_cached_query_interp), the backward
-    pvamd_cached_query_interp_backward -- in range the exact derivative of the interpolated value and gradient w.r.t. the point."""
-
-    @staticmethod
-    def forward(ctx, cached, points):
-        out = CachedQuery.forward(ctx, cached, points)
-        ctx.backward_entry = "pvamd_cached_query_interp_backward"
-        return out
-
-
-def cached_interp_query(cached, points):
-    return CachedInterpQuery.apply(cached, points)
-
-
 # ---------------------------------------------------------------- ComposedSDF.__call__ (sdf.py:392-433)
 class ComposedQuery(torch.autograd.Function):
-    """Forward: pvamd_composed_query (or _f64) with out_leaf -- the one dispatch pinned for a grad-requiring call (every
-    dispatch gives the same bits; the bucketed one cannot emit leaf ids).  Saved: the points, the detached stack, the leaf id
-    per pair, and the inputs themselves for torch's in-place check."""
+    """Forward: ComposedSDF._fused_forward with out_leaf -- the one dispatch pinned for a grad-requiring call (every dispatch
+    gives the same bits; the bucketed one cannot emit leaf ids).  Saved: the points, the detached stack, the leaf id per pair,
+    and the inputs themselves for torch's in-place check."""
 
     @staticmethod
-    def forward(ctx, composed, points, tfm):
+    def forward(ctx, composed, points, tfm, mode):
         ctx.set_materialize_grads(False)
-        S = len(composed.sdfs)
-        A = math.prod(composed.tsf_batch) if composed.tsf_batch is not None else 1
         dev = composed._owner_device()
-        lib = _lib.load()
-        f64 = points.dtype == torch.float64
-        if f64:
-            flat = points.detach().reshape(-1, 3).to(device=dev, dtype=torch.float64).contiguous()
-            tfd = tfm.detach().to(device=dev, dtype=torch.float64).contiguous()
-            dtype = torch.float64
-        else:
-            flat, _, dtype, _ = _lib.as_query_points(points, dev)
-            tfd = composed._tf_device(dev)
-        P = flat.shape[0]
-        val = torch.empty((A, P), dtype=flat.dtype, device=dev)
-        grad = torch.empty((A, P, 3), dtype=flat.dtype, device=dev)
-        leaf = torch.empty((A, P), dtype=torch.int32, device=dev)
-        if P > 0:
-            with _lib.on_device(dev):
-                grids = composed._leaf_grids(dev)
-                if f64:
-                    _lib.check(lib.pvamd_composed_query_f64(_lib.ptr(grids), S, _lib.ptr(tfd), A, _lib.ptr(flat), P, _lib.ptr(val),
-                                                            _lib.ptr(grad), _lib.ptr(leaf), _lib.stream_ptr()),
-                               "pvamd_composed_query_f64")
-                else:
-                    _lib.check(lib.pvamd_composed_query(_lib.ptr(grids), S, _lib.ptr(tfd), A, _lib.ptr(flat), P, _lib.ptr(val),
-                                                        _lib.ptr(grad), _lib.ptr(leaf), composed._direct_flags(), _lib.stream_ptr()),
-                               "pvamd_composed_query")
+        val, grad, leaf, flat, tfd = composed._fused_forward(points, mode, want_leaf=True)
         ctx.composed, ctx.flat, ctx.tfd, ctx.leaf, ctx.grids = composed, flat, tfd, leaf, composed._leaf_grids(dev)
         # flat / tfd may alias the inputs (float32 contiguous device tensors are used where they are): saving the inputs lets
         # torch raise on an in-place write between forward and backward, as it does for the reference's matmul (sdf.py:399)
         ctx.save_for_backward(points, tfm)
-        ctx.S, ctx.A = S, A
-        ctx.backward_entry = "pvamd_composed_query_backward"
+        ctx.S, ctx.A = len(composed.sdfs), leaf.shape[0]
+        ctx.backward_entry = _BACKWARD[mode].format("composed")
         ctx.pshape, ctx.pdtype, ctx.pdevice = points.shape, points.dtype, points.device
         ctx.tdtype, ctx.tdevice = tfm.dtype, tfm.device
-        pts_shape = points.shape
-        if composed.tsf_batch is not None:
-            val = val.reshape(*composed.tsf_batch, *pts_shape[:-1])
-            grad = grad.reshape(*composed.tsf_batch, *pts_shape[:-1], 3)
-        else:
-            val, grad = val.reshape(-1), grad.reshape(-1, 3)
-        out_device = composed.sdfs[0].device  # leaves return on their own device (sdf.py:546)
-        return val.to(device=out_device, dtype=dtype), grad.to(device=out_device, dtype=dtype)
+        return val, grad
 
     @staticmethod
     @once_differentiable
@@ -163,42 +118,15 @@ class ComposedQuery(torch.autograd.Function):
                        ctx.backward_entry)
         gp = dpoints.reshape(ctx.pshape).to(device=ctx.pdevice, dtype=ctx.pdtype) if need_p else None
         gt = dtf.to(device=ctx.tdevice, dtype=ctx.tdtype) if need_tf else None
-        return None, gp, gt
+        return None, gp, gt, None
 
 
-def composed_query(composed, points):
+def composed_query(composed, points, mode):
     if len(composed.sdfs) > MAX_LEAVES:
         raise _lib.PvamdError(f"gradients through a composition need at most {MAX_LEAVES} leaves, this one has {len(composed.sdfs)}")
     if not torch.is_tensor(points):
         points = torch.as_tensor(points)
-    return ComposedQuery.apply(composed, points, composed._tf_matrix)
-
-
-class ComposedInterpQuery(ComposedQuery):
-    """ComposedSDF.__call__ over trilinear leaves: forward pvamd_composed_query_interp (or _f64) with out_leaf, backward
-    pvamd_composed_query_interp_backward -- the same saved state, reductions and conventions as ComposedQuery."""
-
-    @staticmethod
-    def forward(ctx, composed, points, tfm):
-        ctx.set_materialize_grads(False)
-        dev = composed._owner_device()
-        val, grad, leaf, flat, tfd = composed._interp_forward(points, want_leaf=True)
-        ctx.composed, ctx.flat, ctx.tfd, ctx.leaf, ctx.grids = composed, flat, tfd, leaf, composed._leaf_grids(dev)
-        # flat / tfd may alias the inputs: saving them lets torch raise on an in-place write between forward and backward
-        ctx.save_for_backward(points, tfm)
-        ctx.S, ctx.A = len(composed.sdfs), (math.prod(composed.tsf_batch) if composed.tsf_batch is not None else 1)
-        ctx.backward_entry = "pvamd_composed_query_interp_backward"
-        ctx.pshape, ctx.pdtype, ctx.pdevice = points.shape, points.dtype, points.device
-        ctx.tdtype, ctx.tdevice = tfm.dtype, tfm.device
-        return val, grad
-
-
-def composed_interp_query(composed, points):
-    if len(composed.sdfs) > MAX_LEAVES:
-        raise _lib.PvamdError(f"gradients through a composition need at most {MAX_LEAVES} leaves, this one has {len(composed.sdfs)}")
-    if not torch.is_tensor(points):
-        points = torch.as_tensor(points)
-    return ComposedInterpQuery.apply(composed, points, composed._tf_matrix)
+    return ComposedQuery.apply(composed, points, composed._tf_matrix, mode)
 
 
 # ---------------------------------------------------------------- RobotSDF.set_joint_configuration (model_to_sdf.py:82-115)

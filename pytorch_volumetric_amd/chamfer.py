@@ -82,7 +82,7 @@ def chamfer_partial_sums(W, points, obj_factory, obj_sdf, scale):
     if isinstance(obj_sdf, CachedSDF) and obj_sdf.interpolation != "nearest" and torch.is_grad_enabled() and \
             (W.requires_grad or getattr(points, "requires_grad", False)):
         # a trilinear grid (no fused chamfer kernel): the arbitrary-SDF branch below with the graph kept -- transform in torch,
-        # query through the cache's autograd Function (autograd.CachedInterpQuery), reduce in torch
+        # query through the cache's autograd Function (autograd.CachedQuery), reduce in torch
         Wg = W.to(device=dev, dtype=torch.float32)
         pg = torch.as_tensor(points).reshape(-1, 3).to(device=dev, dtype=torch.float32)
         x = pg.unsqueeze(0) @ Wg[:, :3, :3].transpose(-1, -2) + Wg[:, None, :3, 3]

@@ -268,24 +268,7 @@ __global__ __launch_bounds__(256) void voxel_index_kernel(const pvamd_grid_t g, 
     }
 }
 
-// ---- float64 query points (sdf.py:545-547: output dtype = query dtype; torch promotion makes the index arithmetic,
-// the range test and the BOUNDING_BOX branch float64).  One point per lane; 24 B read + 32 B written per point. ----
-__global__ __launch_bounds__(256) void cached_query_f64_kernel(const pvamd_grid_t g, const double* __restrict__ pts,
-                                                                int64_t P, double* __restrict__ val,
-                                                                double* __restrict__ grad, uint8_t* __restrict__ oob) {
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += stride) {
-        const double p[3] = {pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]};
-        double v, gx, gy, gz;
-        const bool valid = cached_lookup_f64(g, p, v, gx, gy, gz);
-        val[i] = v;
-        grad[3 * i] = gx;
-        grad[3 * i + 1] = gy;
-        grad[3 * i + 2] = gz;
-        if (oob) oob[i] = valid ? 0 : 1;
-    }
-}
-
+// ---- float64 query points (the float64 forward is lane_query.hip's) ----
 __global__ __launch_bounds__(256) void cached_outside_f64_kernel(const pvamd_grid_t g, const double* __restrict__ pts,
                                                                   int64_t P, double level, uint8_t* __restrict__ out) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -435,18 +418,6 @@ extern "C" int pvamd_voxel_index(const pvamd_grid_t* grid, const float* points, 
     const dim3 grid_dim(stream_grid(P, 256)), block(256);
     if (grid->index_f64) hipLaunchKernelGGL((voxel_index_kernel<true>), grid_dim, block, 0, (hipStream_t)stream, *grid, points, P, out_key, out_flat, out_valid);
     else hipLaunchKernelGGL((voxel_index_kernel<false>), grid_dim, block, 0, (hipStream_t)stream, *grid, points, P, out_key, out_flat, out_valid);
-    return (int)hipGetLastError();
-}
-
-extern "C" int pvamd_cached_query_f64(const pvamd_grid_t* grid, const double* points, int64_t P, double* out_val,
-                                      double* out_grad, uint8_t* out_oob, void* stream) {
-    if (P < 0) return PVAMD_E_SHAPE;
-    if (P == 0) return 0;
-    if (!grid || !out_val || !out_grad || !points) return PVAMD_E_NULL;
-    if (int e = check_grid(*grid)) return e;
-    if (!aligned_to(points, 8) || !aligned_to(out_val, 8) || !aligned_to(out_grad, 8)) return PVAMD_E_ALIGN;
-    hipLaunchKernelGGL(cached_query_f64_kernel, dim3(stream_grid(P, 256)), dim3(256), 0, (hipStream_t)stream, *grid, points,
-                       P, out_val, out_grad, out_oob);
     return (int)hipGetLastError();
 }
 

@@ -318,36 +318,68 @@ PVAMD_DEV int clamped_flat(const pvamd_grid_t& g, const long long key[3]) {
     return (kx * g.shape[1] + ky) * g.shape[2] + kz;
 }
 
-// (val, gx, gy, gz) of one float64 point: the cached record widened exactly, or the bounding-box statements in float64
-PVAMD_DEV bool cached_lookup_f64(const pvamd_grid_t& g, const double p[3], double& v, double& gx, double& gy, double& gz) {
-    long long key[3];
-    const bool valid = voxel_key_f64(g, p, key);
-    v = gx = gy = gz = 0.0;
-    if (valid) {
-        const float4 r = load_record(g.vox, clamped_flat(g, key));
-        v = (double)r.x; gx = (double)r.y; gy = (double)r.z; gz = (double)r.w;
-    } else if (g.oob_mode == PVAMD_OOB_BOUNDING_BOX) {
-        double t[3];
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            double lo = g.dbb_min[d] - p[d];
-            const bool lo_active = lo > 0.0;
-            lo = lo_active ? lo : 0.0;
-            double hi = p[d] - g.dbb_max[d];
-            hi = (hi > 0.0) ? hi : 0.0;
-            const double s = lo + hi;
-            t[d] = lo_active ? -s : s;
-        }
-        v = __builtin_sqrt(__builtin_fma(t[2], t[2], __builtin_fma(t[1], t[1], t[0] * t[0])));
-        gx = t[0] / v; gy = t[1] / v; gz = t[2] / v;
-    }
-    return valid;
-}
-
 // x' = M p for a row-major 4x4 (column-vector convention), k-ordered fma chain -- the rounding sequence of an
 // f32 MFMA / a bmm k-loop: ((m0*px (+) m1*py) (+) m2*pz) + m3.
 PVAMD_DEV float affine_row(float m0, float m1, float m2, float m3, float px, float py, float pz) {
     return add_rn(fmaf(m2, pz, fmaf(m1, py, mul_rn(m0, px))), m3);
 }
+
+// ---- the leaf-frame statements per precision, shared by the forward and backward kernels: x = L p + t, the range test, the
+// nearest record's gradient, the unnormalised bounding-box vector and its norm (sdf.py:559-568), the division ----
+template <typename T> struct LeafOps;
+
+template <> struct LeafOps<float> {
+    static PVAMD_DEV void xform(const float* M, const float p[3], float x[3]) {
+        x[0] = affine_row(M[0], M[1], M[2], M[3], p[0], p[1], p[2]);
+        x[1] = affine_row(M[4], M[5], M[6], M[7], p[0], p[1], p[2]);
+        x[2] = affine_row(M[8], M[9], M[10], M[11], p[0], p[1], p[2]);
+    }
+    static PVAMD_DEV bool inside(const pvamd_grid_t& g, const float x[3]) { return in_range(g, x[0], x[1], x[2]); }
+    static PVAMD_DEV void record_grad(const pvamd_grid_t& g, const float x[3], float gr[3]) {
+        int flat;
+        if (g.index_f64) voxel_flat<true>(g, x[0], x[1], x[2], flat);
+        else voxel_flat<false>(g, x[0], x[1], x[2], flat);
+        const float4 r = load_record(g.vox, flat);
+        gr[0] = r.y; gr[1] = r.z; gr[2] = r.w;
+    }
+    static PVAMD_DEV float box(const pvamd_grid_t& g, const float x[3], float t[3]) {
+        return bounding_box_vector(g, x[0], x[1], x[2], t);
+    }
+    static PVAMD_DEV float div(float a, float b) { return div_rn(a, b); }
+};
+
+// float64 query points: the transform as a k-ordered fma chain in float64, the range test voxel_key_f64, the bounding box in
+// float64 against dbb_min / dbb_max (sdf.py:556-557 casts the box to the query dtype)
+template <> struct LeafOps<double> {
+    static PVAMD_DEV void xform(const double* M, const double p[3], double x[3]) {
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+            x[r] = __builtin_fma(M[4 * r + 2], p[2], __builtin_fma(M[4 * r + 1], p[1], M[4 * r] * p[0])) + M[4 * r + 3];
+    }
+    static PVAMD_DEV bool inside(const pvamd_grid_t& g, const double x[3]) {
+        long long key[3];
+        return voxel_key_f64(g, x, key);
+    }
+    static PVAMD_DEV void record_grad(const pvamd_grid_t& g, const double x[3], double gr[3]) {
+        long long key[3];
+        voxel_key_f64(g, x, key);
+        const float4 r = load_record(g.vox, clamped_flat(g, key));
+        gr[0] = (double)r.y; gr[1] = (double)r.z; gr[2] = (double)r.w;
+    }
+    static PVAMD_DEV double box(const pvamd_grid_t& g, const double x[3], double t[3]) {
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            double lo = g.dbb_min[d] - x[d];
+            const bool lo_active = lo > 0.0;
+            lo = lo_active ? lo : 0.0;
+            double hi = x[d] - g.dbb_max[d];
+            hi = (hi > 0.0) ? hi : 0.0;
+            const double s = lo + hi;
+            t[d] = lo_active ? -s : s;
+        }
+        return __builtin_sqrt(__builtin_fma(t[2], t[2], __builtin_fma(t[1], t[1], t[0] * t[0])));
+    }
+    static PVAMD_DEV double div(double a, double b) { return a / b; }
+};
 
 }  // namespace pvamd

@@ -1,5 +1,5 @@
 // Trilinear interpolation of the packed (val, gx, gy, gz) records: the per-leaf statements shared by the interpolated
-// forward kernels (interp.hip) and their backward (backward.hip).  The arithmetic contract is include/pvamd.h's
+// forward kernels (lane_query.hip) and their backward (backward.hip).  The arithmetic contract is include/pvamd.h's
 // "Interpolated queries"; tests/interp_ref.c states the same sequence on the CPU.
 //   per axis d:  s = (x_d - min_d) / res_d                   IEEE subtraction, then IEEE division, in the query dtype
 //                c = s < 0 ? 0 : (s > n_d - 1 ? n_d - 1 : s)  clamped_d = (c != s)

@@ -635,8 +635,6 @@ class CachedSDF(ObjectFrameSDF):
         if getattr(p, "requires_grad", False) and torch.is_grad_enabled() and self._dim == 3 and \
                 self.out_of_bounds_strategy == OutOfBoundsStrategy.BOUNDING_BOX:
             from pytorch_volumetric_amd import autograd
-            if self.interpolation == "trilinear":
-                return autograd.cached_interp_query(self, p)
             return autograd.cached_query(self, p)
         # the common call of a planner's inner loop -- float32 points already contiguous on the grid's GPU -- skips every
         # conversion below: two allocations in the final shapes and one C-ABI call (~7.5 us instead of ~18 us of host time per
@@ -659,23 +657,13 @@ class CachedSDF(ObjectFrameSDF):
             if rc != 0:
                 _lib.check(rc, "pvamd_cached_query")
             return val, grad
-        lib = _lib.load()
         # the launch happens on the GPU that holds the grid, whatever device is current in the calling code
         # float64 points are looked up in float64 (index arithmetic, range test and bounding-box branch all promote to
         # the query dtype in the reference: sdf.py:537-540,545-547,556-571); everything else is computed in float32
         flat, lead, dtype, _ = _lib.as_query_points(self._lift(points_in_object_frame), self._packed.device, keep_f64=True)
-        P = flat.shape[0]
         dev = flat.device
-        val = torch.empty((P,), dtype=flat.dtype, device=dev)
-        grad = torch.empty((P, 3), dtype=flat.dtype, device=dev)
         lookup_gt = self.out_of_bounds_strategy == OutOfBoundsStrategy.LOOKUP_GT_SDF
-        oob = torch.empty((P,), dtype=torch.uint8, device=dev) if lookup_gt else None
-        desc = self._grid_desc()
-        name = "pvamd_cached_query" if self.interpolation == "nearest" else "pvamd_cached_query_interp"
-        entry = getattr(lib, name + "_f64" if flat.dtype == torch.float64 else name)
-        with _lib.on_device(dev):
-            _lib.check(entry(ctypes.byref(desc), _lib.ptr(flat), P, _lib.ptr(val), _lib.ptr(grad),
-                             _lib.ptr(oob), _lib.stream_ptr()), name)
+        val, grad, oob = self._forward(flat, want_oob=lookup_gt)
         if lookup_gt:
             idx = oob.nonzero().squeeze(-1)  # sdf.py:552-554: ground truth on the out-of-range subset only
             if idx.numel() > 0:
@@ -731,20 +719,27 @@ class CachedSDF(ObjectFrameSDF):
                                                       _lib.ptr(out_val), _lib.ptr(out_grad), None, _lib.stream_ptr()),
                        "pvamd_cached_query")
 
+    def _forward(self, flat, want_oob):
+        """(val, grad, oob) of contiguous (P, 3) points on the grid's GPU (float64 stays float64) by this cache's interpolation:
+        one launch; oob (uint8, 1 = out of range) only with want_oob, None otherwise."""
+        P = flat.shape[0]
+        val = torch.empty((P,), dtype=flat.dtype, device=flat.device)
+        grad = torch.empty((P, 3), dtype=flat.dtype, device=flat.device)
+        oob = torch.empty((P,), dtype=torch.uint8, device=flat.device) if want_oob else None
+        desc = self._grid_desc()
+        name = "pvamd_cached_query" if self.interpolation == "nearest" else "pvamd_cached_query_interp"
+        entry = getattr(_lib.load(), name + "_f64" if flat.dtype == torch.float64 else name)
+        with _lib.on_device(flat.device):
+            _lib.check(entry(ctypes.byref(desc), _lib.ptr(flat), P, _lib.ptr(val), _lib.ptr(grad), _lib.ptr(oob), _lib.stream_ptr()),
+                       name)
+        return val, grad, oob
+
     def outside_surface(self, points_in_object_frame, surface_level=0):
         """sdf.py:593-602 (trilinear caches: the interpolated value > surface_level in range, True out of range)"""
         lib = _lib.load()
         flat, lead, _, _ = _lib.as_query_points(self._lift(points_in_object_frame), self._packed.device, keep_f64=True)
         if self.interpolation == "trilinear":
-            P = flat.shape[0]
-            val = torch.empty((P,), dtype=flat.dtype, device=flat.device)
-            grad = torch.empty((P, 3), dtype=flat.dtype, device=flat.device)
-            oob = torch.empty((P,), dtype=torch.uint8, device=flat.device)
-            desc = self._grid_desc()
-            entry = lib.pvamd_cached_query_interp_f64 if flat.dtype == torch.float64 else lib.pvamd_cached_query_interp
-            with _lib.on_device(flat.device):
-                _lib.check(entry(ctypes.byref(desc), _lib.ptr(flat), P, _lib.ptr(val), _lib.ptr(grad), _lib.ptr(oob),
-                                 _lib.stream_ptr()), "pvamd_cached_query_interp")
+            val, _, oob = self._forward(flat, want_oob=True)
             return ((oob != 0) | (val > surface_level)).reshape(*lead).to(device=self.device)
         out = torch.empty((flat.shape[0],), dtype=torch.uint8, device=flat.device)
         desc = self._grid_desc()
@@ -914,17 +909,18 @@ class ComposedSDF(ObjectFrameSDF):
         return torch.stack((bounds.amin(dim=dims), bounds.amax(dim=dims)), dim=-1)
 
     # ---- fused path ----
-    def _fusable(self):
-        return len(self.sdfs) > 0 and getattr(self, "_rigid", True) and all(
-            isinstance(s, CachedSDF) and s._dim == 3 and s.out_of_bounds_strategy == OutOfBoundsStrategy.BOUNDING_BOX and
-            s.interpolation == "nearest" for s in self.sdfs)
+    def _fused_mode(self):
+        """The leaf mode of the fused kernels ("nearest" / "trilinear") when every leaf is a 3-D BOUNDING_BOX CachedSDF with that
+        interpolation and the transforms are rigid; None otherwise (compositions that mix the modes take the generic path)."""
+        if not self.sdfs or not getattr(self, "_rigid", True):
+            return None
+        modes = {s.interpolation if isinstance(s, CachedSDF) and s._dim == 3 and
+                 s.out_of_bounds_strategy == OutOfBoundsStrategy.BOUNDING_BOX else None for s in self.sdfs}
+        return modes.pop() if len(modes) == 1 else None
 
-    def _interp_fusable(self):
-        """Every leaf a 3-D BOUNDING_BOX CachedSDF with interpolation="trilinear", rigid transforms: the trilinear fused kernel
-        (pvamd_composed_query_interp).  Compositions that mix nearest and trilinear leaves take the generic path."""
-        return len(self.sdfs) > 0 and getattr(self, "_rigid", True) and all(
-            isinstance(s, CachedSDF) and s._dim == 3 and s.out_of_bounds_strategy == OutOfBoundsStrategy.BOUNDING_BOX and
-            s.interpolation == "trilinear" for s in self.sdfs)
+    def _fusable(self):
+        """The nearest fused kernels serve this composition (what the nearest-only entry points and dist.ShardedSDF ask)."""
+        return self._fused_mode() == "nearest"
 
     bucket_points = "auto"  # True / False / "auto": sort the query points spatially before the fused kernel (see __call__)
     group_points = "auto"   # True / False / "auto": regroup the points spatially inside chunks (pvamd_composed_query_grouped)
@@ -1040,9 +1036,11 @@ class ComposedSDF(ObjectFrameSDF):
         reference -- FLAT (P,) / (P, 3) without one."""
         p = points_in_object_frame
         # gradients (autograd.py): a flag stored by set_transforms and one attribute read of the points in front of the fast paths
-        if (self._tf_grad or getattr(p, "requires_grad", False)) and torch.is_grad_enabled() and self._fusable():
-            from pytorch_volumetric_amd import autograd
-            return autograd.composed_query(self, p)
+        if (self._tf_grad or getattr(p, "requires_grad", False)) and torch.is_grad_enabled():
+            mode = self._fused_mode()
+            if mode is not None:
+                from pytorch_volumetric_amd import autograd
+                return autograd.composed_query(self, p, mode)
         plan = self._call_plan()
         # float32 points already contiguous on the leaves' GPU, fused leaves, rigid transforms, no sort wanted: two
         # allocations in the final shapes around one C-ABI call (RobotSDF.__call__ in a planner's loop)
@@ -1086,21 +1084,17 @@ class ComposedSDF(ObjectFrameSDF):
                 if rc != 0:
                     _lib.check(rc, "pvamd_composed_query")
                 return val, grad
-        if self._interp_fusable():
-            if (self._tf_grad or getattr(p, "requires_grad", False)) and torch.is_grad_enabled():
-                from pytorch_volumetric_amd import autograd
-                return autograd.composed_interp_query(self, p)
-            val, grad, _, _, _ = self._interp_forward(p if torch.is_tensor(p) else torch.as_tensor(p), want_leaf=False)
+        mode = self._fused_mode()
+        if not torch.is_tensor(points_in_object_frame):
+            points_in_object_frame = torch.as_tensor(points_in_object_frame)
+        if mode == "trilinear" or (mode == "nearest" and points_in_object_frame.dtype == torch.float64):
+            val, grad, _, _, _ = self._fused_forward(points_in_object_frame, mode)
             return val, grad
         S = len(self.sdfs)
         A = math.prod(self.tsf_batch) if self.tsf_batch is not None else 1
-        if not torch.is_tensor(points_in_object_frame):
-            points_in_object_frame = torch.as_tensor(points_in_object_frame)
         pts_shape = points_in_object_frame.shape
         out_device = points_in_object_frame.device
-        fused = self._fusable()
-        if fused and points_in_object_frame.dtype == torch.float64:
-            return self._call_f64(points_in_object_frame, S, A)
+        fused = mode == "nearest"
         if not fused and points_in_object_frame.dtype == torch.float64:
             return self._generic_f64(points_in_object_frame, S, A)
         flat, _, dtype, _ = _lib.as_query_points(points_in_object_frame, self._owner_device() if fused else None)
@@ -1144,34 +1138,42 @@ class ComposedSDF(ObjectFrameSDF):
             val, grad = val.reshape(-1), grad.reshape(-1, 3)
         return val.to(device=out_device, dtype=dtype), grad.to(device=out_device, dtype=dtype)
 
-    def _interp_forward(self, points, want_leaf):
-        """The trilinear fused query (pvamd_composed_query_interp / _f64): float64 points with the float64 widening of the stack,
-        anything else in float32.  Returns (val, grad) in the caller's shapes on the leaves' device, and the (A, P) leaf ids
-        (want_leaf), the flat points and the stack the kernel read (what the backward needs)."""
+    _FUSED_ENTRIES = {("nearest", False): "pvamd_composed_query", ("nearest", True): "pvamd_composed_query_f64",
+                      ("trilinear", False): "pvamd_composed_query_interp", ("trilinear", True): "pvamd_composed_query_interp_f64"}
+
+    def _fused_forward(self, points, mode, want_leaf=False, configs=None):
+        """One launch of the fused kernel of leaf mode `mode` over all the points, without sorting or regrouping them: float64
+        points with the float64 widening of the stack (sdf.py:395-431 over sdf.py:545-547; the reference's own bmm would refuse
+        the mixed dtypes), anything else in float32.  Returns (val, grad) in the caller's shapes on the leaves' device, the (A, P)
+        leaf ids (want_leaf), the flat points and the stack the kernel read (what the backward needs).  `configs` (a device index
+        tensor into the flattened batch): those configurations only, (count, P) / (count, P, 3) left on the leaves' GPU."""
         S = len(self.sdfs)
         A = math.prod(self.tsf_batch) if self.tsf_batch is not None else 1
         dev = self._owner_device()
         f64 = points.dtype == torch.float64
         if f64:
-            flat = points.detach().reshape(-1, 3).to(device=dev, dtype=torch.float64).contiguous()
+            flat, dtype = points.detach().reshape(-1, 3).to(device=dev, dtype=torch.float64).contiguous(), torch.float64
             tfd = self.__dict__.get("_tf_dev64")
             if tfd is None or tfd.device != dev:
                 tfd = self._tf_dev64 = self._tf_matrix.detach().to(device=dev, dtype=torch.float64).contiguous()
-            dtype = torch.float64
         else:
             flat, _, dtype, _ = _lib.as_query_points(points, dev)
             tfd = self._tf_device(dev)
+        if configs is not None:
+            tfd, A = tfd.reshape(S, A, 4, 4)[:, configs].contiguous(), configs.numel()
         P = flat.shape[0]
         val = torch.empty((A, P), dtype=flat.dtype, device=dev)
         grad = torch.empty((A, P, 3), dtype=flat.dtype, device=dev)
         leaf = torch.empty((A, P), dtype=torch.int32, device=dev) if want_leaf else None
         if P > 0:
-            lib = _lib.load()
-            name = "pvamd_composed_query_interp_f64" if f64 else "pvamd_composed_query_interp"
+            name = self._FUSED_ENTRIES[mode, f64]
             with _lib.on_device(dev):
                 grids = self._leaf_grids(dev)
-                _lib.check(getattr(lib, name)(_lib.ptr(grids), S, _lib.ptr(tfd), A, _lib.ptr(flat), P, _lib.ptr(val), _lib.ptr(grad),
-                                              _lib.ptr(leaf), _lib.stream_ptr()), name)
+                flags = (self._direct_flags(),) if name == "pvamd_composed_query" else ()
+                _lib.check(getattr(_lib.load(), name)(_lib.ptr(grids), S, _lib.ptr(tfd), A, _lib.ptr(flat), P, _lib.ptr(val),
+                                                      _lib.ptr(grad), _lib.ptr(leaf), *flags, _lib.stream_ptr()), name)
+        if configs is not None:
+            return val, grad, leaf, flat, tfd
         if self.tsf_batch is not None:
             val = val.reshape(*self.tsf_batch, *points.shape[:-1])
             grad = grad.reshape(*self.tsf_batch, *points.shape[:-1], 3)
@@ -1179,6 +1181,10 @@ class ComposedSDF(ObjectFrameSDF):
             val, grad = val.reshape(-1), grad.reshape(-1, 3)
         out_device = self.sdfs[0].device  # leaves return on their own device (sdf.py:546)
         return val.to(device=out_device, dtype=dtype), grad.to(device=out_device, dtype=dtype), leaf, flat, tfd
+
+    def _interp_forward(self, points, want_leaf):
+        """_fused_forward of a trilinear composition (the leaf ids the interpolation tests compare)."""
+        return self._fused_forward(points, "trilinear", want_leaf=want_leaf)
 
     # ---- prepared point sets: a planner that queries the SAME points under many configurations, step after step ----
     def prepare_points(self, points_in_object_frame):
@@ -1248,31 +1254,6 @@ class ComposedSDF(ObjectFrameSDF):
             val, grad = val.reshape(-1), grad.reshape(-1, 3)  # like __call__: flat without a transform batch (sdf.py:433)
         return val.to(device=out_device, dtype=prepared.dtype), grad.to(device=out_device, dtype=prepared.dtype)
 
-    def _call_f64(self, points, S, A):
-        """float64 query points: transform, lookups and gradient rotation in float64 (`pvamd_composed_query_f64`), results
-        in float64 -- the reference's output dtype is the query dtype (sdf.py:395-431 over sdf.py:545-547).  A float32
-        transform stack is widened exactly (the reference's own bmm would refuse the mixed dtypes)."""
-        dev = self._owner_device()
-        flat = points.detach().reshape(-1, 3).to(device=dev, dtype=torch.float64).contiguous()
-        P = flat.shape[0]
-        tf64 = self.__dict__.get("_tf_dev64")
-        if tf64 is None or tf64.device != dev:
-            tf64 = self._tf_dev64 = self._tf_matrix.detach().to(device=dev, dtype=torch.float64).contiguous()
-        val = torch.empty((A, P), dtype=torch.float64, device=dev)
-        grad = torch.empty((A, P, 3), dtype=torch.float64, device=dev)
-        with _lib.on_device(dev):
-            grids = self._leaf_grids(dev)
-            _lib.check(_lib.load().pvamd_composed_query_f64(_lib.ptr(grids), S, _lib.ptr(tf64), A, _lib.ptr(flat), P,
-                                                            _lib.ptr(val), _lib.ptr(grad), None, _lib.stream_ptr()),
-                       "pvamd_composed_query_f64")
-        out_device = self.sdfs[0].device
-        if self.tsf_batch is not None:
-            val = val.reshape(*self.tsf_batch, *points.shape[:-1])
-            grad = grad.reshape(*self.tsf_batch, *points.shape[:-1], 3)
-        else:
-            val, grad = val.reshape(-1), grad.reshape(-1, 3)
-        return val.to(device=out_device), grad.to(device=out_device)
-
     def query_packed(self, points, out=None):
         """Fused query that leaves one (val, gx, gy, gz) record per (configuration, point): (A, P, 4) fp32 for contiguous
         fp32 (P, 3) GPU points, P a multiple of 256.  What a query sharded over GPUs gathers (one buffer instead of two,
@@ -1315,18 +1296,8 @@ class ComposedSDF(ObjectFrameSDF):
         dev = self._owner_device()
         pick = torch.arange(first, first + count, device=dev).clamp_max(A - 1)
         if torch.is_tensor(points) and points.dtype == torch.float64:
-            # float64 query points stay float64 (sdf.py:395-431 over sdf.py:545-547), as in __call__ / _call_f64
-            flat = points.detach().reshape(-1, 3).to(device=dev, dtype=torch.float64).contiguous()
-            P = flat.shape[0]
-            sub = self._tf_matrix.to(device=dev, dtype=torch.float64).reshape(S, A, 4, 4)[:, pick].contiguous()
-            val = torch.empty((count, P), dtype=torch.float64, device=dev)
-            grad = torch.empty((count, P, 3), dtype=torch.float64, device=dev)
-            if P > 0:
-                with _lib.on_device(dev):
-                    grids = self._leaf_grids(dev)
-                    _lib.check(_lib.load().pvamd_composed_query_f64(_lib.ptr(grids), S, _lib.ptr(sub), count, _lib.ptr(flat), P,
-                                                                    _lib.ptr(val), _lib.ptr(grad), None, _lib.stream_ptr()),
-                               "pvamd_composed_query_f64")
+            # float64 query points stay float64 (sdf.py:395-431 over sdf.py:545-547), as in __call__
+            val, grad, _, _, _ = self._fused_forward(points, "nearest", configs=pick)
             return val, grad
         flat, _, _, _ = _lib.as_query_points(points, dev)
         P = flat.shape[0]

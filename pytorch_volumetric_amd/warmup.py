@@ -37,9 +37,9 @@ def warm_up(device=None, freeze_gc=True):
         mesh(few)                                             # mesh.hip (few-points launches), sort.hip (one-block order)
         mesh(many)                                            # mesh.hip (main launch), sort.hip (counting sort)
         cached = pv.CachedSDF("warm_up", 0.02, obj.bounding_box(padding=0.06), mesh, device=dev, cache_path=None)  # cache build
-        cached(few); cached(many); cached.outside_surface(few); cached(few.double())                                 # cached.hip
+        cached(few); cached(many); cached.outside_surface(few); cached(few.double())     # cached.hip, lane_query.hip (float64)
         cached.interpolation = "trilinear"
-        cached(few)                                           # interp.hip
+        cached(few)                                           # lane_query.hip
         cached.interpolation = "nearest"
         rot = tf.Transform3d(matrix=torch.eye(4).repeat(6, 1, 1))
         comp = pv.ComposedSDF([cached, cached], rot)

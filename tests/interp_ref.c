@@ -162,3 +162,55 @@ void composed_forward_f32(int32_t S, const float* const* recs, const int32_t* sh
             leaf[o] = bs;
         }
 }
+
+/* The same composition in float64 (float64 points and stack, default index rule): per leaf s x = ((m0 px + m1 py) + m2 pz) + m3 as
+ * fma, the nearest mode's float64 range test dmin <= x <= dmax, in range the interpolation, outside the bounding-box statements
+ * in float64; the first minimum from the first leaf on (NaN counts as the minimum); the winner's gradient rotated back with
+ * fma(M8, gz, fma(M4, gy, M0 gx)).  mns / ress / dmins / dmaxs / bbs: the descriptors' dmin / dres / dmin / dmax / dbb_min,
+ * dbb_max, in the layouts of composed_forward_f32. */
+void composed_forward_f64(int32_t S, const float* const* recs, const int32_t* shapes, const double* mns, const double* ress,
+                          const double* dmins, const double* dmaxs, const double* bbs, const double* tf, int32_t A,
+                          const double* pts, int64_t P, double* val, double* grad, int32_t* leaf) {
+    for (int a = 0; a < A; ++a)
+        for (int64_t p = 0; p < P; ++p) {
+            const double* q = pts + 3 * p;
+            double bv = 0.0, bg[3] = {0.0, 0.0, 0.0};
+            int bs = -1;
+            for (int s = 0; s < S; ++s) {
+                const double* M = tf + 16 * ((int64_t)s * A + a);
+                double x[3];
+                for (int r = 0; r < 3; ++r) x[r] = fma(M[4 * r + 2], q[2], fma(M[4 * r + 1], q[1], M[4 * r] * q[0])) + M[4 * r + 3];
+                int in = 1;
+                for (int d = 0; d < 3; ++d) in &= (dmins[3 * s + d] <= x[d]) & (x[d] <= dmaxs[3 * s + d]);
+                double o[4];
+                if (in) {
+                    uint8_t one = 1;
+                    interp_forward_f64(recs[s], shapes + 3 * s, mns + 3 * s, ress + 3 * s, x, 1, &one, o, o + 1);
+                } else {
+                    double t[3];
+                    for (int d = 0; d < 3; ++d) {
+                        double lo = bbs[6 * s + d] - x[d];
+                        const int la = lo > 0.0;
+                        lo = la ? lo : 0.0;
+                        double hi = x[d] - bbs[6 * s + 3 + d];
+                        hi = hi > 0.0 ? hi : 0.0;
+                        const double sm = lo + hi;
+                        t[d] = la ? -sm : sm;
+                    }
+                    const double n = sqrt(fma(t[2], t[2], fma(t[1], t[1], t[0] * t[0])));
+                    o[0] = n;
+                    for (int d = 0; d < 3; ++d) o[1 + d] = t[d] / n;
+                }
+                if (bs < 0 || o[0] < bv || (o[0] != o[0] && bv == bv)) {
+                    bv = o[0];
+                    bg[0] = o[1]; bg[1] = o[2]; bg[2] = o[3];
+                    bs = s;
+                }
+            }
+            const double* M = tf + 16 * ((int64_t)bs * A + a);
+            const int64_t o = (int64_t)a * P + p;
+            val[o] = bv;
+            for (int j = 0; j < 3; ++j) grad[3 * o + j] = fma(M[8 + j], bg[2], fma(M[4 + j], bg[1], M[j] * bg[0]));
+            leaf[o] = bs;
+        }
+}

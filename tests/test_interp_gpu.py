@@ -1,4 +1,4 @@
-"""-m gpu: interpolation="trilinear" (csrc/interp.hip, the interpolated leaf of csrc/backward.hip) against the CPU restatement of
+"""-m gpu: interpolation="trilinear" (csrc/lane_query.hip, the interpolated leaf of csrc/backward.hip) against the CPU restatement of
 its arithmetic contract (tests/interp_ref.c: bit for bit) and, for gradients, float64 torch autograd through the same
 expressions given the kernel's decisions."""
 import ctypes
@@ -198,6 +198,30 @@ def composed_ref_f32(leaves, tfm, pts):
     return val, grad, leaf
 
 
+def composed_ref_f64(leaves, tfm, pts):
+    """interp_ref.c's composed_forward_f64 over the leaves' own descriptors."""
+    lib = R.load()
+    S = len(leaves)
+    A = tfm.shape[0] // S
+    P = pts.shape[0]
+    descs = [c._grid_desc() for c in leaves]
+    recs = [np.ascontiguousarray(c._packed.cpu().numpy()) for c in leaves]
+    arr = lambda rows, dt: np.ascontiguousarray(np.array(rows, dt))
+    shapes = arr([list(d.shape) for d in descs], np.int32)
+    mns, ress = arr([list(d.dmin) for d in descs], np.float64), arr([list(d.dres) for d in descs], np.float64)
+    dmins, dmaxs = arr([list(d.dmin) for d in descs], np.float64), arr([list(d.dmax) for d in descs], np.float64)
+    bbs = arr([list(d.dbb_min) + list(d.dbb_max) for d in descs], np.float64)
+    ptrs = (ctypes.c_void_p * S)(*[r.ctypes.data for r in recs])
+    tf_np = np.ascontiguousarray(tfm.detach().cpu().numpy().astype(np.float64))
+    p_np = np.ascontiguousarray(pts.cpu().numpy().astype(np.float64))
+    val = np.empty((A, P), np.float64)
+    grad = np.empty((A, P, 3), np.float64)
+    leaf = np.empty((A, P), np.int32)
+    lib.composed_forward_f64(ctypes.c_int32(S), ptrs, R._p(shapes), R._p(mns), R._p(ress), R._p(dmins), R._p(dmaxs), R._p(bbs),
+                             R._p(tf_np), ctypes.c_int32(A), R._p(p_np), ctypes.c_int64(P), R._p(val), R._p(grad), R._p(leaf))
+    return val, grad, leaf
+
+
 def robot_points(n, seed):
     return W.c4_points(n, seed=seed)
 
@@ -228,6 +252,48 @@ def test_composed_and_robot_forward_bit_exact(robot, robot_nearest):
     v64, _ = robot(pts[:-2].double())
     assert v64.dtype == torch.float64
     assert torch.allclose(v64.float(), val[:, :-2], atol=1e-5, rtol=1e-5)
+
+
+def composed_abi_f64(comp, tfm, pts):
+    """pvamd_composed_query_interp_f64 over comp's leaves with the float64 stack tfm: (val, grad, leaf) on the host."""
+    S = len(comp.sdfs)
+    A = tfm.shape[0] // S
+    P = pts.shape[0]
+    tf64 = tfm.detach().double().cuda().contiguous()
+    val = torch.empty((A, P), dtype=torch.float64, device="cuda")
+    grad = torch.empty((A, P, 3), dtype=torch.float64, device="cuda")
+    leaf = torch.empty((A, P), dtype=torch.int32, device="cuda")
+    _lib.check(_lib.load().pvamd_composed_query_interp_f64(_lib.ptr(comp._leaf_grids(pts.device)), S, _lib.ptr(tf64), A, _lib.ptr(pts),
+                                                           P, _lib.ptr(val), _lib.ptr(grad), _lib.ptr(leaf), _lib.stream_ptr()),
+               "pvamd_composed_query_interp_f64")
+    torch.cuda.synchronize()
+    return val.cpu().numpy(), grad.cpu().numpy(), leaf.cpu().numpy()
+
+
+def test_composed_forward_f64_bit_exact(robot, tri):
+    """The float64 trilinear composed kernel against interp_ref.c's composed_forward_f64: values, gradients and leaf ids, bit for
+    bit, on the robot's link caches and on three placements of one cache, with non-finite rows."""
+    bad = torch.tensor([[math.nan, 0, 0], [0, math.inf, 0], [0, 0, -math.inf], [math.nan] * 3, [1e300, 0, 0], [0, -1e300, 0]],
+                       dtype=torch.float64, device="cuda")
+    q = W.c4_joint_configs(5, seed=7).cuda()
+    robot.set_joint_configuration(q)
+    rpts = torch.cat((robot_points(20000, seed=6).double(), bad)).contiguous()
+    A = 3
+    placed = pv.ComposedSDF([tri, tri, tri], None)
+    placed.set_transforms(W.random_rigid(3 * A, seed=9, trans=0.05).double().cuda(), batch_dim=(A,))
+    cpts = torch.cat((W.c2_points(tri, 20000, seed=8).double(), bad)).contiguous()
+    for comp, pts in ((robot.sdf, rpts), (placed, cpts)):
+        tfm = comp._tf_matrix.detach().double()
+        gv, gg, gl = composed_abi_f64(comp, tfm, pts)
+        rv, rg, rl = composed_ref_f64(comp.sdfs, tfm, pts)
+        assert np.array_equal(gv, rv, equal_nan=True)
+        assert np.array_equal(gg, rg, equal_nan=True)
+        assert np.array_equal(gl, rl)
+        assert len(np.unique(gl)) > 1 and np.isfinite(gv).mean() > 0.9
+        # the public float64 call is the same kernel
+        val, grad = comp(pts)
+        assert np.array_equal(val.reshape(gv.shape).cpu().numpy(), gv, equal_nan=True)
+        assert np.array_equal(grad.reshape(gg.shape).cpu().numpy(), gg, equal_nan=True)
 
 
 # ---------------------------------------------------------------- gradients
