@@ -542,6 +542,51 @@ int pvamd_composed_query_interp_backward_f64(const pvamd_grid_t* grids, int32_t 
                                              const double* points, int64_t P, const int32_t* out_leaf, const double* dval,
                                              const double* dgrad, double* dpoints, double* dtf, void* scratch, void* stream);
 
+
+/* ---- Minimum over points (ComposedSDF.min_over_points / RobotSDF.min_over_points) ----
+ * A composition of S leaves under A configurations (tf: device [S*A][4][4] leaf-major, rigid; every leaf BOUNDING_BOX) and P
+ * points.  v_s(a, p), g_s(a, p): the value and gradient of leaf s alone at point p under transform (s, a) -- the bits of a
+ * one-leaf composition ComposedSDF([sdfs[s]], slice s of the stack).  v(a, p), g(a, p): the composed answer (first minimum over
+ * leaves, NaN counts as the minimum, the winner's gradient rotated back), the bits of the fused forwards.
+ *  1. Order: NaN is below every number, -0.0 and +0.0 tie, ties go to the smallest point index.
+ *  2. per_leaf = 0: one pair per configuration (Z = 1); out_index[a] = the smallest p minimising v(a, .); out_val[a] / out_grad[a]
+ *     = v(a, p) / g(a, p) bit for bit (the composed choice of leaf at p included); out_leaf[a] = that leaf.
+ *     per_leaf = 1: one pair per (a, s) (Z = S), stored [A][S]; out_index[a][s] = the smallest p minimising v_s(a, .); out_val /
+ *     out_grad = v_s / g_s there; out_leaf[a][s] = s.
+ *  3. mode: PVAMD_LEAF_NEAREST or PVAMD_LEAF_TRILINEAR, the leaf statements of pvamd_composed_query / _interp (float32) and
+ *     pvamd_composed_query_f64 / _interp_f64 (float64).
+ *  4. Bitwise reproducible whatever the launch geometry: per-chunk keys (order-preserving value bits, point index) reduced with
+ *     an exact min, then the answer recomputed at the chosen point.  No device -> host synchronisation, no allocation.
+ * pvamd_composed_min_over_points / _f64: out_val [A][Z], out_grad [A][Z][3], out_index [A][Z] int64, out_leaf [A][Z] int32 or
+ *   NULL.  1 <= P <= 2^32 - 2.  scratch: device, PVAMD_MIN_OVER_POINTS_SCRATCH_BYTES(S, A, P, per_leaf) bytes, 16-byte aligned
+ *   (one 16-byte key per pair and 4096-point chunk).
+ * pvamd_composed_min_over_points_backward / _f64: the VJP of the pairs given the forward's out_index and out_leaf (required):
+ *   torch autograd through the composed (per_leaf: one-leaf) query gathered at out_index, decisions held fixed; the per-pair
+ *   statements of pvamd_composed_query_backward / _interp_backward.  dval [A][Z] / dgrad [A][Z][3] may be NULL.  dtf: device
+ *   [S*A][4][4] or NULL, rows of unselected (leaf, configuration) pairs and row 3 zero.  dpoints: device [P][3] or NULL, rows
+ *   no pair selected exactly zero, a row selected by several pairs summed in pair order.  S <= 64.  scratch (when dpoints is
+ *   given): PVAMD_MIN_OVER_POINTS_BACKWARD_SCRATCH_BYTES(S, A, per_leaf) bytes, 16-byte aligned.                                */
+#define PVAMD_LEAF_NEAREST   0
+#define PVAMD_LEAF_TRILINEAR 1
+#define PVAMD_MOP_CHUNK 4096  /* points per partial key */
+#define PVAMD_MIN_OVER_POINTS_SCRATCH_BYTES(S, A, P, per_leaf) \
+    (16 * (int64_t)(A) * ((per_leaf) ? (int64_t)(S) : 1) * (((int64_t)(P) + PVAMD_MOP_CHUNK - 1) / PVAMD_MOP_CHUNK))
+#define PVAMD_MIN_OVER_POINTS_BACKWARD_SCRATCH_BYTES(S, A, per_leaf) (24 * (int64_t)(A) * ((per_leaf) ? (int64_t)(S) : 1))
+int64_t pvamd_min_over_points_scratch_bytes(int32_t S, int32_t A, int64_t P, int32_t per_leaf);
+int pvamd_composed_min_over_points(const pvamd_grid_t* grids, int32_t S, const float* tf, int32_t A, const float* points, int64_t P,
+                                   int32_t mode, int32_t per_leaf, float* out_val, float* out_grad, int64_t* out_index,
+                                   int32_t* out_leaf, void* scratch, void* stream);
+int pvamd_composed_min_over_points_f64(const pvamd_grid_t* grids, int32_t S, const double* tf, int32_t A, const double* points,
+                                       int64_t P, int32_t mode, int32_t per_leaf, double* out_val, double* out_grad,
+                                       int64_t* out_index, int32_t* out_leaf, void* scratch, void* stream);
+int pvamd_composed_min_over_points_backward(const pvamd_grid_t* grids, int32_t S, const float* tf, int32_t A, const float* points,
+                                            int64_t P, int32_t mode, int32_t per_leaf, const int64_t* index, const int32_t* leaf,
+                                            const float* dval, const float* dgrad, float* dpoints, float* dtf, void* scratch,
+                                            void* stream);
+int pvamd_composed_min_over_points_backward_f64(const pvamd_grid_t* grids, int32_t S, const double* tf, int32_t A,
+                                                const double* points, int64_t P, int32_t mode, int32_t per_leaf,
+                                                const int64_t* index, const int32_t* leaf, const double* dval, const double* dgrad,
+                                                double* dpoints, double* dtf, void* scratch, void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,8 @@ RULE_VALID_ON_INDEX = 1
 RULE_ROUND_HALF_AWAY = 2
 RULE_ROUND_FLOOR_HALF = 4
 RULE_RES_F64 = 8
+LEAF_MODES = {"nearest": 0, "trilinear": 1}  # PVAMD_LEAF_NEAREST / PVAMD_LEAF_TRILINEAR
+MOP_CHUNK = 4096  # PVAMD_MOP_CHUNK
 TRI_REC = 24
 TRI_TILE = 256
 TRI_GROUP = 16
@@ -51,6 +53,16 @@ def mesh_scratch_bytes(P):
     """PVAMD_MESH_SCRATCH_BYTES(P)"""
     return 64 + mesh_scratch_slots(P) * (64 * 40 + 8 + 64) + 24 * MESH_SMALL_POINTS
 
+
+
+def min_over_points_scratch_bytes(S, A, P, per_leaf):
+    """PVAMD_MIN_OVER_POINTS_SCRATCH_BYTES(S, A, P, per_leaf): one 16-byte key per pair and point chunk."""
+    return 16 * A * (S if per_leaf else 1) * ((P + MOP_CHUNK - 1) // MOP_CHUNK)
+
+
+def min_over_points_backward_scratch_bytes(S, A, per_leaf):
+    """PVAMD_MIN_OVER_POINTS_BACKWARD_SCRATCH_BYTES(S, A, per_leaf)"""
+    return 24 * A * (S if per_leaf else 1)
 
 _c_float_p = ctypes.POINTER(ctypes.c_float)
 
@@ -221,6 +233,12 @@ SIGNATURES = {
     "pvamd_cached_query_interp_backward_f64": (ctypes.c_int, [ctypes.POINTER(GridDesc), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "pvamd_composed_query_interp_backward": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "pvamd_composed_query_interp_backward_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    # ComposedSDF.min_over_points (include/pvamd.h "Minimum over points")
+    "pvamd_min_over_points_scratch_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32]),
+    "pvamd_composed_min_over_points": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "pvamd_composed_min_over_points_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "pvamd_composed_min_over_points_backward": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "pvamd_composed_min_over_points_backward_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
 }
 
 E_SHAPE = -2  # PVAMD_E_SHAPE (include/pvamd.h)

@@ -129,6 +129,57 @@ def composed_query(composed, points, mode):
     return ComposedQuery.apply(composed, points, composed._tf_matrix, mode)
 
 
+
+# ---------------------------------------------------------------- ComposedSDF.min_over_points (include/pvamd.h "Minimum over points")
+class MinOverPointsQuery(torch.autograd.Function):
+    """Forward: ComposedSDF._min_over_points_fused.  Backward: pvamd_composed_min_over_points_backward over the A (per_leaf: A S)
+    selected pairs only -- the gradient of the composed (one-leaf) query gathered at the indices, decisions held fixed."""
+
+    @staticmethod
+    def forward(ctx, composed, points, tfm, mode, per_leaf):
+        ctx.set_materialize_grads(False)
+        dev = composed._owner_device()
+        val, idx, grad, idx_k, leaf, flat, tfd = composed._min_over_points_fused(points, mode, per_leaf)
+        ctx.mark_non_differentiable(idx)
+        ctx.composed, ctx.flat, ctx.tfd, ctx.idx, ctx.leaf, ctx.grids = composed, flat, tfd, idx_k, leaf, composed._leaf_grids(dev)
+        ctx.save_for_backward(points, tfm)  # torch's in-place check of the inputs flat / tfd may alias
+        ctx.S, ctx.A, ctx.Z = len(composed.sdfs), idx_k.shape[0], idx_k.shape[1]
+        ctx.mode, ctx.per_leaf = mode, per_leaf
+        ctx.pshape, ctx.pdtype, ctx.pdevice = points.shape, points.dtype, points.device
+        ctx.tdtype, ctx.tdevice = tfm.dtype, tfm.device
+        return val, idx, grad
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dval, didx, dgrad):
+        need_p, need_tf = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        ctx.saved_tensors
+        flat, tfd, S, A, Z = ctx.flat, ctx.tfd, ctx.S, ctx.A, ctx.Z
+        P, dev, dt = flat.shape[0], flat.device, flat.dtype
+        dv = _upstream(dval, dev, dt, (A, Z))
+        dg = _upstream(dgrad, dev, dt, (A, Z, 3))
+        dpoints = torch.empty((P, 3), dtype=dt, device=dev) if need_p else None
+        dtf = torch.empty((S * A, 4, 4), dtype=dt, device=dev) if need_tf else None
+        name = "pvamd_composed_min_over_points_backward" + ("_f64" if dt == torch.float64 else "")
+        with _lib.on_device(dev):
+            scratch = torch.empty((max(_lib.min_over_points_backward_scratch_bytes(S, A, ctx.per_leaf), 16),), dtype=torch.uint8,
+                                  device=dev)
+            _lib.check(getattr(_lib.load(), name)(_lib.ptr(ctx.grids), S, _lib.ptr(tfd), A, _lib.ptr(flat), P,
+                                                  _lib.LEAF_MODES[ctx.mode], int(ctx.per_leaf), _lib.ptr(ctx.idx),
+                                                  _lib.ptr(ctx.leaf), _lib.ptr(dv), _lib.ptr(dg), _lib.ptr(dpoints), _lib.ptr(dtf),
+                                                  _lib.ptr(scratch), _lib.stream_ptr()), name)
+        gp = dpoints.reshape(ctx.pshape).to(device=ctx.pdevice, dtype=ctx.pdtype) if need_p else None
+        gt = dtf.to(device=ctx.tdevice, dtype=ctx.tdtype) if need_tf else None
+        return None, gp, gt, None, None
+
+
+def min_over_points(composed, points, mode, per_leaf):
+    from pytorch_volumetric_amd.sdf import MinOverPoints
+    if len(composed.sdfs) > MAX_LEAVES:
+        raise _lib.PvamdError(f"gradients through a composition need at most {MAX_LEAVES} leaves, this one has {len(composed.sdfs)}")
+    val, idx, grad = MinOverPointsQuery.apply(composed, points, composed._tf_matrix, mode, per_leaf)
+    return MinOverPoints(val, idx, grad)
+
 # ---------------------------------------------------------------- RobotSDF.set_joint_configuration (model_to_sdf.py:82-115)
 class ChainConfigure(torch.autograd.Function):
     """Forward: the one-launch HIP configure (pvamd_configure_chain), q (A, M) -> the (S*A, 4, 4) obj->leaf stack.  Backward:

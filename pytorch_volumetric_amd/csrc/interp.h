@@ -1,5 +1,6 @@
 // Trilinear interpolation of the packed (val, gx, gy, gz) records: the per-leaf statements shared by the interpolated
-// forward kernels (lane_query.hip) and their backward (backward.hip).  The arithmetic contract is include/pvamd.h's
+// forward kernels (lane_query.hip, min_over_points.hip) and their backward (backward.hip); and leaf_f64, the float64 leaf of
+// both modes.  The arithmetic contract is include/pvamd.h's
 // "Interpolated queries"; tests/interp_ref.c states the same sequence on the CPU.
 //   per axis d:  s = (x_d - min_d) / res_d                   IEEE subtraction, then IEEE division, in the query dtype
 //                c = s < 0 ? 0 : (s > n_d - 1 ? n_d - 1 : s)  clamped_d = (c != s)
@@ -101,6 +102,31 @@ PVAMD_DEV void interp_fraction_vjp(const float4 r[8], const T f[3], const T u[4]
         df[1] += u[q] * dfy;
         df[2] += u[q] * dfz;
     }
+}
+
+// (val, gx, gy, gz) of one float64 point in a leaf's frame; returns the range test
+template <bool INTERP>
+PVAMD_DEV bool leaf_f64(const pvamd_grid_t& g, const double x[3], double o[4]) {
+    long long key[3];
+    const bool valid = voxel_key_f64(g, x, key);
+    o[0] = o[1] = o[2] = o[3] = 0.0;
+    if (valid) {
+        if constexpr (INTERP) {
+            InterpCell<double> c;
+            interp_cell<double>(g, x, c);
+            float4 r[8];
+            interp_gather(g, c.base, r);
+            interp_combine<double>(r, c.f, o);
+        } else {
+            const float4 r = load_record(g.vox, clamped_flat(g, key));
+            o[0] = (double)r.x; o[1] = (double)r.y; o[2] = (double)r.z; o[3] = (double)r.w;
+        }
+    } else if (g.oob_mode == PVAMD_OOB_BOUNDING_BOX) {
+        double t[3];
+        o[0] = LeafOps<double>::box(g, x, t);
+        o[1] = t[0] / o[0]; o[2] = t[1] / o[0]; o[3] = t[2] / o[0];
+    }
+    return valid;
 }
 
 }  // namespace pvamd

@@ -15,31 +15,6 @@ namespace pvamd {
 
 constexpr int kLaneBlock = 256;
 
-// (val, gx, gy, gz) of one float64 point in a leaf's frame; returns the range test
-template <bool INTERP>
-PVAMD_DEV bool leaf_f64(const pvamd_grid_t& g, const double x[3], double o[4]) {
-    long long key[3];
-    const bool valid = voxel_key_f64(g, x, key);
-    o[0] = o[1] = o[2] = o[3] = 0.0;
-    if (valid) {
-        if constexpr (INTERP) {
-            InterpCell<double> c;
-            interp_cell<double>(g, x, c);
-            float4 r[8];
-            interp_gather(g, c.base, r);
-            interp_combine<double>(r, c.f, o);
-        } else {
-            const float4 r = load_record(g.vox, clamped_flat(g, key));
-            o[0] = (double)r.x; o[1] = (double)r.y; o[2] = (double)r.z; o[3] = (double)r.w;
-        }
-    } else if (g.oob_mode == PVAMD_OOB_BOUNDING_BOX) {
-        double t[3];
-        o[0] = LeafOps<double>::box(g, x, t);
-        o[1] = t[0] / o[0]; o[2] = t[1] / o[0]; o[3] = t[2] / o[0];
-    }
-    return valid;
-}
-
 // ---- CachedSDF.__call__, float64 points: one point per lane (a grid-stride loop costs the trilinear leaf 14 VGPRs and a wave
 // per SIMD) ----
 template <bool INTERP>

@@ -267,6 +267,12 @@ class RobotSDF(sdf.ObjectFrameSDF):
         """
         return self.sdf(points_in_object_frame)
 
+    def min_over_points(self, points, per_leaf=False):
+        """ComposedSDF.min_over_points under the current joint configuration: per configuration (and per link with per_leaf;
+        leaf s is sdf_to_link_name[s]) the closest point of `points`, its value and gradient.  Differentiable w.r.t. q when
+        set_joint_configuration was given a q that requires grad, as __call__ is."""
+        return self.sdf.min_over_points(points, per_leaf=per_leaf)
+
     def query_into(self, points, out_val, out_grad):
         """Allocation-free form of __call__ (see ComposedSDF.query_into); outputs are (A,P) and (A,P,3)."""
         self.sdf.query_into(points, out_val, out_grad)

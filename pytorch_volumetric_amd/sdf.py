@@ -33,6 +33,22 @@ class SDFQuery(NamedTuple):
     normal: Union[torch.Tensor, None]
 
 
+
+class MinOverPoints(NamedTuple):
+    """ComposedSDF.min_over_points / RobotSDF.min_over_points: per pair, the smallest point index that minimises the value, and
+    the value and gradient there (include/pvamd.h "Minimum over points")."""
+    values: torch.Tensor
+    indices: torch.Tensor
+    gradients: torch.Tensor
+
+
+def first_argmin(v):
+    """The index rule of min_over_points along the last dimension: a NaN counts as the minimum, -0.0 and +0.0 tie, and the
+    smallest index among the minima wins.  Plain torch, no device -> host synchronisation."""
+    nan = torch.isnan(v)
+    hit = torch.where(nan.any(dim=-1, keepdim=True), nan, v == v.amin(dim=-1, keepdim=True))
+    return hit.to(torch.uint8).argmax(dim=-1)  # argmax returns the first of equal maxima
+
 def _restore(t, lead, tail, dtype, device):
     return t.reshape(*lead, *tail).to(device=device, dtype=dtype)
 
@@ -1151,14 +1167,7 @@ class ComposedSDF(ObjectFrameSDF):
         A = math.prod(self.tsf_batch) if self.tsf_batch is not None else 1
         dev = self._owner_device()
         f64 = points.dtype == torch.float64
-        if f64:
-            flat, dtype = points.detach().reshape(-1, 3).to(device=dev, dtype=torch.float64).contiguous(), torch.float64
-            tfd = self.__dict__.get("_tf_dev64")
-            if tfd is None or tfd.device != dev:
-                tfd = self._tf_dev64 = self._tf_matrix.detach().to(device=dev, dtype=torch.float64).contiguous()
-        else:
-            flat, _, dtype, _ = _lib.as_query_points(points, dev)
-            tfd = self._tf_device(dev)
+        flat, tfd, dtype = self._fused_inputs(points, dev)
         if configs is not None:
             tfd, A = tfd.reshape(S, A, 4, 4)[:, configs].contiguous(), configs.numel()
         P = flat.shape[0]
@@ -1181,6 +1190,98 @@ class ComposedSDF(ObjectFrameSDF):
             val, grad = val.reshape(-1), grad.reshape(-1, 3)
         out_device = self.sdfs[0].device  # leaves return on their own device (sdf.py:546)
         return val.to(device=out_device, dtype=dtype), grad.to(device=out_device, dtype=dtype), leaf, flat, tfd
+
+    def _fused_inputs(self, points, dev):
+        """(flat points, transform stack, result dtype) as the fused kernels read them: float64 points with the float64 widening
+        of the stack, anything else in float32."""
+        if points.dtype == torch.float64:
+            flat = points.detach().reshape(-1, 3).to(device=dev, dtype=torch.float64).contiguous()
+            tfd = self.__dict__.get("_tf_dev64")
+            if tfd is None or tfd.device != dev:
+                tfd = self._tf_dev64 = self._tf_matrix.detach().to(device=dev, dtype=torch.float64).contiguous()
+            return flat, tfd, torch.float64
+        flat, _, dtype, _ = _lib.as_query_points(points, dev)
+        return flat, self._tf_device(dev), dtype
+
+    # ---- minimum over points ----
+    def min_over_points(self, points, per_leaf=False):
+        """For every configuration, the point of `points` where the composition comes closest, without the (A, P) field.
+
+        :param points: (..., 3); the leading dimensions are flattened into P, and `indices` index that flattened order
+        :param per_leaf: False: the minimum of the composed value (what __call__ returns); True: one minimum per leaf s
+            (leaf s = self.sdfs[s], alone under its own transforms)
+        :return: MinOverPoints(values, indices, gradients) of shapes B, B, B + (3,) (per_leaf: B + (S,), B + (S,), B + (S, 3)),
+            B the transform batch shape (() without one).  indices are int64; values / gradients have the dtype __call__
+            returns.  Ties go to the smallest index, a NaN counts as the minimum, -0.0 and +0.0 tie; values / gradients are the
+            bits __call__ (per_leaf: the one-leaf composition) gives at that index.  Differentiable w.r.t. the points and the
+            transforms (a RobotSDF's joint values) when grad mode is on and they require grad; indices carry no gradient.
+
+        Fused compositions (_fused_mode(): every leaf a BOUNDING_BOX CachedSDF of one interpolation, rigid transforms) with float32
+        or float64 points run two HIP kernels (csrc/min_over_points.hip) whose extra memory is O(A S + A P / 4096); anything else
+        is __call__ plus a torch reduction under the same contract."""
+        if not isinstance(per_leaf, bool):
+            raise TypeError(f"per_leaf must be True or False, got {per_leaf!r}")
+        if not torch.is_tensor(points):
+            points = torch.as_tensor(points)
+        if points.dim() < 1 or points.shape[-1] != 3:
+            raise ValueError(f"query points must have last dimension 3, got {tuple(points.shape)}")
+        if points.numel() == 0:
+            raise ValueError("min_over_points: no points (the minimum over an empty set is undefined, as for torch.min)")
+        if self._tf_matrix is None:
+            raise ValueError("min_over_points needs the transforms to be set")
+        mode = self._fused_mode()
+        if mode is None or points.dtype not in (torch.float32, torch.float64):
+            return self._min_over_points_generic(points, per_leaf)
+        if (self._tf_grad or points.requires_grad) and torch.is_grad_enabled():
+            from pytorch_volumetric_amd import autograd
+            return autograd.min_over_points(self, points, mode, per_leaf)
+        val, idx, grad = self._min_over_points_fused(points, mode, per_leaf)[:3]
+        return MinOverPoints(val, idx, grad)
+
+    def _min_over_points_fused(self, points, mode, per_leaf):
+        """One pvamd_composed_min_over_points[_f64] call.  Returns (values, indices, gradients) in the result shapes on the leaves'
+        device, then what the backward needs: the (A, Z) indices and leaf ids, the flat points and the stack the kernels read."""
+        S = len(self.sdfs)
+        batch = tuple(self.tsf_batch) if self.tsf_batch is not None else ()
+        A = math.prod(batch)
+        dev = self._owner_device()
+        flat, tfd, dtype = self._fused_inputs(points, dev)
+        P, Z = flat.shape[0], S if per_leaf else 1
+        val = torch.empty((A, Z), dtype=flat.dtype, device=dev)
+        grad = torch.empty((A, Z, 3), dtype=flat.dtype, device=dev)
+        idx = torch.empty((A, Z), dtype=torch.int64, device=dev)
+        leaf = torch.empty((A, Z), dtype=torch.int32, device=dev)
+        name = "pvamd_composed_min_over_points" + ("_f64" if flat.dtype == torch.float64 else "")
+        with _lib.on_device(dev):
+            grids = self._leaf_grids(dev)
+            scratch = torch.empty((_lib.min_over_points_scratch_bytes(S, A, P, per_leaf),), dtype=torch.uint8, device=dev)
+            _lib.check(getattr(_lib.load(), name)(_lib.ptr(grids), S, _lib.ptr(tfd), A, _lib.ptr(flat), P, _lib.LEAF_MODES[mode],
+                                                  int(per_leaf), _lib.ptr(val), _lib.ptr(grad), _lib.ptr(idx), _lib.ptr(leaf),
+                                                  _lib.ptr(scratch), _lib.stream_ptr()), name)
+        shape = batch + ((S,) if per_leaf else ())
+        out_device = self.sdfs[0].device  # leaves return on their own device (sdf.py:546)
+        return (val.reshape(shape).to(device=out_device, dtype=dtype), idx.reshape(shape).to(device=out_device),
+                grad.reshape(*shape, 3).to(device=out_device, dtype=dtype), idx, leaf, flat, tfd)
+
+    def _min_over_points_generic(self, points, per_leaf):
+        """Compositions the kernels do not serve (other leaves, mixed modes, other dtypes): __call__ (per leaf: the one-leaf
+        composition) and a torch reduction under the same contract -- not a hot path.  Differentiable through __call__."""
+        batch = tuple(self.tsf_batch) if self.tsf_batch is not None else ()
+        if per_leaf:
+            parts = []
+            for s in range(len(self.sdfs)):
+                one = ComposedSDF([self.sdfs[s]], None)
+                one.set_transforms(self._tf_matrix[self.ith_transform_slice(s)], batch_dim=self.tsf_batch,
+                                   known_rigid=self._rigid)
+                parts.append(one._min_over_points_generic(points, False))
+            return MinOverPoints(*(torch.stack(t, dim=len(batch)) for t in zip(*parts)))
+        A = math.prod(batch)
+        val, grad = self(points)
+        val, grad = val.reshape(A, -1), grad.reshape(A, -1, 3)
+        idx = first_argmin(val.detach())
+        v = val.gather(1, idx.unsqueeze(1)).squeeze(1)
+        g = grad.gather(1, idx.view(A, 1, 1).expand(A, 1, 3)).squeeze(1)
+        return MinOverPoints(v.reshape(batch), idx.reshape(batch), g.reshape(*batch, 3))
 
     def _interp_forward(self, points, want_leaf):
         """_fused_forward of a trilinear composition (the leaf ids the interpolation tests compare)."""
