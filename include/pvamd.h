@@ -587,6 +587,59 @@ int pvamd_composed_min_over_points_backward_f64(const pvamd_grid_t* grids, int32
                                                 const double* points, int64_t P, int32_t mode, int32_t per_leaf,
                                                 const int64_t* index, const int32_t* leaf, const double* dval, const double* dgrad,
                                                 double* dpoints, double* dtf, void* scratch, void* stream);
+
+/* ---- Hinge penalty over points (ComposedSDF.hinge_over_points / RobotSDF.hinge_over_points) ----
+ * The compositions, pairs and per-leaf values of "Minimum over points": v(a, p) the composed value (per_leaf = 0, Z = 1) or
+ * v_s(a, p) the one-leaf composition's (per_leaf = 1, Z = S, pairs stored [A][S]), the bits of the fused forwards.
+ *  1. margin m is given in the query dtype (a Python margin is rounded once to it, torch's rule for a scalar against a tensor).
+ *  2. Each term is rounded in the query dtype as torch rounds (m - v).clamp(min=0) ** power: h = max(m - v, 0) (NaN stays
+ *     NaN), then h (power 1) or h * h (power 2).
+ *  3. out_val[pair] = the sum over p of the terms, in float64, in an order that depends only on (S, A, P) (per lane in point
+ *     order, a wave butterfly, the four waves in order, then the 4096-point chunks in chunk order), rounded once to the query
+ *     dtype: for float32 within 1 ulp of float32(fsum(terms)); for float64 an error of at most P 2^-53 sum(terms).  A NaN v
+ *     makes its pair's value NaN.  Bitwise reproducible; no device -> host synchronisation, no allocation.
+ *  4. out_count[pair] = the number of p with v < m (int64); a NaN is not counted.
+ *  5. power: 1 or 2, else PVAMD_E_MODE.  mode: PVAMD_LEAF_NEAREST or PVAMD_LEAF_TRILINEAR.  1 <= P.
+ * pvamd_composed_hinge_over_points / _f64: out_val [A][Z], out_count [A][Z] int64.  scratch: device,
+ *   PVAMD_HINGE_OVER_POINTS_SCRATCH_BYTES(S, A, P, per_leaf) bytes, 16-byte aligned (a 16-byte (sum, count) per pair and chunk).
+ * pvamd_composed_hinge_over_points_backward / _f64: the VJP given up [A][Z] (the upstream of out_val): torch autograd through
+ *   ((m - v).clamp(min=0) ** power).sum(-1), decisions held fixed, bit for bit.  Per pair the composed value and winning leaf
+ *   are recomputed with the forward's statements and dv = -(up (2 h)) (power 2) or -up (power 1) where m - v >= 0, else -0
+ *   (clamp's mask passes v == m; a NaN v gets a zero upstream); then the per-pair statements and fixed-order sums of
+ *   pvamd_composed_query_backward / _interp_backward with a value upstream only (a nearest leaf in range has no derivative).
+ *   per_leaf = 1: one pass per leaf s as the one-leaf composition (its dtf rows exactly that composition's), dpoints summed
+ *   over the leaves in leaf order.  No stored leaf ids, no (A, P) upstream.  dtf: device [S*A][4][4] or NULL (row 3 zero);
+ *   dpoints: device [P][3] or NULL.  S <= 64.  scratch: PVAMD_HINGE_OVER_POINTS_BACKWARD_SCRATCH_BYTES(S, A, P, per_leaf,
+ *   sizeof(T)) bytes, 16-byte aligned.                                                                                        */
+#define PVAMD_HINGE_OVER_POINTS_SCRATCH_BYTES(S, A, P, per_leaf) PVAMD_MIN_OVER_POINTS_SCRATCH_BYTES(S, A, P, per_leaf)
+/* the composed backward's plan (backward.hip bwd_plan): 1024-point chunks, configurations split until about 2048 workgroups */
+#define PVAMD_HOP_BWD_CHUNKS(P) (((int64_t)(P) + 1023) / 1024)
+#define PVAMD_HOP_BWD_WANT(A, P) \
+    ((2048 + PVAMD_HOP_BWD_CHUNKS(P) - 1) / PVAMD_HOP_BWD_CHUNKS(P) < (int64_t)(A) ? (2048 + PVAMD_HOP_BWD_CHUNKS(P) - 1) / PVAMD_HOP_BWD_CHUNKS(P) : (int64_t)(A))
+#define PVAMD_HOP_BWD_APER(A, P) (((int64_t)(A) + PVAMD_HOP_BWD_WANT(A, P) - 1) / PVAMD_HOP_BWD_WANT(A, P))
+#define PVAMD_HOP_BWD_NSPLIT(A, P) (((int64_t)(A) + PVAMD_HOP_BWD_APER(A, P) - 1) / PVAMD_HOP_BWD_APER(A, P))
+#define PVAMD_HOP_ROUND256(n) ((((int64_t)(n)) + 255) / 256 * 256)
+#define PVAMD_HOP_BWD_PLAN_BYTES(Sg, A, P, elem)                                                         \
+    (PVAMD_HOP_ROUND256(PVAMD_HOP_BWD_CHUNKS(P) * (int64_t)(Sg) * (int64_t)(A) * 12 * (int64_t)(elem)) + \
+     (PVAMD_HOP_BWD_NSPLIT(A, P) > 1 ? PVAMD_HOP_BWD_NSPLIT(A, P) * (int64_t)(P) * 3 * (int64_t)(elem) : 0))
+#define PVAMD_HINGE_OVER_POINTS_BACKWARD_SCRATCH_BYTES(S, A, P, per_leaf, elem)                                             \
+    (((per_leaf) && (S) > 1) ? PVAMD_HOP_ROUND256(PVAMD_HOP_BWD_PLAN_BYTES(1, A, P, elem)) + (int64_t)(P) * 3 * (int64_t)(elem) \
+                             : PVAMD_HOP_BWD_PLAN_BYTES((per_leaf) ? 1 : (S), A, P, elem))
+int64_t pvamd_hinge_over_points_scratch_bytes(int32_t S, int32_t A, int64_t P, int32_t per_leaf);
+int64_t pvamd_hinge_over_points_backward_scratch_bytes(int32_t S, int32_t A, int64_t P, int32_t per_leaf, int32_t is_f64);
+int pvamd_composed_hinge_over_points(const pvamd_grid_t* grids, int32_t S, const float* tf, int32_t A, const float* points,
+                                     int64_t P, int32_t mode, int32_t per_leaf, float margin, int32_t power, float* out_val,
+                                     int64_t* out_count, void* scratch, void* stream);
+int pvamd_composed_hinge_over_points_f64(const pvamd_grid_t* grids, int32_t S, const double* tf, int32_t A, const double* points,
+                                         int64_t P, int32_t mode, int32_t per_leaf, double margin, int32_t power, double* out_val,
+                                         int64_t* out_count, void* scratch, void* stream);
+int pvamd_composed_hinge_over_points_backward(const pvamd_grid_t* grids, int32_t S, const float* tf, int32_t A, const float* points,
+                                              int64_t P, int32_t mode, int32_t per_leaf, float margin, int32_t power,
+                                              const float* up, float* dpoints, float* dtf, void* scratch, void* stream);
+int pvamd_composed_hinge_over_points_backward_f64(const pvamd_grid_t* grids, int32_t S, const double* tf, int32_t A,
+                                                  const double* points, int64_t P, int32_t mode, int32_t per_leaf, double margin,
+                                                  int32_t power, const double* up, double* dpoints, double* dtf, void* scratch,
+                                                  void* stream);
 #ifdef __cplusplus
 }
 #endif

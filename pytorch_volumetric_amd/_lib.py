@@ -64,6 +64,34 @@ def min_over_points_backward_scratch_bytes(S, A, per_leaf):
     """PVAMD_MIN_OVER_POINTS_BACKWARD_SCRATCH_BYTES(S, A, per_leaf)"""
     return 24 * A * (S if per_leaf else 1)
 
+
+def hinge_over_points_scratch_bytes(S, A, P, per_leaf):
+    """PVAMD_HINGE_OVER_POINTS_SCRATCH_BYTES(S, A, P, per_leaf): one 16-byte (sum, count) per pair and point chunk."""
+    return min_over_points_scratch_bytes(S, A, P, per_leaf)
+
+
+def _round256(n):
+    return (n + 255) // 256 * 256
+
+
+def _bwd_plan_bytes(S, A, P, elem):
+    """The composed backward's scratch (backward.hip bwd_plan): the dtf slab of 1024-point chunks, then the split dpoints rows
+    when the configurations are split over workgroups (until about 2048 workgroups exist)."""
+    nchunks = (P + 1023) // 1024
+    want = min(A, (2048 + nchunks - 1) // nchunks)
+    aper = (A + want - 1) // want
+    nsplit = (A + aper - 1) // aper
+    return _round256(nchunks * S * A * 12 * elem) + (nsplit * P * 3 * elem if nsplit > 1 else 0)
+
+
+def hinge_over_points_backward_scratch_bytes(S, A, P, per_leaf, f64):
+    """PVAMD_HINGE_OVER_POINTS_BACKWARD_SCRATCH_BYTES(S, A, P, per_leaf, elem): per_leaf runs one-leaf passes, whose dpoints
+    term needs one more [P][3] buffer when there is more than one leaf."""
+    elem = 8 if f64 else 4
+    if per_leaf and S > 1:
+        return _round256(_bwd_plan_bytes(1, A, P, elem)) + P * 3 * elem
+    return _bwd_plan_bytes(1 if per_leaf else S, A, P, elem)
+
 _c_float_p = ctypes.POINTER(ctypes.c_float)
 
 
@@ -239,6 +267,13 @@ SIGNATURES = {
     "pvamd_composed_min_over_points_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "pvamd_composed_min_over_points_backward": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "pvamd_composed_min_over_points_backward_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    # ComposedSDF.hinge_over_points (include/pvamd.h "Hinge penalty over points")
+    "pvamd_hinge_over_points_scratch_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32]),
+    "pvamd_hinge_over_points_backward_scratch_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]),
+    "pvamd_composed_hinge_over_points": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "pvamd_composed_hinge_over_points_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "pvamd_composed_hinge_over_points_backward": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "pvamd_composed_hinge_over_points_backward_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
 }
 
 E_SHAPE = -2  # PVAMD_E_SHAPE (include/pvamd.h)

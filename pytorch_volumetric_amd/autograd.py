@@ -180,6 +180,61 @@ def min_over_points(composed, points, mode, per_leaf):
     val, idx, grad = MinOverPointsQuery.apply(composed, points, composed._tf_matrix, mode, per_leaf)
     return MinOverPoints(val, idx, grad)
 
+# ---------------------------------------------------------------- ComposedSDF.hinge_over_points (include/pvamd.h "Hinge penalty over points")
+class HingeOverPointsQuery(torch.autograd.Function):
+    """Forward: ComposedSDF._hinge_over_points_fused.  Backward: pvamd_composed_hinge_over_points_backward over all pairs, the
+    composed value and winning leaf recomputed per pair in the kernel -- saved are the flat points and the stack, not the pairs."""
+
+    @staticmethod
+    def forward(ctx, composed, points, tfm, margin, power, mode, per_leaf):
+        ctx.set_materialize_grads(False)
+        dev = composed._owner_device()
+        val, cnt, flat, tfd = composed._hinge_over_points_fused(points, margin, power, mode, per_leaf)
+        ctx.mark_non_differentiable(cnt)
+        ctx.composed, ctx.flat, ctx.tfd, ctx.grids = composed, flat, tfd, composed._leaf_grids(dev)
+        ctx.save_for_backward(points, tfm)  # torch's in-place check of the inputs flat / tfd may alias
+        ctx.S = len(composed.sdfs)
+        ctx.A = tfd.shape[0] // ctx.S
+        ctx.margin, ctx.power, ctx.mode, ctx.per_leaf = margin, power, mode, per_leaf
+        ctx.pshape, ctx.pdtype, ctx.pdevice = points.shape, points.dtype, points.device
+        ctx.tdtype, ctx.tdevice = tfm.dtype, tfm.device
+        return val, cnt
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dval, dcnt):
+        need_p, need_tf = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        ctx.saved_tensors
+        flat, tfd, S, A = ctx.flat, ctx.tfd, ctx.S, ctx.A
+        P, dev, dt = flat.shape[0], flat.device, flat.dtype
+        Z = S if ctx.per_leaf else 1
+        up = _upstream(dval, dev, dt, (A, Z))
+        if up is None:  # nothing flows back
+            return None, None, None, None, None, None, None
+        dpoints = torch.empty((P, 3), dtype=dt, device=dev) if need_p else None
+        dtf = torch.empty((S * A, 4, 4), dtype=dt, device=dev) if need_tf else None
+        f64 = dt == torch.float64
+        name = "pvamd_composed_hinge_over_points_backward" + ("_f64" if f64 else "")
+        with _lib.on_device(dev):
+            scratch = torch.empty((max(_lib.hinge_over_points_backward_scratch_bytes(S, A, P, ctx.per_leaf, f64), 16),),
+                                  dtype=torch.uint8, device=dev)
+            _lib.check(getattr(_lib.load(), name)(_lib.ptr(ctx.grids), S, _lib.ptr(tfd), A, _lib.ptr(flat), P,
+                                                  _lib.LEAF_MODES[ctx.mode], int(ctx.per_leaf), ctx.margin, ctx.power,
+                                                  _lib.ptr(up), _lib.ptr(dpoints), _lib.ptr(dtf), _lib.ptr(scratch),
+                                                  _lib.stream_ptr()), name)
+        gp = dpoints.reshape(ctx.pshape).to(device=ctx.pdevice, dtype=ctx.pdtype) if need_p else None
+        gt = dtf.to(device=ctx.tdevice, dtype=ctx.tdtype) if need_tf else None
+        return None, gp, gt, None, None, None, None
+
+
+def hinge_over_points(composed, points, margin, power, mode, per_leaf):
+    from pytorch_volumetric_amd.sdf import HingeOverPoints
+    if len(composed.sdfs) > MAX_LEAVES:
+        raise _lib.PvamdError(f"gradients through a composition need at most {MAX_LEAVES} leaves, this one has {len(composed.sdfs)}")
+    val, cnt = HingeOverPointsQuery.apply(composed, points, composed._tf_matrix, margin, power, mode, per_leaf)
+    return HingeOverPoints(val, cnt)
+
+
 # ---------------------------------------------------------------- RobotSDF.set_joint_configuration (model_to_sdf.py:82-115)
 class ChainConfigure(torch.autograd.Function):
     """Forward: the one-launch HIP configure (pvamd_configure_chain), q (A, M) -> the (S*A, 4, 4) obj->leaf stack.  Backward:

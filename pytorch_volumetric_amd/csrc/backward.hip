@@ -17,6 +17,7 @@
 #include "grid_lookup.h"
 #include "interp.h"
 #include "leaf_vjp.h"
+#include "composed_point.h"
 
 namespace pvamd {
 
@@ -64,11 +65,16 @@ PVAMD_DEV T wave_sum(T v) {
 // four waves' slots are added in wave order and leave as one slab row [chunk][s*A + a][12] (every row written, zeros for
 // absent leaves: the slab needs no clearing).
 // CHAMFER: one leaf (the grid g0), tf = the B world->object matrices, dv = dsum[a] * d(scale v)^2/dv = dsum[a] 2 scale^2 v.
-template <typename T, bool HAS_V, bool HAS_G, bool WANT_TF, bool CHAMFER, bool INTERP>
+// HINGE (the upstream policy of hinge_over_points): no leaf ids and no (A, P) upstream.  Per pair the composed value v and the
+// winning leaf are recomputed with the forward's statements (mop_point, the same bits), and dv is torch's VJP of
+// (m - v).clamp(min=0) ** power summed over p, with upstream up[a * up_stride]: -(up (2 h)) (power 2) or -up (power 1) where
+// m - v >= 0, else -0.  A per-leaf hinge runs this kernel once per leaf as the one-leaf composition (hinge_backward).
+template <typename T, bool HAS_V, bool HAS_G, bool WANT_TF, bool CHAMFER, bool INTERP, bool HINGE = false>
 __global__ __launch_bounds__(kBwdBlock) void composed_backward_kernel(
     const pvamd_grid_t* __restrict__ grids, const pvamd_grid_t g0, int S, const T* __restrict__ tf, int A,
     const T* __restrict__ pts, int64_t P, const int32_t* __restrict__ leaf, const T* __restrict__ dval,
-    const T* __restrict__ dgrad, T scale, int aper, T* __restrict__ dp_out, T* __restrict__ slab) {
+    const T* __restrict__ dgrad, T scale, int aper, T* __restrict__ dp_out, T* __restrict__ slab,
+    const T* __restrict__ up = nullptr, int64_t up_stride = 0, T margin = T(0), int power = 0) {
     __shared__ T part[kBwdBlock / 64][kBwdMaxLeaves][12];
     __shared__ uint64_t present[kBwdBlock / 64];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -99,7 +105,17 @@ __global__ __launch_bounds__(kBwdBlock) void composed_backward_kernel(
             T c[12] = {};
             if (live[k]) {
                 const int64_t o = (int64_t)a * P + idx[k];
-                s = CHAMFER ? 0 : leaf[o];
+                T hdv = T(0);
+                if constexpr (HINGE) {
+                    T v, g[3];
+                    mop_point<T, INTERP>(grids, 0, S, tf, A, a, p[k], v, g, s);
+                    const T d = margin - v;
+                    const T u = up[(int64_t)a * up_stride];
+                    const T h = (d > T(0) || d != d) ? d : T(0);
+                    hdv = -((d >= T(0)) ? (power == 2 ? u * (T(2) * h) : u) : T(0));
+                } else {
+                    s = CHAMFER ? 0 : leaf[o];
+                }
                 if (s < 0 || s >= S) s = -1;  // a malformed leaf id contributes nothing (and is never dereferenced)
                 if (s >= 0) {
                     const pvamd_grid_t& g = CHAMFER ? g0 : grids[s];
@@ -113,7 +129,7 @@ __global__ __launch_bounds__(kBwdBlock) void composed_backward_kernel(
                     T x[3], gr[3] = {0, 0, 0}, dx[3] = {0, 0, 0};
                     LeafOps<T>::xform(M, p[k], x);
                     if (LeafOps<T>::inside(g, x)) {
-                        if constexpr (INTERP) InterpOps<T>::leaf(g, x, HAS_V ? dval[o] : T(0), dg, HAS_G, gr, dx);
+                        if constexpr (INTERP) InterpOps<T>::leaf(g, x, HINGE ? hdv : (HAS_V ? dval[o] : T(0)), dg, HAS_G, gr, dx);
                         else if (HAS_G) LeafOps<T>::record_grad(g, x, gr);
                         else s = -1;  // value-only upstream: an in-range winner contributes nothing
                     } else if (CHAMFER) {
@@ -123,7 +139,7 @@ __global__ __launch_bounds__(kBwdBlock) void composed_backward_kernel(
 #pragma unroll
                         for (int d = 0; d < 3; ++d) dx[d] = (t[d] != T(0)) ? dv * LeafOps<T>::div(t[d], nrm) : T(0);
                     } else {
-                        const T dv = HAS_V ? dval[o] : T(0);
+                        const T dv = HINGE ? hdv : (HAS_V ? dval[o] : T(0));
                         box_backward<T>(g, x, dv, dg, HAS_G, gr, dx);
                     }
 #pragma unroll
@@ -293,6 +309,76 @@ static int composed_backward(const pvamd_grid_t* grids, const pvamd_grid_t* g0, 
     return (int)hipGetLastError();
 }
 
+// sum[i] += add[i]: the per-leaf hinge's dpoints, leaf after leaf
+template <typename T>
+__global__ __launch_bounds__(256) void accumulate_kernel(const T* __restrict__ add, int64_t n, T* __restrict__ sum) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) sum[i] += add[i];
+}
+
+static int64_t round256(int64_t n) { return ((n + 255) / 256) * 256; }
+
+// pvamd_composed_hinge_over_points_backward: composed_backward_kernel under the HINGE policy.  per_leaf: one pass per leaf s as
+// the one-leaf composition (grids + s, the stack rows of s, upstream column s), its dtf rows written in place and its dpoints
+// added to the sum in leaf order.  Scratch: the plan's slab and split rows, then (per_leaf, S > 1) one [P][3] leaf term.
+static int64_t hinge_bwd_scratch_bytes(int S, int A, int64_t P, int per_leaf, size_t elem) {
+    const int Sg = per_leaf ? 1 : S;
+    const int64_t plan = bwd_scratch_bytes(Sg, A, P, elem);
+    return (per_leaf && S > 1) ? round256(plan) + P * 3 * (int64_t)elem : plan;
+}
+
+template <typename T, bool WANT_TF, bool INTERP>
+static void launch_hinge_backward(const BwdPlan& b, hipStream_t st, const pvamd_grid_t* grids, int S, const T* tf, int A,
+                                  const T* pts, int64_t P, const T* up, int64_t up_stride, T margin, int power, T* dp_out, T* slab) {
+    hipLaunchKernelGGL((composed_backward_kernel<T, true, false, WANT_TF, false, INTERP, true>), dim3((unsigned)b.nchunks, (unsigned)b.nsplit),
+                       dim3(kBwdBlock), 0, st, grids, pvamd_grid_t{}, S, tf, A, pts, P, nullptr, nullptr, nullptr, T(0), b.aper, dp_out,
+                       slab, up, up_stride, margin, power);
+}
+
+template <typename T>
+static int hinge_backward(const pvamd_grid_t* grids, int32_t S, const T* tf, int32_t A, const T* points, int64_t P, int32_t mode,
+                          int32_t per_leaf, T margin, int32_t power, const T* up, T* dpoints, T* dtf, void* scratch, void* stream) {
+    if (S < 1 || S > kBwdMaxLeaves || A < 1 || P < 1) return PVAMD_E_SHAPE;
+    if ((mode != PVAMD_LEAF_NEAREST && mode != PVAMD_LEAF_TRILINEAR) || (per_leaf != 0 && per_leaf != 1) ||
+        (power != 1 && power != 2))
+        return PVAMD_E_MODE;
+    if (!dpoints && !dtf) return 0;
+    if (!grids || !tf || !points || !up || !scratch) return PVAMD_E_NULL;
+    if (!aligned_to(grids, 8) || !aligned_to(tf, sizeof(T)) || !aligned_to(points, sizeof(T)) || !aligned_to(up, sizeof(T)) ||
+        !aligned_to(scratch, 16) || (dpoints && !aligned_to(dpoints, sizeof(T))) || (dtf && !aligned_to(dtf, sizeof(T))))
+        return PVAMD_E_ALIGN;
+    hipStream_t st = (hipStream_t)stream;
+    const int Z = per_leaf ? S : 1, Sg = per_leaf ? 1 : S;
+    const BwdPlan b = bwd_plan(Sg, A, P);
+    if (b.nchunks > 0x7fffffff) return PVAMD_E_SHAPE;
+    T* slab = (T*)scratch;
+    T* split_part = (T*)((char*)scratch + round256(b.slab_elems * (int64_t)sizeof(T)));
+    T* leaf_dp = (T*)((char*)scratch + round256(bwd_scratch_bytes(Sg, A, P, sizeof(T))));
+    const int64_t SgA = (int64_t)Sg * A;
+    for (int z = 0; z < Z; ++z) {
+        const pvamd_grid_t* gz = grids + (per_leaf ? z : 0);
+        const T* tz = tf + (per_leaf ? (int64_t)z * A * 16 : 0);
+        T* target = z == 0 ? dpoints : leaf_dp;
+        T* dp_out = dpoints ? (b.nsplit > 1 ? split_part : target) : nullptr;
+        if (mode == PVAMD_LEAF_TRILINEAR) {
+            if (dtf) launch_hinge_backward<T, true, true>(b, st, gz, Sg, tz, A, points, P, up + z, Z, margin, power, dp_out, slab);
+            else launch_hinge_backward<T, false, true>(b, st, gz, Sg, tz, A, points, P, up + z, Z, margin, power, dp_out, slab);
+        } else {
+            if (dtf) launch_hinge_backward<T, true, false>(b, st, gz, Sg, tz, A, points, P, up + z, Z, margin, power, dp_out, slab);
+            else launch_hinge_backward<T, false, false>(b, st, gz, Sg, tz, A, points, P, up + z, Z, margin, power, dp_out, slab);
+        }
+        if (dtf)
+            hipLaunchKernelGGL(reduce_tf_kernel<T>, dim3(stream_grid(SgA * 16, 256)), dim3(256), 0, st, slab, b.nchunks, SgA,
+                               dtf + (per_leaf ? (int64_t)z * A * 16 : 0));
+        if (dpoints && b.nsplit > 1)
+            hipLaunchKernelGGL(reduce_splits_kernel<T>, dim3(stream_grid(P * 3, 256)), dim3(256), 0, st, split_part, b.nsplit, P * 3,
+                               target);
+        if (dpoints && z > 0)
+            hipLaunchKernelGGL(accumulate_kernel<T>, dim3(stream_grid(P * 3, 256)), dim3(256), 0, st, leaf_dp, P * 3, dpoints);
+    }
+    return (int)hipGetLastError();
+}
+
 template <typename T, bool INTERP = false>
 static int cached_backward(const pvamd_grid_t* grid, const T* points, int64_t P, const T* dval, const T* dgrad, T* dpoints,
                            void* stream) {
@@ -381,4 +467,24 @@ extern "C" int pvamd_composed_query_interp_backward_f64(const pvamd_grid_t* grid
                                                         void* scratch, void* stream) {
     return composed_backward<double, true>(grids, nullptr, S, tf, A, points, P, out_leaf, dval, dgrad, 0.0, dpoints, dtf, scratch,
                                            stream, false);
+}
+
+// ---- hinge_over_points (include/pvamd.h "Hinge penalty over points") ----
+extern "C" int64_t pvamd_hinge_over_points_backward_scratch_bytes(int32_t S, int32_t A, int64_t P, int32_t per_leaf, int32_t is_f64) {
+    if (S < 1 || A < 1 || P < 1) return 0;
+    return hinge_bwd_scratch_bytes(S, A, P, per_leaf, is_f64 ? sizeof(double) : sizeof(float));
+}
+
+extern "C" int pvamd_composed_hinge_over_points_backward(const pvamd_grid_t* grids, int32_t S, const float* tf, int32_t A,
+                                                         const float* points, int64_t P, int32_t mode, int32_t per_leaf, float margin,
+                                                         int32_t power, const float* up, float* dpoints, float* dtf, void* scratch,
+                                                         void* stream) {
+    return hinge_backward<float>(grids, S, tf, A, points, P, mode, per_leaf, margin, power, up, dpoints, dtf, scratch, stream);
+}
+
+extern "C" int pvamd_composed_hinge_over_points_backward_f64(const pvamd_grid_t* grids, int32_t S, const double* tf, int32_t A,
+                                                             const double* points, int64_t P, int32_t mode, int32_t per_leaf,
+                                                             double margin, int32_t power, const double* up, double* dpoints,
+                                                             double* dtf, void* scratch, void* stream) {
+    return hinge_backward<double>(grids, S, tf, A, points, P, mode, per_leaf, margin, power, up, dpoints, dtf, scratch, stream);
 }

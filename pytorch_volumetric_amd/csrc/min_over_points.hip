@@ -20,6 +20,7 @@
 #include "grid_lookup.h"
 #include "interp.h"
 #include "leaf_vjp.h"
+#include "composed_point.h"
 
 namespace pvamd {
 
@@ -27,81 +28,6 @@ constexpr int kMopBlock = 256;
 constexpr int kMopK = PVAMD_MOP_CHUNK / kMopBlock;  // points per lane per chunk
 static_assert(kMopK * kMopBlock == PVAMD_MOP_CHUNK, "whole lanes per chunk");
 constexpr uint32_t kNoIndex = 0xffffffffu;
-
-// (val, gx, gy, gz) of one leaf at the leaf-frame point x
-template <typename T, bool INTERP> struct MopLeaf;
-
-template <> struct MopLeaf<float, false> {
-    static PVAMD_DEV void eval(const pvamd_grid_t& g, const float x[3], float o[4]) {
-        bool valid;
-        const float4 r = cached_lookup<false>(g, x[0], x[1], x[2], valid);
-        o[0] = r.x; o[1] = r.y; o[2] = r.z; o[3] = r.w;
-    }
-};
-
-template <> struct MopLeaf<float, true> {
-    static PVAMD_DEV void eval(const pvamd_grid_t& g, const float x[3], float o[4]) {
-        if (in_range(g, x[0], x[1], x[2])) {
-            InterpCell<float> c;
-            interp_cell<float>(g, x, c);
-            float4 r[8];
-            interp_gather(g, c.base, r);
-            interp_combine<float>(r, c.f, o);
-        } else {
-            const float4 b = bounding_box_sdf(g, x[0], x[1], x[2]);
-            o[0] = b.x; o[1] = b.y; o[2] = b.z; o[3] = b.w;
-        }
-    }
-};
-
-template <bool INTERP> struct MopLeaf<double, INTERP> {
-    static PVAMD_DEV void eval(const pvamd_grid_t& g, const double x[3], double o[4]) { leaf_f64<INTERP>(g, x, o); }
-};
-
-// The composed answer over leaves [s0, s1) at object-frame point p under configuration a: the first minimum (NaN counts as the
-// minimum) and the winner's gradient rotated back -- composed_interp_kernel's statements in float32, composed_query_f64_kernel's
-// in float64.  bs = the winning leaf.
-template <typename T, bool INTERP>
-PVAMD_DEV void mop_point(const pvamd_grid_t* __restrict__ grids, int s0, int s1, const T* __restrict__ tf, int A, int a,
-                         const T p[3], T& bv, T bg[3], int& bs) {
-    if constexpr (sizeof(T) == 4) {
-        bv = __builtin_inff();
-        T lg[3] = {__builtin_nanf(""), __builtin_nanf(""), __builtin_nanf("")};
-        bs = s0;
-        for (int s = s0; s < s1; ++s) {
-            const T* M = tf + 16 * ((int64_t)s * A + a);  // wave-uniform: scalar loads
-            T x[3], o[4];
-            LeafOps<T>::xform(M, p, x);
-            MopLeaf<T, INTERP>::eval(grids[s], x, o);
-            const bool take = !(o[0] >= bv) & (bv == bv);
-            bv = take ? o[0] : bv;
-            lg[0] = take ? o[1] : lg[0];
-            lg[1] = take ? o[2] : lg[1];
-            lg[2] = take ? o[3] : lg[2];
-            bs = take ? s : bs;
-        }
-        const T* M = tf + 16 * ((int64_t)bs * A + a);
-        bg[0] = fmaf(M[8], lg[2], fmaf(M[4], lg[1], mul_rn(M[0], lg[0])));
-        bg[1] = fmaf(M[9], lg[2], fmaf(M[5], lg[1], mul_rn(M[1], lg[0])));
-        bg[2] = fmaf(M[10], lg[2], fmaf(M[6], lg[1], mul_rn(M[2], lg[0])));
-    } else {
-        bv = 0.0;
-        bg[0] = bg[1] = bg[2] = 0.0;
-        bs = -1;
-        for (int s = s0; s < s1; ++s) {
-            const T* M = tf + 16 * ((int64_t)s * A + a);
-            T x[3], o[4];
-            LeafOps<T>::xform(M, p, x);
-            MopLeaf<T, INTERP>::eval(grids[s], x, o);
-            if ((bs < 0) || (o[0] < bv) || (o[0] != o[0] && bv == bv)) {
-                bv = o[0];
-                bs = s;
-#pragma unroll
-                for (int j = 0; j < 3; ++j) bg[j] = __builtin_fma(M[8 + j], o[3], __builtin_fma(M[4 + j], o[2], M[j] * o[1]));
-            }
-        }
-    }
-}
 
 // order-preserving key of a value: NaN -> 0 (below every number), -0 -> +0, then the usual sign-magnitude flip
 PVAMD_DEV uint64_t mop_key(float v) {

@@ -273,6 +273,12 @@ class RobotSDF(sdf.ObjectFrameSDF):
         set_joint_configuration was given a q that requires grad, as __call__ is."""
         return self.sdf.min_over_points(points, per_leaf=per_leaf)
 
+    def hinge_over_points(self, points, margin, power=2, per_leaf=False):
+        """ComposedSDF.hinge_over_points under the current joint configuration: per configuration (and per link with per_leaf;
+        leaf s is sdf_to_link_name[s]) the clearance cost sum_p max(margin - v, 0) ** power and the count of points inside the
+        margin.  Differentiable w.r.t. q when set_joint_configuration was given a q that requires grad, as __call__ is."""
+        return self.sdf.hinge_over_points(points, margin, power=power, per_leaf=per_leaf)
+
     def query_into(self, points, out_val, out_grad):
         """Allocation-free form of __call__ (see ComposedSDF.query_into); outputs are (A,P) and (A,P,3)."""
         self.sdf.query_into(points, out_val, out_grad)

@@ -8,6 +8,7 @@ import ctypes
 import enum
 import logging
 import math
+import numbers
 import os
 import typing
 from functools import partial
@@ -40,6 +41,13 @@ class MinOverPoints(NamedTuple):
     values: torch.Tensor
     indices: torch.Tensor
     gradients: torch.Tensor
+
+
+class HingeOverPoints(NamedTuple):
+    """ComposedSDF.hinge_over_points / RobotSDF.hinge_over_points: per pair, sum over points of max(margin - v, 0) ** power and
+    the number of points with v < margin (include/pvamd.h "Hinge penalty over points")."""
+    values: torch.Tensor
+    counts: torch.Tensor
 
 
 def first_argmin(v):
@@ -1282,6 +1290,107 @@ class ComposedSDF(ObjectFrameSDF):
         v = val.gather(1, idx.unsqueeze(1)).squeeze(1)
         g = grad.gather(1, idx.view(A, 1, 1).expand(A, 1, 3)).squeeze(1)
         return MinOverPoints(v.reshape(batch), idx.reshape(batch), g.reshape(*batch, 3))
+
+    # ---- hinge penalty over points ----
+    def hinge_over_points(self, points, margin, power=2, per_leaf=False):
+        """The clearance cost of an SDF-based trajectory optimiser, ((margin - v).clamp(min=0) ** power).sum over the points, for
+        every configuration, without the (A, P) field.
+
+        :param points: (..., 3); the leading dimensions are flattened into P
+        :param margin: a finite Python real number, rounded once to the query dtype (torch's rule for a scalar against a tensor)
+        :param power: 1 or 2
+        :param per_leaf: False: the hinge of the composed value (what __call__ returns); True: one hinge per leaf s
+            (leaf s = self.sdfs[s], alone under its own transforms)
+        :return: HingeOverPoints(values, counts) of shape B (per_leaf: B + (S,)), B the transform batch shape (() without one).
+            values have the dtype __call__ returns: each term is rounded in that dtype exactly as the torch expression rounds it,
+            and the terms are summed in float64 in a fixed order that depends only on (S, A, P), then rounded once (float32:
+            within 1 ulp of the exactly rounded sum; two calls give the same bits).  A NaN value makes its row NaN, as
+            torch.sum does.  counts are int64: the number of points with v < margin (a NaN is not counted).  No points give
+            zeros.  Differentiable w.r.t. the points and the transforms (a RobotSDF's joint values) when grad mode is on and
+            they require grad: the gradient torch autograd gives through ((margin - __call__(points)[0]).clamp(min=0) **
+            power).sum(-1) with the forward's decisions held fixed (clamp passes the gradient at v == margin; a nearest leaf in
+            range has no derivative w.r.t. the point); counts carry no gradient.  Gradients need at most 64 leaves;
+            create_graph=True raises.
+
+        Fused compositions (_fused_mode(): every leaf a BOUNDING_BOX CachedSDF of one interpolation, rigid transforms) with float32
+        or float64 points run HIP kernels (csrc/hinge_over_points.hip, and the backward in csrc/backward.hip) with extra memory
+        O(A Z P / 4096) (Z = 1, or S per leaf) and nothing that synchronises with the host, so the call can be captured in a
+        graph; anything else is __call__ plus the torch expression, summed in float64, under the same contract (differentiable
+        wherever __call__ is)."""
+        if not isinstance(per_leaf, bool):
+            raise TypeError(f"per_leaf must be True or False, got {per_leaf!r}")
+        if isinstance(margin, bool) or not isinstance(margin, numbers.Real):
+            raise TypeError(f"margin must be a Python real number, got {type(margin).__name__}")
+        margin = float(margin)
+        if not math.isfinite(margin):
+            raise ValueError(f"margin must be finite, got {margin!r}")
+        if isinstance(power, bool) or power not in (1, 2):
+            raise ValueError(f"power must be 1 or 2, got {power!r}")
+        power = int(power)
+        if not torch.is_tensor(points):
+            points = torch.as_tensor(points)
+        if points.dim() < 1 or points.shape[-1] != 3:
+            raise ValueError(f"query points must have last dimension 3, got {tuple(points.shape)}")
+        if self._tf_matrix is None:
+            raise ValueError("hinge_over_points needs the transforms to be set")
+        mode = self._fused_mode()
+        fused = mode is not None and points.dtype in (torch.float32, torch.float64)
+        if points.numel() == 0:  # torch's empty sum: zeros, nothing launched
+            batch = tuple(self.tsf_batch) if self.tsf_batch is not None else ()
+            shape = batch + ((len(self.sdfs),) if per_leaf else ())
+            dtype = points.dtype if points.dtype == torch.float64 or not fused else torch.float32
+            if not dtype.is_floating_point:
+                dtype = torch.get_default_dtype()
+            dev = getattr(self.sdfs[0], "device", self._tf_matrix.device)
+            return HingeOverPoints(torch.zeros(shape, dtype=dtype, device=dev), torch.zeros(shape, dtype=torch.int64, device=dev))
+        if not fused:
+            return self._hinge_over_points_generic(points, margin, power, per_leaf)
+        if (self._tf_grad or points.requires_grad) and torch.is_grad_enabled():
+            from pytorch_volumetric_amd import autograd
+            return autograd.hinge_over_points(self, points, margin, power, mode, per_leaf)
+        val, cnt = self._hinge_over_points_fused(points, margin, power, mode, per_leaf)[:2]
+        return HingeOverPoints(val, cnt)
+
+    def _hinge_over_points_fused(self, points, margin, power, mode, per_leaf):
+        """One pvamd_composed_hinge_over_points[_f64] call.  Returns (values, counts) in the result shapes on the leaves' device,
+        then what the backward needs: the flat points and the stack the kernels read."""
+        S = len(self.sdfs)
+        batch = tuple(self.tsf_batch) if self.tsf_batch is not None else ()
+        A = math.prod(batch)
+        dev = self._owner_device()
+        flat, tfd, dtype = self._fused_inputs(points, dev)
+        P, Z = flat.shape[0], S if per_leaf else 1
+        val = torch.empty((A, Z), dtype=flat.dtype, device=dev)
+        cnt = torch.empty((A, Z), dtype=torch.int64, device=dev)
+        name = "pvamd_composed_hinge_over_points" + ("_f64" if flat.dtype == torch.float64 else "")
+        with _lib.on_device(dev):
+            grids = self._leaf_grids(dev)
+            scratch = torch.empty((_lib.hinge_over_points_scratch_bytes(S, A, P, per_leaf),), dtype=torch.uint8, device=dev)
+            _lib.check(getattr(_lib.load(), name)(_lib.ptr(grids), S, _lib.ptr(tfd), A, _lib.ptr(flat), P, _lib.LEAF_MODES[mode],
+                                                  int(per_leaf), margin, power, _lib.ptr(val), _lib.ptr(cnt), _lib.ptr(scratch),
+                                                  _lib.stream_ptr()), name)
+        shape = batch + ((S,) if per_leaf else ())
+        out_device = self.sdfs[0].device  # leaves return on their own device (sdf.py:546)
+        return val.reshape(shape).to(device=out_device, dtype=dtype), cnt.reshape(shape).to(device=out_device), flat, tfd
+
+    def _hinge_over_points_generic(self, points, margin, power, per_leaf):
+        """Compositions the kernels do not serve (other leaves, mixed modes, other dtypes): __call__ (per leaf: the one-leaf
+        composition) and the torch expression, summed in float64 -- not a hot path.  Differentiable through __call__."""
+        batch = tuple(self.tsf_batch) if self.tsf_batch is not None else ()
+        if per_leaf:
+            parts = []
+            for s in range(len(self.sdfs)):
+                one = ComposedSDF([self.sdfs[s]], None)
+                one.set_transforms(self._tf_matrix[self.ith_transform_slice(s)], batch_dim=self.tsf_batch,
+                                   known_rigid=self._rigid)
+                parts.append(one._hinge_over_points_generic(points, margin, power, False))
+            return HingeOverPoints(*(torch.stack(t, dim=len(batch)) for t in zip(*parts)))
+        A = math.prod(batch)
+        val = self(points)[0].reshape(A, -1)
+        terms = (margin - val).clamp(min=0) ** power
+        values = terms.to(torch.float64).sum(-1).to(val.dtype)
+        counts = (val.detach() < margin).sum(-1)
+        return HingeOverPoints(values.reshape(batch), counts.reshape(batch))
 
     def _interp_forward(self, points, want_leaf):
         """_fused_forward of a trilinear composition (the leaf ids the interpolation tests compare)."""
