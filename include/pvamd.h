@@ -588,6 +588,55 @@ int pvamd_composed_min_over_points_backward_f64(const pvamd_grid_t* grids, int32
                                                 const int64_t* index, const int32_t* leaf, const double* dval, const double* dgrad,
                                                 double* dpoints, double* dtf, void* scratch, void* stream);
 
+/* ---- Leaf-pair distance (ComposedSDF.leaf_pair_distance / RobotSDF.self_collision_distance) ----
+ * A composition of S leaves under A configurations (tf: device [S*A][4][4] leaf-major, rigid, in the query dtype; the float64
+ * stack is the exact widening of the float32 one), K ordered pairs k = (s, t), s != t, and one point set per leaf, given in that
+ * leaf's own frame and packed into one [npoints][3] array.  table: device int64 [K][4] = (s, t, offset of set t in the packed
+ * points, P_t >= 1).
+ *  1. Pair transform.  Ms = stack row (s, a), Mt = stack row (t, a).  For i, j < 3:
+ *       C[i][j] = fma(Ms[i][2], Mt[j][2], fma(Ms[i][1], Mt[j][1], Ms[i][0] * Mt[j][0]))          (Rs Rt^T)
+ *       C[i][3] = Ms[i][3] - fma(C[i][2], Mt[2][3], fma(C[i][1], Mt[1][3], C[i][0] * Mt[0][3]))  (ts - C_rot tt)
+ *     row 3 = (0, 0, 0, 1).  C maps leaf t's frame to leaf s's frame.  Stored [K][A][4][4] (pair-major).
+ *  2. out_val[a][k], out_index[a][k], out_grad[a][k] are bit for bit what pvamd_composed_min_over_points (per_leaf = 0) gives for
+ *     the one-leaf composition (grids[s], stack C[k]) over the P_t points of set t: the same leaf statements, the same index
+ *     rule (NaN is the minimum, -0.0 ties +0.0, the smallest index wins), the index into set t.  The gradient is leaf s's SDF
+ *     gradient at the witness point rotated back by C: it is expressed in LEAF t's FRAME.
+ *  3. Bitwise reproducible whatever the launch geometry; no device -> host synchronisation, no allocation, no float atomics.
+ *     Extra memory: one 16-byte key per pair, configuration and 4096-point chunk when a set holds more than one chunk, else none.
+ *  4. Backward: the VJP of item 2 w.r.t. the pair's transform (the single-pair statements of
+ *     pvamd_composed_min_over_points_backward, decisions held fixed), then the VJP of item 1 to both stack rows, each row's
+ *     gradient summed over the pairs that use it (as s or as t) in increasing k.  Points carry no gradient.  S <= 64.
+ * pvamd_leaf_pair_transforms / _f64: out [K][A][4][4].  K = 0 does nothing.  A pair with a leaf out of range gives NaN rows.
+ * pvamd_leaf_pair_distance / _f64: C = the pair transforms; out_val [A][K], out_grad [A][K][3], out_index [A][K] int64 (-1 and
+ *   NaN for a malformed table row).  max_points = the largest P_t of the table (1 <= max_points <= 2^32 - 2).  scratch: device,
+ *   PVAMD_LEAF_PAIR_SCRATCH_BYTES(K, A, max_points, sizeof(T), 0) bytes, 16-byte aligned (NULL when that is 0).
+ * pvamd_leaf_pair_distance_backward / _f64: given the forward's out_index, dval [A][K] and dgrad [A][K][3] (either may be NULL),
+ *   writes dtf [S*A][4][4] (every row; rows no pair uses and row 3 zero).  scratch: PVAMD_LEAF_PAIR_SCRATCH_BYTES(K, A,
+ *   max_points, sizeof(T), 1) bytes, 16-byte aligned (24 values per pair and configuration: dMs and dMt).                         */
+#define PVAMD_LEAF_PAIR_SCRATCH_BYTES(K, A, max_points, elem, backward)                                           \
+    ((backward) ? 24 * (int64_t)(K) * (int64_t)(A) * (int64_t)(elem)                                             \
+                : ((((int64_t)(max_points) + PVAMD_MOP_CHUNK - 1) / PVAMD_MOP_CHUNK) > 1                          \
+                       ? 16 * (int64_t)(K) * (int64_t)(A) * (((int64_t)(max_points) + PVAMD_MOP_CHUNK - 1) / PVAMD_MOP_CHUNK) \
+                       : 0))
+int64_t pvamd_leaf_pair_scratch_bytes(int32_t K, int32_t A, int64_t max_points, int32_t is_f64, int32_t backward);
+int pvamd_leaf_pair_transforms(const float* tf, int32_t S, int32_t A, const int64_t* table, int32_t K, float* out, void* stream);
+int pvamd_leaf_pair_transforms_f64(const double* tf, int32_t S, int32_t A, const int64_t* table, int32_t K, double* out,
+                                   void* stream);
+int pvamd_leaf_pair_distance(const pvamd_grid_t* grids, int32_t S, const float* C, int32_t A, const float* points, int64_t npoints,
+                             const int64_t* table, int32_t K, int64_t max_points, int32_t mode, float* out_val, float* out_grad,
+                             int64_t* out_index, void* scratch, void* stream);
+int pvamd_leaf_pair_distance_f64(const pvamd_grid_t* grids, int32_t S, const double* C, int32_t A, const double* points,
+                                 int64_t npoints, const int64_t* table, int32_t K, int64_t max_points, int32_t mode, double* out_val,
+                                 double* out_grad, int64_t* out_index, void* scratch, void* stream);
+int pvamd_leaf_pair_distance_backward(const pvamd_grid_t* grids, int32_t S, const float* tf, const float* C, int32_t A,
+                                      const float* points, int64_t npoints, const int64_t* table, int32_t K, int32_t mode,
+                                      const int64_t* index, const float* dval, const float* dgrad, float* dtf, void* scratch,
+                                      void* stream);
+int pvamd_leaf_pair_distance_backward_f64(const pvamd_grid_t* grids, int32_t S, const double* tf, const double* C, int32_t A,
+                                          const double* points, int64_t npoints, const int64_t* table, int32_t K, int32_t mode,
+                                          const int64_t* index, const double* dval, const double* dgrad, double* dtf,
+                                          void* scratch, void* stream);
+
 /* ---- Hinge penalty over points (ComposedSDF.hinge_over_points / RobotSDF.hinge_over_points) ----
  * The compositions, pairs and per-leaf values of "Minimum over points": v(a, p) the composed value (per_leaf = 0, Z = 1) or
  * v_s(a, p) the one-leaf composition's (per_leaf = 1, Z = S, pairs stored [A][S]), the bits of the fused forwards.

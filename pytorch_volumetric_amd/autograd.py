@@ -235,6 +235,99 @@ def hinge_over_points(composed, points, margin, power, mode, per_leaf):
     return HingeOverPoints(val, cnt)
 
 
+
+# ---------------------------------------------------------------- ComposedSDF.leaf_pair_distance (include/pvamd.h "Leaf-pair distance")
+class LeafPairQuery(torch.autograd.Function):
+    """Forward: ComposedSDF._leaf_pair_fused.  Backward: pvamd_leaf_pair_distance_backward -- per (configuration, pair) the
+    single-pair VJP w.r.t. the pair transform, then the pair transform's VJP to both stack rows, summed per row in pair order."""
+
+    @staticmethod
+    def forward(ctx, composed, tfm, plan, mode):
+        ctx.set_materialize_grads(False)
+        val, idx, grad, idx_k, C, tfd = composed._leaf_pair_fused(plan, mode)
+        ctx.mark_non_differentiable(idx)
+        ctx.composed, ctx.plan, ctx.mode, ctx.idx, ctx.C, ctx.tfd = composed, plan, mode, idx_k, C, tfd
+        ctx.grids = composed._leaf_grids(plan["dev"])
+        ctx.save_for_backward(tfm)  # torch's in-place check of the input tfd may alias
+        ctx.S, ctx.A, ctx.K = len(composed.sdfs), idx_k.shape[0], idx_k.shape[1]
+        ctx.tdtype, ctx.tdevice = tfm.dtype, tfm.device
+        return val, idx, grad
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dval, didx, dgrad):
+        ctx.saved_tensors
+        plan, S, A, K = ctx.plan, ctx.S, ctx.A, ctx.K
+        dev, dt = plan["dev"], plan["dtype"]
+        dv = _upstream(dval, dev, dt, (A, K))
+        dg = _upstream(dgrad, dev, dt, (A, K, 3))
+        dtf = torch.empty((S * A, 4, 4), dtype=dt, device=dev)
+        f64 = dt == torch.float64
+        name = "pvamd_leaf_pair_distance_backward" + ("_f64" if f64 else "")
+        with _lib.on_device(dev):
+            scratch = torch.empty((_lib.leaf_pair_scratch_bytes(K, A, plan["max_points"], f64, True),), dtype=torch.uint8,
+                                  device=dev)
+            _lib.check(getattr(_lib.load(), name)(_lib.ptr(ctx.grids), S, _lib.ptr(ctx.tfd), _lib.ptr(ctx.C), A,
+                                                  _lib.ptr(plan["packed"]), plan["npoints"], _lib.ptr(plan["table"]), K,
+                                                  _lib.LEAF_MODES[ctx.mode], _lib.ptr(ctx.idx), _lib.ptr(dv), _lib.ptr(dg),
+                                                  _lib.ptr(dtf), _lib.ptr(scratch), _lib.stream_ptr()), name)
+        return None, dtf.to(device=ctx.tdevice, dtype=ctx.tdtype), None, None
+
+
+def leaf_pair_distance(composed, plan, mode):
+    from pytorch_volumetric_amd.sdf import LeafPairDistance
+    if len(composed.sdfs) > MAX_LEAVES:
+        raise _lib.PvamdError(f"gradients through a composition need at most {MAX_LEAVES} leaves, this one has {len(composed.sdfs)}")
+    val, idx, grad = LeafPairQuery.apply(composed, composed._tf_matrix, plan, mode)
+    return LeafPairDistance(val, idx, grad)
+
+
+def pair_transforms_torch(stack, pairs):
+    """The pair transforms of include/pvamd.h "Leaf-pair distance" 1 in torch (any dtype, differentiable): stack (S, A, 4, 4),
+    pairs (K, 2) -> (K, A, 4, 4).  Rounding aside (torch's matmul does not promise the kernel's fma order), the same C."""
+    Ms, Mt = stack[pairs[:, 0]], stack[pairs[:, 1]]
+    R = Ms[..., :3, :3] @ Mt[..., :3, :3].transpose(-1, -2)
+    t = Ms[..., :3, 3] - (R @ Mt[..., :3, 3:4]).squeeze(-1)
+    top = torch.cat((R, t.unsqueeze(-1)), dim=-1)
+    bottom = torch.zeros_like(top[..., :1, :])
+    bottom[..., 0, 3] = 1
+    return torch.cat((top, bottom), dim=-2)
+
+
+class PairTransforms(torch.autograd.Function):
+    """Forward: pvamd_leaf_pair_transforms (ComposedSDF._pair_transforms).  Backward (the generic leaf-pair path only): the VJP of
+    the same statements in float64 torch on the host, the stack rows summed in pair order -- K x A work, not a hot path."""
+
+    @staticmethod
+    def forward(ctx, composed, tfm, table, pairs, dtype, dev):
+        ctx.set_materialize_grads(False)
+        C, _ = composed._pair_transforms(table, pairs.shape[0], dtype, dev)
+        ctx.save_for_backward(tfm)
+        ctx.pairs = pairs
+        return C
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dC):
+        (tfm,) = ctx.saved_tensors
+        if dC is None:
+            return None, None, None, None, None, None
+        K, A = dC.shape[0], dC.shape[1]
+        S = tfm.shape[0] // A
+        stack = tfm.detach().to(device="cpu", dtype=torch.float64).reshape(S, A, 4, 4)
+        with torch.enable_grad():
+            rows = [stack[u].clone().requires_grad_() for u in range(S)]
+            C = pair_transforms_torch(torch.stack(rows), ctx.pairs)
+            grads = torch.autograd.grad(C, rows, dC.detach().to(device="cpu", dtype=torch.float64), allow_unused=True)
+        d = torch.stack([g if g is not None else torch.zeros_like(stack[0]) for g in grads]).reshape(S * A, 4, 4)
+        return None, d.to(device=tfm.device, dtype=tfm.dtype), None, None, None, None
+
+
+def pair_transforms(composed, table, pairs, dtype, dev):
+    if composed._tf_grad and torch.is_grad_enabled():
+        return PairTransforms.apply(composed, composed._tf_matrix, table, pairs, dtype, dev)
+    return composed._pair_transforms(table, pairs.shape[0], dtype, dev)[0]
+
 # ---------------------------------------------------------------- RobotSDF.set_joint_configuration (model_to_sdf.py:82-115)
 class ChainConfigure(torch.autograd.Function):
     """Forward: the one-launch HIP configure (pvamd_configure_chain), q (A, M) -> the (S*A, 4, 4) obj->leaf stack.  Backward:

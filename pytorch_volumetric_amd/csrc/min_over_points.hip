@@ -27,40 +27,6 @@ namespace pvamd {
 constexpr int kMopBlock = 256;
 constexpr int kMopK = PVAMD_MOP_CHUNK / kMopBlock;  // points per lane per chunk
 static_assert(kMopK * kMopBlock == PVAMD_MOP_CHUNK, "whole lanes per chunk");
-constexpr uint32_t kNoIndex = 0xffffffffu;
-
-// order-preserving key of a value: NaN -> 0 (below every number), -0 -> +0, then the usual sign-magnitude flip
-PVAMD_DEV uint64_t mop_key(float v) {
-    if (v != v) return 0;
-    uint32_t u = (uint32_t)__float_as_int(v == 0.f ? 0.f : v);
-    return (u >> 31) ? (uint64_t)(~u) : (uint64_t)(u | 0x80000000u);
-}
-PVAMD_DEV uint64_t mop_key(double v) {
-    if (v != v) return 0;
-    uint64_t u = (uint64_t)__double_as_longlong(v == 0.0 ? 0.0 : v);
-    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-
-struct MopKey {
-    uint64_t key;  // mop_key of the value; ~0 when the slot saw no point
-    uint32_t idx;  // point index; kNoIndex when the slot saw no point
-    uint32_t pad;
-};
-
-PVAMD_DEV bool mop_less(uint64_t k0, uint32_t i0, uint64_t k1, uint32_t i1) { return k0 < k1 || (k0 == k1 && i0 < i1); }
-
-// the minimum (key, idx) over the wave, in every lane
-PVAMD_DEV void mop_wave_min(uint64_t& k, uint32_t& i) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const uint32_t lo = __shfl_xor((unsigned)(k & 0xffffffffu), off, 64);
-        const uint32_t hi = __shfl_xor((unsigned)(k >> 32), off, 64);
-        const uint32_t oi = __shfl_xor((unsigned)i, off, 64);
-        const uint64_t ok = ((uint64_t)hi << 32) | lo;
-        if (mop_less(ok, oi, k, i)) { k = ok; i = oi; }
-    }
-}
-
 // ---- pass 1: workgroup (chunk, a, z) -> part[(a * Z + z) * nchunks + chunk] ----
 template <typename T, bool INTERP>
 __global__ __launch_bounds__(kMopBlock) void mop_partial_kernel(const pvamd_grid_t* __restrict__ grids, int S,

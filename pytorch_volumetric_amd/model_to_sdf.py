@@ -38,7 +38,9 @@ class RobotSDF(sdf.ObjectFrameSDF):
         self.frame_names = self.chain.get_frame_names(exclude_fixed=False)
         self.sdf: typing.Optional[sdf.ComposedSDF] = None
         self.sdf_to_link_name = []
+        self.link_factories = []
         self.configuration_batch = None
+        self._sc_points, self._sc_pairs = None, None  # set_self_collision_points / self_collision_pairs
 
         sdfs, offsets = self._collect_mesh_links(path_prefix, link_sdf_cls)
         self.offset_transforms = tf.Transform3d(matrix=torch.cat([tf.as_matrix(o) for o in offsets], dim=0)).to(
@@ -55,7 +57,9 @@ class RobotSDF(sdf.ObjectFrameSDF):
                     logger.warning(f"Cannot handle non-mesh link visual type {visual} for {link.name}")
                     continue
                 mesh_file, mesh_scale = visual.geom_param[0], visual.geom_param[1]
-                sdfs.append(link_sdf_cls(sdf.MeshObjectFactory(mesh_file, scale=mesh_scale, path_prefix=path_prefix)))
+                factory = sdf.MeshObjectFactory(mesh_file, scale=mesh_scale, path_prefix=path_prefix)
+                sdfs.append(link_sdf_cls(factory))
+                self.link_factories.append(factory)  # each leaf's mesh, for set_self_collision_points
                 offsets.append(visual.offset)
                 self.sdf_to_link_name.append(link.name)
         if not sdfs:
@@ -279,6 +283,54 @@ class RobotSDF(sdf.ObjectFrameSDF):
         margin.  Differentiable w.r.t. q when set_joint_configuration was given a q that requires grad, as __call__ is."""
         return self.sdf.hinge_over_points(points, margin, power=power, per_leaf=per_leaf)
 
+    def set_self_collision_points(self, points=None, num_points=256, seed=0):
+        """The point set of each leaf that self_collision_distance moves against the other leaves' SDFs.
+
+        :param points: None: num_points surface samples per leaf from that leaf's own mesh (sample_mesh_points, seed `seed`, no
+            cache file); else a sequence of S tensors (P_s, 3), each in its leaf's frame (leaf s is sdf_to_link_name[s])
+        The points are packed onto the GPU once, with the pair table of the default pairs."""
+        S = len(self.sdf_to_link_name)
+        if points is None:
+            dev = _lib.require_gpu()
+            points = [sdf.sample_mesh_points(f, num_points=num_points, seed=seed, dbpath=None, device=dev)[0]
+                      for f in self.link_factories]
+        elif isinstance(points, torch.Tensor) or len(points) != S:
+            raise ValueError(f"points must be a sequence of {S} point sets, one per leaf")
+        pts = []
+        for i, p in enumerate(points):
+            p = torch.as_tensor(p)
+            if p.dim() != 2 or p.shape[-1] != 3:
+                raise ValueError(f"points[{i}] must have shape (P, 3), got {tuple(p.shape)}")
+            pts.append(p.detach().to(dtype=p.dtype if p.dtype == torch.float64 else torch.float32).contiguous())
+        self._sc_points = pts
+        if self.sdf._tf_matrix is not None and self.self_collision_pairs().shape[0]:
+            self.sdf._leaf_pair_plan(self._sc_points, self.self_collision_pairs())
+
+    def self_collision_pairs(self):
+        """The default (K, 2) int64 table of ordered leaf pairs for self_collision_distance: every ordered pair of non-adjacent
+        leaves (model_to_sdf.self_collision_pairs), sorted by (s, t)."""
+        if self._sc_pairs is None:
+            self._sc_pairs = self_collision_pairs(self.chain, self.sdf_to_link_name)
+        return self._sc_pairs
+
+    def self_collision_distance(self, pairs=None):
+        """ComposedSDF.leaf_pair_distance of the self-collision points (set_self_collision_points; sampled with its defaults on
+        first use) under the current joint configuration.  Per configuration and pair (s, t): how close leaf t's points come to
+        leaf s -- values, indices into leaf t's points, and gradients in leaf t's frame.  The two directions of a pair are
+        different queries; torch.minimum of the two gives the symmetric distance.  Differentiable w.r.t. q when
+        set_joint_configuration was given a q that requires grad.
+
+        :param pairs: int (K, 2) ordered leaf pairs; None = self_collision_pairs()
+        :return: LeafPairDistance(values, indices, gradients) of shapes [A] + (K,), [A] + (K,), [A] + (K, 3)"""
+        if self._sc_points is None:
+            self.set_self_collision_points()
+        return self.sdf.leaf_pair_distance(self._sc_points, self.self_collision_pairs() if pairs is None else pairs)
+
+    def link_pair_transforms(self, pairs=None):
+        """ComposedSDF.leaf_pair_transforms under the current joint configuration: [A] + (K, 4, 4) leaf t frame -> leaf s frame
+        transforms of the pairs (None = self_collision_pairs())."""
+        return self.sdf.leaf_pair_transforms(self.self_collision_pairs() if pairs is None else pairs)
+
     def query_into(self, points, out_val, out_grad):
         """Allocation-free form of __call__ (see ComposedSDF.query_into); outputs are (A,P) and (A,P,3)."""
         self.sdf.query_into(points, out_val, out_grad)
@@ -290,6 +342,52 @@ class RobotSDF(sdf.ObjectFrameSDF):
 
     def query_prepared(self, prepared, order="caller"):
         return self.sdf.query_prepared(prepared, order=order)
+
+
+def _link_parents(chain):
+    """{link name: parent link name or None} of a kinematic tree: a kinematics.Chain's frames, or a pytorch_kinematics chain's
+    frame tree (its root frame and the children of each frame)."""
+    frames = getattr(chain, "_frames", None)
+    if frames is not None and all(hasattr(f, "parent") and hasattr(f, "link") for f in frames):
+        return {f.link.name: (None if f.parent is None else frames[f.parent].link.name) for f in frames}
+    root = getattr(chain, "_root", None)
+    if root is not None and hasattr(root, "children") and hasattr(root, "link"):
+        parents, todo = {root.link.name: None}, [root]
+        while todo:
+            f = todo.pop()
+            for c in f.children:
+                parents[c.link.name] = f.link.name
+                todo.append(c)
+        return parents
+    raise ValueError("cannot read the kinematic tree of this chain to choose the self-collision pairs; pass pairs explicitly")
+
+
+def self_collision_pairs(chain, sdf_to_link_name):
+    """The default self-collision pairs of a robot (host only): every ordered pair (s, t), s != t, of non-adjacent leaves, sorted
+    by (s, t), as an int64 (K, 2) tensor.  Leaves are adjacent when they belong to the same link, or when one leaf's link is the
+    nearest leaf-carrying ancestor of the other's (links without a leaf are collapsed, so a mesh-less link between two meshed
+    links does not hide their joint).  Both directions are listed, because they are different queries (the points of t
+    against the SDF of s); torch.minimum of the two gives the symmetric distance.
+
+    :param chain: a kinematics.Chain or a pytorch_kinematics chain (its frame tree); anything else raises ValueError
+    :param sdf_to_link_name: the link of each leaf (RobotSDF.sdf_to_link_name)"""
+    parents = _link_parents(chain)
+    names = list(sdf_to_link_name)
+    missing = sorted(set(names) - set(parents))
+    if missing:
+        raise ValueError(f"links {missing} are not in the chain's kinematic tree; pass pairs explicitly")
+    meshed = set(names)
+
+    def carrier(name):  # the nearest leaf-carrying ancestor
+        p = parents[name]
+        while p is not None and p not in meshed:
+            p = parents.get(p)
+        return p
+
+    anc = {n: carrier(n) for n in meshed}
+    out = [(s, t) for s in range(len(names)) for t in range(len(names))
+           if s != t and names[s] != names[t] and anc[names[s]] != names[t] and anc[names[t]] != names[s]]
+    return torch.tensor(out, dtype=torch.int64).reshape(-1, 2)
 
 
 def cache_link_sdf_factory(resolution=0.01, padding=0.1, **kwargs):

@@ -50,6 +50,15 @@ class HingeOverPoints(NamedTuple):
     counts: torch.Tensor
 
 
+class LeafPairDistance(NamedTuple):
+    """ComposedSDF.leaf_pair_distance / RobotSDF.self_collision_distance: per configuration and ordered leaf pair (s, t), the point
+    of leaf t's set where leaf s's SDF is smallest, the value there and leaf s's gradient expressed in leaf t's frame
+    (include/pvamd.h "Leaf-pair distance")."""
+    values: torch.Tensor
+    indices: torch.Tensor
+    gradients: torch.Tensor
+
+
 def first_argmin(v):
     """The index rule of min_over_points along the last dimension: a NaN counts as the minimum, -0.0 and +0.0 tie, and the
     smallest index among the minima wins.  Plain torch, no device -> host synchronisation."""
@@ -1391,6 +1400,193 @@ class ComposedSDF(ObjectFrameSDF):
         values = terms.to(torch.float64).sum(-1).to(val.dtype)
         counts = (val.detach() < margin).sum(-1)
         return HingeOverPoints(values.reshape(batch), counts.reshape(batch))
+
+    # ---- leaf-pair distance ----
+    def _pair_device(self):
+        """The GPU the pair kernels run on: the leaves' own for fused compositions, else the current one."""
+        return self._owner_device() if self._fused_mode() is not None else _lib.require_gpu()
+
+    def _pairs_host(self, pairs):
+        """pairs -> (K, 2) int64 CPU tensor, validated against the leaf count (a device tensor is read once)."""
+        S = len(self.sdfs)
+        p = pairs if torch.is_tensor(pairs) else torch.as_tensor(pairs, dtype=torch.int64)
+        if p.dtype.is_floating_point or p.dtype.is_complex or p.dtype == torch.bool:
+            raise ValueError(f"pairs must be integers, got {p.dtype}")
+        if p.numel() == 0:
+            p = p.reshape(0, 2)
+        if p.dim() != 2 or p.shape[1] != 2:
+            raise ValueError(f"pairs must have shape (K, 2), got {tuple(p.shape)}")
+        p = p.detach().to(device="cpu", dtype=torch.int64)
+        if p.numel():
+            if int(p.min()) < 0 or int(p.max()) >= S:
+                raise ValueError(f"pair index out of range for {S} leaves")
+            if bool((p[:, 0] == p[:, 1]).any()):
+                raise ValueError("a pair (s, t) needs s != t")
+        return p
+
+    def _stack_for(self, dtype, dev):
+        """The (S*A, 4, 4) stack the pair kernels read: float32, or the exact float64 widening of what __call__ reads."""
+        if dtype == torch.float64:
+            tfd = self.__dict__.get("_tf_dev64")
+            if tfd is None or tfd.device != dev:
+                tfd = self._tf_dev64 = self._tf_matrix.detach().to(device=dev, dtype=torch.float64).contiguous()
+            return tfd
+        return self._tf_device(dev)
+
+    def _leaf_pair_plan(self, leaf_points, pairs):
+        """Validated pairs, the device pair table (s, t, offset, P_t) and the packed points, built once per (pairs, points) and
+        kept while the caller passes the same unmodified tensors (the cache holds them, so their ids cannot be re-used)."""
+        S = len(self.sdfs)
+        if isinstance(leaf_points, torch.Tensor) or len(leaf_points) != S:
+            raise ValueError(f"leaf_points must be a sequence of {S} point sets, one per leaf")
+        inputs = (pairs, *leaf_points)
+        key = tuple((x.data_ptr(), x._version, tuple(x.shape), x.dtype, str(x.device)) if torch.is_tensor(x) else None
+                    for x in inputs)
+        hit = self.__dict__.get("_pair_plan")
+        if hit is not None and None not in key and len(hit[0]) == len(inputs) and \
+                all(a is b for a, b in zip(hit[0], inputs)) and hit[1] == key:
+            return hit[2]
+        ph = self._pairs_host(pairs)
+        pts = [p if torch.is_tensor(p) else torch.as_tensor(p) for p in leaf_points]
+        for i, p in enumerate(pts):
+            if p.dim() < 1 or p.shape[-1] != 3:
+                raise ValueError(f"leaf_points[{i}] must have last dimension 3, got {tuple(p.shape)}")
+        counts = [p.numel() // 3 for p in pts]
+        for t in ph[:, 1].tolist():
+            if counts[t] == 0:
+                raise ValueError(f"leaf_points[{t}] is empty but a pair uses it as its point side")
+        qdtype = torch.float64 if any(p.dtype == torch.float64 for p in pts) else torch.float32
+        if ph.shape[0] == 0:  # nothing to pack or launch
+            dev = getattr(self.sdfs[0], "device", None) or self._tf_matrix.device
+            return dict(pairs=ph, dtype=qdtype, dev=torch.device(dev))
+        dev = self._pair_device()
+        offs = [0]
+        for c in counts:
+            offs.append(offs[-1] + c)
+        packed = torch.cat([p.detach().reshape(-1, 3).to(device=dev, dtype=qdtype) for p in pts]).contiguous()
+        table = torch.tensor([[s, t, offs[t], counts[t]] for s, t in ph.tolist()], dtype=torch.int64).reshape(-1, 4).to(dev)
+        max_points = max((counts[t] for t in ph[:, 1].tolist()), default=0)
+        plan = dict(pairs=ph, table=table, packed=packed, npoints=offs[-1], max_points=max_points, dtype=qdtype, dev=dev,
+                    points=pts)
+        if None not in key:
+            self._pair_plan = (inputs, key, plan)
+        return plan
+
+    def _pair_transforms(self, table, K, dtype, dev):
+        """pvamd_leaf_pair_transforms[_f64]: (K, A, 4, 4) in dtype on dev, from the stack the kernels read."""
+        S = len(self.sdfs)
+        A = math.prod(self.tsf_batch) if self.tsf_batch is not None else 1
+        tfd = self._stack_for(dtype, dev)
+        C = torch.empty((K, A, 4, 4), dtype=dtype, device=dev)
+        if K:
+            name = "pvamd_leaf_pair_transforms" + ("_f64" if dtype == torch.float64 else "")
+            with _lib.on_device(dev):
+                _lib.check(getattr(_lib.load(), name)(_lib.ptr(tfd), S, A, _lib.ptr(table), K, _lib.ptr(C), _lib.stream_ptr()), name)
+        return C, tfd
+
+    def leaf_pair_transforms(self, pairs, dtype=torch.float32):
+        """The leaf t frame -> leaf s frame transforms of the ordered pairs (s, t): C = Ms Mt^-1 with the rigid inverse, the exact
+        bits leaf_pair_distance uses (include/pvamd.h "Leaf-pair distance" 1).
+
+        :param pairs: int (K, 2) ordered leaf pairs (s, t), s != t
+        :param dtype: torch.float32 or torch.float64 (the float64 stack is the exact widening of the float32 one)
+        :return: B + (K, 4, 4), B the transform batch shape (() without one).  Not differentiable."""
+        if dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"dtype must be torch.float32 or torch.float64, got {dtype}")
+        self._check_pair_transforms()
+        ph = self._pairs_host(pairs)
+        K = ph.shape[0]
+        batch = tuple(self.tsf_batch) if self.tsf_batch is not None else ()
+        if K == 0:
+            return torch.empty(batch + (0, 4, 4), dtype=dtype, device=self._tf_matrix.device)
+        dev = self._pair_device()
+        table = torch.cat((ph, torch.zeros_like(ph)), dim=1).to(dev)
+        C, _ = self._pair_transforms(table, K, dtype, dev)
+        return C.transpose(0, 1).reshape(*batch, K, 4, 4)
+
+    def _check_pair_transforms(self):
+        if self._tf_matrix is None:
+            raise ValueError("leaf-pair queries need the transforms to be set")
+        if not self._rigid:
+            raise ValueError("leaf-pair queries need rigid transforms (the pair transform inverts each leaf transform as a rigid one)")
+
+    def leaf_pair_distance(self, leaf_points, pairs):
+        """For every configuration and ordered pair (s, t): the point of leaf t's set where leaf s's SDF is smallest -- how
+        close leaf t comes to leaf s -- without an (A, K, P) buffer.
+
+        :param leaf_points: a sequence of S point sets (P_s, 3), each in its own leaf's frame (leaf s = self.sdfs[s], the frame
+            its SDF is queried in).  A set may be empty only if no pair uses it as its point side.  float64 results when any set
+            is float64 (the others are widened exactly), float32 otherwise.
+        :param pairs: int (K, 2) ordered pairs (s, t), s != t: the points of leaf t against the SDF of leaf s.  The two directions
+            are different queries; torch.minimum of the two gives the symmetric distance.
+        :return: LeafPairDistance(values, indices, gradients) of shapes B + (K,), B + (K,), B + (K, 3), B the transform batch
+            shape (() without one).  Per (configuration, pair) the bits ComposedSDF([sdfs[s]], C[:, k]).min_over_points(
+            leaf_points[t]) returns, C = leaf_pair_transforms(pairs) in the result dtype: indices (int64) index leaf_points[t]
+            (ties to the smallest index, a NaN counts as the minimum, -0.0 and +0.0 tie); gradients are leaf s's SDF gradient at
+            the witness point rotated back by C, so they are expressed in LEAF t's FRAME.  Differentiable w.r.t. the transforms
+            (a RobotSDF's joint values) when grad mode is on and they require grad, decisions held fixed; the points carry no
+            gradient.  Gradients need at most 64 leaves; create_graph=True raises.
+
+        Fused compositions (_fused_mode(): every leaf a BOUNDING_BOX CachedSDF of one interpolation) run HIP kernels
+        (csrc/leaf_pair.hip) with extra memory O(A K chunks) and nothing that synchronises with the host once the pair table
+        is built (it is kept while the same pairs and point tensors are passed), so the call can be captured in a graph.  Any
+        other composition takes the pair transforms from the same kernel and runs one one-leaf min_over_points per pair
+        (differentiable wherever __call__ is)."""
+        self._check_pair_transforms()
+        plan = self._leaf_pair_plan(leaf_points, pairs)
+        K = plan["pairs"].shape[0]
+        batch = tuple(self.tsf_batch) if self.tsf_batch is not None else ()
+        mode = self._fused_mode()
+        if K == 0:
+            dev, dt = plan["dev"], plan["dtype"]
+            return LeafPairDistance(torch.empty(batch + (0,), dtype=dt, device=dev),
+                                    torch.empty(batch + (0,), dtype=torch.int64, device=dev),
+                                    torch.empty(batch + (0, 3), dtype=dt, device=dev))
+        if mode is None:
+            return self._leaf_pair_generic(plan)
+        if self._tf_grad and torch.is_grad_enabled():
+            from pytorch_volumetric_amd import autograd
+            return autograd.leaf_pair_distance(self, plan, mode)
+        return LeafPairDistance(*self._leaf_pair_fused(plan, mode)[:3])
+
+    def _leaf_pair_fused(self, plan, mode):
+        """pvamd_leaf_pair_transforms + pvamd_leaf_pair_distance[_f64].  Returns (values, indices, gradients) in the result shapes,
+        then what the backward needs: the (A, K) indices, the pair transforms and the stack the kernels read."""
+        S = len(self.sdfs)
+        batch = tuple(self.tsf_batch) if self.tsf_batch is not None else ()
+        A = math.prod(batch)
+        dev, dt, table = plan["dev"], plan["dtype"], plan["table"]
+        K = table.shape[0]
+        C, tfd = self._pair_transforms(table, K, dt, dev)
+        val = torch.empty((A, K), dtype=dt, device=dev)
+        grad = torch.empty((A, K, 3), dtype=dt, device=dev)
+        idx = torch.empty((A, K), dtype=torch.int64, device=dev)
+        f64 = dt == torch.float64
+        name = "pvamd_leaf_pair_distance" + ("_f64" if f64 else "")
+        with _lib.on_device(dev):
+            grids = self._leaf_grids(dev)
+            n = _lib.leaf_pair_scratch_bytes(K, A, plan["max_points"], f64, False)
+            scratch = torch.empty((n,), dtype=torch.uint8, device=dev) if n else None
+            _lib.check(getattr(_lib.load(), name)(_lib.ptr(grids), S, _lib.ptr(C), A, _lib.ptr(plan["packed"]), plan["npoints"],
+                                                  _lib.ptr(table), K, plan["max_points"], _lib.LEAF_MODES[mode], _lib.ptr(val),
+                                                  _lib.ptr(grad), _lib.ptr(idx), _lib.ptr(scratch), _lib.stream_ptr()), name)
+        return val.reshape(*batch, K), idx.reshape(*batch, K), grad.reshape(*batch, K, 3), idx, C, tfd
+
+    def _leaf_pair_generic(self, plan):
+        """Compositions the kernels do not serve (MeshSDF leaves, mixed interpolation, other leaves): the pair transforms of the
+        kernel, then one one-leaf min_over_points per pair -- not a hot path.  Differentiable through __call__, and to the
+        transforms through autograd.PairTransforms."""
+        from pytorch_volumetric_amd import autograd
+        batch = tuple(self.tsf_batch) if self.tsf_batch is not None else ()
+        ph = plan["pairs"]
+        C = autograd.pair_transforms(self, plan["table"], ph, plan["dtype"], plan["dev"])  # (K, A, 4, 4)
+        parts = []
+        for k, (s, t) in enumerate(ph.tolist()):
+            one = ComposedSDF([self.sdfs[s]], None)
+            one.set_transforms(C[k], batch_dim=self.tsf_batch, known_rigid=True)
+            pts = plan["points"][t]
+            parts.append(one.min_over_points(pts.to(plan["dtype"]) if pts.dtype != plan["dtype"] else pts))
+        return LeafPairDistance(*(torch.stack(x, dim=len(batch)) for x in zip(*parts)))
 
     def _interp_forward(self, points, want_leaf):
         """_fused_forward of a trilinear composition (the leaf ids the interpolation tests compare)."""
