@@ -689,6 +689,47 @@ int pvamd_composed_hinge_over_points_backward_f64(const pvamd_grid_t* grids, int
                                                   const double* points, int64_t P, int32_t mode, int32_t per_leaf, double margin,
                                                   int32_t power, const double* up, double* dpoints, double* dtf, void* scratch,
                                                   void* stream);
+
+/* ---- Leaf-pair hinge (ComposedSDF.leaf_pair_hinge / RobotSDF.self_collision_hinge) ----
+ * The compositions, pairs, point sets, table and pair transforms C of "Leaf-pair distance"; m and power as in "Hinge penalty
+ * over points".
+ *  1. out_val[a][k], out_count[a][k] are bit for bit what pvamd_composed_hinge_over_points (per_leaf = 0) gives for the
+ *     one-leaf composition (grids[s], stack C[k]) over the P_t points of set t: each term rounded as torch rounds
+ *     (m - v).clamp(min=0) ** power, the float64 sum in that call's order (per lane in point order, the wave butterfly, the
+ *     four waves in order, the 4096-point chunks of set t in chunk order), rounded once; a NaN v makes the value NaN and is not
+ *     counted.  A malformed table row gives NaN and 0.
+ *  2. Bitwise reproducible whatever the launch geometry; no device -> host synchronisation, no allocation, no float atomics.
+ *     Extra memory: one 16-byte (sum, count) per pair, configuration and 4096-point chunk when a set holds more than one chunk,
+ *     else none.
+ *  3. Backward: per (a, k) the VJP of item 1 w.r.t. C[k][a], the bits pvamd_composed_hinge_over_points_backward gives for the
+ *     one-leaf composition's dtf (the same decisions and dv rule, the per-wave slots, the four waves in order, the 1024-point
+ *     chunks in chunk order), given up [A][K]; then the VJP of "Leaf-pair distance" item 1 to both stack rows, each row summed
+ *     over the pairs that use it in increasing k.  Points carry no gradient; a nearest leaf in range has no derivative.  S <= 64.
+ * pvamd_leaf_pair_hinge / _f64: out_val [A][K], out_count [A][K] int64.  max_points = the largest P_t of the table
+ *   (1 <= max_points <= 2^32 - 2).  scratch: device, PVAMD_LEAF_PAIR_HINGE_SCRATCH_BYTES(K, A, max_points, sizeof(T), 0) bytes,
+ *   16-byte aligned (NULL when that is 0).
+ * pvamd_leaf_pair_hinge_backward / _f64: given up [A][K], writes dtf [S*A][4][4] (every row; rows no pair uses and row 3 zero).
+ *   scratch: PVAMD_LEAF_PAIR_HINGE_SCRATCH_BYTES(K, A, max_points, sizeof(T), 1) bytes, 16-byte aligned (the dC slab of
+ *   12 values per pair, configuration and 1024-point chunk, then 24 values per pair and configuration: dMs and dMt).           */
+#define PVAMD_LEAF_PAIR_HINGE_SCRATCH_BYTES(K, A, max_points, elem, backward)                                                  \
+    ((backward) ? PVAMD_HOP_ROUND256(PVAMD_HOP_BWD_CHUNKS(max_points) * (int64_t)(K) * (int64_t)(A) * 12 * (int64_t)(elem)) + \
+                      24 * (int64_t)(K) * (int64_t)(A) * (int64_t)(elem)                                                     \
+                : PVAMD_LEAF_PAIR_SCRATCH_BYTES(K, A, max_points, elem, 0))
+int64_t pvamd_leaf_pair_hinge_scratch_bytes(int32_t K, int32_t A, int64_t max_points, int32_t is_f64, int32_t backward);
+int pvamd_leaf_pair_hinge(const pvamd_grid_t* grids, int32_t S, const float* C, int32_t A, const float* points, int64_t npoints,
+                          const int64_t* table, int32_t K, int64_t max_points, int32_t mode, float margin, int32_t power,
+                          float* out_val, int64_t* out_count, void* scratch, void* stream);
+int pvamd_leaf_pair_hinge_f64(const pvamd_grid_t* grids, int32_t S, const double* C, int32_t A, const double* points,
+                              int64_t npoints, const int64_t* table, int32_t K, int64_t max_points, int32_t mode, double margin,
+                              int32_t power, double* out_val, int64_t* out_count, void* scratch, void* stream);
+int pvamd_leaf_pair_hinge_backward(const pvamd_grid_t* grids, int32_t S, const float* tf, const float* C, int32_t A,
+                                   const float* points, int64_t npoints, const int64_t* table, int32_t K, int64_t max_points,
+                                   int32_t mode, float margin, int32_t power, const float* up, float* dtf, void* scratch,
+                                   void* stream);
+int pvamd_leaf_pair_hinge_backward_f64(const pvamd_grid_t* grids, int32_t S, const double* tf, const double* C, int32_t A,
+                                       const double* points, int64_t npoints, const int64_t* table, int32_t K, int64_t max_points,
+                                       int32_t mode, double margin, int32_t power, const double* up, double* dtf, void* scratch,
+                                       void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -81,6 +81,18 @@ def leaf_pair_scratch_bytes(K, A, max_points, f64, backward):
     return 16 * K * A * nchunks if nchunks > 1 else 0
 
 
+def leaf_pair_hinge_scratch_bytes(K, A, max_points, f64, backward):
+    """PVAMD_LEAF_PAIR_HINGE_SCRATCH_BYTES(K, A, max_points, elem, backward): the forward's one 16-byte (sum, count) per pair,
+    configuration and 4096-point chunk when a set holds more than one chunk (else none); the backward's dC slab of 12 values per
+    pair, configuration and 1024-point chunk, then dMs and dMt per pair and configuration."""
+    if K < 1 or A < 1 or max_points < 1:
+        return 0
+    if backward:
+        elem = 8 if f64 else 4
+        return _round256(((max_points + 1023) // 1024) * K * A * 12 * elem) + 24 * K * A * elem
+    return leaf_pair_scratch_bytes(K, A, max_points, f64, False)
+
+
 def _round256(n):
     return (n + 255) // 256 * 256
 
@@ -286,6 +298,12 @@ SIGNATURES = {
     "pvamd_leaf_pair_distance_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "pvamd_leaf_pair_distance_backward": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "pvamd_leaf_pair_distance_backward_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    # ComposedSDF.leaf_pair_hinge (include/pvamd.h "Leaf-pair hinge")
+    "pvamd_leaf_pair_hinge_scratch_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]),
+    "pvamd_leaf_pair_hinge": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "pvamd_leaf_pair_hinge_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_double, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "pvamd_leaf_pair_hinge_backward": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "pvamd_leaf_pair_hinge_backward_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_double, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     # ComposedSDF.hinge_over_points (include/pvamd.h "Hinge penalty over points")
     "pvamd_hinge_over_points_scratch_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32]),
     "pvamd_hinge_over_points_backward_scratch_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]),

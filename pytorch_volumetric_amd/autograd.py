@@ -282,6 +282,54 @@ def leaf_pair_distance(composed, plan, mode):
     return LeafPairDistance(val, idx, grad)
 
 
+# ---------------------------------------------------------------- ComposedSDF.leaf_pair_hinge (include/pvamd.h "Leaf-pair hinge")
+class LeafPairHingeQuery(torch.autograd.Function):
+    """Forward: ComposedSDF._leaf_pair_hinge_fused.  Backward: pvamd_leaf_pair_hinge_backward -- per (configuration, pair) the
+    one-leaf hinge's VJP w.r.t. the pair transform, then the pair transform's VJP to both stack rows, summed per row in pair
+    order.  The values and decisions are recomputed in the kernel: saved are the plan, the pair transforms and the stack."""
+
+    @staticmethod
+    def forward(ctx, composed, tfm, plan, margin, power, mode):
+        ctx.set_materialize_grads(False)
+        val, cnt, C, tfd = composed._leaf_pair_hinge_fused(plan, margin, power, mode)
+        ctx.mark_non_differentiable(cnt)
+        ctx.plan, ctx.mode, ctx.C, ctx.tfd, ctx.margin, ctx.power = plan, mode, C, tfd, margin, power
+        ctx.grids = composed._leaf_grids(plan["dev"])
+        ctx.save_for_backward(tfm)  # torch's in-place check of the input tfd may alias
+        ctx.S, ctx.A, ctx.K = len(composed.sdfs), C.shape[1], C.shape[0]
+        ctx.tdtype, ctx.tdevice = tfm.dtype, tfm.device
+        return val, cnt
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dval, dcnt):
+        ctx.saved_tensors
+        plan, S, A, K = ctx.plan, ctx.S, ctx.A, ctx.K
+        dev, dt = plan["dev"], plan["dtype"]
+        up = _upstream(dval, dev, dt, (A, K))
+        if up is None:  # nothing flows back
+            return None, None, None, None, None, None
+        dtf = torch.empty((S * A, 4, 4), dtype=dt, device=dev)
+        f64 = dt == torch.float64
+        name = "pvamd_leaf_pair_hinge_backward" + ("_f64" if f64 else "")
+        with _lib.on_device(dev):
+            scratch = torch.empty((_lib.leaf_pair_hinge_scratch_bytes(K, A, plan["max_points"], f64, True),), dtype=torch.uint8,
+                                  device=dev)
+            _lib.check(getattr(_lib.load(), name)(_lib.ptr(ctx.grids), S, _lib.ptr(ctx.tfd), _lib.ptr(ctx.C), A,
+                                                  _lib.ptr(plan["packed"]), plan["npoints"], _lib.ptr(plan["table"]), K,
+                                                  plan["max_points"], _lib.LEAF_MODES[ctx.mode], ctx.margin, ctx.power, _lib.ptr(up),
+                                                  _lib.ptr(dtf), _lib.ptr(scratch), _lib.stream_ptr()), name)
+        return None, dtf.to(device=ctx.tdevice, dtype=ctx.tdtype), None, None, None, None
+
+
+def leaf_pair_hinge(composed, plan, margin, power, mode):
+    from pytorch_volumetric_amd.sdf import LeafPairHinge
+    if len(composed.sdfs) > MAX_LEAVES:
+        raise _lib.PvamdError(f"gradients through a composition need at most {MAX_LEAVES} leaves, this one has {len(composed.sdfs)}")
+    val, cnt = LeafPairHingeQuery.apply(composed, composed._tf_matrix, plan, margin, power, mode)
+    return LeafPairHinge(val, cnt)
+
+
 def pair_transforms_torch(stack, pairs):
     """The pair transforms of include/pvamd.h "Leaf-pair distance" 1 in torch (any dtype, differentiable): stack (S, A, 4, 4),
     pairs (K, 2) -> (K, A, 4, 4).  Rounding aside (torch's matmul does not promise the kernel's fma order), the same C."""

@@ -21,9 +21,6 @@
 
 namespace pvamd {
 
-constexpr int kBwdBlock = 256;                     // four waves
-constexpr int kBwdK = 4;                           // points per lane
-constexpr int kBwdChunk = kBwdBlock * kBwdK;       // points per workgroup
 constexpr int kBwdMaxLeaves = 64;                  // per-wave LDS slots (and the presence mask) hold up to 64 leaves
 constexpr int kBwdTargetBlocks = 2048;             // configurations are split over workgroups until about this many exist
 

@@ -44,6 +44,29 @@ PVAMD_DEV void mop_wave_min(uint64_t& k, uint32_t& i) {
     }
 }
 
+// The hinge's fixed-order float64 sum (hinge_over_points.hip, leaf_pair.hip): per lane in point order over kHopK points of a
+// PVAMD_MOP_CHUNK chunk, a wave butterfly, the four waves in order, then the chunks in chunk order
+constexpr int kHopBlock = 256;
+constexpr int kHopK = PVAMD_MOP_CHUNK / kHopBlock;  // points per lane per chunk
+static_assert(kHopK * kHopBlock == PVAMD_MOP_CHUNK, "whole lanes per chunk");
+
+struct HopPart {
+    double sum;     // the chunk's terms, in float64
+    int64_t count;  // the chunk's points with v < m
+};
+
+template <typename T>
+PVAMD_DEV T hop_wave_sum(T v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;  // a butterfly: every lane holds the same bits
+}
+
+// The composed backward's workgroup (backward.hip composed_backward_kernel, leaf_pair.hip lph_backward_kernel)
+constexpr int kBwdBlock = 256;                     // four waves
+constexpr int kBwdK = 4;                           // points per lane
+constexpr int kBwdChunk = kBwdBlock * kBwdK;       // points per workgroup
+
 // (val, gx, gy, gz) of one leaf at the leaf-frame point x
 template <typename T, bool INTERP> struct MopLeaf;
 

@@ -14,22 +14,6 @@
 
 namespace pvamd {
 
-constexpr int kHopBlock = 256;
-constexpr int kHopK = PVAMD_MOP_CHUNK / kHopBlock;  // points per lane per chunk
-static_assert(kHopK * kHopBlock == PVAMD_MOP_CHUNK, "whole lanes per chunk");
-
-struct HopPart {
-    double sum;     // the chunk's terms, in float64
-    int64_t count;  // the chunk's points with v < m
-};
-
-template <typename T>
-PVAMD_DEV T hop_wave_sum(T v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;  // a butterfly: every lane holds the same bits
-}
-
 // ---- pass 1: workgroup (chunk, a, z) -> part[(a * Z + z) * nchunks + chunk] ----
 template <typename T, bool INTERP>
 __global__ __launch_bounds__(kHopBlock) void hop_partial_kernel(const pvamd_grid_t* __restrict__ grids, int S,

@@ -189,6 +189,34 @@ __global__ __launch_bounds__(64) void lp_finish_kernel(const pvamd_grid_t* __res
     }
 }
 
+// The VJP of the pair transform (include/pvamd.h "Leaf-pair distance" 1): C_rot = Rs Rt^T, C_t = ts - C_rot tt.  dC = the
+// upstream of C[k][a] rows 0-2 -> dMs, dMt = the upstream of stack rows (s, a) and (t, a), rows 0-2
+template <typename T>
+PVAMD_DEV void lp_pair_vjp(const LpPair& q, const T* tf, const T* C, int A, int a, int k, const T (&dC)[12], T (&dMs)[12],
+                           T (&dMt)[12]) {
+    const T* Ms = tf + 16 * ((int64_t)q.s * A + a);
+    const T* Mt = tf + 16 * ((int64_t)q.t * A + a);
+    const T* M = C + 16 * ((int64_t)k * A + a);
+    T dR[9];  // the total upstream of C_rot: its own and that through C_t
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        dMs[4 * r + 3] = dC[4 * r + 3];
+#pragma unroll
+        for (int m = 0; m < 3; ++m) dR[3 * r + m] = dC[4 * r + m] - dC[4 * r + 3] * Mt[4 * m + 3];
+    }
+#pragma unroll
+    for (int m = 0; m < 3; ++m)
+        dMt[4 * m + 3] = -(dC[3] * M[m] + dC[7] * M[4 + m] + dC[11] * M[8 + m]);
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+        for (int m = 0; m < 3; ++m) {
+            dMs[4 * r + m] = dR[3 * r] * Mt[m] + dR[3 * r + 1] * Mt[4 + m] + dR[3 * r + 2] * Mt[8 + m];
+            dMt[4 * r + m] = dR[r] * Ms[m] + dR[3 + r] * Ms[4 + m] + dR[6 + r] * Ms[8 + m];
+        }
+    }
+}
+
 // ---- backward: one lane per (a, k) -> dM[(k * A + a)][24] = (dMs rows 0-2, dMt rows 0-2) ----
 template <typename T, bool INTERP>
 __global__ __launch_bounds__(256) void lp_backward_kernel(const pvamd_grid_t* __restrict__ grids, int S, const T* __restrict__ tf,
@@ -240,33 +268,10 @@ __global__ __launch_bounds__(256) void lp_backward_kernel(const pvamd_grid_t* __
                 }
             }
         }
-        // the VJP of the pair transform (include/pvamd.h "Leaf-pair distance" 1): C_rot = Rs Rt^T, C_t = ts - C_rot tt
         T dMs[12], dMt[12];
 #pragma unroll
         for (int e = 0; e < 12; ++e) { dMs[e] = T(0); dMt[e] = T(0); }
-        if (ok) {
-            const T* Ms = tf + 16 * ((int64_t)q.s * A + a);
-            const T* Mt = tf + 16 * ((int64_t)q.t * A + a);
-            const T* M = C + 16 * ((int64_t)k * A + a);
-            T dR[9];  // the total upstream of C_rot: its own and that through C_t
-#pragma unroll
-            for (int r = 0; r < 3; ++r) {
-                dMs[4 * r + 3] = dC[4 * r + 3];
-#pragma unroll
-                for (int m = 0; m < 3; ++m) dR[3 * r + m] = dC[4 * r + m] - dC[4 * r + 3] * Mt[4 * m + 3];
-            }
-#pragma unroll
-            for (int m = 0; m < 3; ++m)
-                dMt[4 * m + 3] = -(dC[3] * M[m] + dC[7] * M[4 + m] + dC[11] * M[8 + m]);
-#pragma unroll
-            for (int r = 0; r < 3; ++r) {
-#pragma unroll
-                for (int m = 0; m < 3; ++m) {
-                    dMs[4 * r + m] = dR[3 * r] * Mt[m] + dR[3 * r + 1] * Mt[4 + m] + dR[3 * r + 2] * Mt[8 + m];
-                    dMt[4 * r + m] = dR[r] * Ms[m] + dR[3 + r] * Ms[4 + m] + dR[6 + r] * Ms[8 + m];
-                }
-            }
-        }
+        if (ok) lp_pair_vjp<T>(q, tf, C, A, a, k, dC, dMs, dMt);
 #pragma unroll
         for (int e = 0; e < 12; ++e) { out[e] = dMs[e]; out[12 + e] = dMt[e]; }
     }
@@ -388,6 +393,310 @@ static int leaf_pair_distance_backward(const pvamd_grid_t* grids, int32_t S, con
     return (int)hipGetLastError();
 }
 
+
+// ==== Leaf-pair hinge (include/pvamd.h "Leaf-pair hinge") ====
+// For every pair k = (s, t) and configuration a: the bits of ComposedSDF([sdfs[s]], C[:, k]).hinge_over_points(points of t),
+// sum_p max(m - v, 0) ** power and the count of v < m, with hinge_over_points.hip's statements and order of summation.
+//   lph_partial_kernel        workgroup (chunk, a, k): hop_partial_kernel's loop body over a 4096-point chunk of set t, leaf s
+//                             under C[k][a].  FINISH (every set within one chunk): the workgroup writes the answer, 0.0 + sum
+//                             rounded as hop_finish_kernel rounds it; else one HopPart per (k, a, chunk)
+//   lph_finish_kernel         (sets above one chunk) one wave per (a, k): hop_finish_kernel over the pair's own chunks
+//   lph_backward_kernel       workgroup (1024-chunk, a-split, k): composed_backward_kernel's HINGE statements for the one-leaf
+//                             composition, its per-wave slots and wave order -> dC slab [k][a][chunk][12]
+//   lph_pair_vjp_kernel       one lane per (a, k): the slab's chunks in chunk order (reduce_tf_kernel), then lp_pair_vjp -> dM
+//   lp_accumulate_kernel      as for the leaf-pair distance
+template <typename T, bool INTERP, bool FINISH>
+__global__ __launch_bounds__(kHopBlock) void lph_partial_kernel(const pvamd_grid_t* __restrict__ grids, int S, const T* __restrict__ C,
+                                                                int A, const T* __restrict__ pts, int64_t npoints,
+                                                                const int64_t* __restrict__ table, int K, T m, int power,
+                                                                int64_t nchunks, HopPart* __restrict__ part, T* __restrict__ out_val,
+                                                                int64_t* __restrict__ out_count) {
+    __shared__ double ws[kHopBlock / 64];
+    __shared__ int wc[kHopBlock / 64];
+    const int64_t chunk = blockIdx.x;
+    const int k = blockIdx.z;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    LpPair q;
+    const bool ok = lp_pair(table, k, S, npoints, q);  // workgroup-uniform
+    if (!FINISH && (!ok || chunk * PVAMD_MOP_CHUNK >= q.P)) return;  // beyond the pair's own chunks: never read
+    const pvamd_grid_t* g = grids + (ok ? q.s : 0);
+    const T* tfk = C + 16 * (int64_t)k * A;  // the pair's [A][4][4] stack: a one-leaf composition's
+    const T* p0 = pts + 3 * (ok ? q.off : 0);
+    const int64_t P = ok ? q.P : 0;
+    for (int a = blockIdx.y; a < A; a += gridDim.y) {
+        double sum = 0.0;
+        int cnt = 0;
+#pragma unroll 1
+        for (int kk = 0; kk < kHopK; ++kk) {
+            const int64_t i = chunk * PVAMD_MOP_CHUNK + (int64_t)kk * kHopBlock + threadIdx.x;
+            if (i < P) {
+                const T p[3] = {p0[3 * i], p0[3 * i + 1], p0[3 * i + 2]};
+                T v, gr[3];
+                int s;
+                mop_point<T, INTERP>(g, 0, 1, tfk, A, a, p, v, gr, s);
+                const T d = m - v;
+                const T h = (d > T(0) || d != d) ? d : T(0);  // clamp(min=0): NaN stays NaN
+                sum += (double)(power == 2 ? h * h : h);
+                cnt += v < m;
+            }
+        }
+        sum = hop_wave_sum<double>(sum);
+        cnt = hop_wave_sum<int>(cnt);
+        if (lane == 0) { ws[wave] = sum; wc[wave] = cnt; }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            for (int w = 1; w < kHopBlock / 64; ++w) { sum += ws[w]; cnt += wc[w]; }
+            if constexpr (FINISH) {
+                const int64_t pr = (int64_t)a * K + k;
+                double tot = 0.0;
+                tot += sum;  // hop_finish_kernel's first (and only) chunk
+                out_val[pr] = ok ? (T)tot : (T)__builtin_nan("");
+                out_count[pr] = ok ? (int64_t)cnt : 0;
+            } else {
+                HopPart r;
+                r.sum = sum; r.count = cnt;
+                part[((int64_t)k * A + a) * nchunks + chunk] = r;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(64) void lph_finish_kernel(int S, int A, int64_t npoints, const int64_t* __restrict__ table, int K,
+                                                        int64_t nchunks, const HopPart* __restrict__ part, T* __restrict__ out_val,
+                                                        int64_t* __restrict__ out_count) {
+    const int64_t npairs = (int64_t)A * K;
+    for (int64_t pr = blockIdx.x; pr < npairs; pr += gridDim.x) {
+        const int a = (int)(pr / K), k = (int)(pr - (int64_t)a * K);
+        LpPair q;
+        const bool ok = lp_pair(table, k, S, npoints, q);
+        int64_t nc = ok ? (q.P + PVAMD_MOP_CHUNK - 1) / PVAMD_MOP_CHUNK : 0;  // the pair's own chunks
+        nc = nc < nchunks ? nc : nchunks;
+        const HopPart* row = part + ((int64_t)k * A + a) * nchunks;
+        double sum = 0.0;
+        int64_t cnt = 0;
+        for (int64_t base = 0; base < nc; base += 64) {
+            const int64_t c = base + threadIdx.x;
+            HopPart h;
+            h.sum = 0.0; h.count = 0;
+            if (c < nc) h = row[c];
+            cnt += h.count;
+            const int n = (nc - base) < 64 ? (int)(nc - base) : 64;
+            for (int j = 0; j < n; ++j) sum += __shfl(h.sum, j, 64);  // every lane: the same sum in chunk order
+        }
+        cnt = hop_wave_sum<int64_t>(cnt);
+        if (threadIdx.x == 0) {
+            out_val[pr] = ok ? (T)sum : (T)__builtin_nan("");
+            out_count[pr] = cnt;
+        }
+    }
+}
+
+// ---- backward, pass 1: workgroup (chunk, split, k) -> slab[((k * A + a) * nchunks + chunk)][12] ----
+template <typename T, bool INTERP>
+__global__ __launch_bounds__(kBwdBlock) void lph_backward_kernel(const pvamd_grid_t* __restrict__ grids, int S,
+                                                                 const T* __restrict__ C, int A, const T* __restrict__ pts,
+                                                                 int64_t npoints, const int64_t* __restrict__ table, int K, T margin,
+                                                                 int power, const T* __restrict__ up, int aper, int64_t nchunks,
+                                                                 T* __restrict__ slab) {
+    __shared__ T part[kBwdBlock / 64][12];
+    __shared__ int present[kBwdBlock / 64];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t chunk = blockIdx.x;
+    const int k = blockIdx.z;
+    LpPair q;
+    if (!lp_pair(table, k, S, npoints, q) || chunk * kBwdChunk >= q.P) return;  // workgroup-uniform: never read
+    const int a0 = blockIdx.y * aper;
+    const int a1 = (a0 + aper) < A ? (a0 + aper) : A;
+    const pvamd_grid_t& g = grids[q.s];
+    const T* tfk = C + 16 * (int64_t)k * A;
+    const T* p0 = pts + 3 * q.off;
+
+    T p[kBwdK][3];
+    bool live[kBwdK];
+#pragma unroll
+    for (int kk = 0; kk < kBwdK; ++kk) {
+        const int64_t i = chunk * kBwdChunk + (int64_t)kk * kBwdBlock + threadIdx.x;
+        live[kk] = i < q.P;
+#pragma unroll
+        for (int d = 0; d < 3; ++d) p[kk][d] = live[kk] ? p0[3 * i + d] : T(0);
+    }
+
+    for (int a = a0; a < a1; ++a) {
+        if (lane == 0) present[wave] = 0;
+        const T u = up[(int64_t)a * K + k];
+#pragma unroll
+        for (int kk = 0; kk < kBwdK; ++kk) {
+            // composed_backward_kernel<T, true, false, true, false, INTERP, true> for the one-leaf composition (grids + s, C[k])
+            int s = -1;
+            T c[12] = {};
+            if (live[kk]) {
+                T v, gv[3];
+                mop_point<T, INTERP>(&g, 0, 1, tfk, A, a, p[kk], v, gv, s);
+                const T d = margin - v;
+                const T h = (d > T(0) || d != d) ? d : T(0);
+                const T hdv = -((d >= T(0)) ? (power == 2 ? u * (T(2) * h) : u) : T(0));
+                if (s < 0 || s >= 1) s = -1;
+                if (s >= 0) {
+                    const T* M = tfk + 16 * (int64_t)a;
+                    T dg[3] = {0, 0, 0};
+                    T x[3], gr[3] = {0, 0, 0}, dx[3] = {0, 0, 0};
+                    LeafOps<T>::xform(M, p[kk], x);
+                    if (LeafOps<T>::inside(g, x)) {
+                        if constexpr (INTERP) InterpOps<T>::leaf(g, x, hdv, dg, false, gr, dx);
+                        else s = -1;  // a nearest leaf in range has no derivative
+                    } else {
+                        box_backward<T>(g, x, hdv, dg, false, gr, dx);
+                    }
+#pragma unroll
+                    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+                        for (int j = 0; j < 3; ++j) c[4 * r + j] = dx[r] * p[kk][j];
+                        c[4 * r + 3] = dx[r];
+                    }
+                }
+            }
+            if (__builtin_amdgcn_ballot_w64(s >= 0)) {  // wave-uniform: the one leaf wins somewhere in the wave
+                const bool mine = s == 0;
+                const bool seen = present[wave] != 0;
+#pragma unroll
+                for (int j = 0; j < 12; ++j) {
+                    const T v = hop_wave_sum<T>(mine ? c[j] : T(0));
+                    if (lane == 0) part[wave][j] = seen ? part[wave][j] + v : v;
+                }
+                if (lane == 0) present[wave] = 1;
+                PVAMD_WAVE_SYNC();
+            }
+        }
+        __syncthreads();
+        if (threadIdx.x < 12) {
+            const int j = threadIdx.x;
+            T v = T(0);
+#pragma unroll
+            for (int w = 0; w < kBwdBlock / 64; ++w)
+                if (present[w]) v += part[w][j];
+            slab[(((int64_t)k * A + a) * nchunks + chunk) * 12 + j] = v;
+        }
+        __syncthreads();
+    }
+}
+
+// ---- backward, pass 2: one lane per (a, k): dC = the pair's chunks in chunk order, then the pair-transform VJP -> dM ----
+template <typename T>
+__global__ __launch_bounds__(256) void lph_pair_vjp_kernel(int S, const T* __restrict__ tf, const T* __restrict__ C, int A,
+                                                           int64_t npoints, const int64_t* __restrict__ table, int K,
+                                                           int64_t nchunks, const T* __restrict__ slab, T* __restrict__ dM) {
+    const int64_t npairs = (int64_t)A * K;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t pr = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; pr < npairs; pr += stride) {
+        const int a = (int)(pr / K), k = (int)(pr - (int64_t)a * K);
+        LpPair q;
+        const bool ok = lp_pair(table, k, S, npoints, q);
+        int64_t nc = ok ? (q.P + kBwdChunk - 1) / kBwdChunk : 0;  // the pair's own chunks
+        nc = nc < nchunks ? nc : nchunks;
+        const T* row = slab + ((int64_t)k * A + a) * nchunks * 12;
+        T dC[12];
+#pragma unroll
+        for (int e = 0; e < 12; ++e) {
+            T v = T(0);
+            for (int64_t ch = 0; ch < nc; ++ch) v += row[ch * 12 + e];
+            dC[e] = v;
+        }
+        T dMs[12], dMt[12];
+#pragma unroll
+        for (int e = 0; e < 12; ++e) { dMs[e] = T(0); dMt[e] = T(0); }
+        if (ok) lp_pair_vjp<T>(q, tf, C, A, a, k, dC, dMs, dMt);
+        T* out = dM + 24 * ((int64_t)k * A + a);
+#pragma unroll
+        for (int e = 0; e < 12; ++e) { out[e] = dMs[e]; out[12 + e] = dMt[e]; }
+    }
+}
+
+static inline int64_t lph_bwd_chunks(int64_t max_points) { return (max_points + kBwdChunk - 1) / kBwdChunk; }
+
+template <typename T>
+static int lph_check(const pvamd_grid_t* grids, int32_t S, const T* C, int32_t A, const T* points, int64_t npoints,
+                     const int64_t* table, int32_t K, int64_t max_points, int32_t mode, int32_t power) {
+    if (max_points < 1 || max_points > npoints || max_points > (int64_t)0xfffffffe || K > 65535) return PVAMD_E_SHAPE;
+    if (S < 1 || A < 1 || K < 0) return PVAMD_E_SHAPE;
+    if (power != 1 && power != 2) return PVAMD_E_MODE;
+    return lp_check<T>(grids, S, C, A, points, npoints, table, K, mode);
+}
+
+template <typename T, bool INTERP>
+static void lph_launch(const pvamd_grid_t* grids, int S, const T* C, int A, const T* points, int64_t npoints, const int64_t* table,
+                       int K, int64_t nchunks, T m, int power, T* out_val, int64_t* out_count, HopPart* part, hipStream_t st) {
+    // lp_launch's geometry: a few thousand workgroups, each looping over its configurations
+    const int64_t want = (4096 + (int64_t)K * nchunks - 1) / ((int64_t)K * nchunks);
+    const unsigned ay = (unsigned)(A < want ? A : (want < 65535 ? want : 65535));
+    const dim3 grd((unsigned)nchunks, ay, (unsigned)K);
+    if (nchunks == 1) {
+        hipLaunchKernelGGL((lph_partial_kernel<T, INTERP, true>), grd, dim3(kHopBlock), 0, st, grids, S, C, A, points, npoints, table,
+                           K, m, power, nchunks, part, out_val, out_count);
+        return;
+    }
+    hipLaunchKernelGGL((lph_partial_kernel<T, INTERP, false>), grd, dim3(kHopBlock), 0, st, grids, S, C, A, points, npoints, table, K,
+                       m, power, nchunks, part, out_val, out_count);
+    const int64_t npairs = (int64_t)A * K;
+    hipLaunchKernelGGL(lph_finish_kernel<T>, dim3((unsigned)(npairs < 0x7fffffff ? npairs : 0x7fffffff)), dim3(64), 0, st, S, A,
+                       npoints, table, K, nchunks, part, out_val, out_count);
+}
+
+template <typename T>
+static int leaf_pair_hinge(const pvamd_grid_t* grids, int32_t S, const T* C, int32_t A, const T* points, int64_t npoints,
+                           const int64_t* table, int32_t K, int64_t max_points, int32_t mode, T margin, int32_t power, T* out_val,
+                           int64_t* out_count, void* scratch, void* stream) {
+    if (int e = lph_check<T>(grids, S, C, A, points, npoints, table, K, max_points, mode, power)) return e;
+    if (K == 0) return 0;
+    const int64_t nchunks = lp_chunks(max_points);
+    if (!out_val || !out_count || (nchunks > 1 && !scratch)) return PVAMD_E_NULL;
+    if (!aligned_to(out_val, sizeof(T)) || !aligned_to(out_count, 8) || !aligned_to(scratch, 16)) return PVAMD_E_ALIGN;
+    hipStream_t st = (hipStream_t)stream;
+    HopPart* part = (HopPart*)scratch;
+    if (mode == PVAMD_LEAF_TRILINEAR)
+        lph_launch<T, true>(grids, S, C, A, points, npoints, table, K, nchunks, margin, power, out_val, out_count, part, st);
+    else
+        lph_launch<T, false>(grids, S, C, A, points, npoints, table, K, nchunks, margin, power, out_val, out_count, part, st);
+    return (int)hipGetLastError();
+}
+
+template <typename T>
+static int leaf_pair_hinge_backward(const pvamd_grid_t* grids, int32_t S, const T* tf, const T* C, int32_t A, const T* points,
+                                    int64_t npoints, const int64_t* table, int32_t K, int64_t max_points, int32_t mode, T margin,
+                                    int32_t power, const T* up, T* dtf, void* scratch, void* stream) {
+    if (S > 64) return PVAMD_E_SHAPE;  // the limit of every composed backward
+    if (int e = lph_check<T>(grids, S, C, A, points, npoints, table, K, max_points, mode, power)) return e;
+    if (!dtf) return 0;
+    if (!tf || (K > 0 && (!up || !scratch))) return PVAMD_E_NULL;
+    if (!aligned_to(tf, sizeof(T)) || !aligned_to(up, sizeof(T)) || !aligned_to(dtf, sizeof(T)) || !aligned_to(scratch, 16))
+        return PVAMD_E_ALIGN;
+    hipStream_t st = (hipStream_t)stream;
+    if (K == 0)  // nothing flows back: zeros
+        return hipMemsetAsync(dtf, 0, (size_t)S * A * 16 * sizeof(T), st) != hipSuccess ? (int)hipGetLastError() : 0;
+    const int64_t nchunks = lph_bwd_chunks(max_points);
+    // configurations split over workgroups until about 2048 exist (bwd_plan's target); the split does not change any sum
+    int64_t want = (2048 + (int64_t)K * nchunks - 1) / ((int64_t)K * nchunks);
+    if (want > A) want = A;
+    if (want < 1) want = 1;
+    const int aper = (int)((A + want - 1) / want);
+    const unsigned nsplit = (unsigned)((A + aper - 1) / aper);
+    T* slab = (T*)scratch;
+    T* dM = (T*)((char*)scratch + ((nchunks * K * A * 12 * (int64_t)sizeof(T) + 255) / 256) * 256);
+    const dim3 grd((unsigned)nchunks, nsplit, (unsigned)K);
+    if (mode == PVAMD_LEAF_TRILINEAR)
+        hipLaunchKernelGGL((lph_backward_kernel<T, true>), grd, dim3(kBwdBlock), 0, st, grids, S, C, A, points, npoints, table, K,
+                           margin, power, up, aper, nchunks, slab);
+    else
+        hipLaunchKernelGGL((lph_backward_kernel<T, false>), grd, dim3(kBwdBlock), 0, st, grids, S, C, A, points, npoints, table, K,
+                           margin, power, up, aper, nchunks, slab);
+    const int64_t npairs = (int64_t)A * K;
+    hipLaunchKernelGGL(lph_pair_vjp_kernel<T>, dim3(stream_grid(npairs, 256)), dim3(256), 0, st, S, tf, C, A, npoints, table, K,
+                       nchunks, slab, dM);
+    hipLaunchKernelGGL(lp_accumulate_kernel<T>, dim3(stream_grid((int64_t)S * A, 256)), dim3(256), 0, st, dM, S, A, table, K, dtf);
+    return (int)hipGetLastError();
+}
+
 }  // namespace pvamd
 
 using namespace pvamd;
@@ -435,4 +744,40 @@ extern "C" int pvamd_leaf_pair_distance_backward_f64(const pvamd_grid_t* grids, 
                                                      const double* dgrad, double* dtf, void* scratch, void* stream) {
     return leaf_pair_distance_backward<double>(grids, S, tf, C, A, points, npoints, table, K, mode, index, dval, dgrad, dtf, scratch,
                                                stream);
+}
+
+extern "C" int64_t pvamd_leaf_pair_hinge_scratch_bytes(int32_t K, int32_t A, int64_t max_points, int32_t is_f64, int32_t backward) {
+    if (K < 1 || A < 1 || max_points < 1) return 0;
+    return PVAMD_LEAF_PAIR_HINGE_SCRATCH_BYTES(K, A, max_points, is_f64 ? 8 : 4, backward);
+}
+
+extern "C" int pvamd_leaf_pair_hinge(const pvamd_grid_t* grids, int32_t S, const float* C, int32_t A, const float* points,
+                                     int64_t npoints, const int64_t* table, int32_t K, int64_t max_points, int32_t mode, float margin,
+                                     int32_t power, float* out_val, int64_t* out_count, void* scratch, void* stream) {
+    return leaf_pair_hinge<float>(grids, S, C, A, points, npoints, table, K, max_points, mode, margin, power, out_val, out_count,
+                                  scratch, stream);
+}
+
+extern "C" int pvamd_leaf_pair_hinge_f64(const pvamd_grid_t* grids, int32_t S, const double* C, int32_t A, const double* points,
+                                         int64_t npoints, const int64_t* table, int32_t K, int64_t max_points, int32_t mode,
+                                         double margin, int32_t power, double* out_val, int64_t* out_count, void* scratch,
+                                         void* stream) {
+    return leaf_pair_hinge<double>(grids, S, C, A, points, npoints, table, K, max_points, mode, margin, power, out_val, out_count,
+                                   scratch, stream);
+}
+
+extern "C" int pvamd_leaf_pair_hinge_backward(const pvamd_grid_t* grids, int32_t S, const float* tf, const float* C, int32_t A,
+                                              const float* points, int64_t npoints, const int64_t* table, int32_t K, int64_t max_points,
+                                              int32_t mode, float margin, int32_t power, const float* up, float* dtf, void* scratch,
+                                              void* stream) {
+    return leaf_pair_hinge_backward<float>(grids, S, tf, C, A, points, npoints, table, K, max_points, mode, margin, power, up, dtf,
+                                           scratch, stream);
+}
+
+extern "C" int pvamd_leaf_pair_hinge_backward_f64(const pvamd_grid_t* grids, int32_t S, const double* tf, const double* C, int32_t A,
+                                                  const double* points, int64_t npoints, const int64_t* table, int32_t K,
+                                                  int64_t max_points, int32_t mode, double margin, int32_t power, const double* up,
+                                                  double* dtf, void* scratch, void* stream) {
+    return leaf_pair_hinge_backward<double>(grids, S, tf, C, A, points, npoints, table, K, max_points, mode, margin, power, up, dtf,
+                                            scratch, stream);
 }

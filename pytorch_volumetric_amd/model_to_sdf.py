@@ -326,6 +326,22 @@ class RobotSDF(sdf.ObjectFrameSDF):
             self.set_self_collision_points()
         return self.sdf.leaf_pair_distance(self._sc_points, self.self_collision_pairs() if pairs is None else pairs)
 
+    def self_collision_hinge(self, margin, power=2, pairs=None):
+        """ComposedSDF.leaf_pair_hinge of the self-collision points (set_self_collision_points; sampled with its defaults on
+        first use) under the current joint configuration: per configuration and pair (s, t), the sum over leaf t's points of
+        max(margin - v, 0) ** power under leaf s's SDF, and the count of points with v < margin -- the self-collision half of a
+        CHOMP, TrajOpt or MPPI cost (values.sum(-1) sums it over the pairs).  Differentiable w.r.t. q when
+        set_joint_configuration was given a q that requires grad.  With nearest link grids only points outside a link's grid
+        range move q; trilinear link grids (cache_link_sdf_factory(..., interpolation="trilinear")) give a gradient everywhere.
+
+        :param margin: a finite Python real number; :param power: 1 or 2
+        :param pairs: int (K, 2) ordered leaf pairs; None = self_collision_pairs()
+        :return: LeafPairHinge(values, counts), both of shape [A] + (K,)"""
+        if self._sc_points is None:
+            self.set_self_collision_points()
+        return self.sdf.leaf_pair_hinge(self._sc_points, self.self_collision_pairs() if pairs is None else pairs, margin,
+                                        power=power)
+
     def link_pair_transforms(self, pairs=None):
         """ComposedSDF.leaf_pair_transforms under the current joint configuration: [A] + (K, 4, 4) leaf t frame -> leaf s frame
         transforms of the pairs (None = self_collision_pairs())."""

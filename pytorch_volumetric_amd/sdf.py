@@ -50,6 +50,14 @@ class HingeOverPoints(NamedTuple):
     counts: torch.Tensor
 
 
+class LeafPairHinge(NamedTuple):
+    """ComposedSDF.leaf_pair_hinge / RobotSDF.self_collision_hinge: per configuration and ordered leaf pair (s, t), the sum over
+    leaf t's points of max(margin - v, 0) ** power under leaf s's SDF and the number of those points with v < margin
+    (include/pvamd.h "Leaf-pair hinge")."""
+    values: torch.Tensor
+    counts: torch.Tensor
+
+
 class LeafPairDistance(NamedTuple):
     """ComposedSDF.leaf_pair_distance / RobotSDF.self_collision_distance: per configuration and ordered leaf pair (s, t), the point
     of leaf t's set where leaf s's SDF is smallest, the value there and leaf s's gradient expressed in leaf t's frame
@@ -57,6 +65,18 @@ class LeafPairDistance(NamedTuple):
     values: torch.Tensor
     indices: torch.Tensor
     gradients: torch.Tensor
+
+
+def _hinge_args(margin, power):
+    """margin: a finite Python real (rounded to the query dtype by the caller); power: 1 or 2."""
+    if isinstance(margin, bool) or not isinstance(margin, numbers.Real):
+        raise TypeError(f"margin must be a Python real number, got {type(margin).__name__}")
+    margin = float(margin)
+    if not math.isfinite(margin):
+        raise ValueError(f"margin must be finite, got {margin!r}")
+    if isinstance(power, bool) or power not in (1, 2):
+        raise ValueError(f"power must be 1 or 2, got {power!r}")
+    return margin, int(power)
 
 
 def first_argmin(v):
@@ -1328,14 +1348,7 @@ class ComposedSDF(ObjectFrameSDF):
         wherever __call__ is)."""
         if not isinstance(per_leaf, bool):
             raise TypeError(f"per_leaf must be True or False, got {per_leaf!r}")
-        if isinstance(margin, bool) or not isinstance(margin, numbers.Real):
-            raise TypeError(f"margin must be a Python real number, got {type(margin).__name__}")
-        margin = float(margin)
-        if not math.isfinite(margin):
-            raise ValueError(f"margin must be finite, got {margin!r}")
-        if isinstance(power, bool) or power not in (1, 2):
-            raise ValueError(f"power must be 1 or 2, got {power!r}")
-        power = int(power)
+        margin, power = _hinge_args(margin, power)
         if not torch.is_tensor(points):
             points = torch.as_tensor(points)
         if points.dim() < 1 or points.shape[-1] != 3:
@@ -1587,6 +1600,87 @@ class ComposedSDF(ObjectFrameSDF):
             pts = plan["points"][t]
             parts.append(one.min_over_points(pts.to(plan["dtype"]) if pts.dtype != plan["dtype"] else pts))
         return LeafPairDistance(*(torch.stack(x, dim=len(batch)) for x in zip(*parts)))
+
+    # ---- leaf-pair hinge ----
+    def leaf_pair_hinge(self, leaf_points, pairs, margin, power=2):
+        """For every configuration and ordered pair (s, t): the self-collision cost of leaf t's points against leaf s's SDF,
+        sum_p max(margin - v, 0) ** power, and the number of those points with v < margin -- the hinge sum a CHOMP, TrajOpt
+        or MPPI cost needs, without an (A, K, P) buffer.
+
+        :param leaf_points: as for leaf_pair_distance: S point sets (P_s, 3), each in its own leaf's frame; a set may be empty
+            only if no pair uses it as its point side; float64 results when any set is float64
+        :param pairs: as for leaf_pair_distance: int (K, 2) ordered pairs (s, t), s != t (points of leaf t, SDF of leaf s)
+        :param margin: a finite Python real number, rounded once to the result dtype
+        :param power: 1 or 2
+        :return: LeafPairHinge(values, counts), both of shape B + (K,), B the transform batch shape (() without one); counts
+            are int64.  Per (configuration, pair) the bits ComposedSDF([sdfs[s]], C[:, k]).hinge_over_points(leaf_points[t],
+            margin, power) returns, C = leaf_pair_transforms(pairs) in the result dtype: each term rounded as torch rounds
+            (margin - v).clamp(min=0) ** power, summed in float64 in that call's fixed order and rounded once; a NaN v makes
+            its value NaN and is not counted.  Differentiable w.r.t. the transforms (a RobotSDF's joint values) when grad mode
+            is on and they require grad, decisions held fixed (clamp passes the gradient at v == margin); the points carry no
+            gradient.  As for hinge_over_points, a point inside leaf s's grid range has no derivative with nearest leaves:
+            only points in the bounding-box branch move the transforms; trilinear leaves (cache_link_sdf_factory(...,
+            interpolation="trilinear")) give a gradient everywhere in range.  Gradients need at most 64 leaves;
+            create_graph=True raises.
+
+        Fused compositions (_fused_mode(): every leaf a BOUNDING_BOX CachedSDF of one interpolation) run HIP kernels
+        (csrc/leaf_pair.hip) with extra memory O(A K chunks) and nothing that synchronises with the host once the pair table
+        is built, so the call can be captured in a graph.  Any other composition takes the pair transforms from the same
+        kernel and runs one one-leaf hinge_over_points per pair (differentiable wherever __call__ is)."""
+        margin, power = _hinge_args(margin, power)
+        self._check_pair_transforms()
+        plan = self._leaf_pair_plan(leaf_points, pairs)
+        K = plan["pairs"].shape[0]
+        batch = tuple(self.tsf_batch) if self.tsf_batch is not None else ()
+        if K == 0:
+            dev, dt = plan["dev"], plan["dtype"]
+            return LeafPairHinge(torch.empty(batch + (0,), dtype=dt, device=dev),
+                                 torch.empty(batch + (0,), dtype=torch.int64, device=dev))
+        mode = self._fused_mode()
+        if mode is None:
+            return self._leaf_pair_hinge_generic(plan, margin, power)
+        if self._tf_grad and torch.is_grad_enabled():
+            from pytorch_volumetric_amd import autograd
+            return autograd.leaf_pair_hinge(self, plan, margin, power, mode)
+        return LeafPairHinge(*self._leaf_pair_hinge_fused(plan, margin, power, mode)[:2])
+
+    def _leaf_pair_hinge_fused(self, plan, margin, power, mode):
+        """pvamd_leaf_pair_transforms + pvamd_leaf_pair_hinge[_f64].  Returns (values, counts) in the result shapes, then what
+        the backward needs: the pair transforms and the stack the kernels read."""
+        S = len(self.sdfs)
+        batch = tuple(self.tsf_batch) if self.tsf_batch is not None else ()
+        A = math.prod(batch)
+        dev, dt, table = plan["dev"], plan["dtype"], plan["table"]
+        K = table.shape[0]
+        C, tfd = self._pair_transforms(table, K, dt, dev)
+        val = torch.empty((A, K), dtype=dt, device=dev)
+        cnt = torch.empty((A, K), dtype=torch.int64, device=dev)
+        f64 = dt == torch.float64
+        name = "pvamd_leaf_pair_hinge" + ("_f64" if f64 else "")
+        with _lib.on_device(dev):
+            grids = self._leaf_grids(dev)
+            n = _lib.leaf_pair_hinge_scratch_bytes(K, A, plan["max_points"], f64, False)
+            scratch = torch.empty((n,), dtype=torch.uint8, device=dev) if n else None
+            _lib.check(getattr(_lib.load(), name)(_lib.ptr(grids), S, _lib.ptr(C), A, _lib.ptr(plan["packed"]), plan["npoints"],
+                                                  _lib.ptr(table), K, plan["max_points"], _lib.LEAF_MODES[mode], margin, power,
+                                                  _lib.ptr(val), _lib.ptr(cnt), _lib.ptr(scratch), _lib.stream_ptr()), name)
+        return val.reshape(*batch, K), cnt.reshape(*batch, K), C, tfd
+
+    def _leaf_pair_hinge_generic(self, plan, margin, power):
+        """Compositions the kernels do not serve (MeshSDF leaves, mixed interpolation, other leaves): the pair transforms of the
+        kernel, then one one-leaf hinge_over_points per pair -- not a hot path.  Differentiable through __call__, and to the
+        transforms through autograd.PairTransforms."""
+        from pytorch_volumetric_amd import autograd
+        batch = tuple(self.tsf_batch) if self.tsf_batch is not None else ()
+        ph = plan["pairs"]
+        C = autograd.pair_transforms(self, plan["table"], ph, plan["dtype"], plan["dev"])  # (K, A, 4, 4)
+        parts = []
+        for k, (s, t) in enumerate(ph.tolist()):
+            one = ComposedSDF([self.sdfs[s]], None)
+            one.set_transforms(C[k], batch_dim=self.tsf_batch, known_rigid=True)
+            pts = plan["points"][t]
+            parts.append(one.hinge_over_points(pts.to(plan["dtype"]) if pts.dtype != plan["dtype"] else pts, margin, power))
+        return LeafPairHinge(*(torch.stack(x, dim=len(batch)) for x in zip(*parts)))
 
     def _interp_forward(self, points, want_leaf):
         """_fused_forward of a trilinear composition (the leaf ids the interpolation tests compare)."""
