@@ -730,6 +730,49 @@ int pvamd_leaf_pair_hinge_backward_f64(const pvamd_grid_t* grids, int32_t S, con
                                        const double* points, int64_t npoints, const int64_t* table, int32_t K, int64_t max_points,
                                        int32_t mode, double margin, int32_t power, const double* up, double* dtf, void* scratch,
                                        void* stream);
+
+/* ---- Chamfer normal equations (chamfer_normal_equations / refine_poses) ----
+ * The Gauss-Newton normal equations of the chamfer cost sum_i (sdf(W[b] p_i))^2 of B poses against one cached grid, and the
+ * Levenberg-Marquardt step built on them.  grid: 3-D, BOUNDING_BOX (else PVAMD_E_MODE), either index arithmetic (index_f64).
+ *  1. Per pair (b, i): x = W[b] p_i with the bits of pvamd_transform_points (affine_row).  (v, n) = the bits of
+ *     pvamd_cached_query (mode PVAMD_LEAF_NEAREST) or pvamd_cached_query_interp (PVAMD_LEAF_TRILINEAR) at x: value and returned
+ *     gradient, in range or in the bounding-box branch.  The trilinear n is the interpolated stored gradient, not d val / dx:
+ *     the point-to-plane linearisation is the same statement in both modes.
+ *  2. The pose perturbation is a left-multiplied twist in the object frame, xi = (u, w), translation first: x' = x + w cross x
+ *     + u, so j = (n, x cross n).  j is formed in float64 from the float32 x and n: each product of the cross product is exact
+ *     in float64 and each component rounds once.
+ *  3. out_sums[b] = (s0, s1[6], s2 upper triangle row-major [21]): s0 = sum v v, s1 = sum v j, s2 = sum j j^T, in float64, each
+ *     term entering by one fused multiply-add, in an order that depends only on (B, N): per lane in point order over its points
+ *     of a PVAMD_REG_CHUNK-point chunk, a wave butterfly, the four waves in order, then the chunks in chunk order.  Bitwise
+ *     reproducible; no float atomics, no device -> host synchronisation, no allocation.  A NaN v or n makes that pose's sums
+ *     NaN and only that pose's.
+ *  4. out_counts[b] = the number of points of pose b that pass the range decision of the query (int64).
+ *  5. The caller scales: cost = scale^2 s0 / N, gradient = scale^2 s1 / N (half of d cost / d xi at xi = 0 under this
+ *     linearisation), hessian = scale^2 s2 / N.
+ * pvamd_chamfer_normal_eq: W device [B][4][4], points device [N][3], 1 <= N, 0 <= B (B = 0 does nothing).  scratch: device,
+ *   PVAMD_CHAMFER_NORMAL_EQ_SCRATCH_BYTES(B, N) bytes, 8-byte aligned (28 sums and one count per pose and chunk).
+ * pvamd_pose_lm_step: one Levenberg-Marquardt decision per pose on the device, all float64.  sums [B][28]: the raw sums just
+ *   computed at Wtry.  State: Wacc, Wtry [B][3][4], sums_acc [B][28], lambda [B], accepted [B] int32 (the caller zeroes it and
+ *   sets Wtry and lambda before the first call).
+ *   a. Accept if first or s0(sums) < s0(sums_acc) (strict: a NaN never accepts): Wacc = Wtry, sums_acc = sums,
+ *      lambda = max(lambda down, lambda_min), accepted += 1.  Otherwise lambda = min(lambda up, lambda_max).
+ *   b. Solve (S2 + lambda D) xi = -S1 with the accepted sums by Cholesky without pivoting in a fixed order, D diagonal with
+ *      D_k = S2_kk where that is positive and 1 elsewhere (an axis no point observes gets a zero step).  A pivot that is not
+ *      positive and finite, or a non-finite xi: xi = 0 and lambda = min(lambda up, lambda_max).
+ *   c. Retract: Wtry = [Exp(w) R, Exp(w) t + u] from Wacc = [R, t], Exp by Rodrigues' formula (the series below |w| < 1e-8);
+ *      xi = 0 copies Wacc bit for bit.  W_next [B][4][4] = Wtry rounded to float32 with the row 0 0 0 1: what the next
+ *      pvamd_chamfer_normal_eq reads.
+ *   1 < up, 0 < down <= 1, 0 < lambda_min <= lambda_max < inf, first 0 or 1, else PVAMD_E_MODE.                                   */
+#define PVAMD_REG_CHUNK 2048 /* points per slab row */
+#define PVAMD_REG_SUMS 28    /* s0, s1[6], s2 upper triangle [21] */
+#define PVAMD_CHAMFER_NORMAL_EQ_SCRATCH_BYTES(B, N) \
+    (8 * (PVAMD_REG_SUMS + 1) * (int64_t)(B) * (((int64_t)(N) + PVAMD_REG_CHUNK - 1) / PVAMD_REG_CHUNK))
+int64_t pvamd_chamfer_normal_eq_scratch_bytes(int32_t B, int64_t N);
+int pvamd_chamfer_normal_eq(const pvamd_grid_t* grid, int32_t mode, const float* W, int32_t B, const float* points, int64_t N,
+                            double* out_sums, int64_t* out_counts, void* scratch, void* stream);
+int pvamd_pose_lm_step(int32_t B, const double* sums, int32_t first, double* Wacc, double* sums_acc, double* lambda,
+                       int32_t* accepted, double* Wtry, float* W_next, double up, double down, double lambda_min,
+                       double lambda_max, void* stream);
 #ifdef __cplusplus
 }
 #endif

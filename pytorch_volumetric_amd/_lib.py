@@ -70,6 +70,17 @@ def hinge_over_points_scratch_bytes(S, A, P, per_leaf):
     return min_over_points_scratch_bytes(S, A, P, per_leaf)
 
 
+REG_CHUNK = 2048  # PVAMD_REG_CHUNK
+REG_SUMS = 28     # PVAMD_REG_SUMS
+
+
+def chamfer_normal_eq_scratch_bytes(B, N):
+    """PVAMD_CHAMFER_NORMAL_EQ_SCRATCH_BYTES(B, N): 28 float64 sums and one int64 count per pose and point chunk."""
+    if B < 1 or N < 1:
+        return 0
+    return 8 * (REG_SUMS + 1) * B * ((N + REG_CHUNK - 1) // REG_CHUNK)
+
+
 def leaf_pair_scratch_bytes(K, A, max_points, f64, backward):
     """PVAMD_LEAF_PAIR_SCRATCH_BYTES(K, A, max_points, elem, backward): the forward's one 16-byte key per pair, configuration and
     4096-point chunk when a set holds more than one chunk (else none); the backward's dMs and dMt per pair and configuration."""
@@ -311,6 +322,10 @@ SIGNATURES = {
     "pvamd_composed_hinge_over_points_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "pvamd_composed_hinge_over_points_backward": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "pvamd_composed_hinge_over_points_backward_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    # chamfer_normal_equations / refine_poses (include/pvamd.h "Chamfer normal equations")
+    "pvamd_chamfer_normal_eq_scratch_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int64]),
+    "pvamd_chamfer_normal_eq": (ctypes.c_int, [ctypes.POINTER(GridDesc), ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "pvamd_pose_lm_step": (ctypes.c_int, [ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_void_p]),
 }
 
 E_SHAPE = -2  # PVAMD_E_SHAPE (include/pvamd.h)

@@ -1,0 +1,218 @@
+"""Second-order pose refinement against an SDF: the Gauss-Newton normal equations of the chamfer cost
+sum_i (scale * sdf(W p_i))^2 over a left-multiplied twist of every pose (`chamfer_normal_equations`, one fused pass over the
+(pose, point) pairs) and a Levenberg-Marquardt loop around them whose decisions stay on the device (`refine_poses`).
+The contract is include/pvamd.h "Chamfer normal equations"; the kernels are csrc/registration.hip."""
+import ctypes
+import math
+import numbers
+from typing import NamedTuple
+
+import torch
+
+from pytorch_volumetric_amd import _lib
+from pytorch_volumetric_amd import transforms as tf
+from pytorch_volumetric_amd.sdf import CachedSDF, ObjectFrameSDF, OutOfBoundsStrategy
+
+LAMBDA_MIN = 1e-12
+LAMBDA_MAX = 1e12
+
+
+class ChamferNormalEquations(NamedTuple):
+    cost: torch.Tensor      # (B,) float64: scale^2 / N * sum v^2, what batch_chamfer_dist returns before its cast
+    gradient: torch.Tensor  # (B, 6) float64: scale^2 / N * sum v j, half of d cost / d xi at xi = 0; xi = (u, w)
+    hessian: torch.Tensor   # (B, 6, 6) float64: scale^2 / N * sum j j^T, symmetric
+    counts: torch.Tensor    # (B,) int64: points of the pose inside the grid range
+
+
+class PoseRefinement(NamedTuple):
+    world_to_object: torch.Tensor  # (B, 4, 4) the best accepted pose, in the input's dtype and device
+    cost: torch.Tensor             # (B,) float64 its cost
+    initial_cost: torch.Tensor     # (B,) float64 the cost of the input pose
+    accepted: torch.Tensor         # (B,) int64 evaluations accepted (the first one included)
+
+
+def _check_scale(scale):
+    if isinstance(scale, bool) or not isinstance(scale, numbers.Real):
+        raise TypeError(f"scale must be a real number, got {scale!r}")
+    if not math.isfinite(scale):
+        raise ValueError(f"scale must be finite, got {scale!r}")
+    return float(scale)
+
+
+def _check_inputs(world_to_object, points, obj_sdf):
+    """(W (B, 4, 4) as given, points as a tensor); raises before anything touches the device."""
+    if not isinstance(obj_sdf, ObjectFrameSDF):
+        raise TypeError(f"obj_sdf must be an ObjectFrameSDF, got {type(obj_sdf).__name__}")
+    W = tf.as_matrix(world_to_object)
+    if W.dim() != 3 or tuple(W.shape[1:]) != (4, 4):
+        raise ValueError(f"world_to_object must be (B, 4, 4), got {tuple(W.shape)}")
+    pts = points if torch.is_tensor(points) else torch.as_tensor(points)
+    if pts.dim() < 1 or pts.shape[-1] != 3:
+        raise ValueError(f"points must have last dimension 3, got {tuple(pts.shape)}")
+    if pts.numel() == 0:
+        raise ValueError("points must hold at least one point (the cost is a mean over them)")
+    return W, pts
+
+
+def _fused_mode(obj_sdf):
+    """The leaf mode of the fused kernel, or None for the generic path."""
+    if isinstance(obj_sdf, CachedSDF) and obj_sdf._dim == 3 and \
+            obj_sdf.out_of_bounds_strategy == OutOfBoundsStrategy.BOUNDING_BOX and obj_sdf.interpolation in _lib.LEAF_MODES:
+        return _lib.LEAF_MODES[obj_sdf.interpolation]
+    return None
+
+
+def _device_of(obj_sdf, mode):
+    return obj_sdf._packed.device if mode is not None else _lib.require_gpu()
+
+
+_TRIANGLE = {}
+
+
+def _triangle_index(dev):
+    """(6, 6) index into the 21 packed upper-triangle entries, cached per device (creating it copies from the host)."""
+    idx = _TRIANGLE.get(dev)
+    if idx is None:
+        rows, e = [[0] * 6 for _ in range(6)], 0
+        for r in range(6):
+            for c in range(r, 6):
+                rows[r][c] = rows[c][r] = e
+                e += 1
+        idx = _TRIANGLE[dev] = torch.tensor(rows, dtype=torch.int64, device=dev).reshape(-1)
+    return idx
+
+
+class _Evaluator:
+    """The raw sums (B, 28) and counts (B,) at float32 poses (B, 4, 4) on the device; buffers allocated once."""
+
+    def __init__(self, obj_sdf, mode, dev, pts, B):
+        self.obj_sdf, self.mode, self.dev, self.pts, self.B = obj_sdf, mode, dev, pts, B
+        self.N = pts.shape[0]
+        self.sums = torch.empty((B, _lib.REG_SUMS), dtype=torch.float64, device=dev)
+        self.counts = torch.empty((B,), dtype=torch.int64, device=dev)
+        if mode is not None:
+            self.scratch = torch.empty((_lib.chamfer_normal_eq_scratch_bytes(B, self.N) // 8,), dtype=torch.int64, device=dev)
+            self.desc = obj_sdf._grid_desc()
+
+    def __call__(self, W32):
+        if self.B == 0:
+            return
+        lib = _lib.load()
+        if self.mode is not None:
+            _lib.check(lib.pvamd_chamfer_normal_eq(ctypes.byref(self.desc), self.mode, _lib.ptr(W32), self.B, _lib.ptr(self.pts),
+                                                   self.N, _lib.ptr(self.sums), _lib.ptr(self.counts), _lib.ptr(self.scratch),
+                                                   _lib.stream_ptr()), "pvamd_chamfer_normal_eq")
+            return
+        # any other object: transform with the kernel's statements, query the object, the same sums in float64 in torch
+        x = torch.empty((self.B, self.N, 3), dtype=torch.float32, device=self.dev)
+        for b0 in range(0, self.B, 65535):  # the transform kernel carries the transform in a grid dimension
+            nb = min(65535, self.B - b0)
+            _lib.check(lib.pvamd_transform_points(_lib.ptr(W32[b0:b0 + nb]), nb, _lib.ptr(self.pts), self.N, _lib.ptr(x[b0:b0 + nb]),
+                                                  _lib.stream_ptr()), "pvamd_transform_points")
+        with torch.no_grad():
+            v, n = self.obj_sdf(x)
+        v = v.detach().to(device=self.dev, dtype=torch.float64).reshape(self.B, self.N)
+        n = n.detach().to(device=self.dev, dtype=torch.float64).reshape(self.B, self.N, 3)
+        j = torch.cat((n, torch.linalg.cross(x.to(torch.float64), n, dim=-1)), dim=-1)
+        self.sums[:, 0] = (v * v).sum(-1)
+        self.sums[:, 1:7] = (v.unsqueeze(-1) * j).sum(-2)
+        r, c = torch.triu_indices(6, 6).tolist()
+        self.sums[:, 7:] = (j[..., r] * j[..., c]).sum(-2)
+        self.counts.fill_(self.N)  # no grid: every point is answered by the object itself
+
+
+def _prepare(W, pts, dev):
+    pts32 = pts.detach().reshape(-1, 3).to(device=dev, dtype=torch.float32).contiguous()
+    W32 = W.detach().to(device=dev, dtype=torch.float32).contiguous()
+    return W32, pts32
+
+
+def chamfer_normal_equations(world_to_object, points, obj_sdf: ObjectFrameSDF, scale=1000.):
+    """The Gauss-Newton normal equations of `batch_chamfer_dist(world_to_object, points, obj_sdf=obj_sdf, scale=scale)` over a
+    left-multiplied twist xi = (u, w) of every pose, translation first: x' = x + w x x + u.
+
+    :param world_to_object: (B, 4, 4) transforms (or a transform object), used in float32 as batch_chamfer_dist uses them
+    :param points: (N, 3) world-frame points, N >= 1 (leading dimensions are flattened)
+    :param obj_sdf: the object; a 3-D BOUNDING_BOX CachedSDF (nearest or trilinear) runs one fused kernel, anything else
+        is transformed, queried and summed in torch under the same contract
+    :param scale: unit conversion applied to the distance before squaring
+    :return: ChamferNormalEquations(cost (B,), gradient (B, 6), hessian (B, 6, 6), counts (B,)) on the GPU, float64 / int64.
+        Per pair, v and n are the value and the gradient the object returns at x = W p, j = (n, x cross n) in float64;
+        cost = scale^2 / N sum v^2, gradient = scale^2 / N sum v j, hessian = scale^2 / N sum j j^T.  The sums are float64 in
+        an order that depends only on (B, N): two calls give the same bits.  A NaN makes its own pose's outputs NaN.  The
+        result carries no autograd graph (it is a solver's input).  No device -> host synchronisation: the call can be
+        captured in a graph once the object's descriptor exists (after one call)."""
+    scale = _check_scale(scale)
+    W, pts = _check_inputs(world_to_object, points, obj_sdf)
+    mode = _fused_mode(obj_sdf)
+    dev = _device_of(obj_sdf, mode)
+    with _lib.on_device(dev):
+        W32, pts32 = _prepare(W, pts, dev)
+        ev = _Evaluator(obj_sdf, mode, dev, pts32, W32.shape[0])
+        ev(W32)
+        k = scale * scale / ev.N
+        s = ev.sums * k
+        return ChamferNormalEquations(s[:, 0], s[:, 1:7], s[:, 7:][:, _triangle_index(dev)].reshape(-1, 6, 6), ev.counts)
+
+
+def _check_refine_args(iterations, damping, damping_up, damping_down):
+    if isinstance(iterations, bool) or not isinstance(iterations, numbers.Integral):
+        raise TypeError(f"iterations must be an int, got {iterations!r}")
+    if iterations < 1:
+        raise ValueError(f"iterations must be at least 1, got {iterations}")
+    for name, val in (("damping", damping), ("damping_up", damping_up), ("damping_down", damping_down)):
+        if isinstance(val, bool) or not isinstance(val, numbers.Real):
+            raise TypeError(f"{name} must be a real number, got {val!r}")
+    if not (math.isfinite(damping) and damping > 0):
+        raise ValueError(f"damping must be finite and positive, got {damping!r}")
+    if not (math.isfinite(damping_up) and damping_up > 1):
+        raise ValueError(f"damping_up must be finite and above 1, got {damping_up!r}")
+    if not (0 < damping_down <= 1):
+        raise ValueError(f"damping_down must lie in (0, 1], got {damping_down!r}")
+    return int(iterations), float(damping), float(damping_up), float(damping_down)
+
+
+def refine_poses(world_to_object, points, obj_sdf: ObjectFrameSDF, iterations=10, scale=1000., damping=1e-3, damping_up=10.,
+                 damping_down=0.1):
+    """Levenberg-Marquardt refinement of B poses against an SDF: minimises the chamfer cost of `chamfer_normal_equations` by
+    damped Gauss-Newton steps, every accept / reject decision taken on the device (pvamd_pose_lm_step).
+
+    :param iterations: normal-equation evaluations after the initial one, an int >= 1
+    :param damping: initial Marquardt damping (relative to the Hessian's diagonal), multiplied by damping_down after an
+        accepted evaluation and by damping_up after a rejected one, kept within [LAMBDA_MIN, LAMBDA_MAX]
+    :return: PoseRefinement(world_to_object, cost, initial_cost, accepted): the best accepted pose of every input pose (never
+        worse than the input: cost <= initial_cost) in the input's dtype and device, its cost and the input's (float64), and
+        the number of accepted evaluations (>= 1: the first).  A fixed sequence of 1 + iterations x (normal equations, step)
+        launches with no device -> host synchronisation: the call can be captured in a graph."""
+    scale = _check_scale(scale)
+    iterations, damping, up, down = _check_refine_args(iterations, damping, damping_up, damping_down)
+    W, pts = _check_inputs(world_to_object, points, obj_sdf)
+    out_dtype = W.dtype if W.dtype.is_floating_point else torch.float32
+    out_device = W.device
+    mode = _fused_mode(obj_sdf)
+    dev = _device_of(obj_sdf, mode)
+    lib = _lib.load()
+    with _lib.on_device(dev):
+        W32, pts32 = _prepare(W, pts, dev)
+        B = W32.shape[0]
+        ev = _Evaluator(obj_sdf, mode, dev, pts32, B)
+        # the state of pvamd_pose_lm_step
+        w_try = W32[:, :3, :].to(torch.float64).contiguous()
+        w_acc = torch.empty_like(w_try)
+        sums_acc = torch.empty_like(ev.sums)
+        lam = torch.full((B,), damping, dtype=torch.float64, device=dev)
+        accepted = torch.zeros((B,), dtype=torch.int32, device=dev)
+        w_next = W32.clone()
+        initial = None
+        for it in range(iterations + 1):
+            ev(w_next)
+            if it == 0:
+                initial = ev.sums[:, 0].clone()
+            _lib.check(lib.pvamd_pose_lm_step(B, _lib.ptr(ev.sums), int(it == 0), _lib.ptr(w_acc), _lib.ptr(sums_acc), _lib.ptr(lam),
+                                              _lib.ptr(accepted), _lib.ptr(w_try), _lib.ptr(w_next), up, down, LAMBDA_MIN,
+                                              LAMBDA_MAX, _lib.stream_ptr()), "pvamd_pose_lm_step")
+        k = scale * scale / ev.N
+        out = torch.zeros((B, 4, 4), dtype=out_dtype, device=dev)
+        out[:, :3, :] = w_acc.to(out_dtype)
+        out[:, 3, 3] = 1
+        return PoseRefinement(out.to(out_device), sums_acc[:, 0] * k, initial * k, accepted.to(torch.int64))
