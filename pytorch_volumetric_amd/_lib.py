@@ -15,6 +15,10 @@ ABI_VERSION = 13
 OOB_LOOKUP_GT_SDF = 0
 OOB_BOUNDING_BOX = 1
 COMPOSED_INLINE_EXACT = 1
+COMPOSED_FORCE_PER_LANE = 2
+COMPOSED_FORCE_WAVE_TILE = 4
+COMPOSED_POINTS_FASTEST = 8
+COMPOSED_LEGACY_LEAF_LOOP = 16
 COMPOSED_OUT_PACKED = 32
 COMPOSED_NO_GROUPING = 64
 COMPOSED_FORCE_FUSED = 128

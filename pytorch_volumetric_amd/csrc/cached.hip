@@ -12,39 +12,32 @@ namespace pvamd {
 // a wave-private LDS slice; the results go back through the same slice and leave as 1 + 3 contiguous 1 KB stores.
 // No block barrier: a wave's LDS traffic is ordered.  Measured against the previous "4 points per thread, 48-byte
 // strided float4" form: 0.63 ms -> 0.38 ms for 64M points (tools/kbench.hip, profiles/r01_kbench.txt).
-// Which points a lane owns (PVAMD_CQ_OWN4):
-//   0  lane, lane+64, lane+128, lane+192: stride-3 dword LDS reads (conflict-free), 16 dword LDS writes for the results
-//   1  4*lane .. 4*lane+3: the lane's 12 input floats are three ds_read_b128 at a 48-byte lane stride (conflict-free per
-//      16 lanes), its four values are ONE 16-byte global store (no LDS), its 12 gradient floats three ds_write_b128:
-//      12 LDS instructions per tile instead of 35
+// A lane owns points 4*lane .. 4*lane+3: its 12 input floats are three ds_read_b128 at a 48-byte lane stride (conflict-free per
+// 16 lanes), its four values are ONE 16-byte global store (no LDS), its 12 gradient floats three ds_write_b128: 12 LDS
+// instructions per tile instead of the 35 of owning lane, lane+64, lane+128, lane+192 (stride-3 dword reads, 16 dword writes).
 // Any point count >= 256 and any 4-byte aligned buffers: the 16-byte accesses take dword addresses (common.h f32x4_u); a
 // ragged end is covered by moving the last tile back so that it ends at the last point.
 // Waves per workgroup.  Round 4: 16 (1024 threads, 64 KB of LDS, two workgroups per CU) instead of 8 -- found while A/B-ing
 // LDS-DMA point loads (slower at every depth: profiles/r04_cq_variants.txt; the experiment's source is tools/patches/cq_ablate_and_dma.patch): the 64M-point launch 382 -> 346 us (5.43 TB/s =
 // 0.68 of 8 TB/s; 336 us = 0.70 on another box), with EVERY point gathering 568 -> 419 us -- round 3's "gather ceiling that no
 // launch geometry moves" (0.55-0.59 ms) was the 8-wave geometry's; 1M and 8M points unchanged (5.84 / 39.9 us).
-#ifndef PVAMD_CQ_WAVES
-#define PVAMD_CQ_WAVES 16
-#endif
-#ifndef PVAMD_CQ_OWN4
-#define PVAMD_CQ_OWN4 1
-#endif
-constexpr int kWavesPerBlock = PVAMD_CQ_WAVES;
+constexpr int kWavesPerBlock = 16;
 constexpr int kTilePoints = 256;
-constexpr bool kOwn4 = PVAMD_CQ_OWN4 != 0;
-#ifndef PVAMD_CQ_MIN_POINTS
-#define PVAMD_CQ_MIN_POINTS 16384
-#endif
-constexpr int64_t kWaveTileMinPoints = PVAMD_CQ_MIN_POINTS;
+constexpr int64_t kWaveTileMinPoints = 16384;
+constexpr int kCqMinWaves = 1;                          // cached_query_wave's __launch_bounds__ waves per SIMD
+constexpr int64_t kCqStreamFrom = (int64_t)8 << 20;     // more points than this: the streaming instantiation (cq_kind)
+// The streaming regime (> 8M points, far beyond the 256 MB Infinity Cache), round 3 (tools/cq_sweep.py over build
+// variants, profiles/r03_cq_variants.txt; 64M points, 52 % out of range): one tile per wave instead of a capped grid with a
+// grid-stride loop 431 -> 413 us, 8 waves per workgroup 369-374, non-temporal stores as well 361 us (5.2 TB/s); 16 waves
+// 363; plain loads 382.  What bounds it is in profiles/r03_cq64_counters.md: the L1 (TCP) -> L2 request path, not HBM.
+constexpr bool kCqBigStNt = true, kCqBigLdNt = true;
+constexpr int64_t kCqBlocks = 1024, kCqBigBlocks = 0;  // workgroup cap; 0: one tile per wave, no grid-stride loop
 
 // LD_NT / ST_NT: non-temporal loads / stores.  Measured (tools/kbench.hip): batches whose points are cache-resident
 // (<= a few M points, e.g. produced by the previous kernel or re-used) prefer plain loads + nt stores (6.6 -> 6.3 us per
 // 1M points); batches far beyond the 256 MB Infinity Cache prefer nt loads + plain stores (0.370 -> 0.358 ms per 64M).
-#ifndef PVAMD_CQ_MINWAVES
-#define PVAMD_CQ_MINWAVES 1
-#endif
 template <bool F64, bool WRITE_OOB, bool LD_NT, bool ST_NT>
-__global__ __launch_bounds__(kWavesPerBlock * 64, PVAMD_CQ_MINWAVES) void cached_query_wave(const pvamd_grid_t g,
+__global__ __launch_bounds__(kWavesPerBlock * 64, kCqMinWaves) void cached_query_wave(const pvamd_grid_t g,
                                                                          const float* __restrict__ pts, int64_t P,
                                                                          float* __restrict__ val,
                                                                          float* __restrict__ grad,
@@ -53,7 +46,6 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, PVAMD_CQ_MINWAVES) void cached
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float* spf = lds[wave];
     f32x4_alias* sp = reinterpret_cast<f32x4_alias*>(spf);
-    float* svf = spf + 768;
     const int64_t ntiles = (P + kTilePoints - 1) / kTilePoints;
     const int64_t wstride = (int64_t)gridDim.x * kWavesPerBlock;
     int64_t tile = (int64_t)blockIdx.x * kWavesPerBlock + wave;
@@ -84,56 +76,30 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, PVAMD_CQ_MINWAVES) void cached
         if (next < ntiles) load3(next);
         PVAMD_WAVE_SYNC();
         float px[4], py[4], pz[4];
-        if constexpr (kOwn4) {
-            const f32x4 q0 = sp[3 * lane], q1 = sp[3 * lane + 1], q2 = sp[3 * lane + 2];
-            px[0] = q0.x; py[0] = q0.y; pz[0] = q0.z;
-            px[1] = q0.w; py[1] = q1.x; pz[1] = q1.y;
-            px[2] = q1.z; py[2] = q1.w; pz[2] = q2.x;
-            px[3] = q2.y; py[3] = q2.z; pz[3] = q2.w;
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int p = lane + 64 * k;
-                px[k] = spf[3 * p];
-                py[k] = spf[3 * p + 1];
-                pz[k] = spf[3 * p + 2];
-            }
-        }
+        const f32x4 q0 = sp[3 * lane], q1 = sp[3 * lane + 1], q2 = sp[3 * lane + 2];
+        px[0] = q0.x; py[0] = q0.y; pz[0] = q0.z;
+        px[1] = q0.w; py[1] = q1.x; pz[1] = q1.y;
+        px[2] = q1.z; py[2] = q1.w; pz[2] = q2.x;
+        px[3] = q2.y; py[3] = q2.z; pz[3] = q2.w;
         PVAMD_WAVE_SYNC();
         const int64_t o = first_point(tile);
-        f32x4 v4;
-        if constexpr (kOwn4) {
-            float4 r[4];
-            bool valid[4];
+        float4 r[4];
+        bool valid[4];
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                r[k] = cached_lookup<F64, LD_NT>(g, px[k], py[k], pz[k], valid[k]);  // LD_NT = the streaming launch (> 8M points)
-            }
-            sp[3 * lane] = f32x4{r[0].y, r[0].z, r[0].w, r[1].y};
-            sp[3 * lane + 1] = f32x4{r[1].z, r[1].w, r[2].y, r[2].z};
-            sp[3 * lane + 2] = f32x4{r[2].w, r[3].y, r[3].z, r[3].w};
-            v4 = f32x4{r[0].x, r[1].x, r[2].x, r[3].x};
-            if constexpr (WRITE_OOB) {
-                const uint32_t m = (valid[0] ? 0u : 1u) | (valid[1] ? 0u : 1u << 8) | (valid[2] ? 0u : 1u << 16) | (valid[3] ? 0u : 1u << 24);
-                __builtin_memcpy(oob + o + 4 * lane, &m, 4);  // the 4 consecutive flags of this lane
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int p = lane + 64 * k;
-                bool valid;
-                const float4 r = cached_lookup<F64, LD_NT>(g, px[k], py[k], pz[k], valid);
-                svf[p] = r.x;
-                spf[3 * p] = r.y;
-                spf[3 * p + 1] = r.z;
-                spf[3 * p + 2] = r.w;
-                if constexpr (WRITE_OOB) oob[o + p] = valid ? 0 : 1;
-            }
+        for (int k = 0; k < 4; ++k) {
+            r[k] = cached_lookup<F64, LD_NT>(g, px[k], py[k], pz[k], valid[k]);  // LD_NT = the streaming launch (> 8M points)
+        }
+        sp[3 * lane] = f32x4{r[0].y, r[0].z, r[0].w, r[1].y};
+        sp[3 * lane + 1] = f32x4{r[1].z, r[1].w, r[2].y, r[2].z};
+        sp[3 * lane + 2] = f32x4{r[2].w, r[3].y, r[3].z, r[3].w};
+        const f32x4 v4 = f32x4{r[0].x, r[1].x, r[2].x, r[3].x};
+        if constexpr (WRITE_OOB) {
+            const uint32_t m = (valid[0] ? 0u : 1u) | (valid[1] ? 0u : 1u << 8) | (valid[2] ? 0u : 1u << 16) | (valid[3] ? 0u : 1u << 24);
+            __builtin_memcpy(oob + o + 4 * lane, &m, 4);  // the 4 consecutive flags of this lane
         }
         PVAMD_WAVE_SYNC();
         f32x4_u* vdst = reinterpret_cast<f32x4_u*>(val + o);
         f32x4_u* dst = reinterpret_cast<f32x4_u*>(grad + 3 * o);
-        if constexpr (!kOwn4) v4 = sp[192 + lane];
         if (ST_NT) {
             __builtin_nontemporal_store(v4, vdst + lane);
             __builtin_nontemporal_store(sp[lane], dst + lane);
@@ -204,18 +170,12 @@ enum CqKind {
 };
 static inline CqKind cq_kind(int64_t P) {
     if (P < kWaveTileMinPoints) return kCqScalar;
-#ifdef PVAMD_CQ_NO_DIRECT  // A/B: the round-5 choice
-    return P <= ((int64_t)8 << 20) ? kCqWaveTile : kCqStreaming;
-#endif
     if (P <= 160 * 1024) return kCqDirect1;
     if (P <= 896 * 1024) return kCqDirect2;
     if (P <= 1024 * 1024) return kCqDirect2Wide;
     if (P <= 1600 * 1024) return kCqDirect4;
     if (P <= 2304 * 1024) return kCqWaveTile;
-#ifndef PVAMD_CQ_STREAM_FROM
-#define PVAMD_CQ_STREAM_FROM ((int64_t)8 << 20)
-#endif
-    if (P <= PVAMD_CQ_STREAM_FROM) return kCqDirect4;
+    if (P <= kCqStreamFrom) return kCqDirect4;
     return kCqStreaming;
 }
 
@@ -339,28 +299,12 @@ extern "C" int pvamd_cached_query(const pvamd_grid_t* grid, const float* points,
     if (kind == kCqWaveTile || kind == kCqStreaming) {
         const int64_t ntiles = (P + kTilePoints - 1) / kTilePoints;
         const int64_t need = (ntiles + kWavesPerBlock - 1) / kWavesPerBlock;
-// The streaming regime (> 8M points, far beyond the 256 MB Infinity Cache), round 3 (tools/cq_sweep.py over build
-// variants, profiles/r03_cq_variants.txt; 64M points, 52 % out of range): one tile per wave instead of a capped grid with a
-// grid-stride loop 431 -> 413 us, 8 waves per workgroup 369-374, non-temporal stores as well 361 us (5.2 TB/s); 16 waves
-// 363; plain loads 382.  What bounds it is in profiles/r03_cq64_counters.md: the L1 (TCP) -> L2 request path, not HBM.
-#ifndef PVAMD_CQ_BIG_ST_NT
-#define PVAMD_CQ_BIG_ST_NT true
-#endif
-#ifndef PVAMD_CQ_BIG_LD_NT
-#define PVAMD_CQ_BIG_LD_NT true
-#endif
-#ifndef PVAMD_CQ_BLOCKS
-#define PVAMD_CQ_BLOCKS 1024
-#endif
-#ifndef PVAMD_CQ_BIG_BLOCKS
-#define PVAMD_CQ_BIG_BLOCKS 0
-#endif
         const bool big = kind == kCqStreaming;  // > 8M points (96 MB of xyz)
-        const int64_t cap = big ? PVAMD_CQ_BIG_BLOCKS : PVAMD_CQ_BLOCKS;  // 0: one tile per wave, no grid-stride loop
+        const int64_t cap = big ? kCqBigBlocks : kCqBlocks;
         const dim3 grid_dim((unsigned)((cap > 0 && need > cap) ? cap : need)), block(kWavesPerBlock * 64);
 #define PVAMD_LAUNCH_CQ(F64_, OOB_)                                                                                      \
     do {                                                                                                                \
-        if (big) hipLaunchKernelGGL((cached_query_wave<F64_, OOB_, PVAMD_CQ_BIG_LD_NT, PVAMD_CQ_BIG_ST_NT>), grid_dim, block, 0, s, *grid, points, P, out_val, out_grad, out_oob); \
+        if (big) hipLaunchKernelGGL((cached_query_wave<F64_, OOB_, kCqBigLdNt, kCqBigStNt>), grid_dim, block, 0, s, *grid, points, P, out_val, out_grad, out_oob); \
         else hipLaunchKernelGGL((cached_query_wave<F64_, OOB_, false, true>), grid_dim, block, 0, s, *grid, points, P, out_val, out_grad, out_oob);    \
     } while (0)
         if (f64) {

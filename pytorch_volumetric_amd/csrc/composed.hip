@@ -140,10 +140,7 @@ PVAMD_DEV void rotate_back(const float* __restrict__ M, const Best& b, float& ox
 // AND its lower bound exceeds the upper bound some other out-of-range leaf guarantees for every point (strictly, with
 // margin -- first-minimum ties cannot be affected).
 constexpr int kMaxCullLeaves = 64;
-#ifndef PVAMD_COMPOSED_MASK_SPAN
-#define PVAMD_COMPOSED_MASK_SPAN 0.5f
-#endif
-constexpr float kMaskSpan = PVAMD_COMPOSED_MASK_SPAN;
+constexpr float kMaskSpan = 0.5f;
 
 PVAMD_DEV void build_cull_spheres(const pvamd_grid_t* __restrict__ grids, int S, const float* __restrict__ tf, int A,
                                   int a, float (*cull)[8]) {
@@ -238,34 +235,21 @@ PVAMD_DEV uint64_t tile_leaf_mask(const float (*cull)[8], int S, int lane, const
 // through a wave-private LDS slice (same scheme as cached_query_wave, see cached.hip).
 constexpr int kWavesPerBlock = 4;
 constexpr int kTilePoints = 256;
-// configurations per launch (a grid dimension carries them); a build knob so that a test can cross the slab border with
-// a small batch
-#ifndef PVAMD_COMPOSED_SLAB
-#define PVAMD_COMPOSED_SLAB 65535
-#endif
-constexpr int kConfigSlab = PVAMD_COMPOSED_SLAB;
+// configurations per launch (a grid dimension carries them)
+constexpr int kConfigSlab = 65535;
 // fewer (tile, configuration) pairs than this: the one-point-per-lane kernel.  A tile is one wave's work and the chip
 // holds 6,144-8,192 waves: below ~4 rounds of them the last, partly filled round costs more than the tile machinery saves
 // (README case, 200 x 15,251 points = 12,000 tiles: per-lane 0.076 / 0.061 ms on 21 MB / 100 KB link grids against 0.104 /
 // 0.088 ms; C4's 204,800 tiles: wave-tile 0.89 against 0.95 ms; tools/readme_case.py, profiles/r03_readme_case.txt)
-#ifndef PVAMD_COMPOSED_WAVE_MIN_TILES
-#define PVAMD_COMPOSED_WAVE_MIN_TILES 32768
-#endif
-constexpr int64_t kWaveTileMinTiles = PVAMD_COMPOSED_WAVE_MIN_TILES;
-#ifndef PVAMD_COMPOSED_PPP
-#define PVAMD_COMPOSED_PPP 2
-#endif
+constexpr int64_t kWaveTileMinTiles = 32768;
+constexpr int kPointsPerPass = 2;  // points per lane a pass of the tile kernels' leaf loop carries (their PPP)
 // kEstimate (instruction-bound, L2-resident grids): 8 waves per SIMD (<= 64 VGPRs, a few spills) beat the 6 the allocator
 // would pick on its own, C4 0.84 -> 0.80 ms.  kInlineExact (gather-bound, large grids): forcing 8 costs spills around the
 // division sequence, 6.19 -> 6.57 ms on the README-size robot; the allocator's own choice (5-6) is left alone.
-#ifndef PVAMD_COMPOSED_MINWAVES
-#define PVAMD_COMPOSED_MINWAVES 8
-#endif
+constexpr int kMinWaves = 8;
 // the inline-exact build: 6 = what the allocator chose on its own (78-80 VGPRs) until the switchable index rules added
 // statements to the exact path (89); held there
-#ifndef PVAMD_COMPOSED_MINWAVES_INLINE
-#define PVAMD_COMPOSED_MINWAVES_INLINE 6
-#endif
+constexpr int kMinWavesInline = 6;
 
 // The leaf loop of one tile: PPP points per lane at a time, results into the wave's LDS slice (or packed, to memory).
 // MASKED = false: the tile was not worth a leaf mask (every leaf is visited; no bit tests, no refinement).
@@ -370,17 +354,6 @@ PVAMD_DEV void tile_passes(const pvamd_grid_t* __restrict__ grids, int S, const 
 // drained 64 at a time with the leaf constants from per-lane global reads (v1) or an LDS table (v3), and a per-lane leaf
 // bitmask walked after the loop (v2) -- the queue's drains and merges are chains of dependent LDS / memory round trips
 // that the wave waits out (SQ_WAIT_ANY + 64 %), and the bitmask walk runs ~3 iterations at 2 live lanes.
-#ifdef PVAMD_COMPOSED_STATS  // tools/band_rate.py: how often the exact-root band is entered (a variant build only)
-__device__ unsigned long long g_band_stats[4];  // 64-point visits | visits that enter the band | lanes in the band | lanes the exact roots turn back
-extern "C" int pvamd_debug_band_stats(unsigned long long* out, int reset) {
-    (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_band_stats), sizeof(g_band_stats));
-    if (reset) { unsigned long long z[4] = {}; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_band_stats), z, sizeof(z)); }
-    return 0;
-}
-#define BAND_STAT(i, v) do { if ((threadIdx.x & 63) == 0) atomicAdd(&g_band_stats[i], (unsigned long long)(v)); } while (0)
-#else
-#define BAND_STAT(i, v)
-#endif
 constexpr float kNearTie = 0.99999952316284179688f;  // 1 - 2^-21: sqrt_rn(n2_b) == sqrt_rn(n2_a) needs n2_b >= n2_a (1 - 2^-22)
 constexpr int kNoLeaf = kUnnormalised - 1;           // "no candidate yet": loses every (value, leaf) tie
 
@@ -488,7 +461,6 @@ PVAMD_DEV void tile_passes_split(const pvamd_grid_t* __restrict__ grids, int S, 
                 // first minimum, NaN counts as minimum (keep_first_minimum), on the squared norms
                 uint64_t take = __builtin_amdgcn_ballot_w64(!(n2 >= best[k].n2)) &
                                 __builtin_amdgcn_ballot_w64(best[k].n2 == best[k].n2) & ~vm;
-                BAND_STAT(0, 1);
                 // nobody improves (neighbouring points agree on which leaves are far): the near-tie test and the five
                 // selects are skipped for the wave
                 if (take == 0) continue;
@@ -496,7 +468,6 @@ PVAMD_DEV void tile_passes_split(const pvamd_grid_t* __restrict__ grids, int S, 
                 if (__builtin_expect(near != 0, 0)) {
                     // the two roots may round to the same float32, in which case the incumbent stays: decide exactly
                     const float ra = sqrt_rn_sumsq(best[k].n2), rb = sqrt_rn_sumsq(n2);
-                    BAND_STAT(1, 1); BAND_STAT(2, __popcll(near)); BAND_STAT(3, __popcll(near & __builtin_amdgcn_ballot_w64(!(rb < ra))));
                     take &= ~(near & __builtin_amdgcn_ballot_w64(!(rb < ra)));
                 }
                 const bool t = __builtin_amdgcn_inverse_ballot_w64(take);
@@ -648,7 +619,7 @@ PVAMD_DEV Best walk_leaves_split(const pvamd_grid_t* __restrict__ grids, int S, 
 }
 
 template <int PPP, int MODE, bool PACKED, int SPLIT>
-__global__ __launch_bounds__(kWavesPerBlock * 64, MODE == kEstimate ? PVAMD_COMPOSED_MINWAVES : PVAMD_COMPOSED_MINWAVES_INLINE) void composed_query_wave(const pvamd_grid_t* __restrict__ grids, int S,
+__global__ __launch_bounds__(kWavesPerBlock * 64, MODE == kEstimate ? kMinWaves : kMinWavesInline) void composed_query_wave(const pvamd_grid_t* __restrict__ grids, int S,
                                                                            const float* __restrict__ tf, int A,
                                                                            const float* __restrict__ pts,
                                                                            int64_t ntiles, int64_t P,
@@ -692,11 +663,6 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, MODE == kEstimate ? PVAMD_COMP
         sp[lane + 128] = src[lane + 128];
         PVAMD_WAVE_SYNC();
         float lower;
-#ifdef PVAMD_NO_TILE_MASK
-        lower = -__builtin_inff();
-        const uint64_t todo = S >= 64 ? ~0ull : ((1ull << S) - 1ull);
-        const bool masked = false;
-#else
         uint64_t todo;
         bool masked;
         {
@@ -709,7 +675,6 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, MODE == kEstimate ? PVAMD_COMP
                 todo = S >= 64 ? ~0ull : ((1ull << S) - 1ull);
             }
         }
-#endif
         // two copies of the leaf loop only where instructions are what binds (kEstimate: grids that live in L2); the
         // gather-bound kInlineExact build loses more to the larger body than the simpler loop gives (README-size robot,
         // sorted points: 1.00 -> 1.10 ms with both copies)
@@ -821,15 +786,9 @@ __global__ __launch_bounds__(256) void compose_merge_kernel(const float* __restr
 
 // tiles per wave in the un-permute pass (= gathers in flight per lane / 4): 1 is best (whole README-size call 1.65 ms;
 // 1.70 with 2, 1.83 with 4 -- the pass is not latency-bound)
-#ifndef PVAMD_UNPERMUTE_TILES
-#define PVAMD_UNPERMUTE_TILES 1
-#endif
-constexpr int kUnpermuteTiles = PVAMD_UNPERMUTE_TILES;
-// waves per workgroup of the un-permute pass: its own knob (the query kernel's 4 are tuned for its register budget)
-#ifndef PVAMD_UNPERMUTE_WAVES
-#define PVAMD_UNPERMUTE_WAVES 4
-#endif
-constexpr int kUnpermuteWaves = PVAMD_UNPERMUTE_WAVES;
+constexpr int kUnpermuteTiles = 1;
+// waves per workgroup of the un-permute pass: its own constant (the query kernel's 4 are tuned for its register budget)
+constexpr int kUnpermuteWaves = 4;
 // ---- bucketed path: un-permute ----
 // The kernel above ran on spatially sorted points and left one packed record per (configuration, sorted position);
 // this pass brings them back to the caller's point order: out[a][j] = packed[a][inv[j]].  One wave = 256 consecutive
@@ -919,24 +878,12 @@ __global__ __launch_bounds__(kUnpermuteWaves * 64) void composed_unpermute_kerne
 // the LDS slot of its caller-order position, and after a barrier each wave stores one caller-order tile as 1 + 3 contiguous KB.
 // The order inside a Hilbert cell is whatever the LDS atomics gave: no result depends on it (a point's statements do not
 // know its lane).
-#ifndef PVAMD_GROUP_WAVES
-#define PVAMD_GROUP_WAVES 16
-#endif
-constexpr int kGroupWaves = PVAMD_GROUP_WAVES;
-#ifndef PVAMD_FUSED_COHERENT_SPAN
-#define PVAMD_FUSED_COHERENT_SPAN 0.45f
-#endif
-constexpr float kCoherentSpan = PVAMD_FUSED_COHERENT_SPAN;  // a chunk whose tiles each span at most this much of it is not sorted
+constexpr int kGroupWaves = 16;
+constexpr float kCoherentSpan = 0.45f;  // a chunk whose tiles each span at most this much of it is not sorted
 constexpr int kGroupChunk = kGroupWaves * kTilePoints;
-#ifndef PVAMD_FUSED_WAVES
-#define PVAMD_FUSED_WAVES 16
-#endif
-constexpr int kFusedWaves = PVAMD_FUSED_WAVES;  // waves (x 256 points) per chunk of the in-workgroup sort
+constexpr int kFusedWaves = 16;  // waves (x 256 points) per chunk of the in-workgroup sort
 constexpr int kFusedChunk = kFusedWaves * kTilePoints;
-#ifndef PVAMD_FUSED_MIN_BLOCKS
-#define PVAMD_FUSED_MIN_BLOCKS 1024
-#endif
-constexpr int64_t kFusedMinBlocks = PVAMD_FUSED_MIN_BLOCKS;  // (chunk, configuration) workgroups below which the per-lane / wave-tile kernels keep the call
+constexpr int64_t kFusedMinBlocks = 1024;  // (chunk, configuration) workgroups below which the per-lane / wave-tile kernels keep the call
 static_assert(kGroupChunk <= 65536 && 4096 % (kGroupWaves * 64) == 0, "perm is uint16; the scan splits 4096 bins evenly");
 
 template <int NW>
@@ -1099,14 +1046,10 @@ __global__ __launch_bounds__(NW * 64) void group_points_kernel(const float* __re
 
 // how large a run's sphere may be against the scene (the radius about leaf 0's centre that holds every leaf's range) for a leaf
 // mask to be worth its ~60 instructions
-#ifndef PVAMD_GROUP_MASK_SPAN
-#define PVAMD_GROUP_MASK_SPAN 0.5f
-#endif
-#ifndef PVAMD_GROUP_MINWAVES
-#define PVAMD_GROUP_MINWAVES 8
-#endif
+constexpr float kGroupMaskSpan = 0.5f;
+constexpr int kGroupMinWaves = 8;
 template <int NW, int PPP, bool PACKED>
-__global__ __launch_bounds__(NW * 64, PVAMD_GROUP_MINWAVES) void composed_query_grouped(
+__global__ __launch_bounds__(NW * 64, kGroupMinWaves) void composed_query_grouped(
     const pvamd_grid_t* __restrict__ grids, int S, const float* __restrict__ tf, int A, const float* __restrict__ sorted,
     const float* __restrict__ bounds, const uint16_t* __restrict__ perm, int64_t nchunks, int64_t P, float* __restrict__ val,
     float* __restrict__ grad, int* __restrict__ leaf, int a0) {
@@ -1126,7 +1069,7 @@ __global__ __launch_bounds__(NW * 64, PVAMD_GROUP_MINWAVES) void composed_query_
         }
         scene = wave_max(reach);
     }
-    const float span = PVAMD_GROUP_MASK_SPAN * scene;
+    const float span = kGroupMaskSpan * scene;
     for (int64_t chunk = blockIdx.y; chunk < nchunks; chunk += gridDim.y) {
         const int64_t cfirst = chunk * N <= P - N ? chunk * N : P - N;
         const int64_t run = chunk * N + wave * kTilePoints;
@@ -1173,7 +1116,7 @@ __global__ __launch_bounds__(NW * 64, PVAMD_GROUP_MINWAVES) void composed_query_
 // results arrive), and a wave then reads the points of its run through the position table.  ~250 instructions and six barriers
 // per thread against ~1500 of leaf loop (S = 8): worth it wherever the wave-tile kernel ran on scattered points.
 template <int NW, int PPP>
-__global__ __launch_bounds__(NW * 64, PVAMD_GROUP_MINWAVES) void composed_query_fused(
+__global__ __launch_bounds__(NW * 64, kGroupMinWaves) void composed_query_fused(
     const pvamd_grid_t* __restrict__ grids, int S, const float* __restrict__ tf, int A, const float* __restrict__ pts, int64_t nchunks,
     int64_t P, float* __restrict__ val, float* __restrict__ grad, int* __restrict__ leaf, int a0) {
     // one count per Hilbert cell of the 16^3 grid, or per run of 2 / 4 consecutive cells of the curve when the chunk has fewer value
@@ -1334,13 +1277,13 @@ extern "C" int pvamd_composed_query_packed(const pvamd_grid_t* grids, int32_t S,
     // gridDim.y of the query kernel = tile blocks (the configuration is blockIdx.x: any A)
     if (tile_blocks > 65535) return PVAMD_E_SHAPE;  // > 67 M points per call: use the direct entry point
     if (flags & PVAMD_COMPOSED_INLINE_EXACT)
-        hipLaunchKernelGGL((composed_query_wave<PVAMD_COMPOSED_PPP, kInlineExact, true, 0>), dim3(A, (unsigned)tile_blocks),
+        hipLaunchKernelGGL((composed_query_wave<kPointsPerPass, kInlineExact, true, 0>), dim3(A, (unsigned)tile_blocks),
                            dim3(kWavesPerBlock * 64), 0, s, grids, S, tf, A, points, ntiles, Pp, out_rec, nullptr, nullptr, 0);
     else if (legacy_leaf_loop(flags, S))
-        hipLaunchKernelGGL((composed_query_wave<PVAMD_COMPOSED_PPP, kEstimate, true, 0>), dim3(A, (unsigned)tile_blocks),
+        hipLaunchKernelGGL((composed_query_wave<kPointsPerPass, kEstimate, true, 0>), dim3(A, (unsigned)tile_blocks),
                            dim3(kWavesPerBlock * 64), 0, s, grids, S, tf, A, points, ntiles, Pp, out_rec, nullptr, nullptr, 0);
     else
-        hipLaunchKernelGGL((composed_query_wave<PVAMD_COMPOSED_PPP, kEstimate, true, 1>), dim3(A, (unsigned)tile_blocks),
+        hipLaunchKernelGGL((composed_query_wave<kPointsPerPass, kEstimate, true, 1>), dim3(A, (unsigned)tile_blocks),
                            dim3(kWavesPerBlock * 64), 0, s, grids, S, tf, A, points, ntiles, Pp, out_rec, nullptr, nullptr, 0);
     return (int)hipGetLastError();
 }
@@ -1413,19 +1356,19 @@ extern "C" int pvamd_composed_query(const pvamd_grid_t* grids, int32_t S, const 
             int64_t cap = ((int64_t)65536 + A - 1) / A;
             if (cap > 65535) cap = 65535;
             const unsigned gy = (unsigned)(nchunks < cap ? nchunks : (cap < 1 ? 1 : cap));
-            hipLaunchKernelGGL((composed_query_fused<kFusedWaves, PVAMD_COMPOSED_PPP>), dim3(A, gy), dim3(kFusedWaves * 64), 0, s, grids, S, tf,
+            hipLaunchKernelGGL((composed_query_fused<kFusedWaves, kPointsPerPass>), dim3(A, gy), dim3(kFusedWaves * 64), 0, s, grids, S, tf,
                                A, points, nchunks, P, out_val, out_grad, out_leaf, 0);
             return (int)hipGetLastError();
         }
     }
-    const bool wave_tiles = P >= kTilePoints && ((A >= 2 && ntiles * (int64_t)A >= kWaveTileMinTiles && !(flags & 2)) || (flags & 4));
+    const bool wave_tiles = P >= kTilePoints && ((A >= 2 && ntiles * (int64_t)A >= kWaveTileMinTiles && !(flags & PVAMD_COMPOSED_FORCE_PER_LANE)) || (flags & PVAMD_COMPOSED_FORCE_WAVE_TILE));
     // up to ~65536 blocks in total, split over the A configurations: about one 256-point tile per wave.  (Sweep on C4,
     // 200 x 262,144: 1024 blocks 1.40 ms, 4096 1.17, 8192 1.13, 32768 1.09, 65536 1.08 -- the hardware dispatcher
     // balances better than a grid-stride loop over unequal tiles.)
     // The configuration is a grid dimension: blockIdx.x (any count) in the wave-tile kernel and in the per-lane kernel's
     // default order; blockIdx.y (<= 65535) in the per-lane kernel's points-fastest order, whose larger batches go out in
     // slabs (the kernels take the slab's first configuration and index transforms / outputs with the global one)
-    const bool a_is_y = !wave_tiles && (flags & 8);  // only this order carries the configuration in gridDim.y (<= 65535)
+    const bool a_is_y = !wave_tiles && (flags & PVAMD_COMPOSED_POINTS_FASTEST);  // only this order carries the configuration in gridDim.y (<= 65535)
     const int slab = a_is_y ? kConfigSlab : (kConfigSlab < 65535 ? kConfigSlab : A);
     for (int a0 = 0; a0 < A; a0 += slab) {
         const int An = A - a0 < slab ? A - a0 : slab;
@@ -1435,20 +1378,20 @@ extern "C" int pvamd_composed_query(const pvamd_grid_t* grids, int32_t S, const 
             const int64_t need = (ntiles + kWavesPerBlock - 1) / kWavesPerBlock;
             const unsigned gy = (unsigned)(need < cap ? need : (cap < 1 ? 1 : cap));
             if (flags & PVAMD_COMPOSED_INLINE_EXACT)
-                hipLaunchKernelGGL((composed_query_wave<PVAMD_COMPOSED_PPP, kInlineExact, false, 0>), dim3(An, gy), dim3(kWavesPerBlock * 64), 0, s,
+                hipLaunchKernelGGL((composed_query_wave<kPointsPerPass, kInlineExact, false, 0>), dim3(An, gy), dim3(kWavesPerBlock * 64), 0, s,
                                    grids, S, tf, A, points, ntiles, P, out_val, out_grad, out_leaf, a0);
             else if (legacy_leaf_loop(flags, S))
-                hipLaunchKernelGGL((composed_query_wave<PVAMD_COMPOSED_PPP, kEstimate, false, 0>), dim3(An, gy), dim3(kWavesPerBlock * 64), 0, s,
+                hipLaunchKernelGGL((composed_query_wave<kPointsPerPass, kEstimate, false, 0>), dim3(An, gy), dim3(kWavesPerBlock * 64), 0, s,
                                    grids, S, tf, A, points, ntiles, P, out_val, out_grad, out_leaf, a0);
             else
-                hipLaunchKernelGGL((composed_query_wave<PVAMD_COMPOSED_PPP, kEstimate, false, 1>), dim3(An, gy), dim3(kWavesPerBlock * 64),
+                hipLaunchKernelGGL((composed_query_wave<kPointsPerPass, kEstimate, false, 1>), dim3(An, gy), dim3(kWavesPerBlock * 64),
                                    0, s, grids, S, tf, A, points, ntiles, P, out_val, out_grad, out_leaf, a0);
         } else {
             const int64_t need = (P + 255) / 256;
             const unsigned gx = (unsigned)(need < cap ? need : (cap < 1 ? 1 : cap));
             // configuration fastest unless flag 8 asks for the other order (tuning): with it the A = 200 README case runs
             // 0.076 instead of 0.079 ms on the slice and 0.265 instead of 0.323 ms on random points (21 MB link grids)
-            const int cf = (flags & 8) ? 0 : 1;
+            const int cf = (flags & PVAMD_COMPOSED_POINTS_FASTEST) ? 0 : 1;
             // large, gather-bound grids (the inline-exact hint): the two minima cost a second gather of the winner's record
             // and lose 6-12 % there (README-size link grids, 200 x 15,251: 0.087 vs 0.082 ms on the slice, 0.300 vs 0.268 ms
             // on random points); L2-resident grids gain 7-18 % (C4 per-lane 0.975 -> 0.899 ms, README slice 0.062 -> 0.058)
@@ -1507,10 +1450,10 @@ extern "C" int pvamd_composed_query_grouped(const pvamd_grid_t* grids, int32_t S
     const float* bounds = reinterpret_cast<const float*>(base + group_bounds_offset(P));
     const uint16_t* perm = reinterpret_cast<const uint16_t*>(base + group_perm_offset(P));
     if (packed)
-        hipLaunchKernelGGL((composed_query_grouped<kGroupWaves, PVAMD_COMPOSED_PPP, true>), dim3(A, gy), dim3(kGroupWaves * 64), 0,
+        hipLaunchKernelGGL((composed_query_grouped<kGroupWaves, kPointsPerPass, true>), dim3(A, gy), dim3(kGroupWaves * 64), 0,
                            (hipStream_t)stream, grids, S, tf, A, sorted, bounds, perm, nchunks, P, out_val, out_grad, out_leaf, 0);
     else
-        hipLaunchKernelGGL((composed_query_grouped<kGroupWaves, PVAMD_COMPOSED_PPP, false>), dim3(A, gy), dim3(kGroupWaves * 64), 0,
+        hipLaunchKernelGGL((composed_query_grouped<kGroupWaves, kPointsPerPass, false>), dim3(A, gy), dim3(kGroupWaves * 64), 0,
                            (hipStream_t)stream, grids, S, tf, A, sorted, bounds, perm, nchunks, P, out_val, out_grad, out_leaf, 0);
     return (int)hipGetLastError();
 }

@@ -110,14 +110,9 @@ PVAMD_DEV bool in_range(const pvamd_grid_t& g, float x, float y, float z) {
 // as busy as the vector ones in these kernels): per-lane kernel 0.896 -> 0.866 ms on C4's workload, C3 0.0897 -> 0.0886 ms,
 // README slice 0.0572 -> 0.0561 ms; wave-tile kernel within noise (profiles/r05_composed_variants.txt).
 PVAMD_DEV uint64_t in_range_mask(const pvamd_grid_t& g, float x, float y, float z) {
-#ifndef PVAMD_RANGE_SIX_COMPARES
     return __builtin_amdgcn_ballot_w64(__builtin_amdgcn_fmed3f(x, g.vlo[0], g.vhi[0]) == x) &
            __builtin_amdgcn_ballot_w64(__builtin_amdgcn_fmed3f(y, g.vlo[1], g.vhi[1]) == y) &
            __builtin_amdgcn_ballot_w64(__builtin_amdgcn_fmed3f(z, g.vlo[2], g.vhi[2]) == z);
-#endif
-    return __builtin_amdgcn_ballot_w64(g.vlo[0] <= x) & __builtin_amdgcn_ballot_w64(x <= g.vhi[0]) &
-           __builtin_amdgcn_ballot_w64(g.vlo[1] <= y) & __builtin_amdgcn_ballot_w64(y <= g.vhi[1]) &
-           __builtin_amdgcn_ballot_w64(g.vlo[2] <= z) & __builtin_amdgcn_ballot_w64(z <= g.vhi[2]);
 }
 
 // Index of an in-range coordinate: multiply-first estimate in fp32; unless it lies within its rounding bound of a
@@ -159,12 +154,8 @@ PVAMD_DEV float sqrt_rn_sumsq(float n2) {
 // monotone) -- v_max3_f32 with |.| modifiers, a subtract and a compare instead of three of each.  A NaN offset is ignored by
 // the max: it only arises from a non-finite coordinate, which is never in range, and whose index nobody uses.
 PVAMD_DEV bool estimate_unsure(const pvamd_grid_t& g, const float off[3]) {
-#ifdef PVAMD_UNSURE_PER_AXIS
-    return !(sub_rn(0.5f, fabsf(off[0])) > g.err32[0]) | !(sub_rn(0.5f, fabsf(off[1])) > g.err32[1]) | !(sub_rn(0.5f, fabsf(off[2])) > g.err32[2]);
-#else
     const float worst = __builtin_fmaxf(__builtin_fmaxf(fabsf(off[0]), fabsf(off[1])), fabsf(off[2]));
     return !(sub_rn(0.5f, worst) > g.err32[0]);
-#endif
 }
 
 // Index estimate only (no exact fallback inline): returns the flat index of the estimate and sets `unsure` when some
@@ -266,34 +257,29 @@ PVAMD_DEV float4 bounding_box_sdf(const pvamd_grid_t& g, float x, float y, float
 // the gathers of a tile crowd the TCP's pending-request slots sooner; profiles/r05_cq_geometry.txt).
 template <bool F64, bool STREAMING = false>
 PVAMD_DEV float4 cached_lookup(const pvamd_grid_t& g, float x, float y, float z, bool& valid) {
-#ifdef PVAMD_CQ_OLD_LOOKUP
-    constexpr bool kOld = true;
-#else
-    constexpr bool kOld = STREAMING;
-#endif
-    if constexpr (kOld) {
-    valid = in_range(g, x, y, z);
-    if (valid) {
-        // (g is a kernarg here: the compiler already knows vox is global, and routing it through load_record's integer cast
-        // changes the schedule of cached_query_wave for the worse: 64M points 0.626 -> 0.578 of 8 TB/s)
-        return reinterpret_cast<const float4*>(g.vox)[voxel_flat_in_range<F64>(g, x, y, z)];
-    }
-    if (g.oob_mode == PVAMD_OOB_BOUNDING_BOX) {
-        return bounding_box_sdf(g, x, y, z);
-    }
-    return make_float4(0.f, 0.f, 0.f, 0.f);  // LOOKUP_GT_SDF: zeros (sdf.py:546-547), caller fills in
+    if constexpr (STREAMING) {
+        valid = in_range(g, x, y, z);
+        if (valid) {
+            // (g is a kernarg here: the compiler already knows vox is global, and routing it through load_record's integer cast
+            // changes the schedule of cached_query_wave for the worse: 64M points 0.626 -> 0.578 of 8 TB/s)
+            return reinterpret_cast<const float4*>(g.vox)[voxel_flat_in_range<F64>(g, x, y, z)];
+        }
+        if (g.oob_mode == PVAMD_OOB_BOUNDING_BOX) {
+            return bounding_box_sdf(g, x, y, z);
+        }
+        return make_float4(0.f, 0.f, 0.f, 0.f);  // LOOKUP_GT_SDF: zeros (sdf.py:546-547), caller fills in
     } else {
-    valid = (__builtin_amdgcn_fmed3f(x, g.vlo[0], g.vhi[0]) == x) & (__builtin_amdgcn_fmed3f(y, g.vlo[1], g.vhi[1]) == y) &
-            (__builtin_amdgcn_fmed3f(z, g.vlo[2], g.vhi[2]) == z);
-    if (valid) return reinterpret_cast<const float4*>(g.vox)[voxel_flat_in_range_fused(g, x, y, z)];
-    if (g.oob_mode == PVAMD_OOB_BOUNDING_BOX) {
-        const float ta = __builtin_amdgcn_fmed3f(sub_rn(x, g.bb_min[0]), sub_rn(x, g.bb_max[0]), 0.f);
-        const float tb = __builtin_amdgcn_fmed3f(sub_rn(y, g.bb_min[1]), sub_rn(y, g.bb_max[1]), 0.f);
-        const float tc = __builtin_amdgcn_fmed3f(sub_rn(z, g.bb_min[2]), sub_rn(z, g.bb_max[2]), 0.f);
-        const float n = sqrt_rn_sumsq(fmaf(tc, tc, fmaf(tb, tb, mul_rn(ta, ta))));  // sdf.py:568
-        return make_float4(n, div_rn(ta, n), div_rn(tb, n), div_rn(tc, n));          // sdf.py:570
-    }
-    return make_float4(0.f, 0.f, 0.f, 0.f);  // LOOKUP_GT_SDF: zeros (sdf.py:546-547), caller fills in
+        valid = (__builtin_amdgcn_fmed3f(x, g.vlo[0], g.vhi[0]) == x) & (__builtin_amdgcn_fmed3f(y, g.vlo[1], g.vhi[1]) == y) &
+                (__builtin_amdgcn_fmed3f(z, g.vlo[2], g.vhi[2]) == z);
+        if (valid) return reinterpret_cast<const float4*>(g.vox)[voxel_flat_in_range_fused(g, x, y, z)];
+        if (g.oob_mode == PVAMD_OOB_BOUNDING_BOX) {
+            const float ta = __builtin_amdgcn_fmed3f(sub_rn(x, g.bb_min[0]), sub_rn(x, g.bb_max[0]), 0.f);
+            const float tb = __builtin_amdgcn_fmed3f(sub_rn(y, g.bb_min[1]), sub_rn(y, g.bb_max[1]), 0.f);
+            const float tc = __builtin_amdgcn_fmed3f(sub_rn(z, g.bb_min[2]), sub_rn(z, g.bb_max[2]), 0.f);
+            const float n = sqrt_rn_sumsq(fmaf(tc, tc, fmaf(tb, tb, mul_rn(ta, ta))));  // sdf.py:568
+            return make_float4(n, div_rn(ta, n), div_rn(tb, n), div_rn(tc, n));          // sdf.py:570
+        }
+        return make_float4(0.f, 0.f, 0.f, 0.f);  // LOOKUP_GT_SDF: zeros (sdf.py:546-547), caller fills in
     }
 }
 

@@ -16,7 +16,6 @@
 //     tests (the oracle's operation sequences) run densely over the queue.  Bit-identical to the plain double loop of
 //     oracle/pvamd_oracle.c; with spatially sorted triangles and points this is a flat three-level BVH.
 //   * ties in d^2 resolve to the lowest ORIGINAL face id (lexicographic min), independent of processing order.
-#include <cstdlib>
 #include "common.h"
 #include "mesh_math.h"
 #include "morton.h"
@@ -239,25 +238,6 @@ PVAMD_DEV bool rect_may_improve(const LaneState& s, V3 w, float dist2, V3 fu, fl
     return !(lb2 > fmaf(8e-6f, dist2, s.reach2m + m0));
 }
 
-#ifdef PVAMD_MESH_STATS
-__device__ unsigned long long g_stats[32];
-__device__ long long g_nested;  // unused
-#define STAT(i, v) do { if ((threadIdx.x & 63) == 0) atomicAdd(&g_stats[i], (unsigned long long)(v)); } while (0)
-extern "C" int pvamd_debug_stats(unsigned long long* out, int reset) {
-    (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_stats), sizeof(g_stats));
-    if (reset) { unsigned long long z[32] = {}; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_stats), z, sizeof(z)); }
-    return 0;
-}
-#define TIC(t) const long long t = __builtin_readcyclecounter()
-#define TOC(i, t) STAT(i, __builtin_readcyclecounter() - t)
-#define TOC_NET(i, t, inner) STAT(i, __builtin_readcyclecounter() - t - (inner))
-#else
-#define STAT(i, v)
-#define TIC(t)
-#define TOC(i, t)
-#define TOC_NET(i, t, inner)
-#endif
-
 // ---------------------------------------------------------------------------------------------------------------
 // The scan.  One block = 64 points (one per lane; the caller passes a Morton order, so they are neighbours in space) x
 // SLICES waves that all hold the same 64 points.  Wave w walks the tiles ti % SLICES == w on its own -- no barrier between
@@ -398,12 +378,10 @@ template <class Fn>
 PVAMD_DEV void drain(unsigned* q, int& n, bool everything, Fn&& fn) {
     const int lane = threadIdx.x & 63;
     PVAMD_WAVE_SYNC();  // entries were written by other lanes
-    STAT(6, 1);
     fn(n < 64 ? n : 64, q);
     if (n > 64) {
         const int rem = n - 64;
         if (everything) {
-            STAT(6, 1);
             fn(rem, q + 64);
             n = 0;
         } else {
@@ -421,7 +399,6 @@ template <bool WITH_RAY>
 PVAMD_DEV void drain_closest(const MeshArgs& m, GroupShared<WITH_RAY>& g, WaveLocal<WITH_RAY>& wl, Wave<WITH_RAY>& wv, bool everything) {
     if (wv.nc == 0) return;
     const int lane = threadIdx.x & 63;
-    TIC(t_drain);
     drain(wl.qc, wv.nc, everything, [&](int count, const unsigned* q) {
         PVAMD_COUNT_PAIRS(m, 0, count);
         const unsigned e = lane < count ? q[lane] : 0u;
@@ -436,7 +413,6 @@ PVAMD_DEV void drain_closest(const MeshArgs& m, GroupShared<WITH_RAY>& g, WaveLo
         }
     });
     pull_reach(g, wv);
-    TOC(16, t_drain);
 }
 
 template <bool WITH_RAY>
@@ -464,12 +440,7 @@ PVAMD_DEV void visit_tile(const MeshArgs& m, GroupShared<WITH_RAY>& g, WaveLocal
     const int lane = threadIdx.x & 63;
     const int ntiles = (m.F + kTile - 1) / kTile;
     const int n = min(kTile, m.F - ti * kTile);
-    STAT(1, 1);
-    TIC(t_visit);
     unsigned gm = 0u;
-#ifdef PVAMD_MESH_STATS
-    unsigned mine_groups = 0u;
-#endif
     {
         // lanes = groups: the 16 group spheres at (c, Q) ...
         const bool gv = lane < kGroupsPerTile && lane * kGroup < n;
@@ -492,10 +463,6 @@ PVAMD_DEV void visit_tile(const MeshArgs& m, GroupShared<WITH_RAY>& g, WaveLocal
             const float dist2 = dot(w, w);
             bool need = sphere_may_improve(wv.s, dist2, r);
             if (WITH_RAY) need = need || sphere_may_hit(dist2, dot(w, wv.dn), r);
-            STAT(9, 1);
-#ifdef PVAMD_MESH_STATS
-            if (need && wv.live) mine_groups |= 1u << b;
-#endif
             if (__ballot(need && wv.live) != 0ull) gm |= 1u << b;  // (the ballot IS the compare mask: __any materialises 0 / 1 and compares again)
         }
     }
@@ -505,13 +472,6 @@ PVAMD_DEV void visit_tile(const MeshArgs& m, GroupShared<WITH_RAY>& g, WaveLocal
     const f32x4* P4 = tile_plane(m.rec, ti, kPlaneB);
     for (int pass = pass_lo; pass < pass_hi; ++pass) {
         if (((gm >> (pass * (64 / kGroup))) & ((1u << (64 / kGroup)) - 1u)) == 0u) continue;
-        STAT(2, 1);
-#ifdef PVAMD_MESH_STATS
-        {
-            const int st_points = __popcll(__ballot(((mine_groups >> (pass * (64 / kGroup))) & 0xFu) != 0u));
-            STAT(22, st_points);
-        }
-#endif
         const int idx = pass * 64 + lane;
         const f32x4 a0 = P0[idx], a1 = P1[idx], a2 = P2[idx];
         const float am0 = P4[idx].w;
@@ -535,11 +495,9 @@ PVAMD_DEV void visit_tile(const MeshArgs& m, GroupShared<WITH_RAY>& g, WaveLocal
         PVAMD_WAVE_SYNC();
         const int j0 = ti * kTile + pass * 64;
         const unsigned long long live_mask = __ballot(wv.live);
-        TIC(t_surv);
         while (todo != 0ull) {
             const int b = __builtin_ctzll(todo);
             todo &= todo - 1ull;
-            STAT(3, 1);
             const f32x4 o = wl.sphere[b];  // wave-uniform address: LDS broadcast
             const V3 w = v3(o.x - wv.s.p.x, o.y - wv.s.p.y, o.z - wv.s.p.z);
             const float dist2 = dot(w, w);
@@ -550,11 +508,9 @@ PVAMD_DEV void visit_tile(const MeshArgs& m, GroupShared<WITH_RAY>& g, WaveLocal
             if (!WITH_RAY || ((mc >> b) & 1ull)) {  // (without rays every survivor is a closest-point candidate: todo == mc)
                 const unsigned long long near_c = live_mask & __ballot(sphere_may_improve(wv.s, dist2, o.w));
                 if (near_c != 0ull) {
-                    STAT(7, 1);
                     const f32x4 u = wl.fu[b], v = wl.fv[b];
                     const unsigned long long mk = near_c & __ballot(rect_may_improve(wv.s, w, dist2, xyz(u), u.w, xyz(v), v.w, wl.m0[b]));
                     if (mk) {
-                        STAT(4, __popcll(mk)); STAT(8, 1);
                         enqueue(wl.qc, wv.nc, mk, __builtin_amdgcn_inverse_ballot_w64(mk), j0 + b);
                         if (wv.nc >= 64) drain_closest(m, g, wl, wv, false);
                     }
@@ -563,15 +519,12 @@ PVAMD_DEV void visit_tile(const MeshArgs& m, GroupShared<WITH_RAY>& g, WaveLocal
             if (WITH_RAY && ((mr >> b) & 1ull)) {
                 const unsigned long long mk = live_mask & __ballot(sphere_may_hit(dist2, dot(w, wv.dn), o.w));
                 if (mk) {
-                    STAT(5, __popcll(mk)); STAT(8, 1);
                     enqueue(wl.qr, wv.nr, mk, __builtin_amdgcn_inverse_ballot_w64(mk), j0 + b);
                     if (wv.nr >= 64) drain_rays(m, g, wl, wv, false);
                 }
             }
         }
-        TOC(18, t_surv);
     }
-    TOC(17, t_visit);
 }
 
 // Upper bound on every live lane's distance to the mesh from the tile spheres (each contains whole triangles):
@@ -634,7 +587,6 @@ PVAMD_DEV void greedy_reach(const MeshArgs& m, GroupShared<WITH_RAY>& g, Wave<WI
             if (b < nearest) { nearest = b; jn = j0 + k; }
         }
     }
-#ifndef PVAMD_MESH_NO_GREEDY_EXACT
     // ... and the exact distance to that record's triangle, all 64 lanes at once (what a drain does for 64 queued pairs):
     // the bound drops from "the far side of the nearest record's sphere" to a real distance before anything is queued
     // against it, and the pair is a candidate like any other (same operations as in the drain: same bits).
@@ -644,9 +596,7 @@ PVAMD_DEV void greedy_reach(const MeshArgs& m, GroupShared<WITH_RAY>& g, Wave<WI
         const V3 qp = sub(closest_point_triangle(p, xyz(A), xyz(B), xyz(C)), p);
         const float d2 = dot(qp, qp);
         atomicMin(&g.best[threadIdx.x & 63], ((unsigned long long)(unsigned)__float_as_int(d2) << 32) | (unsigned)__float_as_int(A.w));
-        STAT(4, 1);
     }
-#endif
     bound = fminf(bound, nearest) * 1.00001f;
     if (bound < wv.s.reach) set_reach(wv.s, bound);  // a NaN point: never
     pull_reach(g, wv);
@@ -666,7 +616,6 @@ PVAMD_DEV void scan_tiles(const MeshArgs& m, GroupShared<WITH_RAY>& g, WaveLocal
         const V3 w = v3(ts.x - wv.wb.q.p.x, ts.y - wv.wb.q.p.y, ts.z - wv.wb.q.p.z);
         const float dist2 = dot(w, w);
         const bool ray = WITH_RAY && mine && axis_may_hit(wv.wb, w, dist2, ts.w);
-        STAT(0, 1);
         // nearest flagged tile of the pass first (the sooner the reaches are final, the fewer pairs get queued), and a
         // per-point look at its sphere before paying for the visit
         const float lower = mine ? fast_sqrt(dist2) - ts.w : INFINITY;  // ordering only
@@ -779,24 +728,15 @@ static __host__ __device__ inline HandOver hand_over(void* scratch, int cap) {
     h.cap = scratch ? cap : 0;
     return h;
 }
-#ifndef PVAMD_MESH_HEAVY_32NDS
-#define PVAMD_MESH_HEAVY_32NDS 6
-#endif
-#ifndef PVAMD_MESH_HEAVY_PARTS
-#define PVAMD_MESH_HEAVY_PARTS 32
-#endif
 // heavy = still flags this many 32nds of the tiles (of at least kHeavyMinTiles) once its reaches are about final.  C5
 // (389 tiles, 32,768 groups), round 4 (triangles in patches, points along the Hilbert curve, exact greedy bound), whole
 // call / groups listed with 2 waves per group in the main launch: 4/32 3.24 ms / 1782, 5/32 3.20 / 1000, 6/32 3.17 / 745,
 // 7/32 3.18 / 569, 8/32 3.47 / 470, 10/32 3.47 / 301; with 4 waves per group 8/32 3.55, 12/32 3.77, 16/32 3.96 (64 instead
 // of 32 parts: -0.05 with 4 waves, +0.1 with 2); nothing handed over: 5.15 (8 waves).  (Round 3, Z-order: 12/32 and 4
 // waves, 3.71.)
-constexpr int kHeavy32nds = PVAMD_MESH_HEAVY_32NDS;
-#ifndef PVAMD_MESH_HEAVY_MIN_TILES
-#define PVAMD_MESH_HEAVY_MIN_TILES 128
-#endif
-constexpr int kHeavyMinTiles = PVAMD_MESH_HEAVY_MIN_TILES;
-constexpr int kHeavyParts = PVAMD_MESH_HEAVY_PARTS;
+constexpr int kHeavy32nds = 6;
+constexpr int kHeavyMinTiles = 128;
+constexpr int kHeavyParts = 32;
 
 PVAMD_DEV void store_bound(float* __restrict__ b, const WaveBound& wb, bool any_live) {
     if ((threadIdx.x & 63) != 0) return;
@@ -874,15 +814,10 @@ PVAMD_DEV bool scan_mesh(const MeshArgs& m, MeshShared<SLICES, WITH_RAY>& sh, Wa
                          int64_t jitter_index, const HandOver& ho, int group, int transform) {
     const int lane = threadIdx.x & 63;
     bool handed = false;
-    TIC(t_all);
     if (scan_begin(m, sh.g, wv, wave, seed, jitter_index, nullptr) && m.F > 0) {
-        TIC(t_seed);
         const int first = scan_seed(m, wv, wave, SLICES);
         if (first >= 0) {
-#ifndef PVAMD_MESH_NO_GREEDY
             greedy_reach(m, sh.g, wv, first);
-#endif
-            TOC(20, t_seed);
             visit_tile<WITH_RAY>(m, sh.g, sh.w[wave], wv, first);
             drain_closest(m, sh.g, sh.w[wave], wv, true);  // publish what the nearest tile gave before looking further
         }
@@ -923,7 +858,6 @@ PVAMD_DEV bool scan_mesh(const MeshArgs& m, MeshShared<SLICES, WITH_RAY>& sh, Wa
             scan_finish(m, sh.g, sh.w[wave], wv);
         }
     }
-    TOC(19, t_all);
     __syncthreads();
     return handed;
 }
@@ -986,14 +920,10 @@ PVAMD_DEV void write_query(const MeshArgs& m, const QueryOut& out, int64_t i, V3
 // grid: x = groups of 64 points
 // waves per SIMD the allocator is held to (it would settle for 6): 8 fit beside the LDS of an 8-wave block (C5 query with
 // sign 7.4 -> 6.2 ms), 7 beside that of the smaller ones (2.16 M-point cache build 1.84 -> 1.73 ms; 8 spill: 1.85)
-#ifndef PVAMD_MESH_MINWAVES
-#define PVAMD_MESH_MINWAVES(SLICES) ((SLICES) == 8 ? 8 : ((SLICES) == 1 ? 6 : 7))
-#endif
-#ifndef PVAMD_CHAMFER_MINWAVES
-#define PVAMD_CHAMFER_MINWAVES(SLICES) 1  /* the allocator's own choice (88 VGPRs, 5 waves): see profiles/r06_mesh_variants.txt */
-#endif
+constexpr int mesh_min_waves(int slices) { return slices == 8 ? 8 : (slices == 1 ? 6 : 7); }
+constexpr int chamfer_min_waves(int) { return 1; }  // the allocator's own choice (88 VGPRs, 5 waves): see profiles/r06_mesh_variants.txt
 template <int SLICES>
-__global__ __launch_bounds__(64 * SLICES, PVAMD_MESH_MINWAVES(SLICES)) void mesh_query_kernel(MeshArgs m, const int* __restrict__ order,
+__global__ __launch_bounds__(64 * SLICES, mesh_min_waves(SLICES)) void mesh_query_kernel(MeshArgs m, const int* __restrict__ order,
                                                                 const float* __restrict__ pts, int64_t P,
                                                                 uint64_t seed, int64_t index_base, QueryOut out, HandOver ho) {
     __shared__ __attribute__((aligned(16))) MeshShared<SLICES, true> sh;
@@ -1039,7 +969,7 @@ PVAMD_DEV void chamfer_accumulate(const MeshArgs& m, V3 p, bool live, unsigned l
 // grid: x = groups of 64 points, y = transform b (b0 = the slab's first transform).  W == nullptr: the flat call (see
 // chamfer_accumulate) -- `pts` are the N = B * per transformed points of all transforms, y = 1.
 template <int SLICES>
-__global__ __launch_bounds__(64 * SLICES, PVAMD_CHAMFER_MINWAVES(SLICES)) void chamfer_mesh_kernel(MeshArgs m, const int* __restrict__ order,
+__global__ __launch_bounds__(64 * SLICES, chamfer_min_waves(SLICES)) void chamfer_mesh_kernel(MeshArgs m, const int* __restrict__ order,
                                                                   const float* __restrict__ W, int b0,
                                                                   const float* __restrict__ pts, int64_t N, float scale,
                                                                   double* __restrict__ out_sum, HandOver ho, int64_t per) {
@@ -1102,7 +1032,6 @@ PVAMD_DEV float greedy_bound(const MeshArgs& m, V3 p, unsigned long long& found)
         if (b < nearest) { nearest = b; jn = j0 + k; }
     }
     bound = fminf(bound, nearest);
-#ifndef PVAMD_MESH_NO_GREEDY_EXACT
     PVAMD_COUNT_PAIRS(m, 0, __popcll(__ballot(jn >= 0 && fabsf(p.x) < INFINITY && fabsf(p.y) < INFINITY && fabsf(p.z) < INFINITY)));
     if (jn >= 0 && fabsf(p.x) < INFINITY && fabsf(p.y) < INFINITY && fabsf(p.z) < INFINITY) {
         const f32x4 A = record_plane(m.rec, jn, kPlaneA), B = record_plane(m.rec, jn, kPlaneB), C = record_plane(m.rec, jn, kPlaneC);
@@ -1112,7 +1041,6 @@ PVAMD_DEV float greedy_bound(const MeshArgs& m, V3 p, unsigned long long& found)
         if (!(found < kBestInit)) found = kBestInit;  // a NaN d2
         else bound = fminf(bound, fast_sqrt(d2) * 1.00001f + 1.1e-19f);
     }
-#endif
     return bound * 1.00001f;  // a NaN / inf point: never a finite bound
 }
 
@@ -1240,10 +1168,8 @@ __global__ __launch_bounds__(64) void hand_over_gather_kernel(MeshArgs m, const 
     }
 }
 
-#ifndef PVAMD_MESH_PARTS_WAVES
-#define PVAMD_MESH_PARTS_WAVES 7  // waves per SIMD the parts kernels are held to (C1: 0.165 ms at the allocator's 5, 0.144 at 6-7;
-                                  // 30k points 0.201 / 0.190 / 0.207 ms at 6 / 7 / 8)
-#endif
+constexpr int kPartsMinWaves = 7;  // waves per SIMD the parts kernels are held to (C1: 0.165 ms at the allocator's 5, 0.144 at 6-7;
+                                   // 30k points 0.201 / 0.190 / 0.207 ms at 6 / 7 / 8)
 // one listed group in one block: wave w takes the w-th 64-record pass of the tiles ti % gridDim.y == blockIdx.y
 template <bool WITH_RAY, bool WAIT = false, int WAVES = kTile / 64>
 PVAMD_DEV void parts_of_group(const MeshArgs& m, MeshShared<WAVES, WITH_RAY>& sh, const int* __restrict__ order,
@@ -1257,7 +1183,6 @@ PVAMD_DEV void parts_of_group(const MeshArgs& m, MeshShared<WAVES, WITH_RAY>& sh
     wv.s.p = v3(q[0], q[1], q[2]);
     const unsigned long long start = ho.best[(int64_t)slot * 64 + lane];
     const float known = ho.reach[(int64_t)slot * 64 + lane];
-    TIC(t_parts);
     if (scan_begin(m, sh.g, wv, wave, seed, 0, &start, WITH_RAY ? ho.dir + (int64_t)slot * 192 : nullptr,
                    ho.bound + (int64_t)slot * kBoundFloats)) {
         // the bound worked out when the group was listed, or what it had found by then (pulled from the slots in scan_tiles);
@@ -1269,7 +1194,6 @@ PVAMD_DEV void parts_of_group(const MeshArgs& m, MeshShared<WAVES, WITH_RAY>& sh
         scan_tiles<WITH_RAY>(m, sh.g, sh.w[wave], wv, -1, (int)blockIdx.y, (int)gridDim.y, wave * kPasses, (wave + 1) * kPasses);
         scan_finish(m, sh.g, sh.w[wave], wv);
     }
-    TOC(21, t_parts);
     __syncthreads();
     if (wave == 0) {
         if (WAIT) {  // returning atomics: when the old values are back, the updates have been performed
@@ -1289,7 +1213,7 @@ PVAMD_DEV void parts_of_group(const MeshArgs& m, MeshShared<WAVES, WITH_RAY>& sh
 // group's outputs (entries[2g + 1], zeroed by the list launch, counts the parts that are done): no finish launch.
 // kAllWaves waves per block, each (kTile / 64) / kAllWaves of the passes of a tile
 template <int kAllWaves>
-__global__ __launch_bounds__(64 * kAllWaves, PVAMD_MESH_PARTS_WAVES) void mesh_parts_all_kernel(MeshArgs m, const int* __restrict__ order,
+__global__ __launch_bounds__(64 * kAllWaves, kPartsMinWaves) void mesh_parts_all_kernel(MeshArgs m, const int* __restrict__ order,
                                                                           const float* __restrict__ pts, int64_t P,
                                                                           uint64_t seed, int64_t index_base, HandOver ho, QueryOut out) {
     __shared__ __attribute__((aligned(16))) MeshShared<kAllWaves, true> sh;
@@ -1313,7 +1237,7 @@ __global__ __launch_bounds__(64 * kAllWaves, PVAMD_MESH_PARTS_WAVES) void mesh_p
 
 // the listed groups: grid x = slots (strided over the list), y = part
 template <bool WITH_RAY, int WAVES>
-__global__ __launch_bounds__(64 * WAVES, PVAMD_MESH_PARTS_WAVES) void mesh_parts_kernel(MeshArgs m, const int* __restrict__ order,
+__global__ __launch_bounds__(64 * WAVES, kPartsMinWaves) void mesh_parts_kernel(MeshArgs m, const int* __restrict__ order,
                                                                       const float* __restrict__ W,
                                                                       const float* __restrict__ pts, int64_t P,
                                                                       uint64_t seed, int64_t index_base, HandOver ho) {
@@ -1432,13 +1356,8 @@ static MeshArgs mesh_args(const pvamd_mesh_t& mesh) {
 }
 
 constexpr int kMaxFaces = 1 << 26;  // queue entries are record << 6 | lane
-#ifndef PVAMD_MESH_MAX_SLICES
-#define PVAMD_MESH_MAX_SLICES 8
-#endif
-#ifndef PVAMD_MESH_MIN_PARTS
-#define PVAMD_MESH_MIN_PARTS 4
-#endif
-constexpr int kMinParts = PVAMD_MESH_MIN_PARTS;     // fewer parts than this (a mesh of less than ~12 tiles): the single launch
+constexpr int kMaxSlices = 8;    // waves that may share one 64-point group (pick_slices)
+constexpr int kMinParts = 4;     // fewer parts than this (a mesh of less than ~12 tiles): the single launch
 
 // How many waves share one 64-point group (every wave needs tiles of its own: ti % slices == wave).
 //   many groups           -> 2: the least replicated per-wave work (2 M points on the 62-tile drill: 1.9 ms with 2, 2.05
@@ -1486,7 +1405,7 @@ static int pick_slices(int64_t groups, int mesh_tiles, bool hand_over) {
     int s = 2;
     while (s < 8 && (int64_t)s * groups < 16384) s <<= 1;
     if (mesh_tiles > 128 && !hand_over) s = 8;
-    if (s > PVAMD_MESH_MAX_SLICES) s = PVAMD_MESH_MAX_SLICES;
+    if (s > kMaxSlices) s = kMaxSlices;
     while (s > 1 && s > mesh_tiles) s >>= 1;
     return s;
 }
@@ -1543,12 +1462,6 @@ static void launch_heavy_parts(const MeshArgs& m, const int* order, const float*
                                int64_t index_base, const HandOver& ho, int ntiles, hipStream_t s) {
     int parts = kHeavyParts, waves = 4;
     unsigned xb = list_blocks(ho.cap);
-#ifdef PVAMD_MESH_TUNE
-    if (getenv("PVAMD_TUNE_HPARTS")) parts = atoi(getenv("PVAMD_TUNE_HPARTS"));
-    if (getenv("PVAMD_TUNE_HWAVES")) waves = atoi(getenv("PVAMD_TUNE_HWAVES"));
-    if (getenv("PVAMD_TUNE_HBLOCKS")) xb = (unsigned)atoi(getenv("PVAMD_TUNE_HBLOCKS"));
-    if (xb > (unsigned)ho.cap) xb = (unsigned)ho.cap;
-#endif
     if (parts > ntiles) parts = ntiles;
     const dim3 grid(xb, (unsigned)parts);
     if (waves == 2) hipLaunchKernelGGL((mesh_parts_kernel<WITH_RAY, 2>), grid, dim3(128), 0, s, m, order, W, points, P, seed, index_base, ho);
@@ -1587,14 +1500,6 @@ static int mesh_query_impl(const pvamd_mesh_t* mesh, const float* points, const 
     if (parts > 65535) parts = 65535;  // gridDim.y (a mesh of more than 16.7 M triangles)
     int aw = (int64_t)groups * parts * 4 > 100000 ? 2 : 4;
     bool few = parts >= kMinParts;
-#ifdef PVAMD_MESH_TUNE
-    if (getenv("PVAMD_TUNE_PARTS")) {  // parts = 0: the single launch
-        parts = atoi(getenv("PVAMD_TUNE_PARTS"));
-        aw = getenv("PVAMD_TUNE_WAVES") ? atoi(getenv("PVAMD_TUNE_WAVES")) : 4;
-        few = parts > 0;
-        if (parts > ntiles) parts = ntiles;
-    }
-#endif
     const bool two_launches = ho.cap > 0 && groups <= ho.cap && few;
     if (sort_into) {
         order = sort_into;

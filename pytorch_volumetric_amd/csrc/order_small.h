@@ -65,11 +65,7 @@ PVAMD_DEV void order_small_block(const float* __restrict__ pts, int P, int* __re
     for (int k = 0; k < kSmallPer; ++k) {
         cell[k] = 0u;
         if (1024 * k < P) {  // uniform over the block: the one workgroup is bound by its vector ALUs
-#ifdef PVAMD_ORDER_MORTON
-            cell[k] = morton_key30(x[k], y[k], z[k], blo, bhi) >> 18;
-#else
             cell[k] = hilbert_cell16(x[k], y[k], z[k], blo, scale);
-#endif
             if (t + 1024 * k < P) atomicAdd(&hist[cell[k]], 1u);
         }
     }

@@ -15,12 +15,6 @@
 #include "morton.h"
 #include "order_small.h"
 
-#ifdef PVAMD_ORDER_MORTON
-#define PVAMD_ORDER_KEY(x, y, z, lo, hi, b) morton_key30(x, y, z, lo, hi)
-#else
-#define PVAMD_ORDER_KEY(x, y, z, lo, hi, b) hilbert_key30(x, y, z, lo, hi, b)
-#endif
-
 namespace pvamd {
 
 // scratch layout (uint32 words): [0..5] bounds codes, [8 .. 8 + cells) cell counters / offsets, then P keys, then
@@ -82,7 +76,7 @@ __global__ __launch_bounds__(256) void order_count_kernel(const float* __restric
         lo[d] = order_decode(scratch[d]);
         hi[d] = order_decode(scratch[3 + d]);
     }
-    const unsigned key = PVAMD_ORDER_KEY(pts[3 * i], pts[3 * i + 1], pts[3 * i + 2], lo, hi, (30 - shift) / 3);
+    const unsigned key = hilbert_key30(pts[3 * i], pts[3 * i + 1], pts[3 * i + 2], lo, hi, (30 - shift) / 3);
     const unsigned cells = 1u << (30 - shift);
     scratch[kBoxWords + cells + i] = key;
     atomicAdd(scratch + kBoxWords + (key >> shift), 1u);
@@ -208,7 +202,7 @@ __global__ __launch_bounds__(kRadixThreads) void radix_keys_hist_kernel(const fl
     for (int r = 0; r < kRadixRounds; ++r) {
         const int64_t i = t0 + r * kRadixThreads + threadIdx.x;
         if (i < P) {
-            const unsigned key = PVAMD_ORDER_KEY(pts[3 * i], pts[3 * i + 1], pts[3 * i + 2], lo, hi, bits_per_axis) >> (30 - 3 * bits_per_axis);
+            const unsigned key = hilbert_key30(pts[3 * i], pts[3 * i + 1], pts[3 * i + 2], lo, hi, bits_per_axis) >> (30 - 3 * bits_per_axis);
             keys[i] = key;
             atomicAdd(&hist[key & (kRadixBins - 1)], 1u);
         }
@@ -421,11 +415,7 @@ extern "C" int pvamd_morton_order(const float* points, int64_t P, int32_t* order
             hipLaunchKernelGGL(order_gather_kernel, dim3((unsigned)want), dim3(256), 0, s, points, P, order_out, inv_out, sorted_points_out);
         return (int)hipGetLastError();
     }
-#ifdef PVAMD_ORDER_BITS_OVERRIDE
-    const int bits = PVAMD_ORDER_BITS_OVERRIDE < PVAMD_MORTON_ORDER_BITS(P) ? PVAMD_ORDER_BITS_OVERRIDE : PVAMD_MORTON_ORDER_BITS(P), shift = 30 - bits, cells = 1 << bits;
-#else
     const int bits = PVAMD_MORTON_ORDER_BITS(P), shift = 30 - bits, cells = 1 << bits;
-#endif
     hipLaunchKernelGGL(order_init_kernel, dim3((cells + 255) / 256), dim3(256), 0, s, w, cells);
     const int64_t want = (P + 255) / 256;
     hipLaunchKernelGGL(order_bounds_kernel, dim3(want < 512 ? (unsigned)want : 512u), dim3(256), 0, s, points, P, w);  // (2048 blocks: 30-52 us for 2 M points against 20 -- they all reach their six atomics at once)

@@ -140,13 +140,23 @@ def test_product_never_touches_the_oracle():
 def test_no_wrong_result_experiments_in_the_product_sources_and_variants_are_refused():
     """timing experiments that return WRONG results are patches under tools/patches now, not #ifdefs in
     csrc/; an A/B build (tools/build_variant.sh) names itself through `pvamd_variant` and _lib.load() refuses it unless
-    PVAMD_ALLOW_VARIANT=1.  The product library exports no such symbol."""
+    PVAMD_ALLOW_VARIANT=1.  The product library exports no such symbol.
+    Nor do the sources keep build knobs, alternate paths or instrumentation behind PVAMD_ macros ("prune the
+    laboratory out of the product"): every kernel has one configuration, and the only preprocessor conditionals on a PVAMD_
+    macro are the include-order guards and the variant's name."""
     import glob
+    import re
     csrc = os.path.join(ROOT, "pytorch_volumetric_amd", "csrc")
+    conditionals = set()
     for path in glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h")):
         text = open(path).read()
         for word in ("ABLATE", "ONLY_SEED", "WRONG results"):
             assert word not in text, f"{word} in {os.path.basename(path)}"
+        for line in text.splitlines():
+            if re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b", line):
+                conditionals |= {(os.path.basename(path), macro) for macro in re.findall(r"\bPVAMD_\w+", line)}
+    assert conditionals == {("wave_ops.h", "PVAMD_DEV"), ("exact_math.h", "PVAMD_DEV"), ("mesh_math.h", "PVAMD_DEV"),
+                            ("common.h", "PVAMD_VARIANT")}, sorted(conditionals)
     out = subprocess.run(["nm", "-D", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
     assert "pvamd_variant" not in out and "pvamd_debug" not in out
     assert "pvamd_variant" in open(os.path.join(csrc, "common.h")).read()

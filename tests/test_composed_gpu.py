@@ -6,6 +6,8 @@ import torch
 import pytorch_volumetric_amd as pv
 from oracle import oracle
 from tests import helpers as H
+from pytorch_volumetric_amd._lib import (COMPOSED_FORCE_PER_LANE as PER_LANE, COMPOSED_FORCE_WAVE_TILE as WAVE_TILE, COMPOSED_INLINE_EXACT as INLINE_EXACT,
+                                         COMPOSED_LEGACY_LEAF_LOOP as LEGACY_LEAF_LOOP, COMPOSED_POINTS_FASTEST as POINTS_FASTEST)
 
 pytestmark = pytest.mark.gpu
 
@@ -135,7 +137,7 @@ def test_leaf_culling_is_exact_on_coherent_and_far_queries():
     tfm = H.random_rigid(S * A, seed=77, trans=1.5)
     comp = pv.ComposedSDF(leaves, None)
     comp.set_transforms(pv.Transform3d(matrix=tfm), batch_dim=(A,))
-    _force_flags(comp, 4)  # the wave-tile kernel (the one that culls), whatever the entry point would pick at this size
+    _force_flags(comp, WAVE_TILE)  # the wave-tile kernel (the one that culls), whatever the entry point would pick at this size
     ax = torch.linspace(-2.0, 2.0, 48)
     pts = torch.cartesian_prod(ax, ax, ax)[: 48 * 48 * 48 // 256 * 256]
     far = H.uniform_points(2048, [30.0] * 3, [40.0] * 3, seed=1)
@@ -164,7 +166,7 @@ def test_more_leaves_than_the_culling_table_holds():
     tfm = H.random_rigid(S * A, seed=9, trans=0.8)
     comp = pv.ComposedSDF([leaf] * S, None)
     comp.set_transforms(pv.Transform3d(matrix=tfm), batch_dim=(A,))
-    _force_flags(comp, 4)
+    _force_flags(comp, WAVE_TILE)
     pts = scene_points(65_536 + 4, seed=4, extent=1.0)
     val, grad = comp(pts.cuda())
     og = H.oracle_grid_from_cached(leaf)
@@ -192,10 +194,11 @@ def test_compose_of_mesh_sdfs_like_the_reference_test():
     assert torch.allclose(grads, torch.where((v2 < v1).unsqueeze(-1), g2, g1), atol=1e-5)
 
 
-@pytest.mark.parametrize("flags", [4, 4 | 16, 4 | 1, 2])
+@pytest.mark.parametrize("flags", [WAVE_TILE, WAVE_TILE | LEGACY_LEAF_LOOP, WAVE_TILE | INLINE_EXACT, PER_LANE])
 def test_both_index_modes_give_the_reference_index_where_the_estimate_is_shaky(flags):
     """pvamd_composed_query's tuning hints must never change a result: wave-tile kernel with flagged points redone after the
-    loop (4), with the exact statements inline (4 | 1), and the per-lane kernel (2).  A leaf far from its own origin (coordinates ~200 x the resolution -> a wide error bound on the
+    loop (WAVE_TILE; also with the round-3 leaf loop, | LEGACY_LEAF_LOOP), with the exact statements inline (| INLINE_EXACT), and the
+    per-lane kernel (PER_LANE).  A leaf far from its own origin (coordinates ~200 x the resolution -> a wide error bound on the
     fp32 index estimate) and query points sprayed on its half-voxel planes make flagged visits the rule."""
     gt = H.AnalyticEllipsoidSDF([7.0, -5.0, 3.0], [0.3, 0.2, 0.25], [[6.7, 7.3], [-5.2, -4.8], [2.75, 3.25]])
     rng = [(6.5, 7.5), (-5.5, -4.5), (2.5, 3.5)]
@@ -277,12 +280,13 @@ def _force_flags(comp, flags):
     comp._query_flags = flags
 
 
-@pytest.mark.parametrize("A,P,flags", [(200, 15_251, 0), (200, 15_251, 4), (20, 15_251, 4), (20, 15_251, 0), (24, 20_481, 4 | 1), (5, 255, 4),
-                                       (5, 257, 4), (3, 3, 4), (7, 513, 4), (2, 1, 4)])
+@pytest.mark.parametrize("A,P,flags", [(200, 15_251, 0), (200, 15_251, WAVE_TILE), (20, 15_251, WAVE_TILE), (20, 15_251, 0),
+                                       (24, 20_481, WAVE_TILE | INLINE_EXACT), (5, 255, WAVE_TILE), (5, 257, WAVE_TILE), (3, 3, WAVE_TILE),
+                                       (7, 513, WAVE_TILE), (2, 1, WAVE_TILE)])
 def test_any_point_count_goes_through_the_wave_tile_kernel_bitwise(A, P, flags):
     """The reference README's own query has M = 15,251 points (README.md:177-200): (A, P) rows that start at any dword,
     and a last tile of 147 points.  The wave-tile kernel takes them itself (16-byte stores at 4-byte aligned addresses,
-    partial last tile in the kernel); round 2 sent every P % 4 != 0 to the one-point-per-lane kernel.  flags 4 forces the
+    partial last tile in the kernel); round 2 sent every P % 4 != 0 to the one-point-per-lane kernel.  WAVE_TILE forces the
     wave-tile kernel for the small cases; (200, 15251) and (20, 15251) take whatever the entry point picks."""
     S = 8
     leaves = [make_leaf(f64=(s % 2 == 0)) for s in range(S)]
@@ -299,7 +303,7 @@ def test_any_point_count_goes_through_the_wave_tile_kernel_bitwise(A, P, flags):
     assert np.array_equal(grad.cpu().numpy(), ograd, equal_nan=True)
 
 
-@pytest.mark.parametrize("flags", [4, 2, 2 | 8])
+@pytest.mark.parametrize("flags", [WAVE_TILE, PER_LANE, PER_LANE | POINTS_FASTEST])
 def test_buffers_at_any_dword_address(flags):
     """points / out_val / out_grad that are only 4-byte aligned (views into larger buffers), odd P, both kernels; the
     floats around the outputs must stay untouched."""
@@ -324,7 +328,7 @@ def test_buffers_at_any_dword_address(flags):
     assert (vbuf[:3] == -7).all() and (vbuf[3 + A * P:] == -7).all() and (gbuf[:1] == -7).all() and (gbuf[1 + 3 * A * P:] == -7).all()
 
 
-@pytest.mark.parametrize("flags", [0, 2])
+@pytest.mark.parametrize("flags", [0, PER_LANE])
 def test_seventy_thousand_configurations_go_out_in_slabs(flags):
     """pvamd_composed_query carries the configuration in a grid dimension (<= 65535): A = 70,000 x P = 8 crosses the slab
     border in both kernels (the wave-tile kernel with a last -- and only -- tile of 8 points); the reference takes any

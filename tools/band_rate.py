@@ -1,4 +1,5 @@
 """How often does the composed kernel's two-minima loop enter the exact-root band (csrc/composed.hip, kNearTie)?
+Apply tools/patches/composed_band_stats.patch, then build with -DPVAMD_COMPOSED_STATS:
 tools/build_variant.sh band pytorch_volumetric_amd/csrc/composed.hip -DPVAMD_COMPOSED_STATS
 PVAMD_LIB=tools/variants/libpvamd_band.so python tools/band_rate.py"""
 import os, sys, ctypes

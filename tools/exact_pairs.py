@@ -1,4 +1,5 @@
-"""Exact (narrow-phase) point-triangle pairs the mesh kernels actually evaluate on C1 and C5 -- needs the stats build:
+"""Exact (narrow-phase) point-triangle pairs the mesh kernels actually evaluate on C1 and C5 -- needs the stats build: apply
+tools/patches/mesh_stats.patch, then build with -DPVAMD_MESH_STATS:
   tools/build_variant.sh stats pytorch_volumetric_amd/csrc/mesh.hip -DPVAMD_MESH_STATS
   PVAMD_LIB=tools/variants/libpvamd_stats.so python tools/exact_pairs.py > profiles/r03_exact_pairs.json
 tools/bench_configs.py turns these into "flop of the exact tests / time" (the honest work rate of a culling kernel; the

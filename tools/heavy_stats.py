@@ -1,4 +1,5 @@
 """Work counters of the C5 mesh for points near the sphere's centre only (every group is handed over): what a heavy group costs.
+Apply tools/patches/mesh_stats.patch, then build with -DPVAMD_MESH_STATS (as tools/mesh_stats.py).
 PVAMD_LIB=tools/variants/libpvamd_stats.so python tools/heavy_stats.py [radius_m]"""
 import sys, os
 sys.path.insert(0, os.getcwd()); sys.path.insert(0, os.path.join(os.getcwd(), "tools"))

@@ -1,4 +1,4 @@
-"""Broad/narrow-phase counters of the mesh kernels (needs libpvamd built with -DPVAMD_MESH_STATS:
+"""Broad/narrow-phase counters of the mesh kernels (apply tools/patches/mesh_stats.patch, then build with -DPVAMD_MESH_STATS:
 tools/build_variant.sh stats pytorch_volumetric_amd/csrc/mesh.hip -DPVAMD_MESH_STATS; PVAMD_LIB=tools/variants/libpvamd_stats.so).
 Counters are per wave (summed over the waves of a point group); "per-block" = per 64 points."""
 import sys, os, ctypes

@@ -1,4 +1,5 @@
-"""The bench's C1 workload (10k of the 0.002 m grid points of the drill) over parts x waves (-DPVAMD_MESH_TUNE build)."""
+"""The bench's C1 workload (10k of the 0.002 m grid points of the drill) over parts x waves (apply tools/patches/mesh_tune.patch, then
+build with -DPVAMD_MESH_TUNE)."""
 import os, sys
 sys.path.insert(0, os.getcwd())
 import torch

@@ -1,4 +1,5 @@
-"""C5 chamfer through the Python call over (parts, waves per block, x-blocks) of the heavy-groups launch (-DPVAMD_MESH_TUNE build)."""
+"""C5 chamfer through the Python call over (parts, waves per block, x-blocks) of the heavy-groups launch (apply
+tools/patches/mesh_tune.patch, then build with -DPVAMD_MESH_TUNE)."""
 import os, sys
 sys.path.insert(0, os.getcwd())
 import torch

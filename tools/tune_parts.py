@@ -1,4 +1,5 @@
-"""Few-points mesh query: time per call over (points, parts, waves per block) with a -DPVAMD_MESH_TUNE build
+"""Few-points mesh query: time per call over (points, parts, waves per block) with a tuning build: apply
+tools/patches/mesh_tune.patch, then build with -DPVAMD_MESH_TUNE
 (PVAMD_LIB=tools/variants/libpvamd_tune.so; PVAMD_TUNE_PARTS / PVAMD_TUNE_WAVES are read by pvamd_mesh_query per call)."""
 import os, sys
 sys.path.insert(0, os.getcwd())
