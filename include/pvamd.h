@@ -222,17 +222,18 @@ int pvamd_voxel_scatter_u8(const pvamd_grid_t* grid, uint8_t* storage, const flo
  * sit inline (cheapest for large, gather-bound grids, whose larger coordinate / resolution ratios also flag more visits).
  * The transforms must be RIGID (orthonormal 3x3, last row 0 0 0 1): the gradient is rotated back with R^T and the
  * leaf-culling bounds rely on distances being preserved.
- * Any P >= 0 and any A >= 1 (the configuration is blockIdx.x; only the points-fastest tuning order walks slabs of 65535);
- * points / out_val / out_grad need only
- * their natural 4-byte alignment -- rows of an odd P (the reference README's M = 15,251) take the same kernel.      */
+ * Any P >= 0, any A >= 1 (the configuration is blockIdx.x: one launch for any count) and 1 <= S <= 2^30 - 2 (else
+ * PVAMD_E_SHAPE; the same bound holds for the packed, bucketed and grouped entry points below); points / out_val /
+ * out_grad need only their natural 4-byte alignment -- rows of an odd P (the reference README's M = 15,251) take the
+ * same kernel.
+ * Bits 8 and 16 of flags are retired (two tuning orders that nothing selected): ignored like any unassigned bit, and
+ * not to be reused.                                                                                                  */
 #define PVAMD_COMPOSED_INLINE_EXACT 1
 #define PVAMD_COMPOSED_FORCE_PER_LANE 2   /* testing / tuning: take the one-point-per-lane kernel whatever the size */
 #define PVAMD_COMPOSED_FORCE_WAVE_TILE 4  /* testing / tuning: take the wave-tile kernel whatever the size                 */
-#define PVAMD_COMPOSED_POINTS_FASTEST 8   /* tuning: per-lane kernel with blocks ordered points-fastest (default: configuration-fastest) */
 #define PVAMD_COMPOSED_NO_GROUPING 64   /* testing / tuning: never the chunk-grouped kernel (the round-5 kernels whatever the size) */
 #define PVAMD_COMPOSED_FORCE_FUSED 128  /* testing / tuning: the chunk-grouped kernel with the in-workgroup sort whenever P >= one chunk */
 #define PVAMD_COMPOSED_OUT_PACKED 32  /* pvamd_composed_query_grouped only: out_val takes [A][P] (val, gx, gy, gz) records (16-byte aligned), out_grad NULL */
-#define PVAMD_COMPOSED_LEGACY_LEAF_LOOP 16 /* testing / tuning: wave-tile kernel with the round-3 leaf loop (lookups and exact roots inside the leaf loop) */
 int pvamd_composed_query(const pvamd_grid_t* grids, int32_t S, const float* tf, int32_t A,
                          const float* points, int64_t P,
                          float* out_val, float* out_grad, int32_t* out_leaf, int32_t flags, void* stream);
@@ -280,8 +281,8 @@ int pvamd_composed_query_bucketed(const pvamd_grid_t* grids, int32_t S, const fl
  *   configurations of a call -- and later calls on the same points -- share it.  scratch: device,
  *   pvamd_group_scratch_bytes(P) bytes, 16-byte aligned (sorted copy | bounding sphere per run of 256 | uint16 positions).
  * pvamd_composed_query_grouped: the query over that scratch.  flags: 0, or PVAMD_COMPOSED_OUT_PACKED (the records of
- *   pvamd_composed_query_packed, for any P: out_val = [A][P][4], out_grad = NULL); the INLINE_EXACT / LEGACY hints:
- *   PVAMD_E_MODE -- gather-bound grids gain nothing from it.  Any A >= 1, any P >= pvamd_group_chunk_points(), any 4-byte
+ *   pvamd_composed_query_packed, for any P: out_val = [A][P][4], out_grad = NULL); the INLINE_EXACT hint:
+ *   PVAMD_E_MODE -- gather-bound grids gain nothing from the regrouping.  Any A >= 1, any P >= pvamd_group_chunk_points(), any 4-byte
  *   aligned outputs. */
 int64_t pvamd_group_chunk_points(void);
 int64_t pvamd_group_scratch_bytes(int64_t P);

@@ -17,8 +17,8 @@ OOB_BOUNDING_BOX = 1
 COMPOSED_INLINE_EXACT = 1
 COMPOSED_FORCE_PER_LANE = 2
 COMPOSED_FORCE_WAVE_TILE = 4
-COMPOSED_POINTS_FASTEST = 8
-COMPOSED_LEGACY_LEAF_LOOP = 16
+COMPOSED_POINTS_FASTEST = 8      # retired bit: the library ignores it; the name stays for callers that still import it
+COMPOSED_LEGACY_LEAF_LOOP = 16   # retired bit, likewise
 COMPOSED_OUT_PACKED = 32
 COMPOSED_NO_GROUPING = 64
 COMPOSED_FORCE_FUSED = 128

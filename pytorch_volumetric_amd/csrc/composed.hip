@@ -5,7 +5,7 @@
 // CachedSDF calls, cat, argmin, gather): none of those intermediates reaches HBM here.
 //
 // Leaf descriptors and the S transforms of configuration a are wave-uniform, so they are read through the scalar
-// cache into SGPRs (no LDS round trip); blockIdx.y = a keeps them uniform for the whole block.
+// cache into SGPRs (no LDS round trip); blockIdx.x = a keeps them uniform for the whole block.
 //
 // The kernel is VALU-issue-bound (profiles/r02_*: SQ_ACTIVE_INST_VALU = the kernel's duration), so this file counts
 // vector instructions:
@@ -33,15 +33,15 @@ struct Best {
                           // as the vector units in this kernel.)
 };
 
-// How a visit obtains its voxel index (all three give the reference's index, bit for bit):
-//   kEstimate    the fp32 estimate; `unsure` is raised where it cannot be trusted and the CALLER redoes those points with
-//                kExact after its leaf loop -- keeps the division sequence and its registers out of the hot loop; right
-//                when flags are rare (a few per million visits on 100 KB link grids)
-//   kInlineExact the estimate with the exact statements inline behind one rare branch -- right when flags are common
-//                (large coordinate / resolution ratios: 21 MB README-size link grids flag 22 % of the wave passes, and
-//                a redo pass per flag costs 6.2 -> 7.1 ms there)
+// How a visit of the round-3 loop (leaf_candidate) obtains its voxel index (both give the reference's index, bit for bit):
+//   kInlineExact the fp32 estimate with the exact statements inline behind one rare branch -- right when shaky estimates
+//                are common (large coordinate / resolution ratios: 21 MB README-size link grids flag 22 % of the wave
+//                passes, and a redo pass per flag costs 6.2 -> 7.1 ms there)
 //   kExact       the reference's own statements only (IEEE division in the leaf's index dtype)
-enum IndexMode { kEstimate = 0, kInlineExact = 1, kExact = 2 };
+// The split loop (tile_passes_split) calls voxel_flat_estimate itself and redoes the points whose estimate cannot be
+// trusted with walk_leaves<kExact> after its leaf loop: that keeps the division sequence and its registers out of the hot
+// loop, right when such points are rare (a few per million visits on 100 KB link grids).
+enum IndexMode { kInlineExact = 1, kExact = 2 };
 
 // One leaf for one point: candidate (v, a, b, c) and whether it came from the grid (valid) or is the unnormalised
 // bounding-box vector.
@@ -51,7 +51,7 @@ enum IndexMode { kEstimate = 0, kInlineExact = 1, kExact = 2 };
 // (inverse_ballot: the v_cndmask that consumes it reads the SGPR pair directly).
 template <int MODE>
 PVAMD_DEV void leaf_candidate(const pvamd_grid_t& g, const float* __restrict__ M, float px, float py, float pz,
-                               float& v, float& a, float& b, float& c, uint64_t& vmask, bool& unsure) {
+                               float& v, float& a, float& b, float& c, uint64_t& vmask) {
     const float x = affine_row(M[0], M[1], M[2], M[3], px, py, pz);
     const float y = affine_row(M[4], M[5], M[6], M[7], px, py, pz);
     const float z = affine_row(M[8], M[9], M[10], M[11], px, py, pz);
@@ -62,10 +62,8 @@ PVAMD_DEV void leaf_candidate(const pvamd_grid_t& g, const float* __restrict__ M
         if constexpr (MODE == kExact) {
             if (g.index_f64) voxel_flat<true>(g, x, y, z, flat);
             else voxel_flat<false>(g, x, y, z, flat);
-        } else if constexpr (MODE == kInlineExact) {
-            flat = voxel_flat_in_range_fused(g, x, y, z);
         } else {
-            flat = voxel_flat_estimate(g, x, y, z, unsure);
+            flat = voxel_flat_in_range_fused(g, x, y, z);
         }
         const float4 r = load_record(g.vox, flat);
         v = r.x; a = r.y; b = r.z; c = r.w;
@@ -85,9 +83,11 @@ PVAMD_DEV void leaf_candidate(const pvamd_grid_t& g, const float* __restrict__ M
 }
 
 // All leaves of the mask for one point, first-minimum semantics (see keep_first_minimum).
+// `unused` is neither read nor written; taking it out moves constant loads about in the leaf loops of the four split-loop
+// kernels, C3's and C4's among them (profiles/composed_prune.md), so it waits for the timing run that `a0` below waits for.
 template <int MODE>
 PVAMD_DEV void walk_leaves(const pvamd_grid_t* __restrict__ grids, int S, const float* __restrict__ tf, int A, int a,
-                            uint64_t todo, float px, float py, float pz, struct Best& best, bool& unsure);
+                            uint64_t todo, float px, float py, float pz, struct Best& best, bool& unused);
 
 // torch.argmin semantics (sdf.py:421): first minimum wins, NaN counts as the minimum.  `best` starts at +inf, so
 // "v is smaller, or v is NaN and the incumbent is not" is !(v >= best.v) && best.v == best.v.
@@ -108,12 +108,12 @@ PVAMD_DEV Best best_init(int first_leaf) {
 
 template <int MODE>
 PVAMD_DEV void walk_leaves(const pvamd_grid_t* __restrict__ grids, int S, const float* __restrict__ tf, int A, int a,
-                            uint64_t todo, float px, float py, float pz, Best& best, bool& unsure) {
+                            uint64_t todo, float px, float py, float pz, Best& best, bool& unused) {
     for (int s = 0; s < S; ++s) {
         if (s < 64 && !((todo >> s) & 1ull)) continue;  // wave-uniform
         float v, ga, gb, gc;
         uint64_t vm;
-        leaf_candidate<MODE>(grids[s], tf + 16 * ((int64_t)s * A + a), px, py, pz, v, ga, gb, gc, vm, unsure);
+        leaf_candidate<MODE>(grids[s], tf + 16 * ((int64_t)s * A + a), px, py, pz, v, ga, gb, gc, vm);
         keep_first_minimum(best, s, v, ga, gb, gc, __builtin_amdgcn_inverse_ballot_w64(vm));
     }
 }
@@ -235,25 +235,25 @@ PVAMD_DEV uint64_t tile_leaf_mask(const float (*cull)[8], int S, int lane, const
 // through a wave-private LDS slice (same scheme as cached_query_wave, see cached.hip).
 constexpr int kWavesPerBlock = 4;
 constexpr int kTilePoints = 256;
-// configurations per launch (a grid dimension carries them)
-constexpr int kConfigSlab = 65535;
 // fewer (tile, configuration) pairs than this: the one-point-per-lane kernel.  A tile is one wave's work and the chip
 // holds 6,144-8,192 waves: below ~4 rounds of them the last, partly filled round costs more than the tile machinery saves
 // (README case, 200 x 15,251 points = 12,000 tiles: per-lane 0.076 / 0.061 ms on 21 MB / 100 KB link grids against 0.104 /
 // 0.088 ms; C4's 204,800 tiles: wave-tile 0.89 against 0.95 ms; tools/readme_case.py, profiles/r03_readme_case.txt)
 constexpr int64_t kWaveTileMinTiles = 32768;
 constexpr int kPointsPerPass = 2;  // points per lane a pass of the tile kernels' leaf loop carries (their PPP)
-// kEstimate (instruction-bound, L2-resident grids): 8 waves per SIMD (<= 64 VGPRs, a few spills) beat the 6 the allocator
-// would pick on its own, C4 0.84 -> 0.80 ms.  kInlineExact (gather-bound, large grids): forcing 8 costs spills around the
-// division sequence, 6.19 -> 6.57 ms on the README-size robot; the allocator's own choice (5-6) is left alone.
+// The split loop (instruction-bound, L2-resident grids): 8 waves per SIMD (<= 64 VGPRs, a few spills) beat the 6 the
+// allocator would pick on its own, C4 0.84 -> 0.80 ms.  The round-3 loop with the exact index statements inline
+// (gather-bound, large grids): forcing 8 costs spills around the division sequence, 6.19 -> 6.57 ms on the README-size
+// robot; the allocator's own choice (5-6) is left alone.
 constexpr int kMinWaves = 8;
-// the inline-exact build: 6 = what the allocator chose on its own (78-80 VGPRs) until the switchable index rules added
+// the round-3 loop: 6 = what the allocator chose on its own (78-80 VGPRs) until the switchable index rules added
 // statements to the exact path (89); held there
 constexpr int kMinWavesInline = 6;
 
-// The leaf loop of one tile: PPP points per lane at a time, results into the wave's LDS slice (or packed, to memory).
-// MASKED = false: the tile was not worth a leaf mask (every leaf is visited; no bit tests, no refinement).
-template <int PPP, int MODE, bool PACKED, bool MASKED>
+// The round-3 leaf loop of one tile (one first minimum over all candidates, exact index statements inline): PPP points
+// per lane at a time, results into the wave's LDS slice (or packed, to memory).  A tile that was not worth a leaf mask
+// arrives with every bit of `todo` set.
+template <int PPP, bool PACKED>
 PVAMD_DEV void tile_passes(const pvamd_grid_t* __restrict__ grids, int S, const float* __restrict__ tf, int A, int a,
                            int64_t first, int64_t P, float* __restrict__ val, int* __restrict__ leaf, float* spf, int lane,
                            uint64_t todo, float lower) {
@@ -263,7 +263,7 @@ PVAMD_DEV void tile_passes(const pvamd_grid_t* __restrict__ grids, int S, const 
     // every visited leaf the wave's largest running minimum is an upper bound of every point's final value, and the
     // leaves whose lower bound exceeds it are dropped (strictly greater, so ties cannot be affected).  Scattered
     // tiles (nothing dropped statically) skip the ~10 instructions per visited leaf.
-    const bool refine = MASKED && S <= 64 && todo != (S >= 64 ? ~0ull : ((1ull << S) - 1ull));
+    const bool refine = S <= 64 && todo != (S >= 64 ? ~0ull : ((1ull << S) - 1ull));
     // PPP points per lane go through the leaf loop together (fewer live registers -> more waves per SIMD; the
     // leaf constants are scalar loads, so re-walking the leaves per pass costs SALU/SMEM, not VALU)
 #pragma unroll
@@ -278,12 +278,9 @@ PVAMD_DEV void tile_passes(const pvamd_grid_t* __restrict__ grids, int S, const 
             pz[k] = spf[3 * p + 2];
             best[k] = best_init(first_leaf);
         }
-        bool unsure[PPP];
-#pragma unroll
-        for (int k = 0; k < PPP; ++k) unsure[k] = false;
         uint64_t rem = todo;
         for (int s = 0; s < S; ++s) {
-            if (MASKED && s < 64 && !((rem >> s) & 1ull)) continue;  // wave-uniform
+            if (s < 64 && !((rem >> s) & 1ull)) continue;  // wave-uniform
             const float* M = tf + 16 * ((int64_t)s * A + a);  // wave-uniform: scalar loads
             const pvamd_grid_t& g = grids[s];
             // all PPP candidates first, their comparisons after: the gathers of the PPP points are in flight together
@@ -291,7 +288,7 @@ PVAMD_DEV void tile_passes(const pvamd_grid_t* __restrict__ grids, int S, const 
             uint64_t vm[PPP];
 #pragma unroll
             for (int k = 0; k < PPP; ++k)
-                leaf_candidate<MODE>(g, M, px[k], py[k], pz[k], v[k], ga[k], gb[k], gc[k], vm[k], unsure[k]);
+                leaf_candidate<kInlineExact>(g, M, px[k], py[k], pz[k], v[k], ga[k], gb[k], gc[k], vm[k]);
 #pragma unroll
             for (int k = 0; k < PPP; ++k)
                 keep_first_minimum(best[k], s, v[k], ga[k], gb[k], gc[k], __builtin_amdgcn_inverse_ballot_w64(vm[k]));
@@ -301,18 +298,6 @@ PVAMD_DEV void tile_passes(const pvamd_grid_t* __restrict__ grids, int S, const 
                 for (int k = 1; k < PPP; ++k) m = __builtin_fmaxf(m, best[k].v);
                 const float ub = wave_max(m);  // NaN minima are ignored: nothing replaces them anyway
                 rem &= ~__builtin_amdgcn_ballot_w64(lower > ub + 1e-6f * fabsf(ub));
-            }
-        }
-        if constexpr (MODE == kEstimate) {
-            // the few points whose index estimate could not be trusted for some leaf: all over again, exactly
-#pragma unroll
-            for (int k = 0; k < PPP; ++k) {
-                if (__builtin_expect(wave_any(unsure[k]), 0)) {
-                    Best redo = best_init(first_leaf);
-                    bool dummy = false;
-                    walk_leaves<kExact>(grids, S, tf, A, a, todo, px[k], py[k], pz[k], redo, dummy);
-                    if (unsure[k]) best[k] = redo;
-                }
             }
         }
 #pragma unroll
@@ -618,8 +603,9 @@ PVAMD_DEV Best walk_leaves_split(const pvamd_grid_t* __restrict__ grids, int S, 
     return fin;
 }
 
-template <int PPP, int MODE, bool PACKED, int SPLIT>
-__global__ __launch_bounds__(kWavesPerBlock * 64, MODE == kEstimate ? kMinWaves : kMinWavesInline) void composed_query_wave(const pvamd_grid_t* __restrict__ grids, int S,
+// SPLIT: 1 = the two running minima of round 4 (tile_passes_split), 0 = the round-3 loop (tile_passes)
+template <int PPP, bool PACKED, int SPLIT>
+__global__ __launch_bounds__(kWavesPerBlock * 64, SPLIT ? kMinWaves : kMinWavesInline) void composed_query_wave(const pvamd_grid_t* __restrict__ grids, int S,
                                                                            const float* __restrict__ tf, int A,
                                                                            const float* __restrict__ pts,
                                                                            int64_t ntiles, int64_t P,
@@ -634,6 +620,8 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, MODE == kEstimate ? kMinWaves 
     // blockIdx.x = configuration (fastest), blockIdx.y = tile block: the A configurations of one group of tiles run
     // back to back, so the leaf-grid region that tile touches (it moves little between configurations) and the tile's
     // points stay in L2 -- what matters once the grids are far larger than L2 (README-size link grids)
+    // a0 is 0 in every launch; taking the argument out reshuffles this ~11,000-instruction kernel (-129 to +183 instructions
+    // at the same register and scratch counts, profiles/composed_prune.md): left for a timing run of its own
     const int a = a0 + blockIdx.x;
     build_cull_spheres(grids, S, tf, A, a, cull);
     __syncthreads();
@@ -675,15 +663,14 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, MODE == kEstimate ? kMinWaves 
                 todo = S >= 64 ? ~0ull : ((1ull << S) - 1ull);
             }
         }
-        // two copies of the leaf loop only where instructions are what binds (kEstimate: grids that live in L2); the
-        // gather-bound kInlineExact build loses more to the larger body than the simpler loop gives (README-size robot,
-        // sorted points: 1.00 -> 1.10 ms with both copies)
+        // two copies of the leaf loop (with and without the mask's bit tests and refinement) only where instructions are
+        // what binds (the split loop: grids that live in L2); the gather-bound round-3 loop loses more to the larger body
+        // than the simpler loop gives (README-size robot, sorted points: 1.00 -> 1.10 ms with both copies)
         if constexpr (SPLIT != 0) {
             if (masked) tile_passes_split<PPP, PACKED, true>(grids, S, tf, A, a, first, P, val, leaf, spf, lane, todo, lower);
             else tile_passes_split<PPP, PACKED, false>(grids, S, tf, A, a, first, P, val, leaf, spf, lane, todo, lower);
         } else {
-            if (MODE != kEstimate || masked) tile_passes<PPP, MODE, PACKED, true>(grids, S, tf, A, a, first, P, val, leaf, spf, lane, todo, lower);
-            else tile_passes<PPP, MODE, PACKED, false>(grids, S, tf, A, a, first, P, val, leaf, spf, lane, todo, lower);
+            tile_passes<PPP, PACKED>(grids, S, tf, A, a, first, P, val, leaf, spf, lane, todo, lower);
         }
         PVAMD_WAVE_SYNC();
         if constexpr (PACKED) continue;
@@ -701,21 +688,17 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, MODE == kEstimate ? kMinWaves 
 template <bool SPLIT>
 __global__ __launch_bounds__(256) void composed_query_scalar(const pvamd_grid_t* __restrict__ grids, int S,
                                                               const float* __restrict__ tf, int A,
-                                                              const float* __restrict__ pts, int64_t first,
-                                                              int64_t P, float* __restrict__ val,
-                                                              float* __restrict__ grad, int* __restrict__ leaf, int a0,
-                                                              int config_fastest) {
-    // two block orders: points fastest (blockIdx.x = point block, blockIdx.y = configuration) or, like the wave-tile
-    // kernel, configuration fastest (blockIdx.x = configuration): the configurations of one block of points run back to
-    // back and share the grid lines those points touch
-    const int a = a0 + (config_fastest ? blockIdx.x : blockIdx.y);
-    const int64_t bx = config_fastest ? blockIdx.y : blockIdx.x, nbx = config_fastest ? gridDim.y : gridDim.x;
-    const int64_t stride = nbx * blockDim.x;
-    const int64_t n = P - first;
+                                                              const float* __restrict__ pts, int64_t P,
+                                                              float* __restrict__ val, float* __restrict__ grad,
+                                                              int* __restrict__ leaf) {
+    // like the wave-tile kernel, configuration fastest (blockIdx.x = configuration, blockIdx.y = point block): the
+    // configurations of one block of points run back to back and share the grid lines those points touch
+    const int a = blockIdx.x;
+    const int64_t stride = (int64_t)gridDim.y * blockDim.x;
     // whole waves iterate together (leaf_candidate votes across the wave): lanes past the end carry a NaN point
-    const int64_t rounds = (n + stride - 1) / stride;
+    const int64_t rounds = (P + stride - 1) / stride;
     for (int64_t r = 0; r < rounds; ++r) {
-        const int64_t i = first + r * stride + bx * blockDim.x + threadIdx.x;
+        const int64_t i = r * stride + (int64_t)blockIdx.y * blockDim.x + threadIdx.x;
         const bool live = i < P;
         const float nanv = __builtin_nanf("");
         const float px = live ? pts[3 * i] : nanv, py = live ? pts[3 * i + 1] : nanv, pz = live ? pts[3 * i + 2] : nanv;
@@ -723,8 +706,8 @@ __global__ __launch_bounds__(256) void composed_query_scalar(const pvamd_grid_t*
         if constexpr (SPLIT) {
             best = walk_leaves_split(grids, S, tf, A, a, px, py, pz);
         } else {
-            bool unsure = false;
-            walk_leaves<kInlineExact>(grids, S, tf, A, a, ~0ull, px, py, pz, best, unsure);
+            bool dummy = false;
+            walk_leaves<kInlineExact>(grids, S, tf, A, a, ~0ull, px, py, pz, best, dummy);
         }
         if (live) {
             const int s_win = best.tag & (kUnnormalised - 1);
@@ -1263,12 +1246,10 @@ __global__ __launch_bounds__(NW * 64, kGroupMinWaves) void composed_query_fused(
 
 using namespace pvamd;
 
-// the round-3 leaf loop (one register minimum over all candidates, exact roots inside the loop): on request
-static inline bool legacy_leaf_loop(int32_t flags, int32_t S) { return (flags & PVAMD_COMPOSED_LEGACY_LEAF_LOOP) || S >= kNoLeaf; }
-
+// Every composed entry point refuses S >= kNoLeaf: the split loop keeps that value for "no candidate yet".
 extern "C" int pvamd_composed_query_packed(const pvamd_grid_t* grids, int32_t S, const float* tf, int32_t A,
                                            const float* points, int64_t Pp, float* out_rec, int32_t flags, void* stream) {
-    if (S < 1 || A < 1 || Pp < 1 || Pp % kTilePoints != 0 || S >= kUnnormalised) return PVAMD_E_SHAPE;
+    if (S < 1 || A < 1 || Pp < 1 || Pp % kTilePoints != 0 || S >= kNoLeaf) return PVAMD_E_SHAPE;
     if (!grids || !tf || !points || !out_rec) return PVAMD_E_NULL;
     if (!aligned_to(grids, 8) || !aligned_to(tf, 4) || !aligned_to(points, 16) || !aligned_to(out_rec, 16)) return PVAMD_E_ALIGN;
     hipStream_t s = (hipStream_t)stream;
@@ -1276,14 +1257,12 @@ extern "C" int pvamd_composed_query_packed(const pvamd_grid_t* grids, int32_t S,
     const int64_t tile_blocks = (ntiles + kWavesPerBlock - 1) / kWavesPerBlock;
     // gridDim.y of the query kernel = tile blocks (the configuration is blockIdx.x: any A)
     if (tile_blocks > 65535) return PVAMD_E_SHAPE;  // > 67 M points per call: use the direct entry point
+    // large, gather-bound grids (the inline-exact hint): the round-3 loop; else the split loop
     if (flags & PVAMD_COMPOSED_INLINE_EXACT)
-        hipLaunchKernelGGL((composed_query_wave<kPointsPerPass, kInlineExact, true, 0>), dim3(A, (unsigned)tile_blocks),
-                           dim3(kWavesPerBlock * 64), 0, s, grids, S, tf, A, points, ntiles, Pp, out_rec, nullptr, nullptr, 0);
-    else if (legacy_leaf_loop(flags, S))
-        hipLaunchKernelGGL((composed_query_wave<kPointsPerPass, kEstimate, true, 0>), dim3(A, (unsigned)tile_blocks),
+        hipLaunchKernelGGL((composed_query_wave<kPointsPerPass, true, 0>), dim3(A, (unsigned)tile_blocks),
                            dim3(kWavesPerBlock * 64), 0, s, grids, S, tf, A, points, ntiles, Pp, out_rec, nullptr, nullptr, 0);
     else
-        hipLaunchKernelGGL((composed_query_wave<kPointsPerPass, kEstimate, true, 1>), dim3(A, (unsigned)tile_blocks),
+        hipLaunchKernelGGL((composed_query_wave<kPointsPerPass, true, 1>), dim3(A, (unsigned)tile_blocks),
                            dim3(kWavesPerBlock * 64), 0, s, grids, S, tf, A, points, ntiles, Pp, out_rec, nullptr, nullptr, 0);
     return (int)hipGetLastError();
 }
@@ -1321,7 +1300,7 @@ extern "C" int pvamd_composed_query_bucketed(const pvamd_grid_t* grids, int32_t 
 extern "C" int pvamd_composed_query(const pvamd_grid_t* grids, int32_t S, const float* tf, int32_t A,
                                     const float* points, int64_t P, float* out_val, float* out_grad,
                                     int32_t* out_leaf, int32_t flags, void* stream) {
-    if (S < 1 || A < 1 || P < 0 || S >= kUnnormalised) return PVAMD_E_SHAPE;
+    if (S < 1 || A < 1 || P < 0 || S >= kNoLeaf) return PVAMD_E_SHAPE;
     if (P == 0) return 0;
     if (!grids || !tf || !out_val || !out_grad || !points) return PVAMD_E_NULL;
     if (!aligned_to(grids, 8) || !aligned_to(tf, 4) || !aligned_to(points, 4) || !aligned_to(out_val, 4) ||
@@ -1339,22 +1318,26 @@ extern "C" int pvamd_composed_query(const pvamd_grid_t* grids, int32_t S, const 
     // Either kernel takes ANY point count and any 4-byte aligned buffers (round 2 sent P % 4 != 0 -- the reference README's
     // own M = 15,251 -- to the per-lane kernel: the wave-tile kernel's 16-byte stores wanted aligned (A, P) rows; they do
     // not: common.h f32x4_u) and the wave-tile kernel covers a ragged end with a last tile moved back to end at point P - 1:
-    // one launch per slab (fewer than 256 points always take the per-lane kernel).
+    // one launch per call (fewer than 256 points always take the per-lane kernel).
     // (flags bits 1 and 2, for tools/scalar_probe.py and the tests: force the per-lane / the wave-tile kernel.)
     const int64_t ntiles = (P + kTilePoints - 1) / kTilePoints;
+    // The configuration is blockIdx.x (any count) in all three kernels: one launch for any A.  Up to ~65536 blocks in
+    // total, split over the A configurations: about one 256-point tile per wave.  (Sweep on C4, 200 x 262,144: 1024 blocks
+    // 1.40 ms, 4096 1.17, 8192 1.13, 32768 1.09, 65536 1.08 -- the hardware dispatcher balances better than a grid-stride
+    // loop over unequal tiles.)
+    int64_t cap = ((int64_t)65536 + A - 1) / A;
+    if (cap > 65535) cap = 65535;  // gridDim.y
     // Round 6: the chunk-grouped kernel with the sort inside the workgroup (composed_query_fused) wherever there are enough
     // (chunk, configuration) workgroups to fill the chip twice over and the grids are L2-resident: scattered points cost it a
     // sixth more work per chunk and save a third of the leaf loop (C3 0.081 -> see profiles/r06_composed_variants.txt); a caller
     // with scratch and several configurations sorts once instead (pvamd_group_points + pvamd_composed_query_grouped).
     {
         const int64_t nchunks = (P + kFusedChunk - 1) / kFusedChunk;
-        const bool plain_flags = !(flags & (PVAMD_COMPOSED_INLINE_EXACT | PVAMD_COMPOSED_LEGACY_LEAF_LOOP | PVAMD_COMPOSED_FORCE_PER_LANE |
-                                            PVAMD_COMPOSED_FORCE_WAVE_TILE | PVAMD_COMPOSED_POINTS_FASTEST | PVAMD_COMPOSED_NO_GROUPING));
-        const bool fused = P >= kFusedChunk && S < kNoLeaf &&
+        const bool plain_flags = !(flags & (PVAMD_COMPOSED_INLINE_EXACT | PVAMD_COMPOSED_FORCE_PER_LANE |
+                                            PVAMD_COMPOSED_FORCE_WAVE_TILE | PVAMD_COMPOSED_NO_GROUPING));
+        const bool fused = P >= kFusedChunk &&
                            ((plain_flags && nchunks * (int64_t)A >= kFusedMinBlocks) || (flags & PVAMD_COMPOSED_FORCE_FUSED));
         if (fused) {
-            int64_t cap = ((int64_t)65536 + A - 1) / A;
-            if (cap > 65535) cap = 65535;
             const unsigned gy = (unsigned)(nchunks < cap ? nchunks : (cap < 1 ? 1 : cap));
             hipLaunchKernelGGL((composed_query_fused<kFusedWaves, kPointsPerPass>), dim3(A, gy), dim3(kFusedWaves * 64), 0, s, grids, S, tf,
                                A, points, nchunks, P, out_val, out_grad, out_leaf, 0);
@@ -1362,46 +1345,28 @@ extern "C" int pvamd_composed_query(const pvamd_grid_t* grids, int32_t S, const 
         }
     }
     const bool wave_tiles = P >= kTilePoints && ((A >= 2 && ntiles * (int64_t)A >= kWaveTileMinTiles && !(flags & PVAMD_COMPOSED_FORCE_PER_LANE)) || (flags & PVAMD_COMPOSED_FORCE_WAVE_TILE));
-    // up to ~65536 blocks in total, split over the A configurations: about one 256-point tile per wave.  (Sweep on C4,
-    // 200 x 262,144: 1024 blocks 1.40 ms, 4096 1.17, 8192 1.13, 32768 1.09, 65536 1.08 -- the hardware dispatcher
-    // balances better than a grid-stride loop over unequal tiles.)
-    // The configuration is a grid dimension: blockIdx.x (any count) in the wave-tile kernel and in the per-lane kernel's
-    // default order; blockIdx.y (<= 65535) in the per-lane kernel's points-fastest order, whose larger batches go out in
-    // slabs (the kernels take the slab's first configuration and index transforms / outputs with the global one)
-    const bool a_is_y = !wave_tiles && (flags & PVAMD_COMPOSED_POINTS_FASTEST);  // only this order carries the configuration in gridDim.y (<= 65535)
-    const int slab = a_is_y ? kConfigSlab : (kConfigSlab < 65535 ? kConfigSlab : A);
-    for (int a0 = 0; a0 < A; a0 += slab) {
-        const int An = A - a0 < slab ? A - a0 : slab;
-        int64_t cap = ((int64_t)65536 + An - 1) / An;
-        if (cap > 65535) cap = 65535;  // gridDim.y
-        if (wave_tiles) {
-            const int64_t need = (ntiles + kWavesPerBlock - 1) / kWavesPerBlock;
-            const unsigned gy = (unsigned)(need < cap ? need : (cap < 1 ? 1 : cap));
-            if (flags & PVAMD_COMPOSED_INLINE_EXACT)
-                hipLaunchKernelGGL((composed_query_wave<kPointsPerPass, kInlineExact, false, 0>), dim3(An, gy), dim3(kWavesPerBlock * 64), 0, s,
-                                   grids, S, tf, A, points, ntiles, P, out_val, out_grad, out_leaf, a0);
-            else if (legacy_leaf_loop(flags, S))
-                hipLaunchKernelGGL((composed_query_wave<kPointsPerPass, kEstimate, false, 0>), dim3(An, gy), dim3(kWavesPerBlock * 64), 0, s,
-                                   grids, S, tf, A, points, ntiles, P, out_val, out_grad, out_leaf, a0);
-            else
-                hipLaunchKernelGGL((composed_query_wave<kPointsPerPass, kEstimate, false, 1>), dim3(An, gy), dim3(kWavesPerBlock * 64),
-                                   0, s, grids, S, tf, A, points, ntiles, P, out_val, out_grad, out_leaf, a0);
-        } else {
-            const int64_t need = (P + 255) / 256;
-            const unsigned gx = (unsigned)(need < cap ? need : (cap < 1 ? 1 : cap));
-            // configuration fastest unless flag 8 asks for the other order (tuning): with it the A = 200 README case runs
-            // 0.076 instead of 0.079 ms on the slice and 0.265 instead of 0.323 ms on random points (21 MB link grids)
-            const int cf = (flags & PVAMD_COMPOSED_POINTS_FASTEST) ? 0 : 1;
-            // large, gather-bound grids (the inline-exact hint): the two minima cost a second gather of the winner's record
-            // and lose 6-12 % there (README-size link grids, 200 x 15,251: 0.087 vs 0.082 ms on the slice, 0.300 vs 0.268 ms
-            // on random points); L2-resident grids gain 7-18 % (C4 per-lane 0.975 -> 0.899 ms, README slice 0.062 -> 0.058)
-            if (legacy_leaf_loop(flags, S) || (flags & PVAMD_COMPOSED_INLINE_EXACT))
-                hipLaunchKernelGGL(composed_query_scalar<false>, cf ? dim3(An, gx) : dim3(gx, An), dim3(256), 0, s, grids, S, tf, A, points,
-                                   (int64_t)0, P, out_val, out_grad, out_leaf, a0, cf);
-            else
-                hipLaunchKernelGGL(composed_query_scalar<true>, cf ? dim3(An, gx) : dim3(gx, An), dim3(256), 0, s, grids, S, tf, A, points,
-                                   (int64_t)0, P, out_val, out_grad, out_leaf, a0, cf);
-        }
+    if (wave_tiles) {
+        const int64_t need = (ntiles + kWavesPerBlock - 1) / kWavesPerBlock;
+        const unsigned gy = (unsigned)(need < cap ? need : (cap < 1 ? 1 : cap));
+        // large, gather-bound grids (the inline-exact hint): the round-3 loop; else the split loop
+        if (flags & PVAMD_COMPOSED_INLINE_EXACT)
+            hipLaunchKernelGGL((composed_query_wave<kPointsPerPass, false, 0>), dim3(A, gy), dim3(kWavesPerBlock * 64), 0, s,
+                               grids, S, tf, A, points, ntiles, P, out_val, out_grad, out_leaf, 0);
+        else
+            hipLaunchKernelGGL((composed_query_wave<kPointsPerPass, false, 1>), dim3(A, gy), dim3(kWavesPerBlock * 64), 0, s,
+                               grids, S, tf, A, points, ntiles, P, out_val, out_grad, out_leaf, 0);
+    } else {
+        const int64_t need = (P + 255) / 256;
+        const unsigned gy = (unsigned)(need < cap ? need : (cap < 1 ? 1 : cap));
+        // large, gather-bound grids (the inline-exact hint): the two minima cost a second gather of the winner's record
+        // and lose 6-12 % there (README-size link grids, 200 x 15,251: 0.087 vs 0.082 ms on the slice, 0.300 vs 0.268 ms
+        // on random points); L2-resident grids gain 7-18 % (C4 per-lane 0.975 -> 0.899 ms, README slice 0.062 -> 0.058)
+        if (flags & PVAMD_COMPOSED_INLINE_EXACT)
+            hipLaunchKernelGGL(composed_query_scalar<false>, dim3(A, gy), dim3(256), 0, s, grids, S, tf, A, points, P, out_val,
+                               out_grad, out_leaf);
+        else
+            hipLaunchKernelGGL(composed_query_scalar<true>, dim3(A, gy), dim3(256), 0, s, grids, S, tf, A, points, P, out_val,
+                               out_grad, out_leaf);
     }
     return (int)hipGetLastError();
 }
@@ -1433,7 +1398,7 @@ extern "C" int pvamd_composed_query_grouped(const pvamd_grid_t* grids, int32_t S
                                             int64_t P, float* out_val, float* out_grad, int32_t* out_leaf, int32_t flags,
                                             void* stream) {
     if (S < 1 || A < 1 || P < kGroupChunk || S >= kNoLeaf) return PVAMD_E_SHAPE;
-    if (flags & (PVAMD_COMPOSED_INLINE_EXACT | PVAMD_COMPOSED_LEGACY_LEAF_LOOP)) return PVAMD_E_MODE;
+    if (flags & PVAMD_COMPOSED_INLINE_EXACT) return PVAMD_E_MODE;
     const bool packed = (flags & PVAMD_COMPOSED_OUT_PACKED) != 0;
     if (!grids || !tf || !out_val || (!packed && !out_grad) || !scratch) return PVAMD_E_NULL;
     if (packed && out_grad) return PVAMD_E_MODE;  // records go to out_val alone

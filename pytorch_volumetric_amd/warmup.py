@@ -48,7 +48,7 @@ def warm_up(device=None, freeze_gc=True):
         grids = comp._leaf_grids(dev)
         val = torch.empty((3, many.shape[0]), dtype=torch.float32, device=dev)
         grad = torch.empty((3, many.shape[0], 3), dtype=torch.float32, device=dev)
-        for flags in (4, 4 | 16, 4 | 1):                      # the wave-tile kernel's three leaf loops
+        for flags in (4, 4 | 1):                              # the wave-tile kernel's two leaf loops
             _lib.check(lib.pvamd_composed_query(_lib.ptr(grids), 2, _lib.ptr(comp._tf_device(dev)), 3, _lib.ptr(many),
                                                 many.shape[0], _lib.ptr(val), _lib.ptr(grad), None, flags, _lib.stream_ptr()),
                        "pvamd_composed_query")

@@ -55,6 +55,16 @@ def test_backward_argument_checks_before_any_launch():
     assert lib.pvamd_cached_query_backward(ctypes.byref(g), dummy, 10, dummy, null, dummy, null) == -4
 
 
+def test_composed_query_refuses_the_leaf_count_its_split_loop_reserves():
+    """S = 2^30 - 1 is the split leaf loop's "no candidate yet": the direct and the packed forward entry points answer
+    PVAMD_E_SHAPE for it, as the grouped one does, and take 2^30 - 2 as far as the pointer check (no launch either way)."""
+    lib = _lib.load()
+    null = None
+    for S, rc in ((2**30 - 1, _lib.E_SHAPE), (2**30 - 2, -1)):  # -1: PVAMD_E_NULL
+        assert lib.pvamd_composed_query(null, S, null, 1, null, 256, null, null, null, 0, null) == rc
+        assert lib.pvamd_composed_query_packed(null, S, null, 1, null, 256, null, 0, null) == rc
+
+
 def test_composed_routing_flag_is_set_by_set_transforms():
     comp = pv.ComposedSDF([pv.SphereSDF(0.1), pv.SphereSDF(0.2)], None)
     assert comp._tf_grad is False

@@ -6,8 +6,7 @@ import torch
 import pytorch_volumetric_amd as pv
 from oracle import oracle
 from tests import helpers as H
-from pytorch_volumetric_amd._lib import (COMPOSED_FORCE_PER_LANE as PER_LANE, COMPOSED_FORCE_WAVE_TILE as WAVE_TILE, COMPOSED_INLINE_EXACT as INLINE_EXACT,
-                                         COMPOSED_LEGACY_LEAF_LOOP as LEGACY_LEAF_LOOP, COMPOSED_POINTS_FASTEST as POINTS_FASTEST)
+from pytorch_volumetric_amd._lib import (COMPOSED_FORCE_PER_LANE as PER_LANE, COMPOSED_FORCE_WAVE_TILE as WAVE_TILE, COMPOSED_INLINE_EXACT as INLINE_EXACT)
 
 pytestmark = pytest.mark.gpu
 
@@ -194,11 +193,11 @@ def test_compose_of_mesh_sdfs_like_the_reference_test():
     assert torch.allclose(grads, torch.where((v2 < v1).unsqueeze(-1), g2, g1), atol=1e-5)
 
 
-@pytest.mark.parametrize("flags", [WAVE_TILE, WAVE_TILE | LEGACY_LEAF_LOOP, WAVE_TILE | INLINE_EXACT, PER_LANE])
+@pytest.mark.parametrize("flags", [WAVE_TILE, PER_LANE | INLINE_EXACT, WAVE_TILE | INLINE_EXACT, PER_LANE])
 def test_both_index_modes_give_the_reference_index_where_the_estimate_is_shaky(flags):
     """pvamd_composed_query's tuning hints must never change a result: wave-tile kernel with flagged points redone after the
-    loop (WAVE_TILE; also with the round-3 leaf loop, | LEGACY_LEAF_LOOP), with the exact statements inline (| INLINE_EXACT), and the
-    per-lane kernel (PER_LANE).  A leaf far from its own origin (coordinates ~200 x the resolution -> a wide error bound on the
+    loop (WAVE_TILE) and with the exact statements inline (the round-3 leaf loop, | INLINE_EXACT), and the per-lane kernel with
+    either leaf loop (PER_LANE, PER_LANE | INLINE_EXACT).  A leaf far from its own origin (coordinates ~200 x the resolution -> a wide error bound on the
     fp32 index estimate) and query points sprayed on its half-voxel planes make flagged visits the rule."""
     gt = H.AnalyticEllipsoidSDF([7.0, -5.0, 3.0], [0.3, 0.2, 0.25], [[6.7, 7.3], [-5.2, -4.8], [2.75, 3.25]])
     rng = [(6.5, 7.5), (-5.5, -4.5), (2.5, 3.5)]
@@ -303,7 +302,7 @@ def test_any_point_count_goes_through_the_wave_tile_kernel_bitwise(A, P, flags):
     assert np.array_equal(grad.cpu().numpy(), ograd, equal_nan=True)
 
 
-@pytest.mark.parametrize("flags", [WAVE_TILE, PER_LANE, PER_LANE | POINTS_FASTEST])
+@pytest.mark.parametrize("flags", [WAVE_TILE, PER_LANE])
 def test_buffers_at_any_dword_address(flags):
     """points / out_val / out_grad that are only 4-byte aligned (views into larger buffers), odd P, both kernels; the
     floats around the outputs must stay untouched."""
@@ -330,9 +329,9 @@ def test_buffers_at_any_dword_address(flags):
 
 @pytest.mark.parametrize("flags", [0, PER_LANE])
 def test_seventy_thousand_configurations_go_out_in_slabs(flags):
-    """pvamd_composed_query carries the configuration in a grid dimension (<= 65535): A = 70,000 x P = 8 crosses the slab
-    border in both kernels (the wave-tile kernel with a last -- and only -- tile of 8 points); the reference takes any
-    batch (sdf.py:370-383)."""
+    """pvamd_composed_query carries the configuration in blockIdx.x, which takes any count: A = 70,000 x P = 8 goes out in one
+    launch of either kernel, past the 65,535 a blockIdx.y could carry (the wave-tile kernel with a last -- and only -- tile of
+    8 points); the reference takes any batch (sdf.py:370-383)."""
     S, A, P = 2, 70_000, 8
     leaves = [make_leaf(res=0.02) for _ in range(S)]
     tfm = H.random_rigid(S * A, seed=6, trans=0.3)

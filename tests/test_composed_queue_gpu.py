@@ -1,7 +1,8 @@
 """-m gpu: the round-4 leaf loop of the wave-tile composed kernel (csrc/composed.hip: out-of-range candidates ordered by
 their SQUARED norms in registers, in-range (point, leaf) pairs through a per-point LDS slot, sparse ones compacted across
 visits in a wave-private queue) against the CPU oracle, bit for bit, INCLUDING the winning leaf (sdf.py:421 torch.argmin:
-first minimum wins) -- and against the round-3 loop (flag 16) and the per-lane kernel (flag 2) on the same inputs."""
+first minimum wins) -- and the same for the round-3 loop (flag 1) and both loops of the per-lane kernel (flag 2) on the same
+inputs."""
 import numpy as np
 import pytest
 import torch
@@ -13,7 +14,7 @@ from tests import helpers as H
 
 pytestmark = pytest.mark.gpu
 
-WAVE, LEGACY, PER_LANE, PER_LANE_LEGACY = 4, 4 | 16, 2, 2 | 16
+WAVE, WAVE_INLINE, PER_LANE, PER_LANE_INLINE = 4, 4 | 1, 2, 2 | 1
 
 
 def make_leaf(f64=True, res=0.01, padding=0.1, flip=False):
@@ -46,7 +47,7 @@ def check_all_kernels(leaves, tfm, A, pts):
     comp = pv.ComposedSDF(leaves, None)
     comp.set_transforms(pv.Transform3d(matrix=tfm), batch_dim=(A,) if A > 1 else None)
     oval, ograd, oleaf = oracle.composed_query([H.oracle_grid_from_cached(l) for l in leaves], tfm.numpy(), A, pts.numpy())
-    for flags in (WAVE, LEGACY, PER_LANE, PER_LANE_LEGACY):
+    for flags in (WAVE, WAVE_INLINE, PER_LANE, PER_LANE_INLINE):
         if not (flags & 2) and pts.shape[0] < 256:
             continue
         val, grad, leaf = query_with_leaf_ids(comp, pts, flags)

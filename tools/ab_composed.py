@@ -2,6 +2,7 @@
 loaded with ctypes next to the product one and timed in turns on the same buffers.
     python tools/ab_composed.py tools/variants/libpvamd_X.so [...]        C3 (pvamd_composed_query, 8 drills, 4M points) and
                                                                            C4 (pre-pass + grouped, 200 x 262,144)
+    AB_CASES=pl,rg,c3,c4   pl: the C3 scene, 2^20 points, the one-point-per-lane kernel; rg: README-size link grids
 Each figure: median over ROUNDS of (HIP events around a hipGraph of 20 calls) / 20."""
 import ctypes, os, statistics, sys
 sys.path.insert(0, os.getcwd()); sys.path.insert(0, os.path.join(os.getcwd(), "tools"))
@@ -51,7 +52,7 @@ def compare(title, make_call):
 
 
 which = os.environ.get("AB_CASES", "c3,c4").split(",")
-if "c3" in which:
+if "c3" in which or "pl" in which:
     cached = Wk.build_c2_cache()
     comp = Wk.build_c3(cached)
     P = 1 << 22
@@ -60,6 +61,10 @@ if "c3" in which:
     grids = comp._leaf_grids(pts.device); tfd = comp._tf_device(pts.device)
     S = len(comp.sdfs)
     flags = comp._direct_flags()
+if "pl" in which:  # composed_query_scalar<true>: one configuration, the per-lane kernel with the two-minima loop
+    Pl, fl = 1 << 20, _lib.COMPOSED_FORCE_PER_LANE
+    compare("C3 scene 1M per-lane", lambda lib: (lambda: lib.pvamd_composed_query(_lib.ptr(grids), S, _lib.ptr(tfd), 1, _lib.ptr(pts), Pl, _lib.ptr(val), _lib.ptr(grad), None, fl, _lib.stream_ptr())))
+if "c3" in which:
     compare("C3 4M", lambda lib: (lambda: lib.pvamd_composed_query(_lib.ptr(grids), S, _lib.ptr(tfd), 1, _lib.ptr(pts), P, _lib.ptr(val), _lib.ptr(grad), None, flags, _lib.stream_ptr())))
     if "c3ordered" in which:
         n = 2048
@@ -67,6 +72,7 @@ if "c3" in which:
         sl = torch.stack(torch.meshgrid(xs, xs, indexing="ij"), dim=-1).reshape(-1, 2)
         spts = torch.cat((sl, torch.full((n * n, 1), 0.05)), dim=1).cuda().contiguous()
         compare("C3 2048^2 ordered slice", lambda lib: (lambda: lib.pvamd_composed_query(_lib.ptr(grids), S, _lib.ptr(tfd), 1, _lib.ptr(spts), P, _lib.ptr(val), _lib.ptr(grad), None, flags, _lib.stream_ptr())))
+if "c3" in which or "pl" in which:
     del val, grad
 if "c4" in which:
     robot = Wk.build_c4(0.02, 0.1)

@@ -16,7 +16,7 @@ def census(name, leaves, tfm, A, pts):
     S = len(leaves)
     # per-leaf in-range flags of configuration 0 from the oracle pieces
     m = tfm.reshape(S, A, 4, 4).numpy()
-    for flags in (4, 20):
+    for flags in (4, 5):
         val, grad, leaf = query_with_leaf_ids(comp, pts, flags)
         bad = ~((val == oval) | (np.isnan(val) & np.isnan(oval)))
         print(f"{name} flags {flags}: {bad.sum()} of {bad.size} values differ; leaf ids differ {(leaf != oleaf).sum()}")

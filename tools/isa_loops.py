@@ -1,6 +1,6 @@
 """Loops of one kernel in a gfx950 disassembly (tools/disasm.sh output): every backward branch = one loop [target, branch]; per
 loop the instruction mix (VALU / SALU / SMEM / VMEM / LDS / scratch / branches).  No GPU needed.
-    python tools/isa_loops.py /tmp/pvamd_composed.s 'composed_query_wave<2, 0, false, 1>'"""
+    python tools/isa_loops.py /tmp/pvamd_composed.s 'composed_query_wave<2, false, 1>'"""
 import re
 import subprocess
 import sys

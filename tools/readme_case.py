@@ -29,11 +29,11 @@ for padding in (1.0, 0.1):
             comp._leaf_grids(pts.device)
             base = comp._query_flags
             k = []
-            for fl in (base, base | 2, base | 2 | 8, base | 4):
+            for fl in (base, base | 2, base | 4):
                 comp._query_flags = fl
                 k.append(gpu_ms(lambda: comp.query_into(pts, val, grad), reps=30)[0])
             comp._query_flags = base
             print(f"padding {padding}: A={A} x M={M} {name}: robot(pts) %.4f ms (min %.4f) = %.3g (config, point) pairs/s | "
-                  f"kernel only: auto %.4f, per-lane %.4f, per-lane config-fastest %.4f, wave-tile %.4f ms | set_joint_configuration %.3f ms | "
+                  f"kernel only: auto %.4f, per-lane %.4f, wave-tile %.4f ms | set_joint_configuration %.3f ms | "
                   f"published (RTX 2080 Ti, KUKA): {37.688577 if A == 20 else 128.645445:.1f} ms"
-                  % (q[0], q[1], A * M / (q[0] * 1e-3), k[0], k[1], k[2], k[3], s[0]))
+                  % (q[0], q[1], A * M / (q[0] * 1e-3), k[0], k[1], k[2], s[0]))
