@@ -120,21 +120,30 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, kCqMinWaves) void cached_query
 // 12-byte accesses at a 12-byte lane stride: every global_load_dwordx3 / global_store_dwordx3 covers a contiguous 768 B, the value
 // store a contiguous 256 B -- the same bytes per instruction slot of the address path as the 16-byte accesses of the wave-tile
 // kernel above, without the four LDS passes (12 KB per 256 points) and the wave fences that kernel's AoS <-> per-lane transposes
-// need.  One tile per wave, all PPL point loads issued before the first look-up; non-temporal stores (with plain stores the
-// 1M-point launch takes 6.9 us instead of 5.5; non-temporal LOADS cost 5-60 % while the points are cache-resident).  Against
-// the wave-tile kernel, same box, tools/cq_sweep.py (profiles/r06_cq_direct.txt): 16K-512K points 4.5-5.0 -> 2.4-3.7 us, 1M points
-// 5.56 -> 5.18 us (0.65 -> 0.71 of 8 TB/s), 4M 20.4 -> 18.9 us, 8M 36.9 -> 35.3 us (0.80 -> 0.83).  Beyond the Infinity Cache the
-// wave-tile kernel stays: 64M points 337 us against 405-460 us in this form (its 16-byte accesses and its read-ahead matter there),
-// and it keeps the sizes around 2M points where its 512 workgroups are exactly one round (9.13 against 9.3-9.5 us).
+// need.  One tile per wave; non-temporal stores (with plain stores the 1M-point launch takes 6.9 us instead of 5.5; non-temporal
+// LOADS cost 5-60 % while the points are cache-resident).  Against the wave-tile kernel, same box, tools/cq_sweep.py
+// (profiles/r06_cq_direct.txt): 16K-512K points 4.5-5.0 -> 2.4-3.7 us, 1M points 5.56 -> 5.18 us, 4M 20.4 -> 18.9 us, 8M 36.9 ->
+// 35.3 us.  Beyond the Infinity Cache the wave-tile kernel stays: 64M points 337 us against 405-460 us in this form (its 16-byte
+// accesses and its read-ahead matter there), and it keeps the sizes below 2M points where its 512 workgroups are one round.
+// The order inside a wave (profiles/cq_gather_first.md).  All waves of a launch are resident at once and run in lockstep, so the
+// launch lasts as long as ONE wave's chain of dependent memory round trips; it is kept to three:
+//   point loads -> range tests and index estimates of all PPL points (the exact index statements behind ONE rare branch for all
+//   of them) -> every gather, back to back -> the out-of-range records of ALL lanes while the gathers fly (branch-free per lane,
+//   in registers of their own; in-range lanes discard theirs: 0/0 = NaN inside the box) -> ONE s_waitcnt -> selects -> every store.
+// The look-up-per-point form before it (cached_lookup in a loop) compiled to out-of-range arithmetic, THEN the gather, a wait, the
+// stores, per point: PPL gather round trips and, since vmcnt counts stores too, PPL - 1 store acknowledgements on the chain.
+// 1M points 5.16 -> 4.90 us, every point in range 6.95 -> 6.76 us, 16,384 points 2.35 -> 1.95 us.
 // Any point count >= 64 x PPL and any 4-byte aligned buffers; a ragged end moves the last tile back so that it ends at the last point.
 template <bool F64, bool WRITE_OOB, int PPL, int WAVES>
 __global__ __launch_bounds__(WAVES * 64) void cached_query_direct(const pvamd_grid_t g, const float* __restrict__ pts, int64_t P,
                                                                   float* __restrict__ val, float* __restrict__ grad,
                                                                   uint8_t* __restrict__ oob) {
+    static_assert(PPL >= 1 && PPL <= 4, "the gathered records live in four named variables");
     constexpr int kTile = 64 * PPL;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t tile = (int64_t)blockIdx.x * WAVES + wave;
-    if (tile * kTile >= P) return;  // wave-uniform
+    // no early exit: a wave of the last workgroup whose tile starts past the end redoes the last tile like the ragged one (the
+    // same bits written twice), so P is not needed before the point loads and shares one scalar wait with the pointers
     const int64_t o = (tile * kTile <= P - kTile ? tile * kTile : P - kTile) + lane;
     float px[PPL], py[PPL], pz[PPL];
 #pragma unroll
@@ -144,24 +153,66 @@ __global__ __launch_bounds__(WAVES * 64) void cached_query_direct(const pvamd_gr
         py[k] = pts[3 * i + 1];
         pz[k] = pts[3 * i + 2];
     }
+    // range tests and index estimates of all PPL points; the exact index statements behind ONE rare branch for all of them
+    bool valid[PPL], unsure[PPL];
+    int flat[PPL];
+    bool any_unsure = false;
+#pragma unroll
+    for (int k = 0; k < PPL; ++k) {
+        valid[k] = in_range_med3(g, px[k], py[k], pz[k]);
+        unsure[k] = false;
+        flat[k] = voxel_flat_estimate(g, px[k], py[k], pz[k], unsure[k]);
+        unsure[k] &= valid[k];
+        any_unsure |= unsure[k];
+    }
+    if (__builtin_expect(wave_any(any_unsure), 0)) {
+#pragma unroll
+        for (int k = 0; k < PPL; ++k) {
+            if (unsure[k]) voxel_flat<F64>(g, px[k], py[k], pz[k], flat[k]);
+        }
+    }
+    // every gather, back to back; masked by the range test, the index clamped
+    // (written and read by in-range lanes only: with no other value to merge, a load needs no copy -- and no wait -- behind it.
+    // Four variables and not an array: an array the compiler promotes to ONE PPL x 4 register tuple, which every gather then
+    // completes with a wait and a copy of the whole tuple.)
+    record_f32x4 rec_a, rec_b, rec_c, rec_d;
+    if (valid[0]) rec_a = load_record_bits(g.vox, flat[0]);
+    if constexpr (PPL > 1) { if (valid[1]) rec_b = load_record_bits(g.vox, flat[1]); }
+    if constexpr (PPL > 2) { if (valid[2]) rec_c = load_record_bits(g.vox, flat[2]); }
+    if constexpr (PPL > 3) { if (valid[3]) rec_d = load_record_bits(g.vox, flat[3]); }
+    // the out-of-range records of ALL lanes while the gathers fly: branch-free per lane, into registers of their own
+    const bool bbox = g.oob_mode == PVAMD_OOB_BOUNDING_BOX;  // wave-uniform; LOOKUP_GT_SDF: zeros (sdf.py:546-547), caller fills in
+    float4 ob[PPL];
+#pragma unroll
+    for (int k = 0; k < PPL; ++k) {
+        ob[k] = bbox ? bounding_box_record(g, px[k], py[k], pz[k]) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    // one wait, then selects on the bits (a stored NaN, -0 or infinity leaves as it is) and every store
 #pragma unroll
     for (int k = 0; k < PPL; ++k) {
         const int64_t i = o + 64 * k;
-        bool valid;
-        const float4 r = cached_lookup<F64, false>(g, px[k], py[k], pz[k], valid);
-        __builtin_nontemporal_store(r.x, val + i);
-        __builtin_nontemporal_store(r.y, grad + 3 * i);
-        __builtin_nontemporal_store(r.z, grad + 3 * i + 1);
-        __builtin_nontemporal_store(r.w, grad + 3 * i + 2);
-        if constexpr (WRITE_OOB) oob[i] = valid ? 0 : 1;
+        const bool v = valid[k];
+        const record_f32x4& rec = k == 0 ? rec_a : k == 1 ? rec_b : k == 2 ? rec_c : rec_d;
+        const uint32_t r0 = v ? __float_as_uint(rec.x) : __float_as_uint(ob[k].x);
+        const uint32_t r1 = v ? __float_as_uint(rec.y) : __float_as_uint(ob[k].y);
+        const uint32_t r2 = v ? __float_as_uint(rec.z) : __float_as_uint(ob[k].z);
+        const uint32_t r3 = v ? __float_as_uint(rec.w) : __float_as_uint(ob[k].w);
+        __builtin_nontemporal_store(__uint_as_float(r0), val + i);
+        __builtin_nontemporal_store(__uint_as_float(r1), grad + 3 * i);
+        __builtin_nontemporal_store(__uint_as_float(r2), grad + 3 * i + 1);
+        __builtin_nontemporal_store(__uint_as_float(r3), grad + 3 * i + 2);
+        if constexpr (WRITE_OOB) oob[i] = v ? 0 : 1;
     }
 }
 
-// Which kernel serves P points (measured, profiles/r06_cq_direct.txt; one MI355X = 256 CUs x 32 resident waves):
+// Which kernel serves P points (measured, profiles/r06_cq_direct.txt, re-swept with the gather-first order in
+// profiles/cq_gather_first.md; one MI355X = 256 CUs x 32 resident waves):
 //   < 16,384            one point per lane, grid-stride (cached_query_scalar)
 //   .. 160K             direct, 1 point per lane, 8 waves      .. 896K   direct, 2 points per lane, 4 waves
 //   .. 1M               direct, 2 points per lane, 16 waves (8192 waves in 512 workgroups: exactly two per CU)
-//   .. 1.6M             direct, 4 points per lane, 4 waves      .. 2.25M  wave-tile kernel (512 workgroups = one round)
+//   .. 1.6M             direct, 4 points per lane, 4 waves      .. 2M     wave-tile kernel (up to 512 workgroups = one round; one
+//                                                                         point more starts a second round: 2.25M points 12.7 us
+//                                                                         against 11.3 us direct)
 //   .. 8M               direct, 4 points per lane, 4 waves      beyond    wave-tile kernel, streaming instantiation
 enum CqKind {
     kCqScalar = PVAMD_CQ_KERNEL_SCALAR, kCqDirect1 = PVAMD_CQ_KERNEL_DIRECT_1, kCqDirect2 = PVAMD_CQ_KERNEL_DIRECT_2,
@@ -174,7 +225,7 @@ static inline CqKind cq_kind(int64_t P) {
     if (P <= 896 * 1024) return kCqDirect2;
     if (P <= 1024 * 1024) return kCqDirect2Wide;
     if (P <= 1600 * 1024) return kCqDirect4;
-    if (P <= 2304 * 1024) return kCqWaveTile;
+    if (P <= 2048 * 1024) return kCqWaveTile;
     if (P <= kCqStreamFrom) return kCqDirect4;
     return kCqStreaming;
 }

@@ -21,8 +21,9 @@ namespace pvamd {
 // load counts against lgkmcnt as well as vmcnt): say which address space it is.
 typedef float record_f32x4 __attribute__((ext_vector_type(4)));
 typedef const record_f32x4 __attribute__((address_space(1))) * global_record_ptr;
+PVAMD_DEV record_f32x4 load_record_bits(const float* vox, int flat) { return ((global_record_ptr)(uintptr_t)vox)[flat]; }
 PVAMD_DEV float4 load_record(const float* vox, int flat) {
-    const record_f32x4 r = ((global_record_ptr)(uintptr_t)vox)[flat];
+    const record_f32x4 r = load_record_bits(vox, flat);
     return make_float4(r.x, r.y, r.z, r.w);
 }
 
@@ -246,6 +247,23 @@ PVAMD_DEV float4 bounding_box_sdf(const pvamd_grid_t& g, float x, float y, float
     return make_float4(n, div_rn(t[0], n), div_rn(t[1], n), div_rn(t[2], n));
 }
 
+// The BOUNDING_BOX record (|t|, t / |t|) of the query kernels, branch-free apart from sqrt_rn_sumsq's wave-uniform one: the
+// vector as one v_med3_f32 per component (cached_lookup below says why that equals sdf.py:559-567).  Safe on ANY lane: a point
+// inside the box gives (0, NaN, NaN, NaN), which a caller that runs this on in-range lanes too must discard by a select.
+PVAMD_DEV float4 bounding_box_record(const pvamd_grid_t& g, float x, float y, float z) {
+    const float ta = __builtin_amdgcn_fmed3f(sub_rn(x, g.bb_min[0]), sub_rn(x, g.bb_max[0]), 0.f);
+    const float tb = __builtin_amdgcn_fmed3f(sub_rn(y, g.bb_min[1]), sub_rn(y, g.bb_max[1]), 0.f);
+    const float tc = __builtin_amdgcn_fmed3f(sub_rn(z, g.bb_min[2]), sub_rn(z, g.bb_max[2]), 0.f);
+    const float n = sqrt_rn_sumsq(fmaf(tc, tc, fmaf(tb, tb, mul_rn(ta, ta))));  // sdf.py:568
+    return make_float4(n, div_rn(ta, n), div_rn(tb, n), div_rn(tc, n));          // sdf.py:570
+}
+
+// The range test of the query kernels: per axis one v_med3_f32 + one compare (in_range_mask above says why).
+PVAMD_DEV bool in_range_med3(const pvamd_grid_t& g, float x, float y, float z) {
+    return (__builtin_amdgcn_fmed3f(x, g.vlo[0], g.vhi[0]) == x) & (__builtin_amdgcn_fmed3f(y, g.vlo[1], g.vhi[1]) == y) &
+           (__builtin_amdgcn_fmed3f(z, g.vlo[2], g.vhi[2]) == z);
+}
+
 // (val, gx, gy, gz) for one point in the leaf frame; `valid` reports the range test.
 // Round 5: the statements the composed kernels had already been brought down to -- range test as three med3 + compare, ONE
 // rare branch for the exact index statements of all three axes (voxel_flat_in_range_fused), the bounding-box vector as one
@@ -269,16 +287,9 @@ PVAMD_DEV float4 cached_lookup(const pvamd_grid_t& g, float x, float y, float z,
         }
         return make_float4(0.f, 0.f, 0.f, 0.f);  // LOOKUP_GT_SDF: zeros (sdf.py:546-547), caller fills in
     } else {
-        valid = (__builtin_amdgcn_fmed3f(x, g.vlo[0], g.vhi[0]) == x) & (__builtin_amdgcn_fmed3f(y, g.vlo[1], g.vhi[1]) == y) &
-                (__builtin_amdgcn_fmed3f(z, g.vlo[2], g.vhi[2]) == z);
+        valid = in_range_med3(g, x, y, z);
         if (valid) return reinterpret_cast<const float4*>(g.vox)[voxel_flat_in_range_fused(g, x, y, z)];
-        if (g.oob_mode == PVAMD_OOB_BOUNDING_BOX) {
-            const float ta = __builtin_amdgcn_fmed3f(sub_rn(x, g.bb_min[0]), sub_rn(x, g.bb_max[0]), 0.f);
-            const float tb = __builtin_amdgcn_fmed3f(sub_rn(y, g.bb_min[1]), sub_rn(y, g.bb_max[1]), 0.f);
-            const float tc = __builtin_amdgcn_fmed3f(sub_rn(z, g.bb_min[2]), sub_rn(z, g.bb_max[2]), 0.f);
-            const float n = sqrt_rn_sumsq(fmaf(tc, tc, fmaf(tb, tb, mul_rn(ta, ta))));  // sdf.py:568
-            return make_float4(n, div_rn(ta, n), div_rn(tb, n), div_rn(tc, n));          // sdf.py:570
-        }
+        if (g.oob_mode == PVAMD_OOB_BOUNDING_BOX) return bounding_box_record(g, x, y, z);
         return make_float4(0.f, 0.f, 0.f, 0.f);  // LOOKUP_GT_SDF: zeros (sdf.py:546-547), caller fills in
     }
 }
