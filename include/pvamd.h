@@ -659,22 +659,10 @@ int pvamd_leaf_pair_distance_backward_f64(const pvamd_grid_t* grids, int32_t S, 
  *   pvamd_composed_query_backward / _interp_backward with a value upstream only (a nearest leaf in range has no derivative).
  *   per_leaf = 1: one pass per leaf s as the one-leaf composition (its dtf rows exactly that composition's), dpoints summed
  *   over the leaves in leaf order.  No stored leaf ids, no (A, P) upstream.  dtf: device [S*A][4][4] or NULL (row 3 zero);
- *   dpoints: device [P][3] or NULL.  S <= 64.  scratch: PVAMD_HINGE_OVER_POINTS_BACKWARD_SCRATCH_BYTES(S, A, P, per_leaf,
- *   sizeof(T)) bytes, 16-byte aligned.                                                                                        */
+ *   dpoints: device [P][3] or NULL.  S <= 64.  scratch: pvamd_hinge_over_points_backward_scratch_bytes(S, A, P, per_leaf,
+ *   is_f64) bytes, 16-byte aligned.  That function is the definition (the composed backward's launch plan decides the size:
+ *   call it, as for pvamd_composed_backward_scratch_bytes); there is no macro.                                                 */
 #define PVAMD_HINGE_OVER_POINTS_SCRATCH_BYTES(S, A, P, per_leaf) PVAMD_MIN_OVER_POINTS_SCRATCH_BYTES(S, A, P, per_leaf)
-/* the composed backward's plan (backward.hip bwd_plan): 1024-point chunks, configurations split until about 2048 workgroups */
-#define PVAMD_HOP_BWD_CHUNKS(P) (((int64_t)(P) + 1023) / 1024)
-#define PVAMD_HOP_BWD_WANT(A, P) \
-    ((2048 + PVAMD_HOP_BWD_CHUNKS(P) - 1) / PVAMD_HOP_BWD_CHUNKS(P) < (int64_t)(A) ? (2048 + PVAMD_HOP_BWD_CHUNKS(P) - 1) / PVAMD_HOP_BWD_CHUNKS(P) : (int64_t)(A))
-#define PVAMD_HOP_BWD_APER(A, P) (((int64_t)(A) + PVAMD_HOP_BWD_WANT(A, P) - 1) / PVAMD_HOP_BWD_WANT(A, P))
-#define PVAMD_HOP_BWD_NSPLIT(A, P) (((int64_t)(A) + PVAMD_HOP_BWD_APER(A, P) - 1) / PVAMD_HOP_BWD_APER(A, P))
-#define PVAMD_HOP_ROUND256(n) ((((int64_t)(n)) + 255) / 256 * 256)
-#define PVAMD_HOP_BWD_PLAN_BYTES(Sg, A, P, elem)                                                         \
-    (PVAMD_HOP_ROUND256(PVAMD_HOP_BWD_CHUNKS(P) * (int64_t)(Sg) * (int64_t)(A) * 12 * (int64_t)(elem)) + \
-     (PVAMD_HOP_BWD_NSPLIT(A, P) > 1 ? PVAMD_HOP_BWD_NSPLIT(A, P) * (int64_t)(P) * 3 * (int64_t)(elem) : 0))
-#define PVAMD_HINGE_OVER_POINTS_BACKWARD_SCRATCH_BYTES(S, A, P, per_leaf, elem)                                             \
-    (((per_leaf) && (S) > 1) ? PVAMD_HOP_ROUND256(PVAMD_HOP_BWD_PLAN_BYTES(1, A, P, elem)) + (int64_t)(P) * 3 * (int64_t)(elem) \
-                             : PVAMD_HOP_BWD_PLAN_BYTES((per_leaf) ? 1 : (S), A, P, elem))
 int64_t pvamd_hinge_over_points_scratch_bytes(int32_t S, int32_t A, int64_t P, int32_t per_leaf);
 int64_t pvamd_hinge_over_points_backward_scratch_bytes(int32_t S, int32_t A, int64_t P, int32_t per_leaf, int32_t is_f64);
 int pvamd_composed_hinge_over_points(const pvamd_grid_t* grids, int32_t S, const float* tf, int32_t A, const float* points,
@@ -707,15 +695,12 @@ int pvamd_composed_hinge_over_points_backward_f64(const pvamd_grid_t* grids, int
  *     chunks in chunk order), given up [A][K]; then the VJP of "Leaf-pair distance" item 1 to both stack rows, each row summed
  *     over the pairs that use it in increasing k.  Points carry no gradient; a nearest leaf in range has no derivative.  S <= 64.
  * pvamd_leaf_pair_hinge / _f64: out_val [A][K], out_count [A][K] int64.  max_points = the largest P_t of the table
- *   (1 <= max_points <= 2^32 - 2).  scratch: device, PVAMD_LEAF_PAIR_HINGE_SCRATCH_BYTES(K, A, max_points, sizeof(T), 0) bytes,
+ *   (1 <= max_points <= 2^32 - 2).  scratch: device, pvamd_leaf_pair_hinge_scratch_bytes(K, A, max_points, is_f64, 0) bytes,
  *   16-byte aligned (NULL when that is 0).
  * pvamd_leaf_pair_hinge_backward / _f64: given up [A][K], writes dtf [S*A][4][4] (every row; rows no pair uses and row 3 zero).
- *   scratch: PVAMD_LEAF_PAIR_HINGE_SCRATCH_BYTES(K, A, max_points, sizeof(T), 1) bytes, 16-byte aligned (the dC slab of
- *   12 values per pair, configuration and 1024-point chunk, then 24 values per pair and configuration: dMs and dMt).           */
-#define PVAMD_LEAF_PAIR_HINGE_SCRATCH_BYTES(K, A, max_points, elem, backward)                                                  \
-    ((backward) ? PVAMD_HOP_ROUND256(PVAMD_HOP_BWD_CHUNKS(max_points) * (int64_t)(K) * (int64_t)(A) * 12 * (int64_t)(elem)) + \
-                      24 * (int64_t)(K) * (int64_t)(A) * (int64_t)(elem)                                                     \
-                : PVAMD_LEAF_PAIR_SCRATCH_BYTES(K, A, max_points, elem, 0))
+ *   scratch: pvamd_leaf_pair_hinge_scratch_bytes(K, A, max_points, is_f64, 1) bytes, 16-byte aligned (the dC slab of
+ *   12 values per pair, configuration and 1024-point chunk, then 24 values per pair and configuration: dMs and dMt).
+ * pvamd_leaf_pair_hinge_scratch_bytes is the definition of both sizes: call it; there is no macro.                             */
 int64_t pvamd_leaf_pair_hinge_scratch_bytes(int32_t K, int32_t A, int64_t max_points, int32_t is_f64, int32_t backward);
 int pvamd_leaf_pair_hinge(const pvamd_grid_t* grids, int32_t S, const float* C, int32_t A, const float* points, int64_t npoints,
                           const int64_t* table, int32_t K, int64_t max_points, int32_t mode, float margin, int32_t power,

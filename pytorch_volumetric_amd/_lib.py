@@ -4,6 +4,7 @@ The HIP library is the only compute path of this package: there is no CPU or eag
 fails loudly if the shared object is missing, and every query raises if no MI355X is visible.
 """
 import ctypes
+import functools
 import os
 
 import torch
@@ -28,6 +29,8 @@ RULE_ROUND_FLOOR_HALF = 4
 RULE_RES_F64 = 8
 LEAF_MODES = {"nearest": 0, "trilinear": 1}  # PVAMD_LEAF_NEAREST / PVAMD_LEAF_TRILINEAR
 MOP_CHUNK = 4096  # PVAMD_MOP_CHUNK
+REG_CHUNK = 2048  # PVAMD_REG_CHUNK
+REG_SUMS = 28     # PVAMD_REG_SUMS: the row length of pvamd_chamfer_normal_eq's out_sums
 TRI_REC = 24
 TRI_TILE = 256
 TRI_GROUP = 16
@@ -59,76 +62,61 @@ def mesh_scratch_bytes(P):
 
 
 
+# The scratch of the fused reductions and their backwards: the library's exported size functions are the definition
+# (include/pvamd.h) -- what they report is what the launch code carves.  Nothing here restates their arithmetic.  A size
+# depends on the arguments only, and an optimiser loop asks for the same few: remembered, it costs less than the ctypes call.
+_remembered = functools.lru_cache(maxsize=64)
+
+
+@_remembered
 def min_over_points_scratch_bytes(S, A, P, per_leaf):
-    """PVAMD_MIN_OVER_POINTS_SCRATCH_BYTES(S, A, P, per_leaf): one 16-byte key per pair and point chunk."""
-    return 16 * A * (S if per_leaf else 1) * ((P + MOP_CHUNK - 1) // MOP_CHUNK)
+    """pvamd_min_over_points_scratch_bytes: one 16-byte key per pair and point chunk."""
+    return load().pvamd_min_over_points_scratch_bytes(S, A, P, int(per_leaf))
 
 
 def min_over_points_backward_scratch_bytes(S, A, per_leaf):
-    """PVAMD_MIN_OVER_POINTS_BACKWARD_SCRATCH_BYTES(S, A, per_leaf)"""
+    """PVAMD_MIN_OVER_POINTS_BACKWARD_SCRATCH_BYTES(S, A, per_leaf): a header macro only, the library exports no function"""
     return 24 * A * (S if per_leaf else 1)
 
 
+@_remembered
 def hinge_over_points_scratch_bytes(S, A, P, per_leaf):
-    """PVAMD_HINGE_OVER_POINTS_SCRATCH_BYTES(S, A, P, per_leaf): one 16-byte (sum, count) per pair and point chunk."""
-    return min_over_points_scratch_bytes(S, A, P, per_leaf)
+    """pvamd_hinge_over_points_scratch_bytes: one 16-byte (sum, count) per pair and point chunk."""
+    return load().pvamd_hinge_over_points_scratch_bytes(S, A, P, int(per_leaf))
 
 
-REG_CHUNK = 2048  # PVAMD_REG_CHUNK
-REG_SUMS = 28     # PVAMD_REG_SUMS
-
-
-def chamfer_normal_eq_scratch_bytes(B, N):
-    """PVAMD_CHAMFER_NORMAL_EQ_SCRATCH_BYTES(B, N): 28 float64 sums and one int64 count per pose and point chunk."""
-    if B < 1 or N < 1:
-        return 0
-    return 8 * (REG_SUMS + 1) * B * ((N + REG_CHUNK - 1) // REG_CHUNK)
-
-
-def leaf_pair_scratch_bytes(K, A, max_points, f64, backward):
-    """PVAMD_LEAF_PAIR_SCRATCH_BYTES(K, A, max_points, elem, backward): the forward's one 16-byte key per pair, configuration and
-    4096-point chunk when a set holds more than one chunk (else none); the backward's dMs and dMt per pair and configuration."""
-    if K < 1 or A < 1 or max_points < 1:
-        return 0
-    if backward:
-        return 24 * K * A * (8 if f64 else 4)
-    nchunks = (max_points + MOP_CHUNK - 1) // MOP_CHUNK
-    return 16 * K * A * nchunks if nchunks > 1 else 0
-
-
-def leaf_pair_hinge_scratch_bytes(K, A, max_points, f64, backward):
-    """PVAMD_LEAF_PAIR_HINGE_SCRATCH_BYTES(K, A, max_points, elem, backward): the forward's one 16-byte (sum, count) per pair,
-    configuration and 4096-point chunk when a set holds more than one chunk (else none); the backward's dC slab of 12 values per
-    pair, configuration and 1024-point chunk, then dMs and dMt per pair and configuration."""
-    if K < 1 or A < 1 or max_points < 1:
-        return 0
-    if backward:
-        elem = 8 if f64 else 4
-        return _round256(((max_points + 1023) // 1024) * K * A * 12 * elem) + 24 * K * A * elem
-    return leaf_pair_scratch_bytes(K, A, max_points, f64, False)
-
-
-def _round256(n):
-    return (n + 255) // 256 * 256
-
-
-def _bwd_plan_bytes(S, A, P, elem):
-    """The composed backward's scratch (backward.hip bwd_plan): the dtf slab of 1024-point chunks, then the split dpoints rows
-    when the configurations are split over workgroups (until about 2048 workgroups exist)."""
-    nchunks = (P + 1023) // 1024
-    want = min(A, (2048 + nchunks - 1) // nchunks)
-    aper = (A + want - 1) // want
-    nsplit = (A + aper - 1) // aper
-    return _round256(nchunks * S * A * 12 * elem) + (nsplit * P * 3 * elem if nsplit > 1 else 0)
-
-
+@_remembered
 def hinge_over_points_backward_scratch_bytes(S, A, P, per_leaf, f64):
-    """PVAMD_HINGE_OVER_POINTS_BACKWARD_SCRATCH_BYTES(S, A, P, per_leaf, elem): per_leaf runs one-leaf passes, whose dpoints
-    term needs one more [P][3] buffer when there is more than one leaf."""
-    elem = 8 if f64 else 4
-    if per_leaf and S > 1:
-        return _round256(_bwd_plan_bytes(1, A, P, elem)) + P * 3 * elem
-    return _bwd_plan_bytes(1 if per_leaf else S, A, P, elem)
+    """pvamd_hinge_over_points_backward_scratch_bytes: the composed backward's plan; per_leaf runs one-leaf passes, whose
+    dpoints term needs one more [P][3] buffer when there is more than one leaf."""
+    return load().pvamd_hinge_over_points_backward_scratch_bytes(S, A, P, int(per_leaf), int(f64))
+
+
+@_remembered
+def leaf_pair_scratch_bytes(K, A, max_points, f64, backward):
+    """pvamd_leaf_pair_scratch_bytes: the forward's one 16-byte key per pair, configuration and 4096-point chunk when a set
+    holds more than one chunk (else none); the backward's dMs and dMt per pair and configuration."""
+    return load().pvamd_leaf_pair_scratch_bytes(K, A, max_points, int(f64), int(backward))
+
+
+@_remembered
+def leaf_pair_hinge_scratch_bytes(K, A, max_points, f64, backward):
+    """pvamd_leaf_pair_hinge_scratch_bytes: the forward's one 16-byte (sum, count) per pair, configuration and 4096-point chunk
+    when a set holds more than one chunk (else none); the backward's dC slab of 12 values per pair, configuration and
+    1024-point chunk, then dMs and dMt per pair and configuration."""
+    return load().pvamd_leaf_pair_hinge_scratch_bytes(K, A, max_points, int(f64), int(backward))
+
+
+@_remembered
+def chamfer_normal_eq_scratch_bytes(B, N):
+    """pvamd_chamfer_normal_eq_scratch_bytes: 28 float64 sums and one int64 count per pose and point chunk."""
+    return load().pvamd_chamfer_normal_eq_scratch_bytes(B, N)
+
+
+def scratch_buffer(nbytes, dev):
+    """The one place a byte-sized scratch buffer of an entry point is allocated (uint8, uninitialised)."""
+    return torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+
 
 _c_float_p = ctypes.POINTER(ctypes.c_float)
 

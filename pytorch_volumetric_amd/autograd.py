@@ -23,7 +23,7 @@ _BACKWARD = {"nearest": "pvamd_{}_query_backward", "trilinear": "pvamd_{}_query_
 
 def _scratch(S, A, P, f64, dev):
     n = int(_lib.load().pvamd_composed_backward_scratch_bytes(S, A, P, 1 if f64 else 0))
-    return torch.empty((max(n, 16),), dtype=torch.uint8, device=dev)
+    return _lib.scratch_buffer(max(n, 16), dev)
 
 
 def _shares_storage(a, b):
@@ -162,8 +162,7 @@ class MinOverPointsQuery(torch.autograd.Function):
         dtf = torch.empty((S * A, 4, 4), dtype=dt, device=dev) if need_tf else None
         name = "pvamd_composed_min_over_points_backward" + ("_f64" if dt == torch.float64 else "")
         with _lib.on_device(dev):
-            scratch = torch.empty((max(_lib.min_over_points_backward_scratch_bytes(S, A, ctx.per_leaf), 16),), dtype=torch.uint8,
-                                  device=dev)
+            scratch = _lib.scratch_buffer(max(_lib.min_over_points_backward_scratch_bytes(S, A, ctx.per_leaf), 16), dev)
             _lib.check(getattr(_lib.load(), name)(_lib.ptr(ctx.grids), S, _lib.ptr(tfd), A, _lib.ptr(flat), P,
                                                   _lib.LEAF_MODES[ctx.mode], int(ctx.per_leaf), _lib.ptr(ctx.idx),
                                                   _lib.ptr(ctx.leaf), _lib.ptr(dv), _lib.ptr(dg), _lib.ptr(dpoints), _lib.ptr(dtf),
@@ -216,8 +215,7 @@ class HingeOverPointsQuery(torch.autograd.Function):
         f64 = dt == torch.float64
         name = "pvamd_composed_hinge_over_points_backward" + ("_f64" if f64 else "")
         with _lib.on_device(dev):
-            scratch = torch.empty((max(_lib.hinge_over_points_backward_scratch_bytes(S, A, P, ctx.per_leaf, f64), 16),),
-                                  dtype=torch.uint8, device=dev)
+            scratch = _lib.scratch_buffer(max(_lib.hinge_over_points_backward_scratch_bytes(S, A, P, ctx.per_leaf, f64), 16), dev)
             _lib.check(getattr(_lib.load(), name)(_lib.ptr(ctx.grids), S, _lib.ptr(tfd), A, _lib.ptr(flat), P,
                                                   _lib.LEAF_MODES[ctx.mode], int(ctx.per_leaf), ctx.margin, ctx.power,
                                                   _lib.ptr(up), _lib.ptr(dpoints), _lib.ptr(dtf), _lib.ptr(scratch),
@@ -265,8 +263,7 @@ class LeafPairQuery(torch.autograd.Function):
         f64 = dt == torch.float64
         name = "pvamd_leaf_pair_distance_backward" + ("_f64" if f64 else "")
         with _lib.on_device(dev):
-            scratch = torch.empty((_lib.leaf_pair_scratch_bytes(K, A, plan["max_points"], f64, True),), dtype=torch.uint8,
-                                  device=dev)
+            scratch = _lib.scratch_buffer(_lib.leaf_pair_scratch_bytes(K, A, plan["max_points"], f64, True), dev)
             _lib.check(getattr(_lib.load(), name)(_lib.ptr(ctx.grids), S, _lib.ptr(ctx.tfd), _lib.ptr(ctx.C), A,
                                                   _lib.ptr(plan["packed"]), plan["npoints"], _lib.ptr(plan["table"]), K,
                                                   _lib.LEAF_MODES[ctx.mode], _lib.ptr(ctx.idx), _lib.ptr(dv), _lib.ptr(dg),
@@ -313,8 +310,7 @@ class LeafPairHingeQuery(torch.autograd.Function):
         f64 = dt == torch.float64
         name = "pvamd_leaf_pair_hinge_backward" + ("_f64" if f64 else "")
         with _lib.on_device(dev):
-            scratch = torch.empty((_lib.leaf_pair_hinge_scratch_bytes(K, A, plan["max_points"], f64, True),), dtype=torch.uint8,
-                                  device=dev)
+            scratch = _lib.scratch_buffer(_lib.leaf_pair_hinge_scratch_bytes(K, A, plan["max_points"], f64, True), dev)
             _lib.check(getattr(_lib.load(), name)(_lib.ptr(ctx.grids), S, _lib.ptr(ctx.tfd), _lib.ptr(ctx.C), A,
                                                   _lib.ptr(plan["packed"]), plan["npoints"], _lib.ptr(plan["table"]), K,
                                                   plan["max_points"], _lib.LEAF_MODES[ctx.mode], ctx.margin, ctx.power, _lib.ptr(up),

@@ -22,7 +22,6 @@
 namespace pvamd {
 
 constexpr int kBwdMaxLeaves = 64;                  // per-wave LDS slots (and the presence mask) hold up to 64 leaves
-constexpr int kBwdTargetBlocks = 2048;             // configurations are split over workgroups until about this many exist
 
 // ---- CachedSDF.__call__ backward: one point per lane, no reduction ----
 template <typename T, bool HAS_V, bool HAS_G, bool INTERP>
@@ -222,14 +221,17 @@ __global__ __launch_bounds__(256) void reduce_splits_kernel(const T* __restrict_
     }
 }
 
+// The launch geometry and the scratch layout of one composed backward pass.  The size functions report `bytes` (the per-leaf
+// hinge: `leaf_off` plus its leaf term) and the launch code carves at the same offsets: the slab at 0, the split rows, the leaf term.
 struct BwdPlan {
     int64_t nchunks;
     int nsplit, aper;
-    int64_t slab_elems;   // [nchunks][S*A][12]
-    int64_t split_elems;  // [nsplit][P][3] when nsplit > 1, else 0
+    int64_t split_off;  // bytes: past the slab [nchunks][S*A][12]; the dpoints rows [nsplit][P][3] when nsplit > 1
+    int64_t bytes;      // slab and split rows
+    int64_t leaf_off;   // bytes: past both; the per-leaf hinge's one [P][3] leaf term
 };
 
-static BwdPlan bwd_plan(int S, int A, int64_t P) {
+static BwdPlan bwd_plan(int S, int A, int64_t P, size_t elem) {
     BwdPlan b;
     b.nchunks = (P + kBwdChunk - 1) / kBwdChunk;
     if (b.nchunks < 1) b.nchunks = 1;
@@ -238,16 +240,13 @@ static BwdPlan bwd_plan(int S, int A, int64_t P) {
     if (want < 1) want = 1;
     b.aper = (int)((A + want - 1) / want);
     b.nsplit = (A + b.aper - 1) / b.aper;
-    b.slab_elems = b.nchunks * (int64_t)S * A * 12;
-    b.split_elems = b.nsplit > 1 ? (int64_t)b.nsplit * P * 3 : 0;
+    b.split_off = round256(b.nchunks * (int64_t)S * A * 12 * (int64_t)elem);
+    b.bytes = b.split_off + (b.nsplit > 1 ? (int64_t)b.nsplit * P * 3 * (int64_t)elem : 0);
+    b.leaf_off = round256(b.bytes);
     return b;
 }
 
-static int64_t bwd_scratch_bytes(int S, int A, int64_t P, size_t elem) {
-    const BwdPlan b = bwd_plan(S, A, P);
-    const int64_t slab = ((b.slab_elems * (int64_t)elem + 255) / 256) * 256;
-    return slab + b.split_elems * (int64_t)elem;
-}
+static int64_t bwd_scratch_bytes(int S, int A, int64_t P, size_t elem) { return bwd_plan(S, A, P, elem).bytes; }
 
 template <typename T, bool HAS_V, bool HAS_G, bool CHAMFER, bool INTERP>
 static void launch_composed_backward(const BwdPlan& b, hipStream_t st, const pvamd_grid_t* grids, const pvamd_grid_t& g0, int S,
@@ -276,14 +275,14 @@ static int composed_backward(const pvamd_grid_t* grids, const pvamd_grid_t* g0, 
         return (int)hipGetLastError();
     }
     if (!tf || !points || (!chamfer && (!grids || !leaf))) return PVAMD_E_NULL;
-    if (!scratch && (dtf || bwd_plan(S, A, P).nsplit > 1)) return PVAMD_E_NULL;
+    const BwdPlan b = bwd_plan(S, A, P, sizeof(T));
+    if (!scratch && (dtf || b.nsplit > 1)) return PVAMD_E_NULL;
     if (!aligned_to(tf, sizeof(T)) || !aligned_to(points, sizeof(T)) || (scratch && !aligned_to(scratch, 16)) ||
         (dpoints && !aligned_to(dpoints, sizeof(T))) || (dtf && !aligned_to(dtf, sizeof(T))))
         return PVAMD_E_ALIGN;
-    const BwdPlan b = bwd_plan(S, A, P);
     if (b.nchunks > 0x7fffffff) return PVAMD_E_SHAPE;
     T* slab = (T*)scratch;
-    T* split_part = scratch ? (T*)((char*)scratch + ((b.slab_elems * (int64_t)sizeof(T) + 255) / 256) * 256) : nullptr;
+    T* split_part = scratch ? (T*)((char*)scratch + b.split_off) : nullptr;
     T* dp_out = dpoints ? (b.nsplit > 1 ? split_part : dpoints) : nullptr;
     const pvamd_grid_t gz = chamfer ? *g0 : pvamd_grid_t{};
     if (chamfer)
@@ -313,15 +312,12 @@ __global__ __launch_bounds__(256) void accumulate_kernel(const T* __restrict__ a
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) sum[i] += add[i];
 }
 
-static int64_t round256(int64_t n) { return ((n + 255) / 256) * 256; }
-
 // pvamd_composed_hinge_over_points_backward: composed_backward_kernel under the HINGE policy.  per_leaf: one pass per leaf s as
 // the one-leaf composition (grids + s, the stack rows of s, upstream column s), its dtf rows written in place and its dpoints
 // added to the sum in leaf order.  Scratch: the plan's slab and split rows, then (per_leaf, S > 1) one [P][3] leaf term.
 static int64_t hinge_bwd_scratch_bytes(int S, int A, int64_t P, int per_leaf, size_t elem) {
-    const int Sg = per_leaf ? 1 : S;
-    const int64_t plan = bwd_scratch_bytes(Sg, A, P, elem);
-    return (per_leaf && S > 1) ? round256(plan) + P * 3 * (int64_t)elem : plan;
+    const BwdPlan b = bwd_plan(per_leaf ? 1 : S, A, P, elem);
+    return (per_leaf && S > 1) ? b.leaf_off + P * 3 * (int64_t)elem : b.bytes;
 }
 
 template <typename T, bool WANT_TF, bool INTERP>
@@ -346,11 +342,11 @@ static int hinge_backward(const pvamd_grid_t* grids, int32_t S, const T* tf, int
         return PVAMD_E_ALIGN;
     hipStream_t st = (hipStream_t)stream;
     const int Z = per_leaf ? S : 1, Sg = per_leaf ? 1 : S;
-    const BwdPlan b = bwd_plan(Sg, A, P);
+    const BwdPlan b = bwd_plan(Sg, A, P, sizeof(T));
     if (b.nchunks > 0x7fffffff) return PVAMD_E_SHAPE;
     T* slab = (T*)scratch;
-    T* split_part = (T*)((char*)scratch + round256(b.slab_elems * (int64_t)sizeof(T)));
-    T* leaf_dp = (T*)((char*)scratch + round256(bwd_scratch_bytes(Sg, A, P, sizeof(T))));
+    T* split_part = (T*)((char*)scratch + b.split_off);
+    T* leaf_dp = (T*)((char*)scratch + b.leaf_off);
     const int64_t SgA = (int64_t)Sg * A;
     for (int z = 0; z < Z; ++z) {
         const pvamd_grid_t* gz = grids + (per_leaf ? z : 0);

@@ -66,6 +66,10 @@ PVAMD_DEV T hop_wave_sum(T v) {
 constexpr int kBwdBlock = 256;                     // four waves
 constexpr int kBwdK = 4;                           // points per lane
 constexpr int kBwdChunk = kBwdBlock * kBwdK;       // points per workgroup
+constexpr int kBwdTargetBlocks = 2048;             // configurations are split over workgroups until about this many exist
+
+// host: where the next part of a scratch buffer starts
+static inline int64_t round256(int64_t n) { return ((n + 255) / 256) * 256; }
 
 // (val, gx, gy, gz) of one leaf at the leaf-frame point x
 template <typename T, bool INTERP> struct MopLeaf;

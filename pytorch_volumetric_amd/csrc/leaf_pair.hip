@@ -303,7 +303,37 @@ __global__ __launch_bounds__(256) void lp_accumulate_kernel(const T* __restrict_
     }
 }
 
-static inline int64_t lp_chunks(int64_t max_points) { return (max_points + PVAMD_MOP_CHUNK - 1) / PVAMD_MOP_CHUNK; }
+// The scratch of the leaf-pair entry points: the size functions report `bytes`, the launch code carves at the same offsets.
+//   forward (distance and hinge): one 16-byte partial per (k, a, chunk) at 0 when a set holds more than one chunk, else nothing
+//   distance backward:            dM [K][A][24] at 0
+//   hinge backward:               the dC slab [K][A][nchunks][12] at 0, then dM; configurations split over workgroups until
+//                                 about kBwdTargetBlocks exist (the split does not change any sum)
+struct LpPlan {
+    int64_t nchunks;  // chunks of the largest set: PVAMD_MOP_CHUNK points forward, kBwdChunk points in the hinge backward
+    int aper, nsplit; // hinge backward: configurations per workgroup, workgroups per (chunk, k)
+    int64_t dM_off;   // backward, bytes
+    int64_t bytes;
+};
+
+static LpPlan lp_plan(int K, int A, int64_t max_points, size_t elem, bool hinge, bool backward) {
+    LpPlan p = {};
+    if (!backward) {
+        p.nchunks = (max_points + PVAMD_MOP_CHUNK - 1) / PVAMD_MOP_CHUNK;
+        p.bytes = PVAMD_LEAF_PAIR_SCRATCH_BYTES(K, A, max_points, elem, 0);
+        return p;
+    }
+    if (hinge) {
+        p.nchunks = (max_points + kBwdChunk - 1) / kBwdChunk;
+        int64_t want = (kBwdTargetBlocks + (int64_t)K * p.nchunks - 1) / ((int64_t)K * p.nchunks);
+        if (want > A) want = A;
+        if (want < 1) want = 1;
+        p.aper = (int)((A + want - 1) / want);
+        p.nsplit = (A + p.aper - 1) / p.aper;
+        p.dM_off = round256(p.nchunks * K * A * 12 * (int64_t)elem);
+    }
+    p.bytes = p.dM_off + PVAMD_LEAF_PAIR_SCRATCH_BYTES(K, A, max_points, elem, 1);
+    return p;
+}
 
 template <typename T>
 static int leaf_pair_transforms(const T* tf, int32_t S, int32_t A, const int64_t* table, int32_t K, T* out, void* stream) {
@@ -354,7 +384,7 @@ static int leaf_pair_distance(const pvamd_grid_t* grids, int32_t S, const T* C, 
     if (max_points < 1 || max_points > npoints || max_points > (int64_t)0xfffffffe || K > 65535) return PVAMD_E_SHAPE;
     if (int e = lp_check<T>(grids, S, C, A, points, npoints, table, K, mode)) return e;
     if (K == 0) return 0;
-    const int64_t nchunks = lp_chunks(max_points);
+    const int64_t nchunks = lp_plan(K, A, max_points, sizeof(T), false, false).nchunks;
     if (!out_val || !out_grad || !out_index || (nchunks > 1 && !scratch)) return PVAMD_E_NULL;
     if (!aligned_to(out_val, sizeof(T)) || !aligned_to(out_grad, sizeof(T)) || !aligned_to(out_index, 8) || !aligned_to(scratch, 16))
         return PVAMD_E_ALIGN;
@@ -381,7 +411,7 @@ static int leaf_pair_distance_backward(const pvamd_grid_t* grids, int32_t S, con
     hipStream_t st = (hipStream_t)stream;
     if (K == 0 || (!dval && !dgrad))  // nothing flows back: zeros
         return hipMemsetAsync(dtf, 0, (size_t)S * A * 16 * sizeof(T), st) != hipSuccess ? (int)hipGetLastError() : 0;
-    T* dM = (T*)scratch;
+    T* dM = (T*)((char*)scratch + lp_plan(K, A, 1, sizeof(T), false, true).dM_off);  // this layout does not depend on the set sizes
     const int64_t npairs = (int64_t)A * K;
     if (mode == PVAMD_LEAF_TRILINEAR)
         hipLaunchKernelGGL((lp_backward_kernel<T, true>), dim3(stream_grid(npairs, 256)), dim3(256), 0, st, grids, S, tf, C, A, points,
@@ -613,8 +643,6 @@ __global__ __launch_bounds__(256) void lph_pair_vjp_kernel(int S, const T* __res
     }
 }
 
-static inline int64_t lph_bwd_chunks(int64_t max_points) { return (max_points + kBwdChunk - 1) / kBwdChunk; }
-
 template <typename T>
 static int lph_check(const pvamd_grid_t* grids, int32_t S, const T* C, int32_t A, const T* points, int64_t npoints,
                      const int64_t* table, int32_t K, int64_t max_points, int32_t mode, int32_t power) {
@@ -649,7 +677,7 @@ static int leaf_pair_hinge(const pvamd_grid_t* grids, int32_t S, const T* C, int
                            int64_t* out_count, void* scratch, void* stream) {
     if (int e = lph_check<T>(grids, S, C, A, points, npoints, table, K, max_points, mode, power)) return e;
     if (K == 0) return 0;
-    const int64_t nchunks = lp_chunks(max_points);
+    const int64_t nchunks = lp_plan(K, A, max_points, sizeof(T), true, false).nchunks;
     if (!out_val || !out_count || (nchunks > 1 && !scratch)) return PVAMD_E_NULL;
     if (!aligned_to(out_val, sizeof(T)) || !aligned_to(out_count, 8) || !aligned_to(scratch, 16)) return PVAMD_E_ALIGN;
     hipStream_t st = (hipStream_t)stream;
@@ -674,25 +702,19 @@ static int leaf_pair_hinge_backward(const pvamd_grid_t* grids, int32_t S, const 
     hipStream_t st = (hipStream_t)stream;
     if (K == 0)  // nothing flows back: zeros
         return hipMemsetAsync(dtf, 0, (size_t)S * A * 16 * sizeof(T), st) != hipSuccess ? (int)hipGetLastError() : 0;
-    const int64_t nchunks = lph_bwd_chunks(max_points);
-    // configurations split over workgroups until about 2048 exist (bwd_plan's target); the split does not change any sum
-    int64_t want = (2048 + (int64_t)K * nchunks - 1) / ((int64_t)K * nchunks);
-    if (want > A) want = A;
-    if (want < 1) want = 1;
-    const int aper = (int)((A + want - 1) / want);
-    const unsigned nsplit = (unsigned)((A + aper - 1) / aper);
+    const LpPlan p = lp_plan(K, A, max_points, sizeof(T), true, true);
     T* slab = (T*)scratch;
-    T* dM = (T*)((char*)scratch + ((nchunks * K * A * 12 * (int64_t)sizeof(T) + 255) / 256) * 256);
-    const dim3 grd((unsigned)nchunks, nsplit, (unsigned)K);
+    T* dM = (T*)((char*)scratch + p.dM_off);
+    const dim3 grd((unsigned)p.nchunks, (unsigned)p.nsplit, (unsigned)K);
     if (mode == PVAMD_LEAF_TRILINEAR)
         hipLaunchKernelGGL((lph_backward_kernel<T, true>), grd, dim3(kBwdBlock), 0, st, grids, S, C, A, points, npoints, table, K,
-                           margin, power, up, aper, nchunks, slab);
+                           margin, power, up, p.aper, p.nchunks, slab);
     else
         hipLaunchKernelGGL((lph_backward_kernel<T, false>), grd, dim3(kBwdBlock), 0, st, grids, S, C, A, points, npoints, table, K,
-                           margin, power, up, aper, nchunks, slab);
+                           margin, power, up, p.aper, p.nchunks, slab);
     const int64_t npairs = (int64_t)A * K;
     hipLaunchKernelGGL(lph_pair_vjp_kernel<T>, dim3(stream_grid(npairs, 256)), dim3(256), 0, st, S, tf, C, A, npoints, table, K,
-                       nchunks, slab, dM);
+                       p.nchunks, slab, dM);
     hipLaunchKernelGGL(lp_accumulate_kernel<T>, dim3(stream_grid((int64_t)S * A, 256)), dim3(256), 0, st, dM, S, A, table, K, dtf);
     return (int)hipGetLastError();
 }
@@ -703,7 +725,7 @@ using namespace pvamd;
 
 extern "C" int64_t pvamd_leaf_pair_scratch_bytes(int32_t K, int32_t A, int64_t max_points, int32_t is_f64, int32_t backward) {
     if (K < 1 || A < 1 || max_points < 1) return 0;
-    return PVAMD_LEAF_PAIR_SCRATCH_BYTES(K, A, max_points, is_f64 ? 8 : 4, backward);
+    return lp_plan(K, A, max_points, is_f64 ? 8 : 4, false, backward != 0).bytes;
 }
 
 extern "C" int pvamd_leaf_pair_transforms(const float* tf, int32_t S, int32_t A, const int64_t* table, int32_t K, float* out,
@@ -748,7 +770,7 @@ extern "C" int pvamd_leaf_pair_distance_backward_f64(const pvamd_grid_t* grids, 
 
 extern "C" int64_t pvamd_leaf_pair_hinge_scratch_bytes(int32_t K, int32_t A, int64_t max_points, int32_t is_f64, int32_t backward) {
     if (K < 1 || A < 1 || max_points < 1) return 0;
-    return PVAMD_LEAF_PAIR_HINGE_SCRATCH_BYTES(K, A, max_points, is_f64 ? 8 : 4, backward);
+    return lp_plan(K, A, max_points, is_f64 ? 8 : 4, true, backward != 0).bytes;
 }
 
 extern "C" int pvamd_leaf_pair_hinge(const pvamd_grid_t* grids, int32_t S, const float* C, int32_t A, const float* points,

@@ -1291,7 +1291,7 @@ class ComposedSDF(ObjectFrameSDF):
         name = "pvamd_composed_min_over_points" + ("_f64" if flat.dtype == torch.float64 else "")
         with _lib.on_device(dev):
             grids = self._leaf_grids(dev)
-            scratch = torch.empty((_lib.min_over_points_scratch_bytes(S, A, P, per_leaf),), dtype=torch.uint8, device=dev)
+            scratch = _lib.scratch_buffer(_lib.min_over_points_scratch_bytes(S, A, P, per_leaf), dev)
             _lib.check(getattr(_lib.load(), name)(_lib.ptr(grids), S, _lib.ptr(tfd), A, _lib.ptr(flat), P, _lib.LEAF_MODES[mode],
                                                   int(per_leaf), _lib.ptr(val), _lib.ptr(grad), _lib.ptr(idx), _lib.ptr(leaf),
                                                   _lib.ptr(scratch), _lib.stream_ptr()), name)
@@ -1387,7 +1387,7 @@ class ComposedSDF(ObjectFrameSDF):
         name = "pvamd_composed_hinge_over_points" + ("_f64" if flat.dtype == torch.float64 else "")
         with _lib.on_device(dev):
             grids = self._leaf_grids(dev)
-            scratch = torch.empty((_lib.hinge_over_points_scratch_bytes(S, A, P, per_leaf),), dtype=torch.uint8, device=dev)
+            scratch = _lib.scratch_buffer(_lib.hinge_over_points_scratch_bytes(S, A, P, per_leaf), dev)
             _lib.check(getattr(_lib.load(), name)(_lib.ptr(grids), S, _lib.ptr(tfd), A, _lib.ptr(flat), P, _lib.LEAF_MODES[mode],
                                                   int(per_leaf), margin, power, _lib.ptr(val), _lib.ptr(cnt), _lib.ptr(scratch),
                                                   _lib.stream_ptr()), name)
@@ -1579,7 +1579,7 @@ class ComposedSDF(ObjectFrameSDF):
         with _lib.on_device(dev):
             grids = self._leaf_grids(dev)
             n = _lib.leaf_pair_scratch_bytes(K, A, plan["max_points"], f64, False)
-            scratch = torch.empty((n,), dtype=torch.uint8, device=dev) if n else None
+            scratch = _lib.scratch_buffer(n, dev) if n else None
             _lib.check(getattr(_lib.load(), name)(_lib.ptr(grids), S, _lib.ptr(C), A, _lib.ptr(plan["packed"]), plan["npoints"],
                                                   _lib.ptr(table), K, plan["max_points"], _lib.LEAF_MODES[mode], _lib.ptr(val),
                                                   _lib.ptr(grad), _lib.ptr(idx), _lib.ptr(scratch), _lib.stream_ptr()), name)
@@ -1660,7 +1660,7 @@ class ComposedSDF(ObjectFrameSDF):
         with _lib.on_device(dev):
             grids = self._leaf_grids(dev)
             n = _lib.leaf_pair_hinge_scratch_bytes(K, A, plan["max_points"], f64, False)
-            scratch = torch.empty((n,), dtype=torch.uint8, device=dev) if n else None
+            scratch = _lib.scratch_buffer(n, dev) if n else None
             _lib.check(getattr(_lib.load(), name)(_lib.ptr(grids), S, _lib.ptr(C), A, _lib.ptr(plan["packed"]), plan["npoints"],
                                                   _lib.ptr(table), K, plan["max_points"], _lib.LEAF_MODES[mode], margin, power,
                                                   _lib.ptr(val), _lib.ptr(cnt), _lib.ptr(scratch), _lib.stream_ptr()), name)

@@ -89,7 +89,8 @@ def test_oracle_grid_layout_is_one_definition(tmp_path):
 
 def test_buffer_size_macros_match_the_python_mirrors(tmp_path):
     """The sizes the binding allocates are the header's macros (records in whole tiles, tile / group spheres, the scratch of
-    the mesh entry points, the Morton-order scratch)."""
+    the mesh entry points, the Morton-order scratch, the scratch of the minimum's backward): the sizes that have no exported
+    function."""
     src = r'''
     #include <stdio.h>
     #include "pvamd.h"
@@ -99,6 +100,9 @@ def test_buffer_size_macros_match_the_python_mirrors(tmp_path):
         printf("%lld %lld %lld %lld\n", (long long)PVAMD_REC_FLOATS(v[i]), (long long)PVAMD_TILES_FLOATS(v[i]),
                (long long)PVAMD_MESH_SCRATCH_BYTES(v[i]), (long long)PVAMD_MORTON_ORDER_SCRATCH_BYTES(v[i]));
       printf("%d %d %d %d\n", PVAMD_TRI_REC, PVAMD_TRI_TILE, PVAMD_TRI_GROUP, PVAMD_MESH_SCRATCH_GROUPS);
+      printf("%lld %lld %lld %lld\n", (long long)PVAMD_MIN_OVER_POINTS_BACKWARD_SCRATCH_BYTES(1, 1, 0),
+             (long long)PVAMD_MIN_OVER_POINTS_BACKWARD_SCRATCH_BYTES(1, 1, 1), (long long)PVAMD_MIN_OVER_POINTS_BACKWARD_SCRATCH_BYTES(8, 200, 0),
+             (long long)PVAMD_MIN_OVER_POINTS_BACKWARD_SCRATCH_BYTES(8, 200, 1));
       return 0; }'''
     exe = str(tmp_path / "pvamd_sizes")
     subprocess.run(["gcc", "-x", "c", "-", "-I", os.path.join(ROOT, "include"), "-o", exe], input=src.encode(), check=True)
@@ -106,7 +110,90 @@ def test_buffer_size_macros_match_the_python_mirrors(tmp_path):
     for n, row in zip((0, 1, 255, 256, 257, 15728, 99500, 1 << 20, 1 << 21, (1 << 24) + 5, 67108877), out):
         assert row == [_lib.rec_floats(n), _lib.tiles_floats(n), _lib.mesh_scratch_bytes(n),
                        4 * _lib.morton_order_scratch_words(n)], (n, row)
-    assert out[-1] == [_lib.TRI_REC, _lib.TRI_TILE, _lib.TRI_GROUP, _lib.MESH_SCRATCH_GROUPS]
+    assert out[-2] == [_lib.TRI_REC, _lib.TRI_TILE, _lib.TRI_GROUP, _lib.MESH_SCRATCH_GROUPS]
+    assert out[-1] == [_lib.min_over_points_backward_scratch_bytes(S, A, per_leaf)
+                       for S, A in ((1, 1), (8, 200)) for per_leaf in (False, True)]
+    assert out[-1] == [24, 24, 24 * 200, 24 * 200 * 8]
+
+
+SIZE_FUNCTIONS = ("min_over_points_scratch_bytes", "hinge_over_points_scratch_bytes", "hinge_over_points_backward_scratch_bytes",
+                  "leaf_pair_scratch_bytes", "leaf_pair_hinge_scratch_bytes", "chamfer_normal_eq_scratch_bytes")
+
+
+def test_scratch_size_macros_match_the_exported_functions(tmp_path):
+    """The exported pvamd_*_scratch_bytes functions are the definition of every scratch size; the header keeps a macro only for
+    the one-expression sizes the library itself returns.  Each of those against its function, at the branch points of the
+    formulas: one point, a full chunk, one point more, many chunks; both element sizes; per_leaf / backward on and off."""
+    src = r'''
+    #include <stdio.h>
+    #include "pvamd.h"
+    int main(void) {
+      long long P[] = {1, 4096, 4097, 262145}, SA[][2] = {{1, 1}, {8, 200}}, KA[][2] = {{1, 1}, {42, 200}};
+      long long N[] = {1, 2048, 2049}, B[] = {1, 1024};
+      for (int i = 0; i < 4; ++i) for (int j = 0; j < 2; ++j) for (int pl = 0; pl < 2; ++pl)
+        printf("mop %lld %lld %lld %d %lld %lld\n", SA[j][0], SA[j][1], P[i], pl,
+               (long long)PVAMD_MIN_OVER_POINTS_SCRATCH_BYTES(SA[j][0], SA[j][1], P[i], pl),
+               (long long)PVAMD_HINGE_OVER_POINTS_SCRATCH_BYTES(SA[j][0], SA[j][1], P[i], pl));
+      for (int i = 0; i < 4; ++i) for (int j = 0; j < 2; ++j) for (int f64 = 0; f64 < 2; ++f64) for (int bwd = 0; bwd < 2; ++bwd)
+        printf("lp %lld %lld %lld %d %d %lld\n", KA[j][0], KA[j][1], P[i], f64, bwd,
+               (long long)PVAMD_LEAF_PAIR_SCRATCH_BYTES(KA[j][0], KA[j][1], P[i], f64 ? 8 : 4, bwd));
+      for (int i = 0; i < 3; ++i) for (int j = 0; j < 2; ++j)
+        printf("reg %lld %lld %lld\n", B[j], N[i], (long long)PVAMD_CHAMFER_NORMAL_EQ_SCRATCH_BYTES(B[j], N[i]));
+      printf("const %d %d %d\n", PVAMD_MOP_CHUNK, PVAMD_REG_CHUNK, PVAMD_REG_SUMS);
+      return 0; }'''
+    exe = str(tmp_path / "pvamd_scratch_sizes")
+    subprocess.run(["gcc", "-x", "c", "-", "-I", os.path.join(ROOT, "include"), "-o", exe], input=src.encode(), check=True)
+    lines = [line.split() for line in subprocess.run([exe], capture_output=True, check=True).stdout.decode().splitlines()]
+    lib = _lib.load()
+    seen = {"mop": 0, "lp": 0, "reg": 0, "const": 0}
+    for kind, *rest in lines:
+        v = [int(x) for x in rest]
+        seen[kind] += 1
+        if kind == "mop":
+            S, A, P, pl, mop, hop = v
+            assert lib.pvamd_min_over_points_scratch_bytes(S, A, P, pl) == mop, v
+            assert lib.pvamd_hinge_over_points_scratch_bytes(S, A, P, pl) == hop, v
+        elif kind == "lp":
+            K, A, P, f64, bwd, n = v
+            assert lib.pvamd_leaf_pair_scratch_bytes(K, A, P, f64, bwd) == n, v
+            if not bwd:  # the hinge's forward is the distance's; its backward has no macro (a launch plan decides it)
+                assert lib.pvamd_leaf_pair_hinge_scratch_bytes(K, A, P, f64, 0) == n, v
+        elif kind == "reg":
+            B, N, n = v
+            assert lib.pvamd_chamfer_normal_eq_scratch_bytes(B, N) == n, v
+        else:
+            assert v == [_lib.MOP_CHUNK, _lib.REG_CHUNK, _lib.REG_SUMS] == [4096, 2048, 28]
+    assert seen == {"mop": 16, "lp": 32, "reg": 6, "const": 1}
+    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    assert sorted(re.findall(r"#define\s+(PVAMD_\w*SCRATCH_BYTES)\b", text)) == sorted(
+        ["PVAMD_MIN_OVER_POINTS_SCRATCH_BYTES", "PVAMD_MIN_OVER_POINTS_BACKWARD_SCRATCH_BYTES",
+         "PVAMD_HINGE_OVER_POINTS_SCRATCH_BYTES", "PVAMD_LEAF_PAIR_SCRATCH_BYTES", "PVAMD_CHAMFER_NORMAL_EQ_SCRATCH_BYTES",
+         "PVAMD_MESH_SCRATCH_BYTES", "PVAMD_MORTON_ORDER_SCRATCH_BYTES", "PVAMD_MORTON_RADIX_SCRATCH_BYTES",
+         "PVAMD_MORTON_COUNTING_SCRATCH_BYTES"]), "a size macro without a check against its definition"
+
+
+def test_binding_asks_the_library_for_scratch_sizes():
+    """_lib's size functions are one call of the exported function of the same name (bool arguments converted), with no
+    arithmetic of their own to drift from it."""
+    import inspect
+    lib = _lib.load()
+    for S, A, P in ((8, 200, 262145), (1, 1, 1), (3, 64, 33792)):
+        for pl in (False, True):
+            assert _lib.min_over_points_scratch_bytes(S, A, P, pl) == lib.pvamd_min_over_points_scratch_bytes(S, A, P, int(pl))
+            assert _lib.hinge_over_points_scratch_bytes(S, A, P, pl) == lib.pvamd_hinge_over_points_scratch_bytes(S, A, P, int(pl))
+            for f64 in (False, True):
+                assert _lib.hinge_over_points_backward_scratch_bytes(S, A, P, pl, f64) == \
+                    lib.pvamd_hinge_over_points_backward_scratch_bytes(S, A, P, int(pl), int(f64))
+                # (K, A, max_points, f64, backward)
+                assert _lib.leaf_pair_scratch_bytes(S, A, P, f64, pl) == lib.pvamd_leaf_pair_scratch_bytes(S, A, P, int(f64), int(pl))
+                assert _lib.leaf_pair_hinge_scratch_bytes(S, A, P, f64, pl) == \
+                    lib.pvamd_leaf_pair_hinge_scratch_bytes(S, A, P, int(f64), int(pl))
+        assert _lib.chamfer_normal_eq_scratch_bytes(A, P) == lib.pvamd_chamfer_normal_eq_scratch_bytes(A, P)
+    for name in SIZE_FUNCTIONS:
+        source = inspect.getsource(getattr(_lib, name))
+        assert f"load().pvamd_{name}(" in source, name
+        for operator in ("//", "*", "+"):
+            assert operator not in source, (name, operator)
 
 
 def test_no_gpu_means_a_loud_error_not_a_fallback():

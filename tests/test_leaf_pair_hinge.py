@@ -1,7 +1,6 @@
 """CPU: the leaf-pair hinge API surface (pv.LeafPairHinge, ComposedSDF.leaf_pair_hinge, RobotSDF.self_collision_hinge), the
 argument checks, and the _lib mirrors of the new C-ABI symbols (include/pvamd.h "Leaf-pair hinge").  No GPU: every check here
 raises or returns before a kernel is launched."""
-import numpy as np
 import pytest
 import torch
 
@@ -103,14 +102,11 @@ def test_abi_mirrors():
     assert _lib.leaf_pair_hinge_scratch_bytes(42, 200, 4096, False, False) == 0
     assert _lib.leaf_pair_hinge_scratch_bytes(42, 200, 4097, False, False) == 16 * 42 * 200 * 2
     assert _lib.leaf_pair_hinge_scratch_bytes(42, 200, 256, False, True) == 42 * 200 * 12 * 4 + 24 * 42 * 200 * 4
-    rng = np.random.default_rng(0)
-    cases = [(42, 200, 256), (1, 1, 1), (3, 7, 1024), (3, 7, 1025), (3, 7, 4096), (3, 7, 4097), (4032, 1000, 10_000)]
-    cases += [(int(rng.integers(1, 5000)), int(rng.integers(1, 3000)), int(rng.integers(1, 3_000_000))) for _ in range(200)]
-    for K, A, P in cases:
-        for f64 in (0, 1):
-            for bwd in (0, 1):
-                assert lib.pvamd_leaf_pair_hinge_scratch_bytes(K, A, P, f64, bwd) == \
-                    _lib.leaf_pair_hinge_scratch_bytes(K, A, P, bool(f64), bool(bwd)), (K, A, P, f64, bwd)
+    # These values come from the library (tests/test_abi.py: the binding only calls it).  The backward worked by hand at the
+    # chunk boundary: the dC slab [K][A][chunks of 1024][12] rounded up to 256 B, then dMs and dMt.
+    assert _lib.leaf_pair_hinge_scratch_bytes(2, 3, 1024, False, True) == 512 + 24 * 2 * 3 * 4
+    assert _lib.leaf_pair_hinge_scratch_bytes(2, 3, 1025, False, True) == 768 + 24 * 2 * 3 * 4
+    assert _lib.leaf_pair_hinge_scratch_bytes(2, 3, 1025, True, True) == 1280 + 24 * 2 * 3 * 8
     assert lib.pvamd_leaf_pair_hinge_scratch_bytes(0, 200, 256, 0, 0) == 0
     assert lib.pvamd_leaf_pair_hinge_scratch_bytes(42, 0, 256, 0, 1) == 0
 
