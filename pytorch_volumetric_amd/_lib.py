@@ -18,8 +18,6 @@ OOB_BOUNDING_BOX = 1
 COMPOSED_INLINE_EXACT = 1
 COMPOSED_FORCE_PER_LANE = 2
 COMPOSED_FORCE_WAVE_TILE = 4
-COMPOSED_POINTS_FASTEST = 8      # retired bit: the library ignores it; the name stays for callers that still import it
-COMPOSED_LEGACY_LEAF_LOOP = 16   # retired bit, likewise
 COMPOSED_OUT_PACKED = 32
 COMPOSED_NO_GROUPING = 64
 COMPOSED_FORCE_FUSED = 128
@@ -479,10 +477,6 @@ def as_query_points(points, device=None, keep_f64=False):
     flat = points.detach().reshape(-1, 3).to(device=dev, dtype=torch.float64 if keep_f64 and points.dtype == torch.float64
                                               else torch.float32).contiguous()
     return flat, lead, points.dtype if points.dtype.is_floating_point else torch.float32, points.device
-
-
-ORDER_RADIX_SORT_FROM = 3 << 18  # PVAMD_ORDER_RADIX_SORT_FROM of the product build; morton_order_scratch_words() sizes for EITHER sort
-
 
 
 _group_chunk = None

@@ -233,10 +233,10 @@ static inline CqKind cq_kind(int64_t P) {
 // ---- one point per lane: small batches (more waves than 256-point tiles would give) ----
 template <bool F64>
 __global__ __launch_bounds__(256) void cached_query_scalar(const pvamd_grid_t g, const float* __restrict__ pts,
-                                                            int64_t first, int64_t P, float* __restrict__ val,
-                                                            float* __restrict__ grad, uint8_t* __restrict__ oob) {
+                                                            int64_t P, float* __restrict__ val, float* __restrict__ grad,
+                                                            uint8_t* __restrict__ oob) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = first + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += stride) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < P; i += stride) {
         bool valid;
         const float4 r = cached_lookup<F64>(g, pts[3 * i], pts[3 * i + 1], pts[3 * i + 2], valid);
         val[i] = r.x;
@@ -386,8 +386,8 @@ extern "C" int pvamd_cached_query(const pvamd_grid_t* grid, const float* points,
 #undef PVAMD_LAUNCH_DIRECT
     } else {
         const dim3 grid_dim(stream_grid(P, 256)), block(256);
-        if (f64) hipLaunchKernelGGL((cached_query_scalar<true>), grid_dim, block, 0, s, *grid, points, (int64_t)0, P, out_val, out_grad, out_oob);
-        else hipLaunchKernelGGL((cached_query_scalar<false>), grid_dim, block, 0, s, *grid, points, (int64_t)0, P, out_val, out_grad, out_oob);
+        if (f64) hipLaunchKernelGGL((cached_query_scalar<true>), grid_dim, block, 0, s, *grid, points, P, out_val, out_grad, out_oob);
+        else hipLaunchKernelGGL((cached_query_scalar<false>), grid_dim, block, 0, s, *grid, points, P, out_val, out_grad, out_oob);
     }
     return (int)hipGetLastError();
 }

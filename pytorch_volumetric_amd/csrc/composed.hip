@@ -83,11 +83,14 @@ PVAMD_DEV void leaf_candidate(const pvamd_grid_t& g, const float* __restrict__ M
 }
 
 // All leaves of the mask for one point, first-minimum semantics (see keep_first_minimum).
-// `unused` is neither read nor written; taking it out moves constant loads about in the leaf loops of the four split-loop
-// kernels, C3's and C4's among them (profiles/composed_prune.md), so it waits for the timing run that `a0` below waits for.
+// The trailing bool& is neither read nor written, and stays: without it the compiler places the +inf / NaN constant loads of the
+// split loop elsewhere, and C4 without grouping (200 x 262,144, composed_query_wave<2, false, 1>) ran 0.6708 ms against the
+// 0.6703 of this form, where three builds of the same source stood within 0.0002 of each other; C3, grouped C4 and the packed
+// form were 0.0 to 0.2 % faster (profiles/argument_prune.md).  That is one compiler's scheduling (ROCm 7.2, clang 22), not a
+// property of the code: after a compiler change, time it again (tools/ab_composed.py, case c4w) and drop the argument if it is even.
 template <int MODE>
 PVAMD_DEV void walk_leaves(const pvamd_grid_t* __restrict__ grids, int S, const float* __restrict__ tf, int A, int a,
-                            uint64_t todo, float px, float py, float pz, struct Best& best, bool& unused);
+                            uint64_t todo, float px, float py, float pz, struct Best& best, bool&);
 
 // torch.argmin semantics (sdf.py:421): first minimum wins, NaN counts as the minimum.  `best` starts at +inf, so
 // "v is smaller, or v is NaN and the incumbent is not" is !(v >= best.v) && best.v == best.v.
@@ -108,7 +111,7 @@ PVAMD_DEV Best best_init(int first_leaf) {
 
 template <int MODE>
 PVAMD_DEV void walk_leaves(const pvamd_grid_t* __restrict__ grids, int S, const float* __restrict__ tf, int A, int a,
-                            uint64_t todo, float px, float py, float pz, Best& best, bool& unused) {
+                            uint64_t todo, float px, float py, float pz, Best& best, bool&) {
     for (int s = 0; s < S; ++s) {
         if (s < 64 && !((todo >> s) & 1ull)) continue;  // wave-uniform
         float v, ga, gb, gc;
@@ -620,8 +623,11 @@ __global__ __launch_bounds__(kWavesPerBlock * 64, SPLIT ? kMinWaves : kMinWavesI
     // blockIdx.x = configuration (fastest), blockIdx.y = tile block: the A configurations of one group of tiles run
     // back to back, so the leaf-grid region that tile touches (it moves little between configurations) and the tile's
     // points stay in L2 -- what matters once the grids are far larger than L2 (README-size link grids)
-    // a0 is 0 in every launch; taking the argument out reshuffles this ~11,000-instruction kernel (-129 to +183 instructions
-    // at the same register and scratch counts, profiles/composed_prune.md): left for a timing run of its own
+    // a0 is 0 in every launch, and stays: without it (-129 to +183 instructions in the seven kernels that take it, same
+    // registers and scratch) the README-size robot on sorted points ran 1.0121 ms against 1.0110 and 1.0085 against 1.0071 in a
+    // second session, C4 without grouping 0.6729 against 0.6703, where builds of the same source stood 0.07 %, 0.00 % and
+    // 0.03 % apart; C3 and grouped C4 showed no difference (profiles/argument_prune.md).  The figures are this compiler's
+    // scheduling (ROCm 7.2, clang 22): time it again with tools/ab_composed.py after a compiler change, and drop a0 if it is even
     const int a = a0 + blockIdx.x;
     build_cull_spheres(grids, S, tf, A, a, cull);
     __syncthreads();
@@ -727,7 +733,7 @@ __global__ __launch_bounds__(256) void composed_query_scalar(const pvamd_grid_t*
 
 // ---- generic leaves (MeshSDF, SphereSDF, nested compositions): the glue of sdf.py:392-433 around per-leaf queries ----
 // x[a][p] = T[a] p with the fused kernel's rounding (k-ordered fma chain, sdf.py:399)
-__global__ __launch_bounds__(256) void transform_points_kernel(const float* __restrict__ tf, int A,
+__global__ __launch_bounds__(256) void transform_points_kernel(const float* __restrict__ tf,
                                                                 const float* __restrict__ pts, int64_t P,
                                                                 float* __restrict__ out) {
     const int a = blockIdx.y;
@@ -744,7 +750,7 @@ __global__ __launch_bounds__(256) void transform_points_kernel(const float* __re
 
 // fold leaf s into the running first-minimum: g_obj = L^T g_leaf (sdf.py:409; L = linear part of obj->leaf, any affine
 // transform), take where the leaf's value is smaller or is NaN against a number (sdf.py:421 argmin); first = 1 for s = 0
-__global__ __launch_bounds__(256) void compose_merge_kernel(const float* __restrict__ tf, int A, int64_t P,
+__global__ __launch_bounds__(256) void compose_merge_kernel(const float* __restrict__ tf, int64_t P,
                                                              const float* __restrict__ leaf_val,
                                                              const float* __restrict__ leaf_grad, int s, int first,
                                                              float* __restrict__ best_val, float* __restrict__ best_grad,
@@ -1428,7 +1434,7 @@ extern "C" int pvamd_transform_points(const float* tf, int32_t A, const float* p
     if (A < 1 || A > 65535 || P < 0) return PVAMD_E_SHAPE;
     if (P == 0) return 0;
     if (!tf || !points || !out) return PVAMD_E_NULL;
-    hipLaunchKernelGGL(transform_points_kernel, dim3(stream_grid(P, 256), A), dim3(256), 0, (hipStream_t)stream, tf, A, points,
+    hipLaunchKernelGGL(transform_points_kernel, dim3(stream_grid(P, 256), A), dim3(256), 0, (hipStream_t)stream, tf, points,
                        P, out);
     return (int)hipGetLastError();
 }
@@ -1439,7 +1445,7 @@ extern "C" int pvamd_compose_merge(const float* tf, int32_t A, int64_t P, const 
     if (A < 1 || A > 65535 || P < 0 || s < 0) return PVAMD_E_SHAPE;
     if (P == 0) return 0;
     if (!tf || !leaf_val || !leaf_grad || !best_val || !best_grad) return PVAMD_E_NULL;
-    hipLaunchKernelGGL(compose_merge_kernel, dim3(stream_grid(P, 256), A), dim3(256), 0, (hipStream_t)stream, tf, A, P,
+    hipLaunchKernelGGL(compose_merge_kernel, dim3(stream_grid(P, 256), A), dim3(256), 0, (hipStream_t)stream, tf, P,
                        leaf_val, leaf_grad, s, first, best_val, best_grad, best_leaf);
     return (int)hipGetLastError();
 }

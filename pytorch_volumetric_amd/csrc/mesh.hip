@@ -1172,13 +1172,16 @@ constexpr int kPartsMinWaves = 7;  // waves per SIMD the parts kernels are held 
                                    // 30k points 0.201 / 0.190 / 0.207 ms at 6 / 7 / 8)
 // one listed group in one block: wave w takes the w-th 64-record pass of the tiles ti % gridDim.y == blockIdx.y
 template <bool WITH_RAY, bool WAIT = false, int WAVES = kTile / 64>
-PVAMD_DEV void parts_of_group(const MeshArgs& m, MeshShared<WAVES, WITH_RAY>& sh, const int* __restrict__ order,
-                              const float* __restrict__ M, const float* __restrict__ pts, int64_t P, uint64_t seed,
-                              int64_t index_base, const HandOver& ho, int slot, int group) {
+PVAMD_DEV void parts_of_group(const MeshArgs& m, MeshShared<WAVES, WITH_RAY>& sh, uint64_t seed, const HandOver& ho, int slot) {
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (!part_has_work<WITH_RAY>(m, ho.bound + (int64_t)slot * kBoundFloats, (int)blockIdx.y, (int)gridDim.y)) return;  // the whole block
     Wave<WITH_RAY> wv;
-    // everything a block needs to start comes from the slot, in one batch of independent loads
+    // everything a block needs to start comes from the slot, in one batch of independent loads.  The rays as well, drawn when the
+    // group was listed, so scan_begin never uses `seed` here -- and it stays: with the literal 0 in its place the compiler drops
+    // the ~280 instructions of ray hashing it keeps for a null `drawn`, and the kernels ran slower over ten alternated processes:
+    // the 10,000-point drill query 0.0757 ms a call against 0.0751 (a second build of the same source 0.0755; with `seed` 0.0751),
+    // the 48,840-voxel cache build 0.2181 ms against 0.2159 (0.2170; 0.2144).  ROCm 7.2's code layout, not a property of the code:
+    // time it again after a compiler change (profiles/argument_prune.md)
     const float* q = ho.pts + ((int64_t)slot * 64 + lane) * 3;
     wv.s.p = v3(q[0], q[1], q[2]);
     const unsigned long long start = ho.best[(int64_t)slot * 64 + lane];
@@ -1215,10 +1218,10 @@ PVAMD_DEV void parts_of_group(const MeshArgs& m, MeshShared<WAVES, WITH_RAY>& sh
 template <int kAllWaves>
 __global__ __launch_bounds__(64 * kAllWaves, kPartsMinWaves) void mesh_parts_all_kernel(MeshArgs m, const int* __restrict__ order,
                                                                           const float* __restrict__ pts, int64_t P,
-                                                                          uint64_t seed, int64_t index_base, HandOver ho, QueryOut out) {
+                                                                          uint64_t seed, HandOver ho, QueryOut out) {
     __shared__ __attribute__((aligned(16))) MeshShared<kAllWaves, true> sh;
     const int g = (int)blockIdx.x;
-    parts_of_group<true, true, kAllWaves>(m, sh, order, nullptr, pts, P, seed, index_base, ho, g, g);
+    parts_of_group<true, true, kAllWaves>(m, sh, seed, ho, g);
     if (threadIdx.x >= 64) return;
     // No fences: the slots are only ever touched by device-scope read-modify-write atomics inside this launch, this block's
     // have been performed (their old values are back) before its tick, and the block whose tick is the last reads the slots
@@ -1237,15 +1240,11 @@ __global__ __launch_bounds__(64 * kAllWaves, kPartsMinWaves) void mesh_parts_all
 
 // the listed groups: grid x = slots (strided over the list), y = part
 template <bool WITH_RAY, int WAVES>
-__global__ __launch_bounds__(64 * WAVES, kPartsMinWaves) void mesh_parts_kernel(MeshArgs m, const int* __restrict__ order,
-                                                                      const float* __restrict__ W,
-                                                                      const float* __restrict__ pts, int64_t P,
-                                                                      uint64_t seed, int64_t index_base, HandOver ho) {
+__global__ __launch_bounds__(64 * WAVES, kPartsMinWaves) void mesh_parts_kernel(MeshArgs m, uint64_t seed, HandOver ho) {
     __shared__ __attribute__((aligned(16))) MeshShared<WAVES, WITH_RAY> sh;
     const int listed = min(*ho.count, ho.cap);
     for (int slot = blockIdx.x; slot < listed; slot += gridDim.x) {
-        parts_of_group<WITH_RAY, false, WAVES>(m, sh, order, W ? W + 16 * (int64_t)ho.entries[2 * slot + 1] : nullptr, pts, P, seed, index_base,
-                                 ho, slot, ho.entries[2 * slot]);
+        parts_of_group<WITH_RAY, false, WAVES>(m, sh, seed, ho, slot);
         __syncthreads();  // the slots in LDS are reused by the next listed group
     }
 }
@@ -1458,14 +1457,10 @@ static unsigned list_blocks(int cap) { return (unsigned)(cap < 512 ? (cap < 1 ? 
 
 // the parts launch over the listed (heavy) groups: x = slots (a block strides over the list), y = parts
 template <bool WITH_RAY>
-static void launch_heavy_parts(const MeshArgs& m, const int* order, const float* W, const float* points, int64_t P, uint64_t seed,
-                               int64_t index_base, const HandOver& ho, int ntiles, hipStream_t s) {
-    int parts = kHeavyParts, waves = 4;
-    unsigned xb = list_blocks(ho.cap);
-    if (parts > ntiles) parts = ntiles;
-    const dim3 grid(xb, (unsigned)parts);
-    if (waves == 2) hipLaunchKernelGGL((mesh_parts_kernel<WITH_RAY, 2>), grid, dim3(128), 0, s, m, order, W, points, P, seed, index_base, ho);
-    else hipLaunchKernelGGL((mesh_parts_kernel<WITH_RAY, 4>), grid, dim3(256), 0, s, m, order, W, points, P, seed, index_base, ho);
+static void launch_heavy_parts(const MeshArgs& m, uint64_t seed, const HandOver& ho, int ntiles, hipStream_t s) {
+    const int parts = kHeavyParts < ntiles ? kHeavyParts : ntiles;
+    const unsigned xb = list_blocks(ho.cap);
+    hipLaunchKernelGGL((mesh_parts_kernel<WITH_RAY, 4>), dim3(xb, (unsigned)parts), dim3(256), 0, s, m, seed, ho);
 }
 
 // sort_into != nullptr: the caller brings no order; one is worked out into sort_into (P <= kSmallPoints)
@@ -1485,7 +1480,6 @@ static int mesh_query_impl(const pvamd_mesh_t* mesh, const float* points, const 
     hipStream_t s = (hipStream_t)stream;
     const QueryOut out{out_closest, out_dist, out_grad, out_face, out_normal, out_packed};
     const int ntiles = (mesh->F + kTile - 1) / kTile;
-    
     const int cap = (int)PVAMD_MESH_SCRATCH_SLOTS(P);  // what PVAMD_MESH_SCRATCH_BYTES(P) holds
     const HandOver ho = hand_over(scratch, cap);
     const int slices = pick_slices(groups, ntiles, ho.cap > 0 && ntiles >= kHeavyMinTiles);
@@ -1498,8 +1492,8 @@ static int mesh_query_impl(const pvamd_mesh_t* mesh, const float* points, const 
     const int half_tiles = groups <= 64 ? 2 : (groups <= 256 ? 3 : (groups < 2048 ? 6 : (int)(groups / 256)));
     int parts = (2 * ntiles + half_tiles - 1) / half_tiles;
     if (parts > 65535) parts = 65535;  // gridDim.y (a mesh of more than 16.7 M triangles)
-    int aw = (int64_t)groups * parts * 4 > 100000 ? 2 : 4;
-    bool few = parts >= kMinParts;
+    const int aw = (int64_t)groups * parts * 4 > 100000 ? 2 : 4;
+    const bool few = parts >= kMinParts;
     const bool two_launches = ho.cap > 0 && groups <= ho.cap && few;
     if (sort_into) {
         order = sort_into;
@@ -1518,8 +1512,8 @@ static int mesh_query_impl(const pvamd_mesh_t* mesh, const float* points, const 
                                index_base, ho, (int)groups);
         const dim3 grid((unsigned)groups, (unsigned)parts);
         switch (aw) {
-            case 2: hipLaunchKernelGGL((mesh_parts_all_kernel<2>), grid, dim3(128), 0, s, m, order, points, P, jitter_seed, index_base, ho, out); break;
-            default: hipLaunchKernelGGL((mesh_parts_all_kernel<4>), grid, dim3(256), 0, s, m, order, points, P, jitter_seed, index_base, ho, out); break;
+            case 2: hipLaunchKernelGGL((mesh_parts_all_kernel<2>), grid, dim3(128), 0, s, m, order, points, P, jitter_seed, ho, out); break;
+            default: hipLaunchKernelGGL((mesh_parts_all_kernel<4>), grid, dim3(256), 0, s, m, order, points, P, jitter_seed, ho, out); break;
         }
         return (int)hipGetLastError();
     }
@@ -1533,7 +1527,7 @@ static int mesh_query_impl(const pvamd_mesh_t* mesh, const float* points, const 
         default: hipLaunchKernelGGL((mesh_query_kernel<1>), dim3((unsigned)groups), dim3(64), 0, s, m, order, points, P, jitter_seed, index_base, out, heavy ? ho : none); break;
     }
     if (heavy) {
-        launch_heavy_parts<true>(m, order, nullptr, points, P, jitter_seed, index_base, ho, ntiles, s);
+        launch_heavy_parts<true>(m, jitter_seed, ho, ntiles, s);
         hipLaunchKernelGGL(mesh_query_finish_kernel, dim3(list_blocks(ho.cap)), dim3(64), 0, s, m, order, points, P, ho, out);
     }
     return (int)hipGetLastError();
@@ -1602,7 +1596,7 @@ static int launch_chamfer_mesh(const pvamd_mesh_t* mesh, const float* W, int32_t
         }
     }
     if (ho.cap > 0) {
-        launch_heavy_parts<false>(m, order, W, points, N, 0, 0, ho, ntiles, s);
+        launch_heavy_parts<false>(m, 0, ho, ntiles, s);
         hipLaunchKernelGGL(chamfer_finish_kernel, dim3(list_blocks(ho.cap)), dim3(64), 0, s, m, order, W, points, N, scale, ho, out_sum, per);
     }
     return (int)hipGetLastError();

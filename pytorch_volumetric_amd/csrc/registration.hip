@@ -20,10 +20,13 @@ constexpr int kRegK = PVAMD_REG_CHUNK / kRegBlock;  // points per lane per chunk
 static_assert(kRegK * kRegBlock == PVAMD_REG_CHUNK, "whole lanes per chunk");
 constexpr int kRegSums = PVAMD_REG_SUMS;  // 1 + 6 + 21
 
-// slab: double [nchunks][B][28], then int64 [nchunks][B]
+// slab: double [nchunks][B][28], then int64 [nchunks][B].  The kernel does not read nchunks (the grid's x is the chunk); the
+// argument stays: without it (one s_load narrower, other scalar registers) the nearest form ran 20.29 us against 20.15 at 64 x 16,384
+// and 170.48 against 170.34 at 1 x 2^20, where a second build of the same source stood 0.02 and 0.01 us away
+// (profiles/argument_prune.md).  Measured with ROCm 7.2 (clang 22) only: time it again after a compiler change
 template <bool INTERP>
 __global__ __launch_bounds__(kRegBlock) void reg_partial_kernel(const pvamd_grid_t g, const float* __restrict__ W, int B,
-                                                                const float* __restrict__ pts, int64_t N, int64_t nchunks,
+                                                                const float* __restrict__ pts, int64_t N, int64_t /*nchunks*/,
                                                                 double* __restrict__ slab, int64_t* __restrict__ slab_count) {
     __shared__ double ws[kRegBlock / 64][kRegSums];
     __shared__ int wc[kRegBlock / 64];

@@ -2,6 +2,8 @@
 # Build a variant of libpvamd for A/B timing or instrumentation.  A variant is one source file -- an edited copy, or the product
 # source with a patch from tools/patches/ applied -- plus optional flags; every other object is the product's:
 #   tools/build_variant.sh NAME SRC.hip [FLAGS...]     SRC's basename (mesh.hip, composed_x.hip, ...) says which object it replaces
+# Unused parameters are errors, as in csrc/Makefile; a source from before that rule (an older commit's file as the `parent` of an
+# A/B run) builds with -Wno-error=unused-parameter among FLAGS.
 # -> tools/variants/libpvamd_NAME.so ; run a tool against it with PVAMD_LIB=tools/variants/libpvamd_NAME.so
 set -e
 name=$1; src=$2; shift 2
@@ -16,7 +18,7 @@ for o in $C/*.o; do
 done
 [ -n "$which" ] || { echo "$src: no object of csrc/Makefile to replace" >&2; exit 1; }
 extra=""; { [ "$which" = composed ] || [ "$which" = mesh ]; } && extra="-fno-slp-vectorize"   # as csrc/Makefile (FLAGS_*)
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -fno-fast-math -ffp-contract=off -Wno-unused-value -I$C -Iinclude $extra "-DPVAMD_VARIANT=\"$name: $*\"" "$@" -c "$src" -o tools/variants/${which}_$name.o
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -fno-fast-math -ffp-contract=off -Wno-unused-value -Werror=unused-parameter -I$C -Iinclude $extra "-DPVAMD_VARIANT=\"$name: $*\"" "$@" -c "$src" -o tools/variants/${which}_$name.o
 objs=""
 for o in $C/*.o; do   # every object the Makefile built, except the one being replaced
   [ "$(basename $o .o)" = "$which" ] || objs="$objs $o"
