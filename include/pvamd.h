@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define PVAMD_ABI_VERSION 13
+#define PVAMD_ABI_VERSION 14
 
 #define PVAMD_E_NULL      (-1)  /* a required pointer is NULL            */
 #define PVAMD_E_SHAPE     (-2)  /* a size/shape argument is out of range */
@@ -118,6 +118,8 @@ typedef struct pvamd_grid {
 #define PVAMD_TRI_GROUP 16   /* triangles per group sphere */
 #define PVAMD_REC_FLOATS(F) ((((F) + PVAMD_TRI_TILE - 1) / PVAMD_TRI_TILE) * PVAMD_TRI_TILE * PVAMD_TRI_REC)
 #define PVAMD_TILES_FLOATS(F) ((((F) + PVAMD_TRI_TILE - 1) / PVAMD_TRI_TILE) * (4 + 4 * (PVAMD_TRI_TILE / PVAMD_TRI_GROUP)))
+int64_t pvamd_mesh_rec_floats(int32_t F);    /* PVAMD_REC_FLOATS(F) */
+int64_t pvamd_mesh_tiles_floats(int32_t F);  /* PVAMD_TILES_FLOATS(F) */
 typedef struct pvamd_mesh {
     const float* normal;     /* device */
     const float* rec;        /* device */
@@ -333,19 +335,18 @@ int pvamd_morton_keys(const float* points, int64_t P, const float* box, int32_t*
  * a wave are 25 % closer together than along the Z curve.  Points of one cell come out in an arbitrary, run-dependent
  * order -- the kernels that take an `order` return the same bits for any order.
  * order_out: device [P] int32.  inv_out: device [P] int32 or NULL, inv[order[k]] = k.  sorted_points_out: device [P][3] or
- * NULL, the points in that order.  scratch: device, PVAMD_MORTON_ORDER_SCRATCH_BYTES(P) bytes, 4-byte aligned.          */
+ * NULL, the points in that order.  scratch: device, pvamd_morton_order_scratch_bytes(P) bytes, 4-byte aligned (required for
+ * any P, though one launch uses none).                                                                                 */
 #define PVAMD_MORTON_ORDER_BITS(P) ((P) >= (1 << 20) ? 21 : ((P) >= (1 << 16) ? 18 : 15))
 /* from 786,432 points on: (cell, index) pairs through a stable LSD radix sort (three 7-bit passes over 4096-pair tiles;
- * csrc/sort.hip) -- the points of a cell come out in index order.  Scratch: bounds codes, supergroup totals and the tile
- * histogram table (<= 512 words per tile), two key and two index arrays.                                             */
+ * csrc/sort.hip) -- the points of a cell come out in index order.                                                    */
 #ifndef PVAMD_ORDER_RADIX_SORT_FROM
 #define PVAMD_ORDER_RADIX_SORT_FROM (3 << 18)  /* 786,432: counting sort 0.078 ms at 512 k, 0.166 at 1 M; radix 0.097 / 0.105 (profiles/r05_sort.txt) */
 #endif
-/* enough for EITHER sort, so that the size does not depend on the threshold a library was built with */
-#define PVAMD_MORTON_RADIX_SCRATCH_BYTES(P) (4 * (8 + 4 * (int64_t)(P) + 512 * (((int64_t)(P) + 4095) / 4096)))
-#define PVAMD_MORTON_COUNTING_SCRATCH_BYTES(P) (4 * (8 + (1 << PVAMD_MORTON_ORDER_BITS(P)) + (int64_t)(P) + 2048))
-#define PVAMD_MORTON_ORDER_SCRATCH_BYTES(P) (PVAMD_MORTON_RADIX_SCRATCH_BYTES(P) > PVAMD_MORTON_COUNTING_SCRATCH_BYTES(P) \
-    ? PVAMD_MORTON_RADIX_SCRATCH_BYTES(P) : PVAMD_MORTON_COUNTING_SCRATCH_BYTES(P))
+/* The larger of the two sorts' layouts (counting: bounds codes, cell counters, keys, block sums of the scan; radix: bounds
+ * codes, supergroup totals, tile histograms, two key and two index arrays), so that the size does not depend on the threshold
+ * a library was built with.  Host-only.                                                                                */
+int64_t pvamd_morton_order_scratch_bytes(int64_t P);
 int pvamd_morton_order(const float* points, int64_t P, int32_t* order_out, int32_t* inv_out, float* sorted_points_out,
                        void* scratch, void* stream);
 
@@ -368,7 +369,11 @@ int pvamd_morton_order(const float* points, int64_t P, int32_t* order_out, int32
 #define PVAMD_MESH_SCRATCH_SLOTS(P) ((((P) + 63) / 64) < PVAMD_MESH_SCRATCH_GROUPS ? (((P) + 63) / 64) : \
                                      ((((P) + 63) / 64) / 8 > PVAMD_MESH_SCRATCH_GROUPS ? (((P) + 63) / 64) / 8 : PVAMD_MESH_SCRATCH_GROUPS))
 #define PVAMD_MESH_SMALL_POINTS 16384  /* pvamd_mesh_query_unordered: at most this many points */
+/* what pvamd_mesh_scratch_bytes returns (csrc/mesh.hip asserts it against the layout it carves): a header, 8 + 64 * 40 + 64
+ * bytes per slot, 24 bytes per point of an unordered query */
 #define PVAMD_MESH_SCRATCH_BYTES(P) (64 + PVAMD_MESH_SCRATCH_SLOTS(P) * (int64_t)(64 * 40 + 8 + 64) + 24 * PVAMD_MESH_SMALL_POINTS)
+int64_t pvamd_mesh_scratch_bytes(int64_t P);
+int64_t pvamd_mesh_small_points(void);  /* PVAMD_MESH_SMALL_POINTS */
 int pvamd_mesh_query(const pvamd_mesh_t* mesh, const float* points, const int32_t* order, int64_t P,
                      uint64_t jitter_seed, int64_t index_base, float* out_closest, float* out_dist, float* out_grad, int32_t* out_face,
                      float* out_normal, void* scratch, void* stream);
@@ -574,6 +579,7 @@ int pvamd_composed_query_interp_backward_f64(const pvamd_grid_t* grids, int32_t 
     (16 * (int64_t)(A) * ((per_leaf) ? (int64_t)(S) : 1) * (((int64_t)(P) + PVAMD_MOP_CHUNK - 1) / PVAMD_MOP_CHUNK))
 #define PVAMD_MIN_OVER_POINTS_BACKWARD_SCRATCH_BYTES(S, A, per_leaf) (24 * (int64_t)(A) * ((per_leaf) ? (int64_t)(S) : 1))
 int64_t pvamd_min_over_points_scratch_bytes(int32_t S, int32_t A, int64_t P, int32_t per_leaf);
+int64_t pvamd_min_over_points_backward_scratch_bytes(int32_t S, int32_t A, int32_t per_leaf);
 int pvamd_composed_min_over_points(const pvamd_grid_t* grids, int32_t S, const float* tf, int32_t A, const float* points, int64_t P,
                                    int32_t mode, int32_t per_leaf, float* out_val, float* out_grad, int64_t* out_index,
                                    int32_t* out_leaf, void* scratch, void* stream);

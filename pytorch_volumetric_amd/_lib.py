@@ -12,7 +12,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PVAMD_LIB") or os.path.join(_HERE, "csrc", "libpvamd.so")  # PVAMD_LIB: A/B builds (tools/)
 
-ABI_VERSION = 13
+ABI_VERSION = 14
 OOB_LOOKUP_GT_SDF = 0
 OOB_BOUNDING_BOX = 1
 COMPOSED_INLINE_EXACT = 1
@@ -29,41 +29,36 @@ LEAF_MODES = {"nearest": 0, "trilinear": 1}  # PVAMD_LEAF_NEAREST / PVAMD_LEAF_T
 MOP_CHUNK = 4096  # PVAMD_MOP_CHUNK
 REG_CHUNK = 2048  # PVAMD_REG_CHUNK
 REG_SUMS = 28     # PVAMD_REG_SUMS: the row length of pvamd_chamfer_normal_eq's out_sums
-TRI_REC = 24
-TRI_TILE = 256
-TRI_GROUP = 16
 
 
-def rec_floats(F):
-    """PVAMD_REC_FLOATS(F): records are stored in whole tiles."""
-    return ((F + TRI_TILE - 1) // TRI_TILE) * TRI_TILE * TRI_REC
-
-
-def tiles_floats(F):
-    """PVAMD_TILES_FLOATS(F): tile spheres followed by group spheres."""
-    return ((F + TRI_TILE - 1) // TRI_TILE) * (4 + 4 * (TRI_TILE // TRI_GROUP))
-
-
-MESH_SCRATCH_GROUPS = 8192
-MESH_SMALL_POINTS = 16384  # PVAMD_MESH_SMALL_POINTS
-
-
-def mesh_scratch_slots(P):
-    """PVAMD_MESH_SCRATCH_SLOTS(P)"""
-    groups = (P + 63) // 64
-    return groups if groups < MESH_SCRATCH_GROUPS else max(groups // 8, MESH_SCRATCH_GROUPS)
-
-
-def mesh_scratch_bytes(P):
-    """PVAMD_MESH_SCRATCH_BYTES(P)"""
-    return 64 + mesh_scratch_slots(P) * (64 * 40 + 8 + 64) + 24 * MESH_SMALL_POINTS
-
-
-
-# The scratch of the fused reductions and their backwards: the library's exported size functions are the definition
-# (include/pvamd.h) -- what they report is what the launch code carves.  Nothing here restates their arithmetic.  A size
-# depends on the arguments only, and an optimiser loop asks for the same few: remembered, it costs less than the ctypes call.
+# Buffer sizes: the library's exported size functions are the definition (include/pvamd.h) -- what they report is what the
+# launch code carves.  Nothing here restates their arithmetic.  A size depends on the arguments only, and an optimiser loop
+# asks for the same few: remembered, it costs less than the ctypes call.
 _remembered = functools.lru_cache(maxsize=64)
+
+
+@_remembered
+def rec_floats(F):
+    """pvamd_mesh_rec_floats: records are stored in whole tiles."""
+    return load().pvamd_mesh_rec_floats(F)
+
+
+@_remembered
+def tiles_floats(F):
+    """pvamd_mesh_tiles_floats: tile spheres followed by group spheres."""
+    return load().pvamd_mesh_tiles_floats(F)
+
+
+@_remembered
+def mesh_scratch_bytes(P):
+    """pvamd_mesh_scratch_bytes: the slots of the point groups a mesh query hands over, then the by-point part of an unordered one."""
+    return load().pvamd_mesh_scratch_bytes(P)
+
+
+@_remembered
+def morton_order_scratch_bytes(P):
+    """pvamd_morton_order_scratch_bytes: enough for either sort, whichever the library was built to pick at P."""
+    return load().pvamd_morton_order_scratch_bytes(P)
 
 
 @_remembered
@@ -72,9 +67,10 @@ def min_over_points_scratch_bytes(S, A, P, per_leaf):
     return load().pvamd_min_over_points_scratch_bytes(S, A, P, int(per_leaf))
 
 
+@_remembered
 def min_over_points_backward_scratch_bytes(S, A, per_leaf):
-    """PVAMD_MIN_OVER_POINTS_BACKWARD_SCRATCH_BYTES(S, A, per_leaf): a header macro only, the library exports no function"""
-    return 24 * A * (S if per_leaf else 1)
+    """pvamd_min_over_points_backward_scratch_bytes: three values per pair, sized for float64."""
+    return load().pvamd_min_over_points_backward_scratch_bytes(S, A, int(per_leaf))
 
 
 @_remembered
@@ -229,6 +225,11 @@ SIGNATURES = {
                                          ctypes.c_void_p]),
     "pvamd_morton_order": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "pvamd_morton_order_scratch_bytes": (ctypes.c_int64, [ctypes.c_int64]),
+    "pvamd_mesh_rec_floats": (ctypes.c_int64, [ctypes.c_int32]),
+    "pvamd_mesh_tiles_floats": (ctypes.c_int64, [ctypes.c_int32]),
+    "pvamd_mesh_small_points": (ctypes.c_int64, []),
+    "pvamd_mesh_scratch_bytes": (ctypes.c_int64, [ctypes.c_int64]),
     "pvamd_mesh_prepare": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_float,
                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "pvamd_mesh_query": (ctypes.c_int, [ctypes.POINTER(MeshDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
@@ -287,6 +288,7 @@ SIGNATURES = {
     "pvamd_composed_query_interp_backward_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     # ComposedSDF.min_over_points (include/pvamd.h "Minimum over points")
     "pvamd_min_over_points_scratch_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32]),
+    "pvamd_min_over_points_backward_scratch_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
     "pvamd_composed_min_over_points": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "pvamd_composed_min_over_points_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "pvamd_composed_min_over_points_backward": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
@@ -480,6 +482,7 @@ def as_query_points(points, device=None, keep_f64=False):
 
 
 _group_chunk = None
+_mesh_small = None
 
 
 def group_chunk_points():
@@ -490,22 +493,21 @@ def group_chunk_points():
     return _group_chunk
 
 
+def mesh_small_points():
+    """The most points pvamd_mesh_query_unordered takes (a build constant of the library)."""
+    global _mesh_small
+    if _mesh_small is None:
+        _mesh_small = int(load().pvamd_mesh_small_points())
+    return _mesh_small
+
+
 def group_points(flat):
     """pvamd_group_points over contiguous fp32 (P, 3) GPU points: the scratch (uint8 tensor) pvamd_composed_query_grouped reads."""
     lib = load()
     P = flat.shape[0]
-    scratch = torch.empty((int(lib.pvamd_group_scratch_bytes(P)),), dtype=torch.uint8, device=flat.device)
+    scratch = scratch_buffer(int(lib.pvamd_group_scratch_bytes(P)), flat.device)
     check(lib.pvamd_group_points(ptr(flat), P, ptr(scratch), stream_ptr()), "pvamd_group_points")
     return scratch
-
-def morton_order_scratch_words(P):
-    """PVAMD_MORTON_ORDER_SCRATCH_BYTES(P) / 4"""
-    # The library picks the sort by a compile-time threshold the binding cannot see in an A/B build (ADVICE r5: an env override
-    # here let Python size the counting sort's scratch while the C side ran the radix sort past it): size for whichever needs
-    # more.  Radix: supergroup totals + tile histograms (<= 512 words per 4096-pair tile), 2 key + 2 index arrays.
-    radix = 8 + 4 * P + 512 * ((P + 4095) // 4096)
-    counting = 8 + (1 << (21 if P >= (1 << 20) else (18 if P >= (1 << 16) else 15))) + P + 2048
-    return max(radix, counting)
 
 
 def morton_order(points, min_points=2048, want_inverse=False, want_sorted=False):
@@ -520,7 +522,7 @@ def morton_order(points, min_points=2048, want_inverse=False, want_sorted=False)
     order = torch.empty((P,), dtype=torch.int32, device=dev)
     inv = torch.empty((P,), dtype=torch.int32, device=dev) if want_inverse else None
     spts = torch.empty((P, 3), dtype=torch.float32, device=dev) if want_sorted else None
-    scratch = torch.empty((morton_order_scratch_words(P),), dtype=torch.int32, device=dev)
+    scratch = scratch_buffer(morton_order_scratch_bytes(P), dev)
     check(load().pvamd_morton_order(ptr(points), P, ptr(order), ptr(inv), ptr(spts), ptr(scratch), stream_ptr()),
           "pvamd_morton_order")
     return (order, inv, spts) if (want_inverse or want_sorted) else order

@@ -115,14 +115,14 @@ def chamfer_partial_sums(W, points, obj_factory, obj_sdf, scale):
                                                           _lib.stream_ptr()), "pvamd_transform_points")
                 flat = x.view(-1, 3)
                 order = _lib.morton_order(flat)
-                scratch = torch.empty((_lib.mesh_scratch_bytes(B * N) // 8,), dtype=torch.int64, device=dev)
+                scratch = _lib.scratch_buffer(_lib.mesh_scratch_bytes(B * N), dev)
                 _lib.check(lib.pvamd_chamfer_mesh_flat(ctypes.byref(desc), B, _lib.ptr(flat), _lib.ptr(order), N, float(scale),
                                                        _lib.ptr(sums), _lib.ptr(scratch), _lib.stream_ptr()),
                            "pvamd_chamfer_mesh_flat")
             else:
                 order = _lib.morton_order(pts)
                 # slots for the point groups the kernel hands over (those about equidistant to much of the mesh)
-                scratch = torch.empty((_lib.mesh_scratch_bytes(N) // 8,), dtype=torch.int64, device=dev)
+                scratch = _lib.scratch_buffer(_lib.mesh_scratch_bytes(N), dev)
                 _lib.check(lib.pvamd_chamfer_mesh(ctypes.byref(desc), _lib.ptr(Wd), B, _lib.ptr(pts), _lib.ptr(order), N,
                                                   float(scale), _lib.ptr(sums), _lib.ptr(scratch), _lib.stream_ptr()),
                            "pvamd_chamfer_mesh")

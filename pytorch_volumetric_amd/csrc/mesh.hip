@@ -710,21 +710,49 @@ struct HandOver {
 constexpr int kBoundFloats = 16;
 constexpr int kSmallPoints = PVAMD_MESH_SMALL_POINTS;
 constexpr int kHandOverHeader = 64;  // bytes
-static __host__ __device__ inline HandOver hand_over(void* scratch, int cap) {
-    HandOver h;
+// The scratch of the mesh entry points, in bytes: pvamd_mesh_scratch_bytes reports `bytes`, hand_over() carves at the same
+// offsets.  Each field starts where the one before it ends.
+struct HandOverLayout {
+    size_t entries, best, hits, dir, reach, bound, pts;  // by slot
+    size_t p_best, p_dir, p_reach;                       // by point index
+    size_t bytes;
+};
+constexpr HandOverLayout hand_over_layout(int64_t cap) {
+    const size_t slots = (size_t)cap, lanes = slots * 64, small = (size_t)kSmallPoints;
+    HandOverLayout l = {};
+    l.entries = kHandOverHeader;
+    l.best = l.entries + slots * 2 * sizeof(int);
+    l.hits = l.best + lanes * sizeof(unsigned long long);
+    l.dir = l.hits + lanes * sizeof(int);
+    l.reach = l.dir + lanes * 3 * sizeof(float);
+    l.bound = l.reach + lanes * sizeof(float);
+    l.pts = l.bound + slots * kBoundFloats * sizeof(float);
+    l.p_best = l.pts + lanes * 3 * sizeof(float);
+    l.p_dir = l.p_best + small * sizeof(unsigned long long);
+    l.p_reach = l.p_dir + small * 3 * sizeof(float);
+    l.bytes = l.p_reach + small * sizeof(float);
+    return l;
+}
+// both sides are linear in the slots: equal for none and for one, they are equal for any number
+static_assert(hand_over_layout(PVAMD_MESH_SCRATCH_SLOTS(0)).bytes == PVAMD_MESH_SCRATCH_BYTES(0) &&
+              hand_over_layout(PVAMD_MESH_SCRATCH_SLOTS(1)).bytes == PVAMD_MESH_SCRATCH_BYTES(1),
+              "PVAMD_MESH_SCRATCH_BYTES is not the hand-over layout's total");
+
+static HandOver hand_over(void* scratch, int cap) {
+    const HandOverLayout l = hand_over_layout(cap);
     char* base = reinterpret_cast<char*>(scratch);
+    HandOver h;
     h.count = reinterpret_cast<int*>(base);
-    h.entries = reinterpret_cast<int*>(base + kHandOverHeader);
-    h.best = reinterpret_cast<unsigned long long*>(base + kHandOverHeader + (size_t)cap * 8);
-    h.hits = reinterpret_cast<int*>(base + kHandOverHeader + (size_t)cap * 8 + (size_t)cap * 64 * 8);
-    h.dir = reinterpret_cast<float*>(base + kHandOverHeader + (size_t)cap * 8 + (size_t)cap * 64 * 12);
-    h.reach = reinterpret_cast<float*>(base + kHandOverHeader + (size_t)cap * 8 + (size_t)cap * 64 * 24);
-    h.bound = reinterpret_cast<float*>(base + kHandOverHeader + (size_t)cap * 8 + (size_t)cap * 64 * 28);
-    h.pts = reinterpret_cast<float*>(base + kHandOverHeader + (size_t)cap * 8 + (size_t)cap * 64 * 28 + (size_t)cap * 64);
-    char* tail = base + kHandOverHeader + (size_t)cap * (8 + 64 * 40 + 64);
-    h.p_best = reinterpret_cast<unsigned long long*>(tail);
-    h.p_dir = reinterpret_cast<float*>(tail + (size_t)kSmallPoints * 8);
-    h.p_reach = reinterpret_cast<float*>(tail + (size_t)kSmallPoints * 20);
+    h.entries = reinterpret_cast<int*>(base + l.entries);
+    h.best = reinterpret_cast<unsigned long long*>(base + l.best);
+    h.hits = reinterpret_cast<int*>(base + l.hits);
+    h.dir = reinterpret_cast<float*>(base + l.dir);
+    h.reach = reinterpret_cast<float*>(base + l.reach);
+    h.bound = reinterpret_cast<float*>(base + l.bound);
+    h.pts = reinterpret_cast<float*>(base + l.pts);
+    h.p_best = reinterpret_cast<unsigned long long*>(base + l.p_best);
+    h.p_dir = reinterpret_cast<float*>(base + l.p_dir);
+    h.p_reach = reinterpret_cast<float*>(base + l.p_reach);
     h.cap = scratch ? cap : 0;
     return h;
 }
@@ -1438,6 +1466,13 @@ extern "C" int pvamd_morton_keys(const float* points, int64_t P, const float* bo
     return (int)hipGetLastError();
 }
 
+extern "C" int64_t pvamd_mesh_rec_floats(int32_t F) { return F < 0 ? 0 : PVAMD_REC_FLOATS((int64_t)F); }
+extern "C" int64_t pvamd_mesh_tiles_floats(int32_t F) { return F < 0 ? 0 : PVAMD_TILES_FLOATS((int64_t)F); }
+extern "C" int64_t pvamd_mesh_small_points(void) { return kSmallPoints; }
+extern "C" int64_t pvamd_mesh_scratch_bytes(int64_t P) {
+    return P < 0 ? 0 : (int64_t)hand_over_layout(PVAMD_MESH_SCRATCH_SLOTS(P)).bytes;
+}
+
 extern "C" int pvamd_mesh_prepare(const float* tri, const int32_t* face_id, int32_t F, float abs_margin, float* rec_out,
                                   float* tiles_out, int32_t* rec_of_face_out, void* stream) {
     if (F < 0) return PVAMD_E_SHAPE;
@@ -1480,7 +1515,7 @@ static int mesh_query_impl(const pvamd_mesh_t* mesh, const float* points, const 
     hipStream_t s = (hipStream_t)stream;
     const QueryOut out{out_closest, out_dist, out_grad, out_face, out_normal, out_packed};
     const int ntiles = (mesh->F + kTile - 1) / kTile;
-    const int cap = (int)PVAMD_MESH_SCRATCH_SLOTS(P);  // what PVAMD_MESH_SCRATCH_BYTES(P) holds
+    const int cap = (int)PVAMD_MESH_SCRATCH_SLOTS(P);  // what pvamd_mesh_scratch_bytes(P) holds
     const HandOver ho = hand_over(scratch, cap);
     const int slices = pick_slices(groups, ntiles, ho.cap > 0 && ntiles >= kHeavyMinTiles);
     // few point groups, many tiles: spread each group's tiles over `parts` blocks of `aw` waves (see mesh_parts_kernel)

@@ -269,6 +269,13 @@ extern "C" int64_t pvamd_min_over_points_scratch_bytes(int32_t S, int32_t A, int
     return PVAMD_MIN_OVER_POINTS_SCRATCH_BYTES(S, A, P, per_leaf);
 }
 
+// the backward's dp_pair: three values of either element size per pair
+static_assert(PVAMD_MIN_OVER_POINTS_BACKWARD_SCRATCH_BYTES(1, 1, 0) == 3 * sizeof(double), "dp_pair holds [pairs][3] doubles");
+extern "C" int64_t pvamd_min_over_points_backward_scratch_bytes(int32_t S, int32_t A, int32_t per_leaf) {
+    if (S < 0 || A < 0) return 0;
+    return PVAMD_MIN_OVER_POINTS_BACKWARD_SCRATCH_BYTES(S, A, per_leaf);
+}
+
 extern "C" int pvamd_composed_min_over_points(const pvamd_grid_t* grids, int32_t S, const float* tf, int32_t A, const float* points,
                                               int64_t P, int32_t mode, int32_t per_leaf, float* out_val, float* out_grad,
                                               int64_t* out_index, int32_t* out_leaf, void* scratch, void* stream) {

@@ -17,9 +17,26 @@
 
 namespace pvamd {
 
-// scratch layout (uint32 words): [0..5] bounds codes, [8 .. 8 + cells) cell counters / offsets, then P keys, then
-// cells / 1024 block sums of the scan
+// The scratch of both sorts starts with the bounds codes ([0..5] of kBoxWords uint32 words).
 constexpr int kBoxWords = 8;
+constexpr int kMaxBlockSums = (1 << PVAMD_MORTON_ORDER_BITS(1ll << 40)) / 1024;  // one per 1024 cells (order_blocksum_kernel), at the most cells
+
+// The counting sort's scratch in uint32 words: pvamd_morton_order_scratch_bytes reports `words`, pvamd_morton_order carves at
+// the same offsets (its count and scatter kernels find the keys behind the cells themselves).
+struct CountingLayout {
+    int64_t cells;     // [1 << bits] cell counters, then offsets
+    int64_t keys;      // [P]
+    int64_t blocksum;  // [kMaxBlockSums] block sums of the scan, whatever the number of cells
+    int64_t words;
+};
+static CountingLayout counting_layout(int64_t P) {
+    CountingLayout l;
+    l.cells = kBoxWords;
+    l.keys = l.cells + (1ll << PVAMD_MORTON_ORDER_BITS(P));
+    l.blocksum = l.keys + P;
+    l.words = l.blocksum + kMaxBlockSums;
+    return l;
+}
 
 __global__ __launch_bounds__(256) void order_init_kernel(unsigned* __restrict__ scratch, int cells) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -173,6 +190,33 @@ constexpr int kRadixRounds = 16;                          // keys per thread
 constexpr int kRadixTile = kRadixThreads * kRadixRounds;  // 4096 pairs per block
 constexpr int kRadixMaxPasses = 3;
 static_assert(PVAMD_MORTON_ORDER_BITS(1ll << 40) <= kRadixBits * kRadixMaxPasses, "more key bits than radix passes");
+
+// The radix sort's scratch in uint32 words, behind the bounds codes: pvamd_morton_order_scratch_bytes reports `words`,
+// pvamd_morton_order carves at the same offsets.
+struct RadixLayout {
+    int64_t tiles;
+    int G, nsg;        // tiles per supergroup (~sqrt(tiles)), supergroups
+    int64_t sgtotal;   // [kRadixMaxPasses][nsg][kRadixBins] supergroup totals
+    int64_t table;     // [tiles][kRadixBins] tile histograms
+    int64_t keys[2];   // [P] each
+    int64_t index[2];  // [P] each
+    int64_t words;
+};
+static RadixLayout radix_layout(int64_t P) {
+    RadixLayout l;
+    l.tiles = (P + kRadixTile - 1) / kRadixTile;
+    l.G = 1;
+    while ((int64_t)l.G * l.G < l.tiles) ++l.G;
+    l.nsg = (int)((l.tiles + l.G - 1) / l.G);
+    l.sgtotal = kBoxWords;
+    l.table = l.sgtotal + (int64_t)kRadixMaxPasses * l.nsg * kRadixBins;
+    l.keys[0] = l.table + l.tiles * kRadixBins;
+    l.keys[1] = l.keys[0] + P;
+    l.index[0] = l.keys[1] + P;
+    l.index[1] = l.index[0] + P;
+    l.words = l.index[1] + P;
+    return l;
+}
 
 // table[tile][digit] and the supergroup totals from this block's LDS histogram
 PVAMD_DEV void radix_publish_histogram(const unsigned* hist, unsigned* __restrict__ table, unsigned* __restrict__ sgtotal, int G) {
@@ -360,6 +404,14 @@ __global__ __launch_bounds__(1024) void order_small_kernel(const float* __restri
 
 using namespace pvamd;
 
+// Enough for EITHER sort, so that the size does not depend on the threshold a library was built with.  (A single launch, up
+// to 16,384 points, uses none: the counting sort's size is reported there all the same.)
+extern "C" int64_t pvamd_morton_order_scratch_bytes(int64_t P) {
+    if (P < 0 || P > 0x7fffffffLL) return 0;  // what pvamd_morton_order refuses
+    const int64_t counting = counting_layout(P).words, radix = radix_layout(P).words;
+    return (int64_t)sizeof(unsigned) * (radix > counting ? radix : counting);
+}
+
 extern "C" int pvamd_morton_order(const float* points, int64_t P, int32_t* order_out, int32_t* inv_out,
                                   float* sorted_points_out, void* scratch, void* stream) {
     if (P < 0 || P > 0x7fffffffLL) return PVAMD_E_SHAPE;
@@ -373,20 +425,16 @@ extern "C" int pvamd_morton_order(const float* points, int64_t P, int32_t* order
     }
     unsigned* w = reinterpret_cast<unsigned*>(scratch);
     if (P >= PVAMD_ORDER_RADIX_SORT_FROM) {
-        // scratch (words): [8] bounds codes | supergroup totals [3][nsg][128] | table [tiles][128] | keys A [P] | keys B [P] |
-        // index A [P] | index B [P]
-        const int64_t want = (P + 255) / 256;
-        const int64_t tiles = (P + kRadixTile - 1) / kRadixTile;
-        int G = 1;
-        while ((int64_t)G * G < tiles) ++G;  // ~sqrt(tiles) tiles per supergroup
-        const int nsg = (int)((tiles + G - 1) / G);
+        const RadixLayout l = radix_layout(P);
+        const int64_t want = (P + 255) / 256, tiles = l.tiles;
+        const int G = l.G, nsg = l.nsg;
         const int bits = PVAMD_MORTON_ORDER_BITS(P);
         const int passes = (bits + kRadixBits - 1) / kRadixBits;
-        unsigned* sgtotal = w + kBoxWords;
-        unsigned* table = sgtotal + (int64_t)kRadixMaxPasses * nsg * kRadixBins;
-        unsigned* keys[2] = {table + tiles * kRadixBins, table + tiles * kRadixBins + P};
-        int* index[2] = {reinterpret_cast<int*>(keys[1] + P), reinterpret_cast<int*>(keys[1] + 2 * P)};
-        const int zero_words = kRadixMaxPasses * nsg * kRadixBins;
+        unsigned* sgtotal = w + l.sgtotal;
+        unsigned* table = w + l.table;
+        unsigned* keys[2] = {w + l.keys[0], w + l.keys[1]};
+        int* index[2] = {reinterpret_cast<int*>(w + l.index[0]), reinterpret_cast<int*>(w + l.index[1])};
+        const int zero_words = (int)(l.table - l.sgtotal);  // the supergroup totals of every pass
         hipLaunchKernelGGL(order_init_kernel, dim3((zero_words + 255) / 256), dim3(256), 0, s, w, zero_words);
         hipLaunchKernelGGL(order_bounds_kernel, dim3(want < 512 ? (unsigned)want : 512u), dim3(256), 0, s, points, P, w);  // (2048 blocks: 30-52 us for 2 M points against 20 -- they all reach their six atomics at once)
         for (int p = 0; p < passes; ++p) {
@@ -415,6 +463,7 @@ extern "C" int pvamd_morton_order(const float* points, int64_t P, int32_t* order
             hipLaunchKernelGGL(order_gather_kernel, dim3((unsigned)want), dim3(256), 0, s, points, P, order_out, inv_out, sorted_points_out);
         return (int)hipGetLastError();
     }
+    const CountingLayout l = counting_layout(P);
     const int bits = PVAMD_MORTON_ORDER_BITS(P), shift = 30 - bits, cells = 1 << bits;
     hipLaunchKernelGGL(order_init_kernel, dim3((cells + 255) / 256), dim3(256), 0, s, w, cells);
     const int64_t want = (P + 255) / 256;
@@ -422,11 +471,11 @@ extern "C" int pvamd_morton_order(const float* points, int64_t P, int32_t* order
     hipLaunchKernelGGL(order_count_kernel, dim3((unsigned)want), dim3(256), 0, s, points, P, w, shift);
     {   // exclusive scan of the cell counters: block sums, scan of the <= 2048 block sums, per-block scan.  (One block
         // walking 32 consecutive counters per thread took 51 us for 32768 cells: serial, uncoalesced.)
-        unsigned* blocksum = w + kBoxWords + cells + P;
+        unsigned* blocksum = w + l.blocksum;
         const int nblocks = cells / 1024;
-        hipLaunchKernelGGL(order_blocksum_kernel, dim3(nblocks), dim3(1024), 0, s, w + kBoxWords, blocksum);
+        hipLaunchKernelGGL(order_blocksum_kernel, dim3(nblocks), dim3(1024), 0, s, w + l.cells, blocksum);
         hipLaunchKernelGGL(order_scan_kernel, dim3(1), dim3(1024), 0, s, blocksum, nblocks < 1024 ? 1024 : nblocks);
-        hipLaunchKernelGGL(order_blockscan_kernel, dim3(nblocks), dim3(1024), 0, s, w + kBoxWords, blocksum);
+        hipLaunchKernelGGL(order_blockscan_kernel, dim3(nblocks), dim3(1024), 0, s, w + l.cells, blocksum);
     }
     hipLaunchKernelGGL(order_scatter_kernel, dim3((unsigned)want), dim3(256), 0, s, points, P, w, shift, order_out, inv_out,
                        sorted_points_out);

@@ -286,8 +286,8 @@ class ObjectFactory(abc.ABC):
             if P > 0 and getattr(self, "tile_split", True):
                 # lets the kernel spread a point group's tiles over several workgroups (every group of a small query, the
                 # heavy groups of a large one)
-                scratch = torch.empty((_lib.mesh_scratch_bytes(P) // 8,), dtype=torch.int64, device=dev)
-            if order is None and 0 < P <= _lib.MESH_SMALL_POINTS and scratch is not None:
+                scratch = _lib.scratch_buffer(_lib.mesh_scratch_bytes(P), dev)
+            if order is None and 0 < P <= _lib.mesh_small_points() and scratch is not None:
                 # few points: the processing order is worked out inside the query's first launch (one workgroup of it)
                 order_scratch = torch.empty((P,), dtype=torch.int32, device=dev)
                 _lib.check(lib.pvamd_mesh_query_unordered(ctypes.byref(desc), _lib.ptr(flat), P,
@@ -610,7 +610,7 @@ class CachedSDF(ObjectFrameSDF):
             packed = torch.empty((n, 4), dtype=torch.float32, device=dev)
             pts = torch.empty((n, 3), dtype=torch.float32, device=dev)
             order = torch.empty((n,), dtype=torch.int32, device=dev)
-            scratch = torch.empty((_lib.mesh_scratch_bytes(n) // 8,), dtype=torch.int64, device=dev) \
+            scratch = _lib.scratch_buffer(_lib.mesh_scratch_bytes(n), dev) \
                 if getattr(obj, "tile_split", True) else None
             _lib.check(lib.pvamd_cache_build(ctypes.byref(desc), _lib.ptr(cx), _lib.ptr(cy), _lib.ptr(cz), shape[0], shape[1], shape[2],
                                              ctypes.c_uint64(obj.jitter_seed), _lib.ptr(packed), _lib.ptr(pts), _lib.ptr(order),

@@ -87,19 +87,18 @@ def test_oracle_grid_layout_is_one_definition(tmp_path):
     assert "pvamd_oracle.h" in open(os.path.join(ROOT, "tests", "cabi", "cabi_check.c")).read()
 
 
-def test_buffer_size_macros_match_the_python_mirrors(tmp_path):
-    """The sizes the binding allocates are the header's macros (records in whole tiles, tile / group spheres, the scratch of
-    the mesh entry points, the Morton-order scratch, the scratch of the minimum's backward): the sizes that have no exported
-    function."""
+def test_buffer_size_macros_match_the_exported_functions(tmp_path):
+    """The buffer-size macros the header keeps (records in whole tiles, tile / group spheres, the scratch of the mesh entry
+    points, the scratch of the minimum's backward) are what the exported functions of the library return."""
     src = r'''
     #include <stdio.h>
     #include "pvamd.h"
     int main(void) {
       long long v[] = {0, 1, 255, 256, 257, 15728, 99500, 1 << 20, 1 << 21, (1 << 24) + 5, 67108877};
       for (int i = 0; i < 11; ++i)
-        printf("%lld %lld %lld %lld\n", (long long)PVAMD_REC_FLOATS(v[i]), (long long)PVAMD_TILES_FLOATS(v[i]),
-               (long long)PVAMD_MESH_SCRATCH_BYTES(v[i]), (long long)PVAMD_MORTON_ORDER_SCRATCH_BYTES(v[i]));
-      printf("%d %d %d %d\n", PVAMD_TRI_REC, PVAMD_TRI_TILE, PVAMD_TRI_GROUP, PVAMD_MESH_SCRATCH_GROUPS);
+        printf("%lld %lld %lld\n", (long long)PVAMD_REC_FLOATS(v[i]), (long long)PVAMD_TILES_FLOATS(v[i]),
+               (long long)PVAMD_MESH_SCRATCH_BYTES(v[i]));
+      printf("%d\n", PVAMD_MESH_SMALL_POINTS);
       printf("%lld %lld %lld %lld\n", (long long)PVAMD_MIN_OVER_POINTS_BACKWARD_SCRATCH_BYTES(1, 1, 0),
              (long long)PVAMD_MIN_OVER_POINTS_BACKWARD_SCRATCH_BYTES(1, 1, 1), (long long)PVAMD_MIN_OVER_POINTS_BACKWARD_SCRATCH_BYTES(8, 200, 0),
              (long long)PVAMD_MIN_OVER_POINTS_BACKWARD_SCRATCH_BYTES(8, 200, 1));
@@ -107,17 +106,34 @@ def test_buffer_size_macros_match_the_python_mirrors(tmp_path):
     exe = str(tmp_path / "pvamd_sizes")
     subprocess.run(["gcc", "-x", "c", "-", "-I", os.path.join(ROOT, "include"), "-o", exe], input=src.encode(), check=True)
     out = [[int(x) for x in line.split()] for line in subprocess.run([exe], capture_output=True, check=True).stdout.decode().splitlines()]
+    lib = _lib.load()
+    assert len(out) == 13
     for n, row in zip((0, 1, 255, 256, 257, 15728, 99500, 1 << 20, 1 << 21, (1 << 24) + 5, 67108877), out):
-        assert row == [_lib.rec_floats(n), _lib.tiles_floats(n), _lib.mesh_scratch_bytes(n),
-                       4 * _lib.morton_order_scratch_words(n)], (n, row)
-    assert out[-2] == [_lib.TRI_REC, _lib.TRI_TILE, _lib.TRI_GROUP, _lib.MESH_SCRATCH_GROUPS]
-    assert out[-1] == [_lib.min_over_points_backward_scratch_bytes(S, A, per_leaf)
-                       for S, A in ((1, 1), (8, 200)) for per_leaf in (False, True)]
+        assert row == [lib.pvamd_mesh_rec_floats(n), lib.pvamd_mesh_tiles_floats(n), lib.pvamd_mesh_scratch_bytes(n)], (n, row)
+    assert out[-2] == [lib.pvamd_mesh_small_points()] == [16384]
+    assert out[-1] == [lib.pvamd_min_over_points_backward_scratch_bytes(S, A, per_leaf)
+                       for S, A in ((1, 1), (8, 200)) for per_leaf in (0, 1)]
     assert out[-1] == [24, 24, 24 * 200, 24 * 200 * 8]
 
 
+def test_morton_order_scratch_size_steps_up_and_stays_under_the_old_bound():
+    """pvamd_morton_order_scratch_bytes is the larger of the two sorts' layouts: across each branch point (one launch / 2^15 /
+    2^18 cells, counting / radix sort, 196 -> 197 tiles where the supergroups round, 2^21 cells) it does not shrink, and it
+    never exceeds what the header's macro asked for before the function existed (<= 512 words per radix tile)."""
+    lib = _lib.load()
+    sizes = []
+    for P in (1, 16384, 16385, 65535, 65536, 786431, 786432, 806912, 1048575, 1048576, (1 << 24) + 5):
+        bits = 21 if P >= (1 << 20) else (18 if P >= (1 << 16) else 15)
+        old = 4 * max(8 + 4 * P + 512 * ((P + 4095) // 4096), 8 + (1 << bits) + P + 2048)
+        sizes.append(lib.pvamd_morton_order_scratch_bytes(P))
+        assert 0 < sizes[-1] <= old, (P, sizes[-1], old)
+    assert sizes == sorted(sizes), sizes
+
+
 SIZE_FUNCTIONS = ("min_over_points_scratch_bytes", "hinge_over_points_scratch_bytes", "hinge_over_points_backward_scratch_bytes",
-                  "leaf_pair_scratch_bytes", "leaf_pair_hinge_scratch_bytes", "chamfer_normal_eq_scratch_bytes")
+                  "leaf_pair_scratch_bytes", "leaf_pair_hinge_scratch_bytes", "chamfer_normal_eq_scratch_bytes",
+                  "min_over_points_backward_scratch_bytes", "mesh_scratch_bytes", "morton_order_scratch_bytes")
+MESH_SIZE_FUNCTIONS = ("rec_floats", "tiles_floats")  # _lib.NAME asks pvamd_mesh_NAME
 
 
 def test_scratch_size_macros_match_the_exported_functions(tmp_path):
@@ -168,8 +184,7 @@ def test_scratch_size_macros_match_the_exported_functions(tmp_path):
     assert sorted(re.findall(r"#define\s+(PVAMD_\w*SCRATCH_BYTES)\b", text)) == sorted(
         ["PVAMD_MIN_OVER_POINTS_SCRATCH_BYTES", "PVAMD_MIN_OVER_POINTS_BACKWARD_SCRATCH_BYTES",
          "PVAMD_HINGE_OVER_POINTS_SCRATCH_BYTES", "PVAMD_LEAF_PAIR_SCRATCH_BYTES", "PVAMD_CHAMFER_NORMAL_EQ_SCRATCH_BYTES",
-         "PVAMD_MESH_SCRATCH_BYTES", "PVAMD_MORTON_ORDER_SCRATCH_BYTES", "PVAMD_MORTON_RADIX_SCRATCH_BYTES",
-         "PVAMD_MORTON_COUNTING_SCRATCH_BYTES"]), "a size macro without a check against its definition"
+         "PVAMD_MESH_SCRATCH_BYTES"]), "a size macro without a check against its definition"
 
 
 def test_binding_asks_the_library_for_scratch_sizes():
@@ -188,10 +203,17 @@ def test_binding_asks_the_library_for_scratch_sizes():
                 assert _lib.leaf_pair_scratch_bytes(S, A, P, f64, pl) == lib.pvamd_leaf_pair_scratch_bytes(S, A, P, int(f64), int(pl))
                 assert _lib.leaf_pair_hinge_scratch_bytes(S, A, P, f64, pl) == \
                     lib.pvamd_leaf_pair_hinge_scratch_bytes(S, A, P, int(f64), int(pl))
+            assert _lib.min_over_points_backward_scratch_bytes(S, A, pl) == lib.pvamd_min_over_points_backward_scratch_bytes(S, A, int(pl))
         assert _lib.chamfer_normal_eq_scratch_bytes(A, P) == lib.pvamd_chamfer_normal_eq_scratch_bytes(A, P)
-    for name in SIZE_FUNCTIONS:
+        for n in (P, A * 64 * 8192, 0):
+            assert _lib.mesh_scratch_bytes(n) == lib.pvamd_mesh_scratch_bytes(n) > 0
+            assert _lib.morton_order_scratch_bytes(n) == lib.pvamd_morton_order_scratch_bytes(n) > 0
+            assert _lib.rec_floats(n) == lib.pvamd_mesh_rec_floats(n)
+            assert _lib.tiles_floats(n) == lib.pvamd_mesh_tiles_floats(n)
+    assert _lib.mesh_small_points() == lib.pvamd_mesh_small_points()
+    for name in SIZE_FUNCTIONS + MESH_SIZE_FUNCTIONS:
         source = inspect.getsource(getattr(_lib, name))
-        assert f"load().pvamd_{name}(" in source, name
+        assert f"load().pvamd_{'mesh_' if name in MESH_SIZE_FUNCTIONS else ''}{name}(" in source, name
         for operator in ("//", "*", "+"):
             assert operator not in source, (name, operator)
 

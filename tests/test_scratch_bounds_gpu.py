@@ -1,5 +1,5 @@
 """-m gpu: no entry point writes past the scratch the library's own size function reports.  Every byte-sized scratch of the
-fused reductions and their backwards is allocated by _lib.scratch_buffer; here it hands out the requested bytes in front of a
+fused reductions and their backwards, of the mesh entry points and of the spatial sort is allocated by _lib.scratch_buffer; here it hands out the requested bytes in front of a
 1 MiB tail of 0xA5 that belongs to the test, so an overrun shows up as a changed byte, never as a fault.  The shapes are the
 smallest at which each layout changes (chunk boundaries, split configurations, the per-leaf hinge's extra term)."""
 import pytest
@@ -104,3 +104,65 @@ def test_leaf_pairs_stay_inside_their_scratch(leaves, guard, dtype, largest):
     res = comp.leaf_pair_hinge(sets, pairs, MARGIN)
     torch.autograd.grad(res.values.sum(), t)
     assert guard() == forward + 1
+
+
+@pytest.mark.parametrize("P", [16385, 65536, 786431, 786432, 806912, 1048576])
+def test_spatial_sort_stays_inside_its_scratch(guard, P):
+    """The first size that uses scratch (2^15 cells), 2^18 cells, the last counting-sort and the first radix size (192 tiles),
+    197 tiles (one past a perfect square, where the number of supergroups rounds), 2^21 cells and a third radix pass."""
+    pts = points(P, torch.float32, seed=P)
+    order, inverse, spts = _lib.morton_order(pts, min_points=0, want_inverse=True, want_sorted=True)
+    assert guard() == 1
+    idx = torch.arange(P, device="cuda", dtype=torch.int32)
+    assert torch.equal(torch.sort(order).values, idx)
+    assert torch.equal(inverse[order.long()], idx)
+    assert torch.equal(spts, pts[order.long()])
+
+
+@pytest.fixture(scope="module")
+def drill():
+    obj = pv.MeshObjectFactory(H.mesh_path("ycb_power_drill.npz"))
+    assert obj.num_faces == 15728
+    return obj
+
+
+@pytest.mark.parametrize("P,ordered", [(1, False), (16384, False), (16385, True), (8192 * 64, True)])
+def test_mesh_query_stays_inside_its_scratch(drill, guard, P, ordered):
+    """Without an order: the by-point part of the scratch up to its last entry (pvamd_mesh_query_unordered).  With one: the first
+    size past it, and as many point groups as the scratch has slots, where the two-launch path writes the last slot.  Same bits
+    as the single-launch scan that takes no scratch."""
+    bb = drill.bounding_box(padding_ratio=0.3)
+    pts = H.uniform_points(P, bb[:, 0], bb[:, 1], seed=P).float().cuda()
+    order = _lib.morton_order(pts, min_points=0) if ordered else None
+    outs = []
+    try:
+        for split in (True, False):
+            drill.tile_split = split
+            r = drill.object_frame_closest_point(pts, compute_normal=True, order=order)
+            outs.append((r.closest, r.distance, r.gradient, r.normal, drill._last_face_ids))
+            if split:
+                assert guard() == 1 + int(ordered)  # the mesh scratch, and the sort's above
+    finally:
+        drill.tile_split = True
+    guard(0)
+    for a, b in zip(*outs):
+        assert torch.equal(a, b)
+
+
+def test_heavy_point_groups_stay_inside_the_mesh_scratch(guard):
+    """The centre points of test_mesh_gpu's heavy-groups test: more heavy groups than the list has slots for."""
+    from pytorch_volumetric_amd import mesh_io
+    obj = pv.MeshObjectFactory(mesh=mesh_io.uv_sphere_mesh(0.1, 150, 120))
+    g = torch.Generator().manual_seed(3)
+    torch.rand(4096, 3, generator=g)
+    many = ((torch.rand(9000 * 64, 3, generator=g) - 0.5) * 0.02).float().cuda().contiguous()
+    obj.object_frame_closest_point(many[:140_000])
+    assert guard() == 2  # the sort's and the mesh scratch
+    pv.batch_chamfer_dist(torch.eye(4).unsqueeze(0), many, obj_factory=obj)
+    assert guard() == 2
+
+
+def test_cache_build_stays_inside_the_mesh_scratch(drill, guard):
+    cached = pv.CachedSDF("drill", 0.02, drill.bounding_box(padding=0.013), pv.MeshSDF(drill), device="cuda", cache_path=None)
+    assert cached._packed.shape[0] > 0
+    assert guard() == 1
