@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define PVAMD_ABI_VERSION 14
+#define PVAMD_ABI_VERSION 15
 
 #define PVAMD_E_NULL      (-1)  /* a required pointer is NULL            */
 #define PVAMD_E_SHAPE     (-2)  /* a size/shape argument is out of range */
@@ -228,6 +228,8 @@ int pvamd_voxel_scatter_u8(const pvamd_grid_t* grid, uint8_t* storage, const flo
  * PVAMD_E_SHAPE; the same bound holds for the packed, bucketed and grouped entry points below); points / out_val /
  * out_grad need only their natural 4-byte alignment -- rows of an odd P (the reference README's M = 15,251) take the
  * same kernel.
+ * The other bits below are for tests and tuning: they change which of three kernels serves the call, never a result;
+ * pvamd_composed_query_kernel (below) tells which kernel a call takes.
  * Bits 8 and 16 of flags are retired (two tuning orders that nothing selected): ignored like any unassigned bit, and
  * not to be reused.                                                                                                  */
 #define PVAMD_COMPOSED_INLINE_EXACT 1
@@ -239,6 +241,15 @@ int pvamd_voxel_scatter_u8(const pvamd_grid_t* grid, uint8_t* storage, const flo
 int pvamd_composed_query(const pvamd_grid_t* grids, int32_t S, const float* tf, int32_t A,
                          const float* points, int64_t P,
                          float* out_val, float* out_grad, int32_t* out_leaf, int32_t flags, void* stream);
+
+/* Host-side, pure: which kernel pvamd_composed_query launches for A configurations of P points under `flags` (one launch
+ * for any A and P; the choice depends on these three only, csrc/composed.hip composed_kind) -- for tests that want every
+ * kernel covered at its default sizes and for callers that size their own path by it.  PVAMD_E_SHAPE for A < 1 or P < 0;
+ * PVAMD_COMPOSED_INLINE_EXACT picks an instantiation inside the wave-tile and per-lane kernels and is not a kind. (ABI 15) */
+#define PVAMD_CO_KERNEL_PER_LANE   0  /* composed_query_scalar: one point per lane, grid-stride                    */
+#define PVAMD_CO_KERNEL_WAVE_TILE  1  /* composed_query_wave: 256-point tiles through LDS, per-tile leaf mask      */
+#define PVAMD_CO_KERNEL_FUSED      2  /* composed_query_fused: 4096-point chunks regrouped inside the workgroup    */
+int pvamd_composed_query_kernel(int32_t A, int64_t P, int32_t flags);
 
 /* The same query for FLOAT64 points with a float64 transform stack (sdf.py:392-433 when the chain / the Transform3d is
  * float64: the transform, every leaf's index arithmetic, range test and bounding-box branch -- sdf.py:545-547 -- and the

@@ -12,7 +12,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PVAMD_LIB") or os.path.join(_HERE, "csrc", "libpvamd.so")  # PVAMD_LIB: A/B builds (tools/)
 
-ABI_VERSION = 14
+ABI_VERSION = 15
 OOB_LOOKUP_GT_SDF = 0
 OOB_BOUNDING_BOX = 1
 COMPOSED_INLINE_EXACT = 1
@@ -21,6 +21,7 @@ COMPOSED_FORCE_WAVE_TILE = 4
 COMPOSED_OUT_PACKED = 32
 COMPOSED_NO_GROUPING = 64
 COMPOSED_FORCE_FUSED = 128
+CO_KERNEL_PER_LANE, CO_KERNEL_WAVE_TILE, CO_KERNEL_FUSED = 0, 1, 2  # PVAMD_CO_KERNEL_* (include/pvamd.h)
 RULE_VALID_ON_INDEX = 1
 RULE_ROUND_HALF_AWAY = 2
 RULE_ROUND_FLOOR_HALF = 4
@@ -105,6 +106,12 @@ def leaf_pair_hinge_scratch_bytes(K, A, max_points, f64, backward):
 def chamfer_normal_eq_scratch_bytes(B, N):
     """pvamd_chamfer_normal_eq_scratch_bytes: 28 float64 sums and one int64 count per pose and point chunk."""
     return load().pvamd_chamfer_normal_eq_scratch_bytes(B, N)
+
+
+@_remembered
+def composed_query_kernel(A, P, flags):
+    """pvamd_composed_query_kernel: the kernel (CO_KERNEL_*) pvamd_composed_query launches for A configurations of P points."""
+    return load().pvamd_composed_query_kernel(A, P, flags)
 
 
 def scratch_buffer(nbytes, dev):
@@ -201,6 +208,7 @@ SIGNATURES = {
                                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
                                                      ctypes.c_void_p]),
     "pvamd_cached_query_kernel": (ctypes.c_int, [ctypes.c_int64]),
+    "pvamd_composed_query_kernel": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int64, ctypes.c_int32]),
     "pvamd_group_chunk_points": (ctypes.c_int64, []),
     "pvamd_group_scratch_bytes": (ctypes.c_int64, [ctypes.c_int64]),
     "pvamd_group_points": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),

@@ -46,6 +46,18 @@ static inline unsigned stream_grid(int64_t n, int block) {
     return (unsigned)(need < cap ? (need < 1 ? 1 : need) : cap);
 }
 
+// gridDim.y of a kernel that takes the configuration as blockIdx.x (any count: one launch for any A) and grid-strides over
+// `need` rows of work per configuration in y: up to ~65536 blocks in total, split over the A configurations (about one
+// 256-point tile per wave in the composed query), at least 1 and at most the 65535 HIP allows.  (Sweep on C4, 200 x 262,144:
+// 1024 blocks 1.40 ms, 4096 1.17, 8192 1.13, 32768 1.09, 65536 1.08 -- the hardware dispatcher balances better than a
+// grid-stride loop over unequal tiles.)
+static inline unsigned config_rows(int32_t A, int64_t need) {
+    int64_t cap = ((int64_t)65536 + A - 1) / A;
+    if (cap > 65535) cap = 65535;
+    const int64_t rows = need < cap ? need : cap;
+    return (unsigned)(rows < 1 ? 1 : rows);
+}
+
 static inline int check_grid(const pvamd_grid_t& g, bool need_vox = true) {
     if (need_vox && !g.vox) return PVAMD_E_NULL;
     if (need_vox && !aligned_to(g.vox, 16)) return PVAMD_E_ALIGN;

@@ -875,6 +875,51 @@ constexpr int kFusedChunk = kFusedWaves * kTilePoints;
 constexpr int64_t kFusedMinBlocks = 1024;  // (chunk, configuration) workgroups below which the per-lane / wave-tile kernels keep the call
 static_assert(kGroupChunk <= 65536 && 4096 % (kGroupWaves * 64) == 0, "perm is uint16; the scan splits 4096 bins evenly");
 
+// Which kernel pvamd_composed_query launches for A configurations of P points under `flags` (one launch for any A and P;
+// pvamd_composed_query_kernel reports the choice).  chunks = ceil(P / 4096), tiles = ceil(P / 256); the first row that holds:
+//   FORCE_FUSED, P >= 4096                                                    fused (whatever the other bits say)
+//   plain flags, P >= 4096, chunks x A >= 1024 (kFusedMinBlocks)              fused
+//   FORCE_WAVE_TILE, P >= 256                                                 wave-tile (also over FORCE_PER_LANE)
+//   no FORCE_PER_LANE, A >= 2, P >= 256, tiles x A >= 32768 (kWaveTileMinTiles)  wave-tile
+//   anything else (fewer than 256 points always)                              one point per lane
+// "plain flags": none of INLINE_EXACT, FORCE_PER_LANE, FORCE_WAVE_TILE, NO_GROUPING.  INLINE_EXACT is not a kind: it picks the
+// instantiation of the wave-tile and per-lane kernels (the entry point), and keeps a call away from the fused kernel.
+// At plain flags tiles <= 16 x chunks, so tiles x A >= 32768 implies chunks x A >= 2048 >= kFusedMinBlocks: from P = 4096 on,
+// every call in the wave-tile regime is a fused one.  The wave-tile kernel is reached at flags 0 only for 256 <= P < 4096
+// (which needs A >= 2048); everywhere else it serves NO_GROUPING and INLINE_EXACT calls.
+//
+// Wave-tile against per-lane.  The wave-tile kernel (256 points per wave through LDS, per-tile leaf mask, configuration-fastest
+// block order) is the one that scales with configurations and exploits coherent points; the one-point-per-lane kernel has
+// 4x the parallelism, no per-tile overhead, and 44 VGPRs (8 waves per SIMD without spills).  Measured (tools/
+// scalar_probe.py, ms, wave-tile | one-point-per-lane): C3 4M random 0.106 | 0.095, C3 Morton-sorted 0.064 | 0.074,
+// C4 200 x 262k random 0.85 | 0.97, sorted 0.60 | 0.82, README-size grids 4.9 | 6.4 and 1.0 | 2.6.  So: a single
+// configuration, or too few tiles to fill the chip (100k points x 8 leaves: 36 -> 17 us), takes the per-lane kernel.
+// Either kernel takes ANY point count and any 4-byte aligned buffers (round 2 sent P % 4 != 0 -- the reference README's
+// own M = 15,251 -- to the per-lane kernel: the wave-tile kernel's 16-byte stores wanted aligned (A, P) rows; they do
+// not: common.h f32x4_u) and the wave-tile kernel covers a ragged end with a last tile moved back to end at point P - 1:
+// one launch per call (fewer than 256 points always take the per-lane kernel).
+// (flags bits 1 and 2, for tools/scalar_probe.py and the tests: force the per-lane / the wave-tile kernel.)
+//
+// Fused.  Round 6: the chunk-grouped kernel with the sort inside the workgroup (composed_query_fused) wherever there are enough
+// (chunk, configuration) workgroups to fill the chip twice over and the grids are L2-resident: scattered points cost it a
+// sixth more work per chunk and save a third of the leaf loop (C3 0.081 -> see profiles/r06_composed_variants.txt); a caller
+// with scratch and several configurations sorts once instead (pvamd_group_points + pvamd_composed_query_grouped).
+enum ComposedKind {
+    kCoPerLane = PVAMD_CO_KERNEL_PER_LANE, kCoWaveTile = PVAMD_CO_KERNEL_WAVE_TILE, kCoFused = PVAMD_CO_KERNEL_FUSED
+};
+static inline ComposedKind composed_kind(int32_t A, int64_t P, int32_t flags) {
+    const int64_t nchunks = (P + kFusedChunk - 1) / kFusedChunk;
+    const bool plain_flags = !(flags & (PVAMD_COMPOSED_INLINE_EXACT | PVAMD_COMPOSED_FORCE_PER_LANE |
+                                        PVAMD_COMPOSED_FORCE_WAVE_TILE | PVAMD_COMPOSED_NO_GROUPING));
+    if (P >= kFusedChunk && ((plain_flags && nchunks * (int64_t)A >= kFusedMinBlocks) || (flags & PVAMD_COMPOSED_FORCE_FUSED)))
+        return kCoFused;
+    const int64_t ntiles = (P + kTilePoints - 1) / kTilePoints;
+    if (P >= kTilePoints && ((A >= 2 && ntiles * (int64_t)A >= kWaveTileMinTiles && !(flags & PVAMD_COMPOSED_FORCE_PER_LANE)) ||
+                             (flags & PVAMD_COMPOSED_FORCE_WAVE_TILE)))
+        return kCoWaveTile;
+    return kCoPerLane;
+}
+
 template <int NW>
 __global__ __launch_bounds__(NW * 64) void group_points_kernel(const float* __restrict__ pts, int64_t P,
                                                                float* __restrict__ sorted, float* __restrict__ bounds,
@@ -1315,45 +1360,17 @@ extern "C" int pvamd_composed_query(const pvamd_grid_t* grids, int32_t S, const 
     hipStream_t s = (hipStream_t)stream;
     // The leaf descriptors live in device memory; whether any of them asks for float64 index arithmetic is not
     // known host-side, so the kernels are built for the general case and test the (wave-uniform) flag per leaf.
-    // Two kernels.  The wave-tile kernel (256 points per wave through LDS, per-tile leaf mask, configuration-fastest block
-    // order) is the one that scales with configurations and exploits coherent points; the one-point-per-lane kernel has
-    // 4x the parallelism, no per-tile overhead, and 44 VGPRs (8 waves per SIMD without spills).  Measured (tools/
-    // scalar_probe.py, ms, wave-tile | one-point-per-lane): C3 4M random 0.106 | 0.095, C3 Morton-sorted 0.064 | 0.074,
-    // C4 200 x 262k random 0.85 | 0.97, sorted 0.60 | 0.82, README-size grids 4.9 | 6.4 and 1.0 | 2.6.  So: a single
-    // configuration, or too few tiles to fill the chip (100k points x 8 leaves: 36 -> 17 us), takes the per-lane kernel.
-    // Either kernel takes ANY point count and any 4-byte aligned buffers (round 2 sent P % 4 != 0 -- the reference README's
-    // own M = 15,251 -- to the per-lane kernel: the wave-tile kernel's 16-byte stores wanted aligned (A, P) rows; they do
-    // not: common.h f32x4_u) and the wave-tile kernel covers a ragged end with a last tile moved back to end at point P - 1:
-    // one launch per call (fewer than 256 points always take the per-lane kernel).
-    // (flags bits 1 and 2, for tools/scalar_probe.py and the tests: force the per-lane / the wave-tile kernel.)
-    const int64_t ntiles = (P + kTilePoints - 1) / kTilePoints;
-    // The configuration is blockIdx.x (any count) in all three kernels: one launch for any A.  Up to ~65536 blocks in
-    // total, split over the A configurations: about one 256-point tile per wave.  (Sweep on C4, 200 x 262,144: 1024 blocks
-    // 1.40 ms, 4096 1.17, 8192 1.13, 32768 1.09, 65536 1.08 -- the hardware dispatcher balances better than a grid-stride
-    // loop over unequal tiles.)
-    int64_t cap = ((int64_t)65536 + A - 1) / A;
-    if (cap > 65535) cap = 65535;  // gridDim.y
-    // Round 6: the chunk-grouped kernel with the sort inside the workgroup (composed_query_fused) wherever there are enough
-    // (chunk, configuration) workgroups to fill the chip twice over and the grids are L2-resident: scattered points cost it a
-    // sixth more work per chunk and save a third of the leaf loop (C3 0.081 -> see profiles/r06_composed_variants.txt); a caller
-    // with scratch and several configurations sorts once instead (pvamd_group_points + pvamd_composed_query_grouped).
-    {
+    // The configuration is blockIdx.x (any count) in all three kernels: one launch for any A (common.h config_rows).
+    switch (composed_kind(A, P, flags)) {
+    case kCoFused: {
         const int64_t nchunks = (P + kFusedChunk - 1) / kFusedChunk;
-        const bool plain_flags = !(flags & (PVAMD_COMPOSED_INLINE_EXACT | PVAMD_COMPOSED_FORCE_PER_LANE |
-                                            PVAMD_COMPOSED_FORCE_WAVE_TILE | PVAMD_COMPOSED_NO_GROUPING));
-        const bool fused = P >= kFusedChunk &&
-                           ((plain_flags && nchunks * (int64_t)A >= kFusedMinBlocks) || (flags & PVAMD_COMPOSED_FORCE_FUSED));
-        if (fused) {
-            const unsigned gy = (unsigned)(nchunks < cap ? nchunks : (cap < 1 ? 1 : cap));
-            hipLaunchKernelGGL((composed_query_fused<kFusedWaves, kPointsPerPass>), dim3(A, gy), dim3(kFusedWaves * 64), 0, s, grids, S, tf,
-                               A, points, nchunks, P, out_val, out_grad, out_leaf, 0);
-            return (int)hipGetLastError();
-        }
+        hipLaunchKernelGGL((composed_query_fused<kFusedWaves, kPointsPerPass>), dim3(A, config_rows(A, nchunks)), dim3(kFusedWaves * 64), 0,
+                           s, grids, S, tf, A, points, nchunks, P, out_val, out_grad, out_leaf, 0);
+        break;
     }
-    const bool wave_tiles = P >= kTilePoints && ((A >= 2 && ntiles * (int64_t)A >= kWaveTileMinTiles && !(flags & PVAMD_COMPOSED_FORCE_PER_LANE)) || (flags & PVAMD_COMPOSED_FORCE_WAVE_TILE));
-    if (wave_tiles) {
-        const int64_t need = (ntiles + kWavesPerBlock - 1) / kWavesPerBlock;
-        const unsigned gy = (unsigned)(need < cap ? need : (cap < 1 ? 1 : cap));
+    case kCoWaveTile: {
+        const int64_t ntiles = (P + kTilePoints - 1) / kTilePoints;
+        const unsigned gy = config_rows(A, (ntiles + kWavesPerBlock - 1) / kWavesPerBlock);
         // large, gather-bound grids (the inline-exact hint): the round-3 loop; else the split loop
         if (flags & PVAMD_COMPOSED_INLINE_EXACT)
             hipLaunchKernelGGL((composed_query_wave<kPointsPerPass, false, 0>), dim3(A, gy), dim3(kWavesPerBlock * 64), 0, s,
@@ -1361,9 +1378,10 @@ extern "C" int pvamd_composed_query(const pvamd_grid_t* grids, int32_t S, const 
         else
             hipLaunchKernelGGL((composed_query_wave<kPointsPerPass, false, 1>), dim3(A, gy), dim3(kWavesPerBlock * 64), 0, s,
                                grids, S, tf, A, points, ntiles, P, out_val, out_grad, out_leaf, 0);
-    } else {
-        const int64_t need = (P + 255) / 256;
-        const unsigned gy = (unsigned)(need < cap ? need : (cap < 1 ? 1 : cap));
+        break;
+    }
+    case kCoPerLane: {
+        const unsigned gy = config_rows(A, (P + 255) / 256);
         // large, gather-bound grids (the inline-exact hint): the two minima cost a second gather of the winner's record
         // and lose 6-12 % there (README-size link grids, 200 x 15,251: 0.087 vs 0.082 ms on the slice, 0.300 vs 0.268 ms
         // on random points); L2-resident grids gain 7-18 % (C4 per-lane 0.975 -> 0.899 ms, README slice 0.062 -> 0.058)
@@ -1373,8 +1391,16 @@ extern "C" int pvamd_composed_query(const pvamd_grid_t* grids, int32_t S, const 
         else
             hipLaunchKernelGGL(composed_query_scalar<true>, dim3(A, gy), dim3(256), 0, s, grids, S, tf, A, points, P, out_val,
                                out_grad, out_leaf);
+        break;
+    }
     }
     return (int)hipGetLastError();
+}
+
+// Host-side, pure: the kernel pvamd_composed_query launches for these arguments (include/pvamd.h PVAMD_CO_KERNEL_*).
+extern "C" int pvamd_composed_query_kernel(int32_t A, int64_t P, int32_t flags) {
+    if (A < 1 || P < 0) return PVAMD_E_SHAPE;
+    return (int)composed_kind(A, P, flags);
 }
 
 // ---- chunk-grouped query (round 6): scratch layout = sorted points | run bounds | perm ----
@@ -1413,10 +1439,8 @@ extern "C" int pvamd_composed_query_grouped(const pvamd_grid_t* grids, int32_t S
         return PVAMD_E_ALIGN;
     const char* base = static_cast<const char*>(scratch);
     const int64_t nchunks = group_chunks(P);
-    // configuration = blockIdx.x (any count), chunks = blockIdx.y (grid-strided beyond 65535)
-    int64_t cap = ((int64_t)65536 + A - 1) / A;
-    if (cap > 65535) cap = 65535;
-    const unsigned gy = (unsigned)(nchunks < cap ? nchunks : (cap < 1 ? 1 : cap));
+    // configuration = blockIdx.x (any count), chunks = blockIdx.y (grid-strided beyond what config_rows gives)
+    const unsigned gy = config_rows(A, nchunks);
     const float* sorted = reinterpret_cast<const float*>(base);
     const float* bounds = reinterpret_cast<const float*>(base + group_bounds_offset(P));
     const uint16_t* perm = reinterpret_cast<const uint16_t*>(base + group_perm_offset(P));

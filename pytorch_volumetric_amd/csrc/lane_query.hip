@@ -196,11 +196,8 @@ static int composed_f64(const pvamd_grid_t* grids, int32_t S, const double* tf, 
                         double* out_val, double* out_grad, int32_t* out_leaf, void* stream) {
     if (int e = check_composed<double>(grids, S, tf, A, points, P, out_val, out_grad)) return e;
     if (P == 0) return 0;
-    int64_t gy = (P + 255) / 256;
-    int64_t cap = ((int64_t)65536 + A - 1) / A;
-    if (cap > 65535) cap = 65535;  // gridDim.y; the kernel grid-strides over the points
-    if (gy > cap) gy = cap;
-    hipLaunchKernelGGL(composed_query_f64_kernel<INTERP>, dim3(A, (unsigned)(gy < 1 ? 1 : gy)), dim3(256), 0, (hipStream_t)stream,
+    // the kernel grid-strides over the points
+    hipLaunchKernelGGL(composed_query_f64_kernel<INTERP>, dim3(A, config_rows(A, (P + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        grids, S, tf, A, points, P, out_val, out_grad, out_leaf);
     return (int)hipGetLastError();
 }

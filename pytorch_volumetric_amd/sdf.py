@@ -837,6 +837,23 @@ class PreparedPoints:
         return int(self.points.shape[0])
 
 
+# ComposedSDF's choices between its query paths (module globals: the eager fast path of __call__ reads them on every call).
+# The INLINE_EXACT tuning hint (ComposedSDF._leaf_grids): leaf grids that together fit the 4 MB L2 of an XCD make the kernel
+# instruction-bound, larger ones gather-bound.
+_XCD_L2_BYTES = 4 << 20
+_INLINE_EXACT = _lib.COMPOSED_INLINE_EXACT
+# Regrouping under group_points "auto" (ComposedSDF._grouping_pays): wherever the library itself would launch its wave-tile
+# kernel were regrouping off -- asked of the library (remembered per shape), not restated here.
+_composed_kernel, _NO_GROUPING, _WAVE_TILE = _lib.composed_query_kernel, _lib.COMPOSED_NO_GROUPING, _lib.CO_KERNEL_WAVE_TILE
+# The spatial sort under bucket_points "auto" (ComposedSDF._bucketing_pays has the measurements): gather-bound grids, enough
+# configurations to share one sort, enough points, the (A, P) 16-byte records of the sorted pass within 8 GiB -- and the
+# leaf-grid bytes one configuration's query can touch (_footprint_bytes) above 8 MB: a planar slice stays below and is not sorted.
+_SORT_MIN_CONFIGS = 8
+_SORT_MIN_POINTS = 32768
+_SORT_MAX_RECORD_BYTES = 8 << 30
+_SORT_MIN_FOOTPRINT_BYTES = 8 << 20
+
+
 class ComposedSDF(ObjectFrameSDF):
     """Minimum over S rigidly placed leaf SDFs (sdf.py:332-433).
 
@@ -987,13 +1004,14 @@ class ComposedSDF(ObjectFrameSDF):
         """The chunk-grouped kernel (round 6): one small sort launch shared by the A configurations, then waves of
         neighbouring points -- most leaf visits become all-outside instead of paying the look-up half for a few lanes (C4:
         0.68 -> 0.5 ms).  "auto": the regime of the wave-tile kernel (several configurations, enough tiles to fill the
-        chip) on L2-resident grids; a single configuration cannot amortise the extra pass over the points."""
+        chip: what pvamd_composed_query_kernel answers under NO_GROUPING) on L2-resident grids; a single configuration cannot
+        amortise the extra pass over the points."""
         gp = self.group_points
         if gp is False or flags != 0 or P < _lib.group_chunk_points():
             return False
         if gp is True:
             return True
-        return A >= 2 and A * (-(-P // 256)) >= 32768
+        return _composed_kernel(A, P, _NO_GROUPING) == _WAVE_TILE
 
     def _bucketing_pays(self, A, P, points=None):
         """Sorting the points costs a sort + a second pass over the outputs (~0.6 ms for 200 x 262,144); it pays when
@@ -1009,9 +1027,11 @@ class ComposedSDF(ObjectFrameSDF):
         if not self._fusable():
             return False
         self._leaf_grids(self._owner_device())  # derives _query_flags from the grid sizes
-        if not (self._query_flags & _lib.COMPOSED_INLINE_EXACT and A >= 8 and P >= 32768 and A * P * 16 <= (8 << 30)):
+        # (the fast path of __call__ carries this line too, on the same names: a call through a shared method cost it 0.1 us)
+        if not (self._query_flags & _INLINE_EXACT and A >= _SORT_MIN_CONFIGS and P >= _SORT_MIN_POINTS and
+                A * P * 16 <= _SORT_MAX_RECORD_BYTES):
             return False
-        return points is None or self._footprint_bytes(points) > (8 << 20)
+        return points is None or self._footprint_bytes(points) > _SORT_MIN_FOOTPRINT_BYTES
 
     def _footprint_bytes(self, flat):
         """Upper estimate of the leaf-grid bytes one configuration's query touches: the cells of the finest leaf grid that
@@ -1051,7 +1071,7 @@ class ComposedSDF(ObjectFrameSDF):
             # it).  Larger grids make it gather-bound and, with their larger coordinate / resolution ratios, flag far more
             # visits (21 MB README-size link grids: 22 % of the wave passes): the inline fallback is cheaper there.
             grid_bytes = sum(int(s._packed.numel()) * 4 for s in {id(s): s for s in self.sdfs}.values())
-            self._query_flags = _lib.COMPOSED_INLINE_EXACT if grid_bytes > (4 << 20) else 0
+            self._query_flags = _lib.COMPOSED_INLINE_EXACT if grid_bytes > _XCD_L2_BYTES else 0
         return self._grids_dev
 
     def _tf_device(self, dev):
@@ -1105,7 +1125,9 @@ class ComposedSDF(ObjectFrameSDF):
             A = math.prod(batch) if batch is not None else 1
             bp = self.bucket_points
             flags = self._query_flags
-            sort = (flags & 1 and A >= 8 and P >= 32768 and A * P * 16 <= (8 << 30)) if bp == "auto" else (bool(bp) and P >= 256)
+            # the arithmetic half of _bucketing_pays, inline (its footprint probe waits in the general path)
+            sort = (flags & _INLINE_EXACT and A >= _SORT_MIN_CONFIGS and P >= _SORT_MIN_POINTS and
+                    A * P * 16 <= _SORT_MAX_RECORD_BYTES) if bp == "auto" else (bool(bp) and P >= 256)
             if P > 0 and not sort:
                 dev = plan[0]
                 tfd = self._tf_dev

@@ -317,3 +317,69 @@ def test_fused_kernel_on_points_that_are_already_ordered():
     assert same_bits(f[0], n[0]) and same_bits(f[1], n[1])
     oval, ograd, _ = oracle.composed_query([H.oracle_grid_from_cached(l) for l in leaves], tfm.numpy(), 1, pts.cpu().numpy())
     assert np.array_equal(f[0], oval, equal_nan=True) and np.array_equal(f[1], ograd, equal_nan=True)
+
+
+def _default_dispatch_shapes(A, flags, top=1 << 17):
+    """(P, kind) either side of every point count at which pvamd_composed_query_kernel(A, ., flags) changes up to `top` (scan
+    in steps of 256, bisect inside a step, so the test follows the thresholds if they are retuned), moved to a ragged size
+    where the kind stays the same."""
+    kind = lambda p: _lib.composed_query_kernel(A, p, flags)
+    out, prev = [], 1
+    for p in range(256, top + 1, 256):
+        if kind(p) != kind(prev):
+            a, b = prev, p
+            while b - a > 1:  # kind(a) == kind(prev) != kind(b)
+                m = (a + b) // 2
+                a, b = (m, b) if kind(m) == kind(prev) else (a, m)
+            a = a - 65 if a > 65 and kind(a - 65) == kind(a) else a
+            b = b + 191 if kind(b + 191) == kind(b) else b
+            out += [(a, kind(a)), (b, kind(b))]
+        prev = p
+    return out
+
+
+def test_every_kernel_the_default_dispatch_picks_matches_the_oracle_bitwise():
+    """pvamd_composed_query at the smallest shapes at which it takes each of its three kernels on its own (no FORCE_* flag), as
+    pvamd_composed_query_kernel reports them: at flags 0 (A = 64: per-lane, then fused from ceil(P / 4096) x A = 1024 on;
+    A = 2048: the only window in which plain flags reach the wave-tile kernel, between 256-point tiles x A = 32768 and
+    P = 4096) and with NO_GROUPING (A = 128: per-lane, then wave-tile).  Values, gradients and leaf ids: every row the bits
+    of the same call under FORCE_PER_LANE, the first and the last row the bits of the CPU oracle."""
+    S = 2
+    leaves = [make_leaf(f64=True, res=0.02), make_leaf(f64=False, res=0.02)]
+    ogrids = [H.oracle_grid_from_cached(l) for l in leaves]
+    lib = _lib.load()
+    cases = [(A, flags, P, kind) for A, flags in ((64, 0), (2048, 0), (128, _lib.COMPOSED_NO_GROUPING))
+             for P, kind in _default_dispatch_shapes(A, flags)]
+    seen = {flags: {kind for _, f, _, kind in cases if f == flags} for flags in (0, _lib.COMPOSED_NO_GROUPING)}
+    assert seen[0] == {_lib.CO_KERNEL_PER_LANE, _lib.CO_KERNEL_WAVE_TILE, _lib.CO_KERNEL_FUSED}, seen
+    assert seen[_lib.COMPOSED_NO_GROUPING] == {_lib.CO_KERNEL_PER_LANE, _lib.CO_KERNEL_WAVE_TILE}, seen
+    pool = scene_points(max(P for _, _, P, _ in cases) + 2, seed=17, extent=0.6)
+    pool[5] = float("nan")
+    pool[300, 1] = float("inf")
+    pool = pool.cuda()
+    dev = pool.device
+    comp = pv.ComposedSDF(leaves, None)
+    for i, (A, flags, P, kind) in enumerate(cases):
+        assert lib.pvamd_composed_query_kernel(A, P, flags) == kind
+        tfm = H.random_rigid(S * A, seed=50 + i, trans=0.3)
+        comp.set_transforms(pv.Transform3d(matrix=tfm), batch_dim=(A,))
+        grids, tfd = comp._leaf_grids(dev), comp._tf_device(dev)
+        pts = pool[1 + i % 2:1 + i % 2 + P]  # windows at 12- and 24-byte offsets
+        out = {}
+        for fl in (flags, flags | _lib.COMPOSED_FORCE_PER_LANE):
+            val = torch.empty((A, P), device=dev)
+            grad = torch.empty((A, P, 3), device=dev)
+            leaf = torch.full((A, P), -1, dtype=torch.int32, device=dev)
+            _lib.check(lib.pvamd_composed_query(_lib.ptr(grids), S, _lib.ptr(tfd), A, _lib.ptr(pts), P, _lib.ptr(val), _lib.ptr(grad),
+                                                _lib.ptr(leaf), fl, _lib.stream_ptr()), "pvamd_composed_query")
+            out[fl] = (val, grad, leaf)
+        (val, grad, leaf), (val0, grad0, leaf0) = out[flags], out[flags | _lib.COMPOSED_FORCE_PER_LANE]
+        assert torch.equal(val.view(torch.int32), val0.view(torch.int32)), (A, flags, P)
+        assert torch.equal(grad.view(torch.int32), grad0.view(torch.int32)), (A, flags, P)
+        assert torch.equal(leaf, leaf0), (A, flags, P)
+        rows = [0, A - 1]
+        otf = tfm.view(S, A, 4, 4)[:, rows].reshape(S * 2, 4, 4).contiguous().numpy()
+        oval, ograd, oleaf = oracle.composed_query(ogrids, otf, 2, pts.cpu().numpy())
+        assert np.array_equal(val[rows].cpu().numpy(), oval, equal_nan=True), (A, flags, P)
+        assert np.array_equal(grad[rows].cpu().numpy(), ograd, equal_nan=True), (A, flags, P)
+        assert np.array_equal(leaf[rows].cpu().numpy(), oleaf), (A, flags, P)

@@ -2,6 +2,7 @@
 value-range view, transforms, kinematics, mesh loading, transform bookkeeping of ComposedSDF, pose-set reductions."""
 import math
 import os
+import re
 
 import numpy as np
 import pytest
@@ -591,3 +592,56 @@ def test_the_disagreement_accounting_of_the_composed_tests():
     shifted[0, 0, 3] = -0.27  # leaf frame x = p.x - 0.27: points 2 and 4 (x = 0.52) now land on the 0.25 plane,
     n_bad, n_unexplained = H.composed_disagreements_explained([leaf], shifted, 1, pts, a, b)  # points 1, 3, 5 on nothing
     assert n_bad == 5 and n_unexplained == 3
+
+
+def _composed_kind_flips(A, flags, top):
+    """Point counts either side of every change of pvamd_composed_query_kernel(A, ., flags) up to `top` (scan in steps of 256,
+    bisect inside a step: the choice is made on whole tiles and chunks)."""
+    kind = lambda p: pv._lib.composed_query_kernel(A, p, flags)
+    out, prev = [], 0
+    for p in range(256, top + 1, 256):
+        if kind(p) != kind(prev):
+            a, b = prev, p
+            while b - a > 1:
+                m = (a + b) // 2
+                a, b = (m, b) if kind(m) == kind(prev) else (a, m)
+            out += [a, b]
+        prev = p
+    return out
+
+
+def test_composed_kernel_choice_is_reported_and_grouping_follows_it():
+    """pvamd_composed_query_kernel (the library's own statement of which kernel pvamd_composed_query launches) and the one Python
+    decision derived from it: "auto" regrouping = from one chunk on, wherever the library would run its wave-tile kernel were
+    regrouping off.  Checked either side of every change of the library's choice, at several configuration counts."""
+    _lib = pv._lib
+    lib = _lib.load()
+    header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "pvamd.h")).read()
+    for name in ("PER_LANE", "WAVE_TILE", "FUSED"):
+        assert getattr(_lib, f"CO_KERNEL_{name}") == int(re.search(rf"#define PVAMD_CO_KERNEL_{name}\s+(\d+)", header).group(1))
+    assert lib.pvamd_composed_query_kernel(0, 100, 0) == _lib.E_SHAPE and lib.pvamd_composed_query_kernel(1, -1, 0) == _lib.E_SHAPE
+    assert lib.pvamd_composed_query_kernel(1, 0, 0) == _lib.CO_KERNEL_PER_LANE
+    # the regimes the header and DESIGN.md name
+    assert _lib.composed_query_kernel(200, 15_251, 0) == _lib.CO_KERNEL_PER_LANE      # the README shape
+    assert _lib.composed_query_kernel(200, 1 << 18, 0) == _lib.CO_KERNEL_FUSED         # C4, handed to the entry point as it is
+    assert _lib.composed_query_kernel(200, 1 << 18, _lib.COMPOSED_NO_GROUPING) == _lib.CO_KERNEL_WAVE_TILE
+    assert _lib.composed_query_kernel(1, 1 << 22, 0) == _lib.CO_KERNEL_FUSED           # C3
+    assert _lib.composed_query_kernel(1, 1 << 22, _lib.COMPOSED_NO_GROUPING) == _lib.CO_KERNEL_PER_LANE
+    assert _lib.composed_query_kernel(200, 255, _lib.COMPOSED_FORCE_WAVE_TILE | _lib.COMPOSED_FORCE_FUSED) == _lib.CO_KERNEL_PER_LANE
+    comp = pv.ComposedSDF([pv.SphereSDF(0.1), pv.SphereSDF(0.2)], None)
+    assert comp.group_points == "auto"
+    chunk = _lib.group_chunk_points()
+    pairs = 0
+    for A in (1, 2, 3, 7, 8, 9, 40, 64, 127, 128, 129, 200, 513, 2047, 2048, 2185, 9000, 32768, 65535, 70000):
+        flips = _composed_kind_flips(A, _lib.COMPOSED_NO_GROUPING, 1 << 17) + _composed_kind_flips(A, 0, 1 << 17)
+        for P in sorted({0, 1, chunk - 1, chunk, chunk + 1, 15_251, 1 << 18, 1 << 22, *flips, *(p + 191 for p in flips), *(max(p - 256, 0) for p in flips)}):
+            rule = P >= chunk and lib.pvamd_composed_query_kernel(A, P, _lib.COMPOSED_NO_GROUPING) == _lib.CO_KERNEL_WAVE_TILE
+            assert comp._grouping_pays(A, P, 0) == rule, (A, P)
+            assert not comp._grouping_pays(A, P, _lib.COMPOSED_INLINE_EXACT)
+            pairs += 1
+    assert pairs >= 200, pairs
+    assert comp._grouping_pays(200, 1 << 18, 0) and not comp._grouping_pays(200, 15_251, 0) and not comp._grouping_pays(1, 1 << 22, 0)
+    comp.group_points = True
+    assert comp._grouping_pays(1, chunk, 0) and not comp._grouping_pays(200, chunk - 1, 0) and not comp._grouping_pays(200, chunk, 1)
+    comp.group_points = False
+    assert not comp._grouping_pays(200, 1 << 18, 0)
