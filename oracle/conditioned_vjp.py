@@ -19,6 +19,23 @@ Besides the VJP, every function returns, per output entry, sum |term|: the sum o
 magnitude of the pair's contribution, taken over the kernel's own intermediate products (|L| |dgg|, |n_d| (|n| . |dg|),
 ...), so that the rounding of a kernel that computes the same expressions in another order is bounded by
 k eps sum|term| whatever cancels.
+
+The trilinear mode (interpolation="trilinear"; composed_vjp / cached_vjp with `interp`; tests/test_interp_edges_gpu.py, as
+tests/test_autograd_edges_gpu.py is the nearest mode's) holds the trilinear forward's decisions the same way.  The winner is
+the trilinear forward's (tests/interp_ref.c composed_forward_f32 / _f64, handed in as `leaf`), the range test is the nearest
+mode's (the C oracle, as above), and for an in-range pair the cell i, the fractions f and the clamped flags come from a cell
+function that runs the forward's statements in the forward's dtype on the forward's x (tests/interp_ref.c interp_cell_f32 /
+_f64); none of them is re-derived in float64, and no floor, minimum or maximum is differentiated:
+  * in range: (v, g) = the blend of the eight records R[i + (a, b, e)] with the weights f or 1 - f per axis, in float64, at
+    f = f_fwd + (xs - x_fwd) / res (1 - clamped): the value is the forward's fraction, the derivative 1 / res, exactly 0 on a
+    clamped axis (include/pvamd.h "Interpolated queries": clamped means c != s, otherwise the full derivative -- at an integer s
+    the upper cell's, at s == n - 1 cell n - 2's with f = 1);
+  * out of range, gg = L^T g and the matrix gradient: as above.
+Its magnitudes: with u = (dv, L dgg) and |u| = (|dv|, |L| |dgg|), dx_mag_d = (1 - clamped_d) / res_d sum_q |u_q| sum over the
+eight corners of (the product of the OTHER two axes' weights) |R_q(corner)| -- every difference b - a along axis d replaced
+by |a| + |b|, which, f lying in [0, 1], covers the kernel's lerps and differences whatever cancels; exactly 0 on a clamped
+axis, so the bound demands an exact zero there.  The gr magnitude is the same blend (all three axes' weights) of |R|; dp_mag
+and dtf_mag follow from dx_mag and gr_mag as above.
 """
 import numpy as np
 import torch
@@ -65,7 +82,44 @@ def _segment_sum(t, key, nkeys):
     return out
 
 
-def composed_vjp(grids, tf, A, pts, dval=None, dgrad=None, leaf=None, chamfer_scale=None):
+def _corner_records(rec, shape, i):
+    """The eight corner records of the cells i (P, 3): (P, 2, 2, 2, 4) float64, [a][b][e] = R[i+a, j+b, k+e]."""
+    ny, nz = int(shape[1]), int(shape[2])
+    i = i.astype(np.int64)
+    out = np.empty((i.shape[0], 2, 2, 2, 4), np.float64)
+    for a in (0, 1):
+        for b in (0, 1):
+            for e in (0, 1):
+                out[:, a, b, e] = rec[((i[:, 0] + a) * ny + (i[:, 1] + b)) * nz + (i[:, 2] + e)]
+    return out
+
+
+def _interp_decisions(interp, x, leaf, oob):
+    """The forward's cell decisions of the in-range pairs, per pair: corner records (A,P,2,2,2,4) f64, fractions (A,P,3) f64
+    (the forward dtype's bits), clamped (A,P,3), resolution (A,P,3) f64 in the forward's statement."""
+    numbers, cell = interp
+    A, P = leaf.shape
+    R = np.zeros((A, P, 2, 2, 2, 4), np.float64)
+    f = np.zeros((A, P, 3), np.float64)
+    cl = np.zeros((A, P, 3), bool)
+    res = np.ones((A, P, 3), np.float64)
+    for s, (rec, shape, mn, rs) in enumerate(numbers):
+        m = (leaf == s) & ~oob
+        if not m.any():
+            continue
+        i, fr, c = cell(shape, mn, rs, np.ascontiguousarray(x[m]))
+        assert fr.dtype == x.dtype, "the cell function must answer in the forward's dtype"
+        R[m] = _corner_records(np.asarray(rec, np.float64), shape, i)
+        f[m], cl[m], res[m] = fr, c, np.asarray(rs, np.float64)
+    return R, f, cl, res
+
+
+def _blend(R, w):
+    """sum over the corners of w_x w_y w_z R: R (P,2,2,2,Q), w a list of three (P,2) weight pairs -> (P,Q)."""
+    return torch.einsum("pa,pb,pe,pabeq->pq", w[0], w[1], w[2], R)
+
+
+def composed_vjp(grids, tf, A, pts, dval=None, dgrad=None, leaf=None, chamfer_scale=None, interp=None):
     """VJP of ComposedSDF.__call__ over the leaves `grids` (list of S oracle.Grid) given the forward's decisions.
 
     tf: (S*A, 4, 4) obj->leaf stack, leaf-major, in the dtype the kernels read (float32, or float64 for float64 points);
@@ -73,6 +127,9 @@ def composed_vjp(grids, tf, A, pts, dval=None, dgrad=None, leaf=None, chamfer_sc
     None; leaf: the forward's winner per pair (A, P) -- from the oracle when None.
     chamfer_scale: the grid-chamfer backward instead (S = 1, every pair on leaf 0, dval = the (B,) upstream of the sums of
     (scale v)^2, dgrad unused).
+    interp: the trilinear mode (module docstring): (numbers, cell) -- numbers[s] = (records [n][4] float32, shape, min, res) of
+    leaf s in the query dtype's statement, cell(shape, min, res, x) -> (i, f, clamped) per point by the forward's statements in
+    x's dtype (tests/interp_ref.py: grid_numbers, cell).  `leaf` must then be given: the trilinear forward's winners.
     Returns dict(dpoints (P,3), dtf (S*A,4,4), dpoints_mag, dtf_mag, leaf (A,P), oob (A,P)), float64 torch on the CPU."""
     pts = np.ascontiguousarray(np.asarray(pts))
     f64 = pts.dtype == np.float64
@@ -82,12 +139,16 @@ def composed_vjp(grids, tf, A, pts, dval=None, dgrad=None, leaf=None, chamfer_sc
     S, P = len(grids), pts.shape[0]
     assert tf.shape[0] == S * A
     if leaf is None:
+        assert interp is None, "the trilinear mode takes its winners from the trilinear forward's restatement"
         if chamfer_scale is not None:
             leaf = np.zeros((A, P), np.int32)
         else:
             leaf = (oracle.composed_query_f64 if f64 else oracle.composed_query)(grids, tf, A, pts)[2]
     leaf = np.ascontiguousarray(leaf, dtype=np.int32).reshape(A, P)
     x, oob, rec, bblo, bbhi = _decisions(grids, tf, A, pts, leaf)
+    if interp is not None:
+        assert chamfer_scale is None and len(interp[0]) == S
+        cR, cf, ccl, cres = _interp_decisions(interp, x, leaf, oob)
 
     T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(torch.float64)
     tf64, p64 = T(tf), T(pts)
@@ -119,6 +180,15 @@ def composed_vjp(grids, tf, A, pts, dval=None, dgrad=None, leaf=None, chamfer_sc
         n = torch.where(ok[:, None], d / nrm[:, None], torch.full_like(d, float("nan")))  # 0 / 0 where the box is not left
         v = torch.where(ok, nrm, torch.zeros_like(nrm))  # in range: a record value, no derivative
         g = torch.where(out[:, None], n, T(rec[a]))
+        if interp is not None:
+            # in range: the blend of the eight records at the forward's fractions (straight-through: the value is the forward's
+            # f, the derivative 1 / res, 0 on a clamped axis); no floor, minimum or maximum is differentiated
+            Ra, keep = T(cR[a]), T(~ccl[a])
+            fs = T(cf[a]) + ((xs - T(x[a])) / T(cres[a])) * keep
+            w3 = [torch.stack((1 - fs[:, d], fs[:, d]), dim=1) for d in range(3)]
+            o = _blend(Ra, w3)
+            v = torch.where(out, v, o[:, 0])
+            g = torch.where(out[:, None], n, o[:, 1:])
         gg = (L.transpose(-1, -2) @ g.unsqueeze(-1)).squeeze(-1)  # gg = L^T g
         loss = torch.zeros((), dtype=torch.float64)
         dv_mag = torch.zeros(P, dtype=torch.float64)
@@ -150,6 +220,15 @@ def composed_vjp(grids, tf, A, pts, dval=None, dgrad=None, leaf=None, chamfer_sc
                 dx_m = dx_m + (dg_m + nm * (nm * dg_m).sum(-1, keepdim=True)) / nrm_d[:, None]
             dx_m = torch.where(act & ok[:, None], dx_m, torch.zeros_like(dx_m))
             gr_m = torch.where(out[:, None], nm, T(rec[a]).abs()) if chamfer_scale is None else torch.zeros_like(nm)
+            if interp is not None:
+                w0 = [w.detach() for w in w3]
+                one = [torch.ones_like(w) for w in w0]
+                u_m = torch.cat((dv_mag[:, None], dg_m), dim=1)  # |u_q|: (|dv|, |L| |dgg|)
+                Rm = Ra.abs()
+                in_m = torch.stack([(_blend(Rm, [one[e] if e == d else w0[e] for e in range(3)]) * u_m).sum(-1)
+                                    for d in range(3)], dim=1) * keep / T(cres[a])
+                dx_m = torch.where(out[:, None], dx_m, in_m)
+                gr_m = torch.where(out[:, None], nm, _blend(Rm, w0)[:, 1:])
             dp_m = (Lm.transpose(-1, -2) @ dx_m.unsqueeze(-1)).squeeze(-1)
             tf_m = torch.zeros(P, 4, 4, dtype=torch.float64)
             tf_m[:, :3, :3] = dx_m.unsqueeze(-1) * p64.abs().unsqueeze(1) + gr_m.unsqueeze(-1) * dgg.abs().unsqueeze(1)
@@ -161,13 +240,15 @@ def composed_vjp(grids, tf, A, pts, dval=None, dgrad=None, leaf=None, chamfer_sc
     return dict(dpoints=dp, dtf=dtf, dpoints_mag=dp_mag, dtf_mag=dtf_mag, leaf=torch.from_numpy(leaf), oob=torch.from_numpy(oob))
 
 
-def cached_vjp(grid, pts, dval=None, dgrad=None):
-    """VJP of CachedSDF.__call__ (one leaf, the identity frame): dict(dpoints, dpoints_mag, oob)."""
+def cached_vjp(grid, pts, dval=None, dgrad=None, interp=None):
+    """VJP of CachedSDF.__call__ (one leaf, the identity frame): dict(dpoints, dpoints_mag, oob).  interp: composed_vjp's, for
+    the one leaf."""
     pts = np.asarray(pts)
     eye = np.eye(4, dtype=pts.dtype if pts.dtype == np.float64 else np.float32)[None]
     P = pts.shape[0]
     r = composed_vjp([grid], eye, 1, pts, None if dval is None else torch.as_tensor(dval).reshape(1, P),
-                     None if dgrad is None else torch.as_tensor(dgrad).reshape(1, P, 3), leaf=np.zeros((1, P), np.int32))
+                     None if dgrad is None else torch.as_tensor(dgrad).reshape(1, P, 3), leaf=np.zeros((1, P), np.int32),
+                     interp=interp)
     return dict(dpoints=r["dpoints"], dpoints_mag=r["dpoints_mag"], oob=r["oob"][0])
 
 

@@ -4,7 +4,9 @@
  * the nearest kernel's out_oob by the tests: points with valid[p] == 0 are left untouched here.
  *
  * rec: [n][4] float (val, gx, gy, gz), C order over shape[3].  mn / res: the query dtype's (fmin / fres for float32 points,
- * dmin / dres for float64).  Forward: val[P], grad[P][3].  VJP: dpts[P][3] for upstream dval[P] and dgrad[P][3]. */
+ * dmin / dres for float64).  Forward: val[P], grad[P][3].  VJP: dpts[P][3] for upstream dval[P] and dgrad[P][3].
+ * interp_cell_* / interp_blend_*: the forward split in two -- its cell decisions (index triple, fractions, clamped flags) and
+ * its lerp sequence for given decisions -- for the decision-conditioned VJP (oracle/conditioned_vjp.py, trilinear mode). */
 #include <math.h>
 #include <stdint.h>
 
@@ -67,6 +69,76 @@ void interp_forward_f64(const float* rec, const int32_t* shape, const double* mn
         double f[3];
         CELL(double, floor, sub_, div_)
         (void)cl;
+        const float* r[8];
+        corners(rec, shape, i, r);
+        double o[4];
+        for (int q = 0; q < 4; ++q) {
+            double e[4];
+            for (int ab = 0; ab < 4; ++ab) e[ab] = lerp_((double)r[2 * ab][q], (double)r[2 * ab + 1][q], f[2]);
+            o[q] = lerp_(lerp_(e[0], e[1], f[1]), lerp_(e[2], e[3], f[1]), f[0]);
+        }
+        val[p] = o[0];
+        for (int d = 0; d < 3; ++d) grad[3 * p + d] = o[1 + d];
+    }
+}
+
+/* The cell decisions alone, by the forward's own CELL statements: per point the corner index triple idx[P][3], the fractions
+ * frac[P][3] in the query dtype and clamped[P][3] (0 / 1).  Every point is evaluated (the range decision is the caller's). */
+void interp_cell_f32(const int32_t* shape, const float* mn, const float* res, const float* pts, int64_t P, int32_t* idx,
+                     float* frac, uint8_t* clamped) {
+    for (int64_t p = 0; p < P; ++p) {
+        const float* x = pts + 3 * p;
+        int i[3], cl[3];
+        float f[3];
+        CELL(float, floorf, subf_, divf_)
+        for (int d = 0; d < 3; ++d) {
+            idx[3 * p + d] = i[d];
+            frac[3 * p + d] = f[d];
+            clamped[3 * p + d] = (uint8_t)cl[d];
+        }
+    }
+}
+
+void interp_cell_f64(const int32_t* shape, const double* mn, const double* res, const double* pts, int64_t P, int32_t* idx,
+                     double* frac, uint8_t* clamped) {
+    for (int64_t p = 0; p < P; ++p) {
+        const double* x = pts + 3 * p;
+        int i[3], cl[3];
+        double f[3];
+        CELL(double, floor, sub_, div_)
+        for (int d = 0; d < 3; ++d) {
+            idx[3 * p + d] = i[d];
+            frac[3 * p + d] = f[d];
+            clamped[3 * p + d] = (uint8_t)cl[d];
+        }
+    }
+}
+
+/* The forward's blend of the eight corner records for GIVEN cell decisions (idx, frac as interp_cell_* returns them): the lerp
+ * sequence of interp_forward_*, so that cell + blend is the forward bit for bit. */
+void interp_blend_f32(const float* rec, const int32_t* shape, const int32_t* idx, const float* frac, int64_t P, float* val,
+                      float* grad) {
+    for (int64_t p = 0; p < P; ++p) {
+        const int i[3] = {idx[3 * p], idx[3 * p + 1], idx[3 * p + 2]};
+        const float* f = frac + 3 * p;
+        const float* r[8];
+        corners(rec, shape, i, r);
+        float o[4];
+        for (int q = 0; q < 4; ++q) {
+            float e[4];
+            for (int ab = 0; ab < 4; ++ab) e[ab] = lerpf_(r[2 * ab][q], r[2 * ab + 1][q], f[2]);
+            o[q] = lerpf_(lerpf_(e[0], e[1], f[1]), lerpf_(e[2], e[3], f[1]), f[0]);
+        }
+        val[p] = o[0];
+        for (int d = 0; d < 3; ++d) grad[3 * p + d] = o[1 + d];
+    }
+}
+
+void interp_blend_f64(const float* rec, const int32_t* shape, const int32_t* idx, const double* frac, int64_t P, double* val,
+                      double* grad) {
+    for (int64_t p = 0; p < P; ++p) {
+        const int i[3] = {idx[3 * p], idx[3 * p + 1], idx[3 * p + 2]};
+        const double* f = frac + 3 * p;
         const float* r[8];
         corners(rec, shape, i, r);
         double o[4];

@@ -1,6 +1,6 @@
 """Restatements of the trilinear contract (include/pvamd.h "Interpolated queries") for the interpolation tests -- TEST
-INFRASTRUCTURE: interp_ref.c compiled on the fly (bit-exact forward, float64 per-point VJP) and a float64 torch restatement
-that autograd differentiates given the kernel's decisions."""
+INFRASTRUCTURE: interp_ref.c compiled on the fly (bit-exact forward, the forward's cell decisions and blend on their own,
+float64 per-point VJP) and a float64 torch restatement that autograd differentiates given the kernel's decisions."""
 import ctypes
 import os
 import subprocess
@@ -48,6 +48,35 @@ def forward(rec, shape, mn, res, pts, valid):
     fn = load().interp_forward_f64 if f64 else load().interp_forward_f32
     fn(_p(rec), _p(shape), _p(np.ascontiguousarray(mn, pts.dtype)), _p(np.ascontiguousarray(res, pts.dtype)), _p(pts),
        ctypes.c_int64(P), _p(valid), _p(val), _p(grad))
+    return val, grad
+
+
+def cell(shape, mn, res, pts):
+    """The forward's cell decisions per point, in pts' dtype (float32 / float64): (i (P, 3) int32, f (P, 3), clamped (P, 3) bool).
+    The signature oracle.conditioned_vjp's trilinear mode asks of its cell function."""
+    pts = np.ascontiguousarray(pts)
+    assert pts.dtype in (np.float32, np.float64)
+    f64 = pts.dtype == np.float64
+    P = pts.shape[0]
+    idx = np.zeros((P, 3), np.int32)
+    frac = np.zeros((P, 3), pts.dtype)
+    cl = np.zeros((P, 3), np.uint8)
+    fn = load().interp_cell_f64 if f64 else load().interp_cell_f32
+    fn(_p(np.ascontiguousarray(shape, np.int32)), _p(np.ascontiguousarray(mn, pts.dtype)), _p(np.ascontiguousarray(res, pts.dtype)),
+       _p(pts), ctypes.c_int64(P), _p(idx), _p(frac), _p(cl))
+    return idx, frac, cl.astype(bool)
+
+
+def blend(rec, shape, idx, frac):
+    """(val, grad) of the forward's lerp sequence for given cell decisions, in frac's dtype."""
+    frac = np.ascontiguousarray(frac)
+    f64 = frac.dtype == np.float64
+    P = frac.shape[0]
+    val = np.empty((P,), frac.dtype)
+    grad = np.empty((P, 3), frac.dtype)
+    fn = load().interp_blend_f64 if f64 else load().interp_blend_f32
+    fn(_p(rec), _p(np.ascontiguousarray(shape, np.int32)), _p(np.ascontiguousarray(idx, np.int32)), _p(frac), ctypes.c_int64(P),
+       _p(val), _p(grad))
     return val, grad
 
 

@@ -1,6 +1,7 @@
 """-m gpu: interpolation="trilinear" (csrc/lane_query.hip, the interpolated leaf of csrc/backward.hip) against the CPU restatement of
 its arithmetic contract (tests/interp_ref.c: bit for bit) and, for gradients, float64 torch autograd through the same
-expressions given the kernel's decisions."""
+expressions given the kernel's decisions.  The gradient checks here keep away from cell, range and box faces; the backward's
+behaviour AT those edges is held to a worst-case bound in tests/test_interp_edges_gpu.py."""
 import ctypes
 import math
 import tempfile
