@@ -776,6 +776,58 @@ int pvamd_chamfer_normal_eq(const pvamd_grid_t* grid, int32_t mode, const float*
 int pvamd_pose_lm_step(int32_t B, const double* sums, int32_t first, double* Wacc, double* sums_acc, double* lambda,
                        int32_t* accepted, double* Wtry, float* W_next, double up, double down, double lambda_min,
                        double lambda_max, void* stream);
+
+/* ---- Ray casting (CachedSDF.ray_cast / ComposedSDF.ray_cast / RobotSDF.ray_cast) ----
+ * Sphere tracing: where the ray o + t d first meets the surface of one cached grid (3-D, BOUNDING_BOX, else PVAMD_E_MODE; either
+ * index arithmetic) or of a composition ("Minimum over points": S leaves, A configurations, tf device [S*A][4][4] leaf-major,
+ * rigid; the rays are given in the object frame and shared by the configurations).  sdf(p) = (v, g): the bits of
+ * pvamd_cached_query / _interp / _f64 / _interp_f64 (one grid) or of the fused composed forwards (a composition) at p, chosen by
+ * mode (PVAMD_LEAF_NEAREST / PVAMD_LEAF_TRILINEAR) and the element type T of the entry point.
+ *  1. Scalars, all in T: t_min and t_max not NaN (t_max = +inf allowed), eps finite and >= 0, step_scale finite and > 0, else
+ *     PVAMD_E_MODE; 1 <= max_steps <= 65535, else PVAMD_E_SHAPE.
+ *  2. Per ray, every product and sum rounded separately in T (no fused multiply-add): what an elementwise o + t * d gives.
+ *         t = t_min; steps = 0; status = MAX_STEPS; v = NaN; g = (NaN, NaN, NaN)
+ *         if not (t <= t_max): status = MISS
+ *         else repeat max_steps times:
+ *             p_j = o_j + t * d_j   (j = 0..2)
+ *             (v, g) = sdf(p); steps += 1
+ *             if v != v:  status = INVALID; stop
+ *             if v <= eps: status = HIT; stop
+ *             tn = t + step_scale * v
+ *             if not (tn <= t_max): status = MISS; stop
+ *             t = tn
+ *  3. Outputs per ray: out_t = the t of the last evaluated p (t_min when none was; for MAX_STEPS the t of evaluation max_steps,
+ *     not the tn after it), so o + out_t d is where out_val / out_grad were read; out_status uint8 (PVAMD_RAY_*); out_val /
+ *     out_grad the last (v, g); out_steps int32.
+ *  4. Directions are the caller's: meant to be unit length, any other length scales the step.  A NaN in o or d ends as INVALID
+ *     or MISS by the rules above; the loop is bounded by max_steps whatever the input.
+ *  5. Nearest-mode values are piecewise constant (one voxel-centre sample per voxel), so a nearest grid can overshoot the
+ *     surface by up to half a voxel diagonal; PVAMD_LEAF_TRILINEAR or step_scale < 1 is the remedy.
+ * One lane per (configuration, ray), rays in caller order; a wave leaves the step loop when all its rays have stopped.  Raw device
+ * pointers, stream-ordered, no allocation, no scratch, no device -> host synchronisation, no atomics: capturable in a graph.
+ * Argument errors return before any launch.
+ * pvamd_cached_ray_cast / _f64: origins, directions device [R][3]; out_t, out_val, out_steps [R], out_status [R] uint8, out_grad
+ *   [R][3].  0 <= R (R = 0 does nothing).
+ * pvamd_composed_ray_cast / _f64: the outputs are [A][R] ([A][R][3]): row a is the loop above under configuration a alone.
+ *   1 <= S, 0 <= A, 0 <= R (A = 0 or R = 0 does nothing).                                                                          */
+#define PVAMD_RAY_MISS      0  /* left [t_min, t_max] (or t_min > t_max) without a hit */
+#define PVAMD_RAY_HIT       1  /* v <= eps at out_t                                    */
+#define PVAMD_RAY_MAX_STEPS 2  /* max_steps evaluations without a decision             */
+#define PVAMD_RAY_INVALID   3  /* the query returned NaN at out_t                      */
+int pvamd_cached_ray_cast(const pvamd_grid_t* grid, int32_t mode, const float* origins, const float* directions, int64_t R,
+                          float t_min, float t_max, float eps, float step_scale, int32_t max_steps, float* out_t,
+                          uint8_t* out_status, float* out_val, float* out_grad, int32_t* out_steps, void* stream);
+int pvamd_cached_ray_cast_f64(const pvamd_grid_t* grid, int32_t mode, const double* origins, const double* directions, int64_t R,
+                              double t_min, double t_max, double eps, double step_scale, int32_t max_steps, double* out_t,
+                              uint8_t* out_status, double* out_val, double* out_grad, int32_t* out_steps, void* stream);
+int pvamd_composed_ray_cast(const pvamd_grid_t* grids, int32_t S, const float* tf, int32_t A, const float* origins,
+                            const float* directions, int64_t R, int32_t mode, float t_min, float t_max, float eps,
+                            float step_scale, int32_t max_steps, float* out_t, uint8_t* out_status, float* out_val, float* out_grad,
+                            int32_t* out_steps, void* stream);
+int pvamd_composed_ray_cast_f64(const pvamd_grid_t* grids, int32_t S, const double* tf, int32_t A, const double* origins,
+                                const double* directions, int64_t R, int32_t mode, double t_min, double t_max, double eps,
+                                double step_scale, int32_t max_steps, double* out_t, uint8_t* out_status, double* out_val,
+                                double* out_grad, int32_t* out_steps, void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -30,6 +30,7 @@ LEAF_MODES = {"nearest": 0, "trilinear": 1}  # PVAMD_LEAF_NEAREST / PVAMD_LEAF_T
 MOP_CHUNK = 4096  # PVAMD_MOP_CHUNK
 REG_CHUNK = 2048  # PVAMD_REG_CHUNK
 REG_SUMS = 28     # PVAMD_REG_SUMS: the row length of pvamd_chamfer_normal_eq's out_sums
+RAY_MISS, RAY_HIT, RAY_MAX_STEPS, RAY_INVALID = 0, 1, 2, 3  # PVAMD_RAY_*: the status codes of the ray-cast entry points
 
 
 # Buffer sizes: the library's exported size functions are the definition (include/pvamd.h) -- what they report is what the
@@ -326,6 +327,11 @@ SIGNATURES = {
     "pvamd_chamfer_normal_eq_scratch_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int64]),
     "pvamd_chamfer_normal_eq": (ctypes.c_int, [ctypes.POINTER(GridDesc), ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "pvamd_pose_lm_step": (ctypes.c_int, [ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_void_p]),
+    # CachedSDF / ComposedSDF.ray_cast (include/pvamd.h "Ray casting")
+    "pvamd_cached_ray_cast": (ctypes.c_int, [ctypes.POINTER(GridDesc), ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "pvamd_cached_ray_cast_f64": (ctypes.c_int, [ctypes.POINTER(GridDesc), ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "pvamd_composed_ray_cast": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "pvamd_composed_ray_cast_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
 }
 
 E_SHAPE = -2  # PVAMD_E_SHAPE (include/pvamd.h)

@@ -43,6 +43,20 @@ class MinOverPoints(NamedTuple):
     gradients: torch.Tensor
 
 
+class RayCast(NamedTuple):
+    """CachedSDF.ray_cast / ComposedSDF.ray_cast / RobotSDF.ray_cast: per ray the parameter t of the last evaluated point
+    o + t d, why the march stopped (RAY_MISS / RAY_HIT / RAY_MAX_STEPS / RAY_INVALID, uint8), the value and gradient read there
+    and the number of evaluations (int32) (include/pvamd.h "Ray casting")."""
+    t: torch.Tensor
+    status: torch.Tensor
+    values: torch.Tensor
+    gradients: torch.Tensor
+    steps: torch.Tensor
+
+
+RAY_MISS, RAY_HIT, RAY_MAX_STEPS, RAY_INVALID = _lib.RAY_MISS, _lib.RAY_HIT, _lib.RAY_MAX_STEPS, _lib.RAY_INVALID
+
+
 class HingeOverPoints(NamedTuple):
     """ComposedSDF.hinge_over_points / RobotSDF.hinge_over_points: per pair, sum over points of max(margin - v, 0) ** power and
     the number of points with v < margin (include/pvamd.h "Hinge penalty over points")."""
@@ -77,6 +91,92 @@ def _hinge_args(margin, power):
     if isinstance(power, bool) or power not in (1, 2):
         raise ValueError(f"power must be 1 or 2, got {power!r}")
     return margin, int(power)
+
+
+def _ray_args(t_min, t_max, hit_tolerance, step_scale, max_steps):
+    """The five scalars of a ray cast as (float, float, float, float, int), or the error include/pvamd.h "Ray casting" asks for;
+    the caller rounds the reals once to the query dtype."""
+    reals = {"t_min": t_min, "t_max": t_max, "hit_tolerance": hit_tolerance, "step_scale": step_scale}
+    for name, x in reals.items():
+        if isinstance(x, bool) or not isinstance(x, numbers.Real):
+            raise TypeError(f"{name} must be a Python real number, got {type(x).__name__}")
+        reals[name] = float(x)
+    if isinstance(max_steps, bool) or not isinstance(max_steps, numbers.Integral):
+        raise TypeError(f"max_steps must be an integer, got {type(max_steps).__name__}")
+    if math.isnan(reals["t_min"]) or math.isnan(reals["t_max"]):
+        raise ValueError(f"t_min and t_max must not be NaN, got {t_min!r} and {t_max!r}")
+    if not (math.isfinite(reals["hit_tolerance"]) and reals["hit_tolerance"] >= 0):
+        raise ValueError(f"hit_tolerance must be finite and >= 0, got {hit_tolerance!r}")
+    if not (math.isfinite(reals["step_scale"]) and reals["step_scale"] > 0):
+        raise ValueError(f"step_scale must be finite and > 0, got {step_scale!r}")
+    if not 1 <= max_steps <= 65535:
+        raise ValueError(f"max_steps must lie in [1, 65535], got {max_steps!r}")
+    return reals["t_min"], reals["t_max"], reals["hit_tolerance"], reals["step_scale"], int(max_steps)
+
+
+def _ray_inputs(origins, directions):
+    """(origins, directions) broadcast against each other -> (origins, directions, lead, dtype): both detached, of the broadcast
+    shape lead + (3,) (views, not yet contiguous) and of one floating dtype (an integer dtype counts as float32, as for points)."""
+    if not torch.is_tensor(origins):
+        origins = torch.as_tensor(origins)
+    if not torch.is_tensor(directions):
+        directions = torch.as_tensor(directions)
+    for name, x in (("origins", origins), ("directions", directions)):
+        if x.dim() < 1 or x.shape[-1] != 3:
+            raise ValueError(f"ray {name} must have last dimension 3, got {tuple(x.shape)}")
+    try:
+        shape = torch.broadcast_shapes(origins.shape, directions.shape)
+    except RuntimeError as e:
+        raise ValueError(f"ray origins {tuple(origins.shape)} and directions {tuple(directions.shape)} do not broadcast") from e
+    dtype = torch.promote_types(origins.dtype, directions.dtype)
+    if not dtype.is_floating_point:
+        dtype = torch.float32
+    return origins.detach().expand(shape), directions.detach().expand(shape), tuple(shape[:-1]), dtype
+
+
+def _ray_outputs(shape, dtype, dev):
+    """(t, status, values, gradients, steps) buffers of the ray-cast entry points, in the C ABI's argument order."""
+    return (torch.empty(shape, dtype=dtype, device=dev), torch.empty(shape, dtype=torch.uint8, device=dev),
+            torch.empty(shape, dtype=dtype, device=dev), torch.empty((*shape, 3), dtype=dtype, device=dev),
+            torch.empty(shape, dtype=torch.int32, device=dev))
+
+
+def _ray_result(out, shape, device):
+    t, status, val, grad, steps = out
+    return RayCast(t.reshape(shape).to(device), status.reshape(shape).to(device), val.reshape(shape).to(device),
+                   grad.reshape(*shape, 3).to(device), steps.reshape(shape).to(device))
+
+
+def _ray_march(sdf, o, d, t_min, t_max, eps, step_scale, max_steps):
+    """The loop of include/pvamd.h "Ray casting" in torch around sdf(points) for (R, 3) rays of one dtype on one device: every
+    step queries all the rays and torch.where keeps the finished ones as they were.  Stops early (one device -> host
+    synchronisation per step) when no ray is left marching.  Returns the five (R,) / (R, 3) results."""
+    R, dtype, dev = o.shape[0], o.dtype, o.device
+    t_max, eps, step_scale = (torch.tensor(x, dtype=dtype, device=dev) for x in (t_max, eps, step_scale))
+    t = torch.full((R,), t_min, dtype=dtype, device=dev)
+    t_read = t  # the parameter of each ray's last evaluated point: what is reported (after max_steps, t itself has moved on)
+    v = torch.full((R,), math.nan, dtype=dtype, device=dev)
+    g = torch.full((R, 3), math.nan, dtype=dtype, device=dev)
+    steps = torch.zeros((R,), dtype=torch.int32, device=dev)
+    active = t <= t_max
+    status = torch.where(active, RAY_MAX_STEPS, RAY_MISS).to(torch.uint8)
+    for _ in range(max_steps):
+        if not bool(active.any()):
+            break
+        vv, gg = sdf(o + t.unsqueeze(-1) * d)
+        vv, gg = vv.reshape(R).to(device=dev, dtype=dtype), gg.reshape(R, 3).to(device=dev, dtype=dtype)
+        v, g, t_read = torch.where(active, vv, v), torch.where(active.unsqueeze(-1), gg, g), torch.where(active, t, t_read)
+        steps = steps + active.to(torch.int32)
+        nan = vv != vv
+        hit = ~nan & (vv <= eps)
+        tn = t + step_scale * vv
+        miss = ~nan & ~hit & ~(tn <= t_max)
+        go = active & ~nan & ~hit & ~miss
+        for code, stop in ((RAY_INVALID, nan), (RAY_HIT, hit), (RAY_MISS, miss)):
+            status = torch.where(active & stop, torch.tensor(code, dtype=torch.uint8, device=dev), status)
+        t = torch.where(go, tn, t)
+        active = go
+    return t_read, status, v, g, steps
 
 
 def first_argmin(v):
@@ -351,6 +451,37 @@ class ObjectFrameSDF(abc.ABC):
     def outside_surface(self, points_in_object_frame, surface_level=0):
         sdf_values, _ = self.__call__(points_in_object_frame)
         return sdf_values > surface_level
+
+    def ray_cast(self, origins, directions, t_min=0., t_max=math.inf, hit_tolerance=1e-3, step_scale=1., max_steps=128):
+        """Sphere tracing: where each ray origins + t * directions first meets the surface (include/pvamd.h "Ray casting").
+
+        :param origins, directions: (..., 3), broadcast against each other and promoted to one dtype (the dtype and device rules
+            of __call__; an integer dtype counts as float32).  Directions are meant to be unit length: any other length scales
+            the step.
+        :param t_min, t_max: the march starts at t_min and stops as MISS once the next t would pass t_max (+inf allowed)
+        :param hit_tolerance: a ray stops as HIT at the first evaluated point whose value is <= hit_tolerance
+        :param step_scale: each step advances t by step_scale * value
+        :param max_steps: at most this many evaluations per ray (1 .. 65535); a ray still marching then reports MAX_STEPS
+        :return: RayCast(t, status, values, gradients, steps) of shapes (...), (...), (...), (..., 3), (...): t is the parameter of
+            the last evaluated point (t_min when none was), values / gradients are the bits __call__ returns there (NaN when none
+            was), status is uint8 (RAY_MISS, RAY_HIT, RAY_MAX_STEPS, RAY_INVALID: the query returned NaN), steps int32.  Each real
+            scalar is rounded once to the rays' dtype, and every product and sum is rounded separately in it.  No rays give empty
+            results.  The result carries no autograd graph: rays that require grad are accepted and detached.
+
+        This is the loop in torch around __call__ -- every SDF has it; it is not a hot path and synchronises once per step.
+        CachedSDF and ComposedSDF run it as one HIP kernel where they can (csrc/ray_cast.hip)."""
+        args = _ray_args(t_min, t_max, hit_tolerance, step_scale, max_steps)
+        o, d, lead, dtype = _ray_inputs(origins, directions)
+        return self._ray_cast_generic(o, d, lead, dtype, args)
+
+    def _ray_cast_generic(self, o, d, lead, dtype, args):
+        """ray_cast after the argument checks: the torch loop around __call__ on the rays' own device."""
+        dev = o.device if o.device.type != "cpu" else d.device
+        o = o.reshape(-1, 3).to(device=dev, dtype=dtype)
+        d = d.reshape(-1, 3).to(device=dev, dtype=dtype)
+        with torch.no_grad():
+            t, status, v, g, steps = _ray_march(self.__call__, o, d, *args)
+        return RayCast(t.reshape(lead), status.reshape(lead), v.reshape(lead), g.reshape(*lead, 3), steps.reshape(lead))
 
     def get_voxel_view(self, voxels=None, dtype=torch.float, device='cpu'):
         """The SDF sampled at the centres of a voxel grid, addressed by coordinates (sdf.py:248-264): ONE batched
@@ -786,6 +917,33 @@ class CachedSDF(ObjectFrameSDF):
             _lib.check(entry(ctypes.byref(desc), _lib.ptr(flat), P, _lib.ptr(val), _lib.ptr(grad), _lib.ptr(oob), _lib.stream_ptr()),
                        name)
         return val, grad, oob
+
+    def ray_cast(self, origins, directions, t_min=0., t_max=math.inf, hit_tolerance=1e-3, step_scale=1., max_steps=128):
+        """ObjectFrameSDF.ray_cast (arguments, results and contract there; include/pvamd.h "Ray casting") against this cache, in the
+        cache's interpolation.  A 3-D BOUNDING_BOX cache with float32 or float64 rays is ONE kernel launch (csrc/ray_cast.hip:
+        a lane per ray, the whole march in registers, nothing but the results written) with nothing that synchronises with the
+        host, so it can be captured in a graph; LOOKUP_GT_SDF caches and other dtypes run the torch loop around __call__.
+        Planar caches raise.  Results are returned on this cache's device; they carry no autograd graph.
+
+        A nearest cache is piecewise constant -- one voxel-centre sample per voxel -- so the march can overshoot the surface
+        by up to half a voxel diagonal: interpolation="trilinear" or step_scale < 1 is the remedy."""
+        args = _ray_args(t_min, t_max, hit_tolerance, step_scale, max_steps)
+        o, d, lead, dtype = _ray_inputs(origins, directions)
+        if self._dim != 3:
+            raise ValueError("ray_cast needs a 3-D cache, this one is planar")
+        if self.out_of_bounds_strategy != OutOfBoundsStrategy.BOUNDING_BOX or self.debug_check_sdf or \
+                dtype not in (torch.float32, torch.float64):
+            return self._ray_cast_generic(o, d, lead, dtype, args)
+        dev = self._packed.device
+        o = o.reshape(-1, 3).to(device=dev, dtype=dtype).contiguous()
+        d = d.reshape(-1, 3).to(device=dev, dtype=dtype).contiguous()
+        R = o.shape[0]
+        out = _ray_outputs((R,), dtype, dev)
+        name = "pvamd_cached_ray_cast" + ("_f64" if dtype == torch.float64 else "")
+        with _lib.on_device(dev):
+            _lib.check(getattr(_lib.load(), name)(ctypes.byref(self._grid_desc()), _lib.LEAF_MODES[self.interpolation], _lib.ptr(o),
+                                                  _lib.ptr(d), R, *args, *map(_lib.ptr, out), _lib.stream_ptr()), name)
+        return _ray_result(out, lead, self.device)
 
     def outside_surface(self, points_in_object_frame, surface_level=0):
         """sdf.py:593-602 (trilinear caches: the interpolated value > surface_level in range, True out of range)"""
@@ -1341,6 +1499,58 @@ class ComposedSDF(ObjectFrameSDF):
         v = val.gather(1, idx.unsqueeze(1)).squeeze(1)
         g = grad.gather(1, idx.view(A, 1, 1).expand(A, 1, 3)).squeeze(1)
         return MinOverPoints(v.reshape(batch), idx.reshape(batch), g.reshape(*batch, 3))
+
+    # ---- ray casting ----
+    def ray_cast(self, origins, directions, t_min=0., t_max=math.inf, hit_tolerance=1e-3, step_scale=1., max_steps=128):
+        """ObjectFrameSDF.ray_cast (arguments and contract there; include/pvamd.h "Ray casting") against the composition under every
+        configuration: the rays are given in the composition's object frame and shared by all configurations.
+
+        :return: RayCast(t, status, values, gradients, steps) of shapes B + (...) (gradients B + (..., 3)), B the transform batch
+            shape (() without one) and (...) the broadcast shape of origins and directions without its last dimension.  Row a is,
+            bit for bit, the loop over configuration a alone, with the values and gradients __call__ returns.  The result carries
+            no autograd graph: rays (and transforms) that require grad are accepted and detached.
+
+        Fused compositions (_fused_mode(): every leaf a BOUNDING_BOX CachedSDF of one interpolation, rigid transforms) with float32
+        or float64 rays run ONE kernel (csrc/ray_cast.hip: a lane per configuration and ray) that writes nothing but the results
+        and does not synchronise with the host, so the call can be captured in a graph; anything else runs the torch loop around
+        __call__, one configuration at a time.  Nearest leaves can overshoot the surface by up to half a voxel diagonal (see
+        CachedSDF.ray_cast)."""
+        args = _ray_args(t_min, t_max, hit_tolerance, step_scale, max_steps)
+        o, d, lead, dtype = _ray_inputs(origins, directions)
+        if self._tf_matrix is None:
+            raise ValueError("ray_cast needs the transforms to be set")
+        batch = tuple(self.tsf_batch) if self.tsf_batch is not None else ()
+        mode = self._fused_mode()
+        if mode is None or dtype not in (torch.float32, torch.float64):
+            return self._ray_cast_per_configuration(o, d, lead, dtype, args, batch)
+        S, A = len(self.sdfs), math.prod(batch)
+        dev = self._owner_device()
+        o = o.reshape(-1, 3).to(device=dev, dtype=dtype).contiguous()
+        d = d.reshape(-1, 3).to(device=dev, dtype=dtype).contiguous()
+        _, tfd, _ = self._fused_inputs(o, dev)
+        R = o.shape[0]
+        out = _ray_outputs((A, R), dtype, dev)
+        name = "pvamd_composed_ray_cast" + ("_f64" if dtype == torch.float64 else "")
+        with _lib.on_device(dev):
+            grids = self._leaf_grids(dev)
+            _lib.check(getattr(_lib.load(), name)(_lib.ptr(grids), S, _lib.ptr(tfd), A, _lib.ptr(o), _lib.ptr(d), R,
+                                                  _lib.LEAF_MODES[mode], *args, *map(_lib.ptr, out), _lib.stream_ptr()), name)
+        return _ray_result(out, batch + lead, self.sdfs[0].device)  # leaves return on their own device (sdf.py:546)
+
+    def _ray_cast_per_configuration(self, o, d, lead, dtype, args, batch):
+        """Compositions the kernel does not serve (other leaves, mixed modes, non-rigid transforms, other dtypes): the torch loop
+        around __call__ for each configuration's own composition -- not a hot path."""
+        S, A = len(self.sdfs), math.prod(batch)
+        stack = self._tf_matrix.detach().reshape(S, A, 4, 4)
+        rows = []
+        for a in range(A):
+            one = ComposedSDF(self.sdfs, None)
+            one.set_transforms(stack[:, a], known_rigid=self._rigid)
+            rows.append(one._ray_cast_generic(o, d, lead, dtype, args))
+        if not rows:
+            dev = o.device if o.device.type != "cpu" else d.device
+            return _ray_result(_ray_outputs(batch + lead, dtype, dev), batch + lead, dev)
+        return RayCast(*(torch.stack(x).reshape(*batch, *x[0].shape) for x in zip(*rows)))
 
     # ---- hinge penalty over points ----
     def hinge_over_points(self, points, margin, power=2, per_leaf=False):
