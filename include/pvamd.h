@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define PVAMD_ABI_VERSION 15
+#define PVAMD_ABI_VERSION 16
 
 #define PVAMD_E_NULL      (-1)  /* a required pointer is NULL            */
 #define PVAMD_E_SHAPE     (-2)  /* a size/shape argument is out of range */
@@ -361,6 +361,16 @@ int64_t pvamd_morton_order_scratch_bytes(int64_t P);
 int pvamd_morton_order(const float* points, int64_t P, int32_t* order_out, int32_t* inv_out, float* sorted_points_out,
                        void* scratch, void* stream);
 
+/* Host-side, pure: which sort pvamd_morton_order runs for P points (the choice depends on P only, csrc/sort.hip order_kind),
+ * and on how many leading bits of the 30-bit curve key it sorts: 12 in the one workgroup, PVAMD_MORTON_ORDER_BITS(P) beyond
+ * -- for tests that want both sides of every threshold and restate neither.  PVAMD_E_SHAPE for a P that pvamd_morton_order
+ * refuses. (ABI 16)                                                                                                    */
+#define PVAMD_ORDER_KERNEL_SMALL     0  /* order_small_kernel: one workgroup, one launch, no scratch used             */
+#define PVAMD_ORDER_KERNEL_COUNTING  1  /* the seven-launch counting sort; points of a cell in a run-dependent order  */
+#define PVAMD_ORDER_KERNEL_RADIX     2  /* the LSD radix sort of (cell, index) pairs; points of a cell in index order */
+int pvamd_morton_order_kernel(int64_t P);
+int pvamd_morton_order_bits(int64_t P);
+
 /* ObjectFactory._do_object_frame_closest_point (sdf.py:122-172): closest surface point, signed distance by
  * ray-hit parity, gradient, face id, optional face normal.
  * mesh: host struct with device pointers.  order: device [P] int32 permutation or NULL -- the k-th lane processes
@@ -388,6 +398,34 @@ int64_t pvamd_mesh_small_points(void);  /* PVAMD_MESH_SMALL_POINTS */
 int pvamd_mesh_query(const pvamd_mesh_t* mesh, const float* points, const int32_t* order, int64_t P,
                      uint64_t jitter_seed, int64_t index_base, float* out_closest, float* out_dist, float* out_grad, int32_t* out_face,
                      float* out_normal, void* scratch, void* stream);
+
+/* Host-side, pure: the launches pvamd_mesh_query (unordered = 0), pvamd_mesh_query_unordered (unordered = 1) and
+ * pvamd_cache_build (P = nx*ny*nz, unordered = 0) make for P points against a mesh of F faces, with (has_scratch != 0) or
+ * without a scratch buffer -- csrc/mesh.hip mesh_query_plan, the one place that decides them; for tests that want every
+ * path and every kernel instantiation covered at the sizes that reach it, and for a profile that wants to name what it
+ * measured.  pvamd_chamfer_mesh_plan: the same for pvamd_chamfer_mesh (rows = B) and pvamd_chamfer_mesh_flat (rows = 1,
+ * N = B * per).  Both return PVAMD_E_SHAPE for sizes the entry points refuse (and unordered with more than
+ * PVAMD_MESH_SMALL_POINTS points), PVAMD_E_NULL without plan_out; a call that launches no mesh kernel (no points, no
+ * rows, a chamfer against no faces) is PVAMD_MESH_PATH_NONE with every field 0. (ABI 16)                              */
+#define PVAMD_MESH_PATH_NONE        0  /* nothing to do                                                                   */
+#define PVAMD_MESH_PATH_LISTED      1  /* every group listed (hand_over_all / small_prep + gather), then mesh_parts_all_kernel<part_waves>,
+                                          grid (groups, parts), which also writes the outputs                              */
+#define PVAMD_MESH_PATH_SCAN        2  /* one launch of mesh_query_kernel / chamfer_mesh_kernel<scan_waves>                */
+#define PVAMD_MESH_PATH_SCAN_HEAVY  3  /* that scan listing its heavy groups, mesh_parts_kernel over (list, parts), a finish launch */
+#define PVAMD_MESH_ORDER_GIVEN      0  /* the caller's `order` (or none)                                                   */
+#define PVAMD_MESH_ORDER_INSIDE     1  /* unordered: worked out by one workgroup of the first launch of the listed path    */
+#define PVAMD_MESH_ORDER_SORT_CALL  2  /* unordered: a pvamd_morton_order call in front of the scan                        */
+typedef struct pvamd_mesh_plan_t {
+    int32_t path;        /* PVAMD_MESH_PATH_*                                                                             */
+    int32_t order;       /* PVAMD_MESH_ORDER_*                                                                            */
+    int32_t groups;      /* groups of 64 points: grid.x of the scan and of the listed launches (per row for a chamfer)     */
+    int32_t slots;       /* PVAMD_MESH_SCRATCH_SLOTS of the point count: the groups a scratch buffer can list              */
+    int32_t scan_waves;  /* waves per point group of the scan launch, 1 / 2 / 4 / 8; 0 on the listed path                  */
+    int32_t parts;       /* workgroups the tiles of one listed group are spread over (grid.y of the parts launch); 0: scan */
+    int32_t part_waves;  /* waves per workgroup of the parts launch, 2 or 4; 0 on the scan path                            */
+} pvamd_mesh_plan_t;
+int pvamd_mesh_query_plan(int64_t P, int32_t F, int32_t has_scratch, int32_t unordered, pvamd_mesh_plan_t* plan_out);
+int pvamd_chamfer_mesh_plan(int64_t N, int32_t rows, int32_t F, int32_t has_scratch, pvamd_mesh_plan_t* plan_out);
 
 /* CachedSDF construction from a mesh on the device (sdf.py:498-516: the ground-truth SDF over every voxel centre of the grid
  * voxel.py:20-25 builds, then the two arrays the reference keeps), in at most three launches for a small grid: the voxel

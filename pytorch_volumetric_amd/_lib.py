@@ -12,7 +12,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PVAMD_LIB") or os.path.join(_HERE, "csrc", "libpvamd.so")  # PVAMD_LIB: A/B builds (tools/)
 
-ABI_VERSION = 15
+ABI_VERSION = 16
 OOB_LOOKUP_GT_SDF = 0
 OOB_BOUNDING_BOX = 1
 COMPOSED_INLINE_EXACT = 1
@@ -22,6 +22,9 @@ COMPOSED_OUT_PACKED = 32
 COMPOSED_NO_GROUPING = 64
 COMPOSED_FORCE_FUSED = 128
 CO_KERNEL_PER_LANE, CO_KERNEL_WAVE_TILE, CO_KERNEL_FUSED = 0, 1, 2  # PVAMD_CO_KERNEL_* (include/pvamd.h)
+ORDER_KERNEL_SMALL, ORDER_KERNEL_COUNTING, ORDER_KERNEL_RADIX = 0, 1, 2  # PVAMD_ORDER_KERNEL_*
+MESH_PATH_NONE, MESH_PATH_LISTED, MESH_PATH_SCAN, MESH_PATH_SCAN_HEAVY = 0, 1, 2, 3  # PVAMD_MESH_PATH_*
+MESH_ORDER_GIVEN, MESH_ORDER_INSIDE, MESH_ORDER_SORT_CALL = 0, 1, 2  # PVAMD_MESH_ORDER_*
 RULE_VALID_ON_INDEX = 1
 RULE_ROUND_HALF_AWAY = 2
 RULE_ROUND_FLOOR_HALF = 4
@@ -165,6 +168,26 @@ class MeshDesc(ctypes.Structure):
     ]
 
 
+class MeshPlan(ctypes.Structure):
+    """pvamd_mesh_plan_t: the launches of a mesh query / mesh chamfer call (pvamd_mesh_query_plan, pvamd_chamfer_mesh_plan)."""
+    _fields_ = [("path", ctypes.c_int32), ("order", ctypes.c_int32), ("groups", ctypes.c_int32), ("slots", ctypes.c_int32),
+                ("scan_waves", ctypes.c_int32), ("parts", ctypes.c_int32), ("part_waves", ctypes.c_int32)]
+
+
+def mesh_query_plan(P, F, has_scratch, unordered=False):
+    """pvamd_mesh_query_plan as a MeshPlan."""
+    plan = MeshPlan()
+    check(load().pvamd_mesh_query_plan(P, F, int(has_scratch), int(unordered), ctypes.byref(plan)), "pvamd_mesh_query_plan")
+    return plan
+
+
+def chamfer_mesh_plan(N, rows, F, has_scratch):
+    """pvamd_chamfer_mesh_plan as a MeshPlan."""
+    plan = MeshPlan()
+    check(load().pvamd_chamfer_mesh_plan(N, rows, F, int(has_scratch), ctypes.byref(plan)), "pvamd_chamfer_mesh_plan")
+    return plan
+
+
 class JointDesc(ctypes.Structure):
     """pvamd_joint_t"""
     _fields_ = [("parent", ctypes.c_int32), ("jtype", ctypes.c_int32), ("jcol", ctypes.c_int32),
@@ -235,6 +258,10 @@ SIGNATURES = {
     "pvamd_morton_order": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "pvamd_morton_order_scratch_bytes": (ctypes.c_int64, [ctypes.c_int64]),
+    "pvamd_morton_order_kernel": (ctypes.c_int, [ctypes.c_int64]),
+    "pvamd_morton_order_bits": (ctypes.c_int, [ctypes.c_int64]),
+    "pvamd_mesh_query_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(MeshPlan)]),
+    "pvamd_chamfer_mesh_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(MeshPlan)]),
     "pvamd_mesh_rec_floats": (ctypes.c_int64, [ctypes.c_int32]),
     "pvamd_mesh_tiles_floats": (ctypes.c_int64, [ctypes.c_int32]),
     "pvamd_mesh_small_points": (ctypes.c_int64, []),

@@ -709,6 +709,7 @@ struct HandOver {
 };
 constexpr int kBoundFloats = 16;
 constexpr int kSmallPoints = PVAMD_MESH_SMALL_POINTS;
+static_assert(PVAMD_MESH_SMALL_POINTS <= kOrderSmallPoints, "an unordered query is sorted by ONE workgroup (order_small_block), which drops the points beyond its capacity");
 constexpr int kHandOverHeader = 64;  // bytes
 // The scratch of the mesh entry points, in bytes: pvamd_mesh_scratch_bytes reports `bytes`, hand_over() carves at the same
 // offsets.  Each field starts where the one before it ends.
@@ -737,6 +738,8 @@ constexpr HandOverLayout hand_over_layout(int64_t cap) {
 static_assert(hand_over_layout(PVAMD_MESH_SCRATCH_SLOTS(0)).bytes == PVAMD_MESH_SCRATCH_BYTES(0) &&
               hand_over_layout(PVAMD_MESH_SCRATCH_SLOTS(1)).bytes == PVAMD_MESH_SCRATCH_BYTES(1),
               "PVAMD_MESH_SCRATCH_BYTES is not the hand-over layout's total");
+static_assert(hand_over_layout(0).bytes - hand_over_layout(0).p_best == (size_t)kSmallPoints * (sizeof(unsigned long long) + 4 * sizeof(float)),
+              "the by-point part holds one (best, dir, reach) per point of the largest unordered query");
 
 static HandOver hand_over(void* scratch, int cap) {
     const HandOverLayout l = hand_over_layout(cap);
@@ -1129,13 +1132,16 @@ __global__ __launch_bounds__(128) void hand_over_all_kernel(MeshArgs m, const in
 }
 __global__ void hand_over_none_kernel(HandOver ho) { *ho.count = 0; }
 
-// Few points that bring no processing order (pvamd_mesh_query_unordered, P <= 16384): the sort is one workgroup on one CU
+// Few points that bring no processing order (pvamd_mesh_query_unordered, P <= kSmallPoints): the sort is one workgroup on one CU
 // for ~16 us, and what the list launch works out per POINT -- the jittered ray, the greedy bound and the first candidate --
 // does not need the order.  ONE launch: block 0 sorts, every other block takes 512 points in caller order (waves 0-7 the
 // rays, waves 8-15 the bounds: two independent serial chains side by side) and stores by point index; the list launch that
 // follows only gathers them into the slots and works out the groups' wave bounds.  C1: sort 15.8 + list 12.1 us ->
 // 15.8 + 4.
 constexpr int kPrepPoints = 512;
+static unsigned small_prep_blocks(int64_t P) { return 1 + (unsigned)((P + kPrepPoints - 1) / kPrepPoints); }  // block 0 sorts
+static_assert(kOrderSmallThreads == 1024 && kPrepPoints * 2 == kOrderSmallThreads,
+              "mesh_small_prep_kernel: block 0 runs order_small_block, the others 512 points on two halves of 1024 threads");
 __global__ __launch_bounds__(1024) void mesh_small_prep_kernel(MeshArgs m, const float* __restrict__ pts, int P, uint64_t seed,
                                                                int64_t index_base, int* __restrict__ order, HandOver ho) {
     if (blockIdx.x == 0) {
@@ -1383,19 +1389,7 @@ static MeshArgs mesh_args(const pvamd_mesh_t& mesh) {
 }
 
 constexpr int kMaxFaces = 1 << 26;  // queue entries are record << 6 | lane
-constexpr int kMaxSlices = 8;    // waves that may share one 64-point group (pick_slices)
-constexpr int kMinParts = 4;     // fewer parts than this (a mesh of less than ~12 tiles): the single launch
 
-// How many waves share one 64-point group (every wave needs tiles of its own: ti % slices == wave).
-//   many groups           -> 2: the least replicated per-wave work (2 M points on the 62-tile drill: 1.9 ms with 2, 2.05
-//                            with 4, 2.4 with 1, 3.1 with 8);
-//   fewer groups          -> 4, 8, so that the 1024 SIMDs still fill (100k points on the drill: 0.40 ms with 8, 0.47 with
-//                            4, 0.79 with 2);
-//   many tiles            -> the work per group is heavy-tailed (a point near the medial axis is equidistant to much of
-//                            the surface and needs most tiles) and the slowest groups set the kernel time: 8 when nothing
-//                            can be handed over (C5, 389 tiles: 5.2 ms with 8, 11.5 with 2); when the heavy groups go
-//                            to a launch of their own the tail is gone and the count of groups decides as above (C5:
-//                            3.17 ms with 2, 3.55 with 4).
 // Voxel centres of a regular grid (the cartesian product of three coordinate arrays, x slowest: voxel.py:20-25) and a
 // processing order for them in ONE launch: thread i writes centre i (caller order = the cache's C order) and its position in an
 // order that walks the grid in 4 x 4 x 4 bricks (clipped at the far faces) -- so that a run of 64 consecutive positions is a cube
@@ -1428,14 +1422,98 @@ __global__ __launch_bounds__(256) void grid_points_kernel(const float* __restric
     order[j] = (int)i;
 }
 
-static int pick_slices(int64_t groups, int mesh_tiles, bool hand_over) {
+// ---- the launch plan ------------------------------------------------------------------------------------------
+// Which launches a mesh query or a mesh chamfer call makes, with how many waves and workgroups per 64-point group: worked
+// out here, once, from the sizes of the call.  mesh_query_impl, launch_chamfer_mesh and launch_heavy_parts read it and
+// launch; pvamd_mesh_query_plan / pvamd_chamfer_mesh_plan report it.
+//   listed      few point groups, a mesh of ~12 tiles or more, scratch given: EVERY group is listed, the tiles of each are
+//               spread over `parts` workgroups of `part_waves` waves, and the parts launch writes the outputs
+//   scan        one launch: a workgroup of `scan_waves` waves per group walks the whole mesh
+//   scan_heavy  the scan lists the heavy groups (a mesh of kHeavyMinTiles tiles or more, scratch given), then their parts
+//               (`parts` workgroups of `part_waves` waves per listed group), then a finish launch for their outputs
+using MeshPlan = pvamd_mesh_plan_t;
+constexpr int kMaxSlices = 8;        // waves that may share one 64-point group
+constexpr int kMinParts = 4;         // fewer parts than this (a mesh of less than ~12 tiles): no listed path
+constexpr int kHeavyPartWaves = 4;   // waves per workgroup of mesh_parts_kernel: one per 64-record pass of a tile
+// The two tests on 128 tiles.  kHeavyMinTiles (above; the scan kernels read it too) is compared with >=: a mesh of 128 tiles
+// or more hands its heavy groups over when there is a scratch.  kWideScanOverTiles is compared with >: a mesh of MORE than
+// 128 tiles that cannot hand over scans with 8 waves whatever the number of groups.  So a mesh of exactly 128 tiles hands
+// over with a scratch and, without one, picks its waves by the group count like a small mesh; no measurement says the
+// second was meant, and both are kept as they were.
+constexpr int kWideScanOverTiles = 128;
+
+// How many waves share one 64-point group in the scan (every wave needs tiles of its own: ti % waves == wave).
+//   many groups           -> 2: the least replicated per-wave work (2 M points on the 62-tile drill: 1.9 ms with 2, 2.05
+//                            with 4, 2.4 with 1, 3.1 with 8);
+//   fewer groups          -> 4, 8, so that the 1024 SIMDs still fill (100k points on the drill: 0.40 ms with 8, 0.47 with
+//                            4, 0.79 with 2);
+//   many tiles            -> the work per group is heavy-tailed (a point near the medial axis is equidistant to much of
+//                            the surface and needs most tiles) and the slowest groups set the kernel time: 8 when nothing
+//                            can be handed over (C5, 389 tiles: 5.2 ms with 8, 11.5 with 2); when the heavy groups go
+//                            to a launch of their own the tail is gone and the count of groups decides as above (C5:
+//                            3.17 ms with 2, 3.55 with 4).
+static int scan_waves_for(int64_t groups, int ntiles, bool hands_over) {
     int s = 2;
     while (s < 8 && (int64_t)s * groups < 16384) s <<= 1;
-    if (mesh_tiles > 128 && !hand_over) s = 8;
+    if (ntiles > kWideScanOverTiles && !hands_over) s = 8;
     if (s > kMaxSlices) s = kMaxSlices;
-    while (s > 1 && s > mesh_tiles) s >>= 1;
+    while (s > 1 && s > ntiles) s >>= 1;
     return s;
 }
+
+// the scan of `groups` groups per row over `rows` rows (the chamfer's transforms; 1 for a query), heavy groups handed over
+// when there is a scratch and the mesh has the tiles for it
+static void plan_scan(MeshPlan& pl, int64_t rows, int ntiles, bool has_scratch) {
+    const bool hands_over = has_scratch && ntiles >= kHeavyMinTiles;
+    pl.path = hands_over ? PVAMD_MESH_PATH_SCAN_HEAVY : PVAMD_MESH_PATH_SCAN;
+    pl.scan_waves = scan_waves_for(pl.groups * rows, ntiles, hands_over);
+    pl.parts = hands_over ? (kHeavyParts < ntiles ? kHeavyParts : ntiles) : 0;
+    pl.part_waves = hands_over ? kHeavyPartWaves : 0;
+}
+
+// P >= 1 points against F <= kMaxFaces faces, at most INT32_MAX groups (the entry points refuse the rest).  unordered: the
+// caller brings no processing order (pvamd_mesh_query_unordered, P <= kSmallPoints).
+static MeshPlan mesh_query_plan(int64_t P, int F, bool has_scratch, bool unordered) {
+    MeshPlan pl = {};
+    const int64_t groups = (P + 63) / 64;
+    const int ntiles = (F + kTile - 1) / kTile;
+    pl.groups = (int32_t)groups;
+    pl.slots = (int32_t)PVAMD_MESH_SCRATCH_SLOTS(P);  // what pvamd_mesh_scratch_bytes(P) holds
+    // few point groups, many tiles: spread each group's tiles over `parts` blocks of `part_waves` waves (see mesh_parts_all_kernel)
+    // Sweep over 1k .. 520k points x parts x waves on the 62-tile drill and the 389-tile sphere (profiles/r04_mesh_variants.txt,
+    // section 7): tiles per block by the number of point groups whatever the size of the mesh -- one for up to 64 groups, one
+    // and a half up to 256, three up to ~2000, then a five-hundredth of the groups --, two waves per block instead of four once the
+    // launch is beyond ~100k waves.
+    // (in halves of a tile)
+    const int half_tiles = groups <= 64 ? 2 : (groups <= 256 ? 3 : (groups < 2048 ? 6 : (int)(groups / 256)));
+    int parts = (2 * ntiles + half_tiles - 1) / half_tiles;
+    if (parts > 65535) parts = 65535;  // gridDim.y (a mesh of more than 16.7 M triangles)
+    if (has_scratch && groups <= pl.slots && parts >= kMinParts) {
+        pl.path = PVAMD_MESH_PATH_LISTED;
+        pl.parts = parts;
+        pl.part_waves = groups * parts * 4 > 100000 ? 2 : 4;
+        // the sort in block 0 of the launch that works the rays and bounds out per point
+        pl.order = unordered ? PVAMD_MESH_ORDER_INSIDE : PVAMD_MESH_ORDER_GIVEN;
+        return pl;
+    }
+    plan_scan(pl, 1, ntiles, has_scratch);
+    pl.order = unordered ? PVAMD_MESH_ORDER_SORT_CALL : PVAMD_MESH_ORDER_GIVEN;
+    return pl;
+}
+
+// N >= 1 points per row, `rows` >= 1 rows (the B transforms of pvamd_chamfer_mesh; 1 for the flat call, whose N is all the
+// points), F >= 1 faces.  The chamfer has no listed path, and its order is always the caller's.
+static MeshPlan chamfer_mesh_plan(int64_t N, int64_t rows, int F, bool has_scratch) {
+    MeshPlan pl = {};
+    pl.groups = (int32_t)((N + 63) / 64);
+    pl.slots = (int32_t)PVAMD_MESH_SCRATCH_SLOTS(N);
+    plan_scan(pl, rows, (F + kTile - 1) / kTile, has_scratch);
+    pl.order = PVAMD_MESH_ORDER_GIVEN;
+    return pl;
+}
+
+// what both plans' entry points refuse in their sizes
+static bool mesh_sizes_ok(int64_t points, int F) { return points >= 0 && F >= 0 && F <= kMaxFaces && (points + 63) / 64 <= 0x7fffffff; }
 
 }  // namespace pvamd
 
@@ -1492,10 +1570,9 @@ static unsigned list_blocks(int cap) { return (unsigned)(cap < 512 ? (cap < 1 ? 
 
 // the parts launch over the listed (heavy) groups: x = slots (a block strides over the list), y = parts
 template <bool WITH_RAY>
-static void launch_heavy_parts(const MeshArgs& m, uint64_t seed, const HandOver& ho, int ntiles, hipStream_t s) {
-    const int parts = kHeavyParts < ntiles ? kHeavyParts : ntiles;
-    const unsigned xb = list_blocks(ho.cap);
-    hipLaunchKernelGGL((mesh_parts_kernel<WITH_RAY, 4>), dim3(xb, (unsigned)parts), dim3(256), 0, s, m, seed, ho);
+static void launch_heavy_parts(const MeshArgs& m, uint64_t seed, const HandOver& ho, const MeshPlan& plan, hipStream_t s) {
+    hipLaunchKernelGGL((mesh_parts_kernel<WITH_RAY, kHeavyPartWaves>), dim3(list_blocks(ho.cap), (unsigned)plan.parts),
+                       dim3(64 * kHeavyPartWaves), 0, s, m, seed, ho);
 }
 
 // sort_into != nullptr: the caller brings no order; one is worked out into sort_into (P <= kSmallPoints)
@@ -1508,64 +1585,62 @@ static int mesh_query_impl(const pvamd_mesh_t* mesh, const float* points, const 
     if (mesh->F < 0) return PVAMD_E_SHAPE;
     if (!points || (mesh->F > 0 && (!mesh->rec || !mesh->tiles || !mesh->normal || !mesh->rec_of_face))) return PVAMD_E_NULL;
     if (scratch && !aligned_to(scratch, 8)) return PVAMD_E_ALIGN;
-    if (mesh->F > kMaxFaces) return PVAMD_E_SHAPE;
+    if (!mesh_sizes_ok(P, mesh->F)) return PVAMD_E_SHAPE;
     const MeshArgs m = mesh_args(*mesh);
-    const int64_t groups = (P + 63) / 64;
-    if (groups > 0x7fffffff) return PVAMD_E_SHAPE;
     hipStream_t s = (hipStream_t)stream;
     const QueryOut out{out_closest, out_dist, out_grad, out_face, out_normal, out_packed};
-    const int ntiles = (mesh->F + kTile - 1) / kTile;
-    const int cap = (int)PVAMD_MESH_SCRATCH_SLOTS(P);  // what pvamd_mesh_scratch_bytes(P) holds
-    const HandOver ho = hand_over(scratch, cap);
-    const int slices = pick_slices(groups, ntiles, ho.cap > 0 && ntiles >= kHeavyMinTiles);
-    // few point groups, many tiles: spread each group's tiles over `parts` blocks of `aw` waves (see mesh_parts_kernel)
-    // Sweep over 1k .. 520k points x parts x waves on the 62-tile drill and the 389-tile sphere (profiles/r04_mesh_variants.txt,
-    // section 7): tiles per block by the number of point groups whatever the size of the mesh -- one for up to 64 groups, one
-    // and a half up to 256, three up to ~2000, then a five-hundredth of the groups --, two waves per block instead of four once the
-    // launch is beyond ~100k waves.
-    // (in halves of a tile)
-    const int half_tiles = groups <= 64 ? 2 : (groups <= 256 ? 3 : (groups < 2048 ? 6 : (int)(groups / 256)));
-    int parts = (2 * ntiles + half_tiles - 1) / half_tiles;
-    if (parts > 65535) parts = 65535;  // gridDim.y (a mesh of more than 16.7 M triangles)
-    const int aw = (int64_t)groups * parts * 4 > 100000 ? 2 : 4;
-    const bool few = parts >= kMinParts;
-    const bool two_launches = ho.cap > 0 && groups <= ho.cap && few;
-    if (sort_into) {
-        order = sort_into;
-        if (two_launches) {  // the sort in block 0 of the launch that works the rays and bounds out per point
-            hipLaunchKernelGGL(mesh_small_prep_kernel, dim3(1 + (unsigned)((P + kPrepPoints - 1) / kPrepPoints)), dim3(1024), 0, s, m,
-                               points, (int)P, jitter_seed, index_base, sort_into, ho);
-            hipLaunchKernelGGL(hand_over_gather_kernel, dim3((unsigned)groups), dim3(64), 0, s, m, order, points, P, ho, (int)groups);
-        } else {
-            const int rc = pvamd_morton_order(points, P, sort_into, nullptr, nullptr, sort_into, stream);  // (one launch: no scratch used)
-            if (rc != 0) return rc;
-        }
+    const MeshPlan plan = mesh_query_plan(P, mesh->F, scratch != nullptr, sort_into != nullptr);
+    const unsigned groups = (unsigned)plan.groups;
+    const HandOver ho = hand_over(scratch, plan.slots);
+    if (plan.order != PVAMD_MESH_ORDER_GIVEN) order = sort_into;
+    if (plan.order == PVAMD_MESH_ORDER_SORT_CALL) {
+        const int rc = pvamd_morton_order(points, P, sort_into, nullptr, nullptr, sort_into, stream);  // (one launch: no scratch used)
+        if (rc != 0) return rc;
     }
-    if (two_launches) {
-        if (!sort_into)
-            hipLaunchKernelGGL(hand_over_all_kernel, dim3((unsigned)groups), dim3(128), 0, s, m, order, points, P, jitter_seed,
-                               index_base, ho, (int)groups);
-        const dim3 grid((unsigned)groups, (unsigned)parts);
-        switch (aw) {
+    if (plan.path == PVAMD_MESH_PATH_LISTED) {
+        if (plan.order == PVAMD_MESH_ORDER_INSIDE) {
+            hipLaunchKernelGGL(mesh_small_prep_kernel, dim3(small_prep_blocks(P)), dim3(kOrderSmallThreads), 0, s, m, points, (int)P,
+                               jitter_seed, index_base, sort_into, ho);
+            hipLaunchKernelGGL(hand_over_gather_kernel, dim3(groups), dim3(64), 0, s, m, order, points, P, ho, plan.groups);
+        } else {
+            hipLaunchKernelGGL(hand_over_all_kernel, dim3(groups), dim3(128), 0, s, m, order, points, P, jitter_seed, index_base, ho,
+                               plan.groups);
+        }
+        const dim3 grid(groups, (unsigned)plan.parts);
+        switch (plan.part_waves) {
             case 2: hipLaunchKernelGGL((mesh_parts_all_kernel<2>), grid, dim3(128), 0, s, m, order, points, P, jitter_seed, ho, out); break;
             default: hipLaunchKernelGGL((mesh_parts_all_kernel<4>), grid, dim3(256), 0, s, m, order, points, P, jitter_seed, ho, out); break;
         }
         return (int)hipGetLastError();
     }
-    const bool heavy = ho.cap > 0 && ntiles >= kHeavyMinTiles;
+    const bool heavy = plan.path == PVAMD_MESH_PATH_SCAN_HEAVY;
     const HandOver none = hand_over(nullptr, 0);
     if (heavy) hipLaunchKernelGGL(hand_over_none_kernel, dim3(1), dim3(1), 0, s, ho);
-    switch (slices) {
-        case 8: hipLaunchKernelGGL((mesh_query_kernel<8>), dim3((unsigned)groups), dim3(512), 0, s, m, order, points, P, jitter_seed, index_base, out, heavy ? ho : none); break;
-        case 4: hipLaunchKernelGGL((mesh_query_kernel<4>), dim3((unsigned)groups), dim3(256), 0, s, m, order, points, P, jitter_seed, index_base, out, heavy ? ho : none); break;
-        case 2: hipLaunchKernelGGL((mesh_query_kernel<2>), dim3((unsigned)groups), dim3(128), 0, s, m, order, points, P, jitter_seed, index_base, out, heavy ? ho : none); break;
-        default: hipLaunchKernelGGL((mesh_query_kernel<1>), dim3((unsigned)groups), dim3(64), 0, s, m, order, points, P, jitter_seed, index_base, out, heavy ? ho : none); break;
+    switch (plan.scan_waves) {
+        case 8: hipLaunchKernelGGL((mesh_query_kernel<8>), dim3(groups), dim3(512), 0, s, m, order, points, P, jitter_seed, index_base, out, heavy ? ho : none); break;
+        case 4: hipLaunchKernelGGL((mesh_query_kernel<4>), dim3(groups), dim3(256), 0, s, m, order, points, P, jitter_seed, index_base, out, heavy ? ho : none); break;
+        case 2: hipLaunchKernelGGL((mesh_query_kernel<2>), dim3(groups), dim3(128), 0, s, m, order, points, P, jitter_seed, index_base, out, heavy ? ho : none); break;
+        default: hipLaunchKernelGGL((mesh_query_kernel<1>), dim3(groups), dim3(64), 0, s, m, order, points, P, jitter_seed, index_base, out, heavy ? ho : none); break;
     }
     if (heavy) {
-        launch_heavy_parts<true>(m, jitter_seed, ho, ntiles, s);
+        launch_heavy_parts<true>(m, jitter_seed, ho, plan, s);
         hipLaunchKernelGGL(mesh_query_finish_kernel, dim3(list_blocks(ho.cap)), dim3(64), 0, s, m, order, points, P, ho, out);
     }
     return (int)hipGetLastError();
+}
+
+extern "C" int pvamd_mesh_query_plan(int64_t P, int32_t F, int32_t has_scratch, int32_t unordered, pvamd_mesh_plan_t* plan_out) {
+    if (!plan_out) return PVAMD_E_NULL;
+    if (!mesh_sizes_ok(P, F) || (unordered && P > kSmallPoints)) return PVAMD_E_SHAPE;
+    *plan_out = P == 0 ? MeshPlan{} : mesh_query_plan(P, F, has_scratch != 0, unordered != 0);
+    return 0;
+}
+
+extern "C" int pvamd_chamfer_mesh_plan(int64_t N, int32_t rows, int32_t F, int32_t has_scratch, pvamd_mesh_plan_t* plan_out) {
+    if (!plan_out) return PVAMD_E_NULL;
+    if (rows < 0 || !mesh_sizes_ok(N, F)) return PVAMD_E_SHAPE;
+    *plan_out = (rows == 0 || N == 0 || F == 0) ? MeshPlan{} : chamfer_mesh_plan(N, rows, F, has_scratch != 0);
+    return 0;
 }
 
 extern "C" int pvamd_mesh_query(const pvamd_mesh_t* mesh, const float* points, const int32_t* order, int64_t P,
@@ -1609,29 +1684,26 @@ static int launch_chamfer_mesh(const pvamd_mesh_t* mesh, const float* W, int32_t
     hipLaunchKernelGGL(zero_f64_kernel, dim3((B + 255) / 256), dim3(256), 0, s, out_sum, B);
     if (N == 0 || mesh->F == 0) return (int)hipGetLastError();
     if (!points || !mesh->rec || !mesh->tiles || !mesh->rec_of_face) return PVAMD_E_NULL;
-    if (mesh->F > kMaxFaces) return PVAMD_E_SHAPE;
+    if (!mesh_sizes_ok(N, mesh->F)) return PVAMD_E_SHAPE;
     const MeshArgs m = mesh_args(*mesh);
-    const int64_t groups = (N + 63) / 64;
-    if (groups > 0x7fffffff) return PVAMD_E_SHAPE;
-    const int ntiles = (mesh->F + kTile - 1) / kTile;
-    const int cap = (int)PVAMD_MESH_SCRATCH_SLOTS(N);
-    const HandOver ho = hand_over(ntiles >= kHeavyMinTiles ? scratch : nullptr, cap);
     const int32_t ny = W ? B : 1;
-    const int slices = pick_slices(groups * (int64_t)ny, ntiles, ho.cap > 0);
-    if (ho.cap > 0) hipLaunchKernelGGL(hand_over_none_kernel, dim3(1), dim3(1), 0, s, ho);
+    const MeshPlan plan = chamfer_mesh_plan(N, ny, mesh->F, scratch != nullptr);
+    const bool heavy = plan.path == PVAMD_MESH_PATH_SCAN_HEAVY;
+    const HandOver ho = hand_over(heavy ? scratch : nullptr, plan.slots);
+    if (heavy) hipLaunchKernelGGL(hand_over_none_kernel, dim3(1), dim3(1), 0, s, ho);
     // y-dimension of a HIP grid is limited to 65535: walk B in slabs
     for (int32_t b0 = 0; b0 < ny; b0 += 65535) {
         const int32_t nb = (ny - b0) < 65535 ? (ny - b0) : 65535;
-        const dim3 grid((unsigned)groups, nb);
-        switch (slices) {
+        const dim3 grid((unsigned)plan.groups, nb);
+        switch (plan.scan_waves) {
             case 8: hipLaunchKernelGGL((chamfer_mesh_kernel<8>), grid, dim3(512), 0, s, m, order, W, b0, points, N, scale, out_sum, ho, per); break;
             case 4: hipLaunchKernelGGL((chamfer_mesh_kernel<4>), grid, dim3(256), 0, s, m, order, W, b0, points, N, scale, out_sum, ho, per); break;
             case 2: hipLaunchKernelGGL((chamfer_mesh_kernel<2>), grid, dim3(128), 0, s, m, order, W, b0, points, N, scale, out_sum, ho, per); break;
             default: hipLaunchKernelGGL((chamfer_mesh_kernel<1>), grid, dim3(64), 0, s, m, order, W, b0, points, N, scale, out_sum, ho, per); break;
         }
     }
-    if (ho.cap > 0) {
-        launch_heavy_parts<false>(m, 0, ho, ntiles, s);
+    if (heavy) {
+        launch_heavy_parts<false>(m, 0, ho, plan, s);
         hipLaunchKernelGGL(chamfer_finish_kernel, dim3(list_blocks(ho.cap)), dim3(64), 0, s, m, order, W, points, N, scale, ho, out_sum, per);
     }
     return (int)hipGetLastError();

@@ -1,16 +1,23 @@
-// The one-workgroup spatial sort of up to 16384 points (1024 threads).  gfx950 only.
+// The one-workgroup spatial sort of up to kOrderSmallPoints points (1024 threads).  gfx950 only.
 #pragma once
 #include "common.h"
 #include "morton.h"
 
 namespace pvamd {
 
-// ---- up to 16384 points: the whole thing in ONE workgroup (bounds, 16^3-cell histogram in LDS, scan, scatter) ----
+// ---- up to kOrderSmallPoints points: the whole thing in ONE workgroup (bounds, 16^3-cell histogram in LDS, scan, scatter) ----
 // The seven launches above cost ~4.5 us each whatever their size; for the 10k-point query of BASELINE C1 that was a
 // quarter of the call.  Every thread keeps its (up to 16) points and their cells in registers: the points are read once,
 // the curve position is worked out once, and the scan of the 4096 cell counters is a wave scan + 16 wave totals (five
 // barriers in all; the first version read the points three times and scanned with twenty barriers: 25 us for 10k points).
 constexpr int kSmallCells = 4096, kSmallPer = 16;  // 16^3 cells: the leading 12 bits of a 30-bit key
+constexpr int kSmallBits = 12;                      // log2(kSmallCells)
+// The workgroup is 1024 threads (order_small_block strides its points and its cell counters by that number; the kernels that
+// call it are launched with it) of kSmallPer points each: 16384 points.  A larger P would silently lose the points beyond --
+// pvamd_morton_order takes this path up to here and no further, and PVAMD_MESH_SMALL_POINTS may not exceed it (csrc/mesh.hip).
+constexpr int kOrderSmallThreads = 1024;
+constexpr int kOrderSmallPoints = kOrderSmallThreads * kSmallPer;
+static_assert(1 << kSmallBits == kSmallCells, "kSmallBits is the number of key bits of kSmallCells cells");
 // (a device function so that the few-points mesh query can run it in ONE block of a launch whose other blocks do the work
 // that does not need the order: csrc/mesh.hip, mesh_small_prep_kernel)
 PVAMD_DEV void order_small_block(const float* __restrict__ pts, int P, int* __restrict__ order,

@@ -395,36 +395,53 @@ __global__ __launch_bounds__(256) void order_gather_kernel(const float* __restri
     }
 }
 
+static_assert(kOrderSmallThreads == 1024, "order_small_kernel is compiled for, and launched with, the 1024 threads order_small_block strides by");
 __global__ __launch_bounds__(1024) void order_small_kernel(const float* __restrict__ pts, int P, int* __restrict__ order,
                                                            int* __restrict__ inv, float* __restrict__ sorted_pts) {
     order_small_block(pts, P, order, inv, sorted_pts);
 }
 
+// Which sort pvamd_morton_order runs for P points (pvamd_morton_order_kernel reports it): the one workgroup while it holds
+// them, the radix sort from its threshold on, the counting sort in between.
+enum class OrderKind { kSmall = PVAMD_ORDER_KERNEL_SMALL, kCounting = PVAMD_ORDER_KERNEL_COUNTING, kRadix = PVAMD_ORDER_KERNEL_RADIX };
+static OrderKind order_kind(int64_t P) {
+    if (P <= kOrderSmallPoints) return OrderKind::kSmall;
+    return P >= PVAMD_ORDER_RADIX_SORT_FROM ? OrderKind::kRadix : OrderKind::kCounting;
+}
+static bool order_size_ok(int64_t P) { return P >= 0 && P <= 0x7fffffffLL; }  // what pvamd_morton_order takes
+
 }  // namespace pvamd
 
 using namespace pvamd;
 
-// Enough for EITHER sort, so that the size does not depend on the threshold a library was built with.  (A single launch, up
-// to 16,384 points, uses none: the counting sort's size is reported there all the same.)
+extern "C" int pvamd_morton_order_kernel(int64_t P) { return order_size_ok(P) ? (int)order_kind(P) : PVAMD_E_SHAPE; }
+extern "C" int pvamd_morton_order_bits(int64_t P) {
+    if (!order_size_ok(P)) return PVAMD_E_SHAPE;
+    return order_kind(P) == OrderKind::kSmall ? kSmallBits : PVAMD_MORTON_ORDER_BITS(P);
+}
+
+// Enough for EITHER sort, so that the size does not depend on the threshold a library was built with.  (A single launch, the
+// one-workgroup sort, uses none: the counting sort's size is reported there all the same.)
 extern "C" int64_t pvamd_morton_order_scratch_bytes(int64_t P) {
-    if (P < 0 || P > 0x7fffffffLL) return 0;  // what pvamd_morton_order refuses
+    if (!order_size_ok(P)) return 0;
     const int64_t counting = counting_layout(P).words, radix = radix_layout(P).words;
     return (int64_t)sizeof(unsigned) * (radix > counting ? radix : counting);
 }
 
 extern "C" int pvamd_morton_order(const float* points, int64_t P, int32_t* order_out, int32_t* inv_out,
                                   float* sorted_points_out, void* scratch, void* stream) {
-    if (P < 0 || P > 0x7fffffffLL) return PVAMD_E_SHAPE;
+    if (!order_size_ok(P)) return PVAMD_E_SHAPE;
     if (P == 0) return 0;
     if (!points || !order_out || !scratch) return PVAMD_E_NULL;
     if (!aligned_to(scratch, 4) || !aligned_to(points, 4)) return PVAMD_E_ALIGN;
     hipStream_t s = (hipStream_t)stream;
-    if (P <= 16384) {
-        hipLaunchKernelGGL(order_small_kernel, dim3(1), dim3(1024), 0, s, points, (int)P, order_out, inv_out, sorted_points_out);
+    const OrderKind kind = order_kind(P);
+    if (kind == OrderKind::kSmall) {
+        hipLaunchKernelGGL(order_small_kernel, dim3(1), dim3(kOrderSmallThreads), 0, s, points, (int)P, order_out, inv_out, sorted_points_out);
         return (int)hipGetLastError();
     }
     unsigned* w = reinterpret_cast<unsigned*>(scratch);
-    if (P >= PVAMD_ORDER_RADIX_SORT_FROM) {
+    if (kind == OrderKind::kRadix) {
         const RadixLayout l = radix_layout(P);
         const int64_t want = (P + 255) / 256, tiles = l.tiles;
         const int G = l.G, nsg = l.nsg;

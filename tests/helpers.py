@@ -78,6 +78,11 @@ def oracle_mesh_from_factory(obj):
                        obj.bounding_box(padding=1.0)[:, 1])
 
 
+def plan_key(plan):
+    """Of a _lib.MeshPlan, what decides the kernels that run: two calls with equal keys take the same code paths."""
+    return (plan.path, plan.order, plan.scan_waves, plan.part_waves)
+
+
 random_rigid = workloads.random_rigid
 uniform_points = workloads.uniform_points
 

@@ -56,6 +56,12 @@ def test_struct_layouts_match_the_header(tmp_path):
              offsetof(pvamd_grid_t, bb_min), offsetof(pvamd_grid_t, shape), offsetof(pvamd_grid_t, index_f64),
              offsetof(pvamd_grid_t, oob_mode));
       printf("%zu %zu %zu\n", sizeof(pvamd_mesh_t), offsetof(pvamd_mesh_t, F), offsetof(pvamd_mesh_t, ray_dir));
+      printf("%zu %zu %zu %zu %zu %zu %zu %zu\n", sizeof(pvamd_mesh_plan_t), offsetof(pvamd_mesh_plan_t, path),
+             offsetof(pvamd_mesh_plan_t, order), offsetof(pvamd_mesh_plan_t, groups), offsetof(pvamd_mesh_plan_t, slots),
+             offsetof(pvamd_mesh_plan_t, scan_waves), offsetof(pvamd_mesh_plan_t, parts), offsetof(pvamd_mesh_plan_t, part_waves));
+      printf("%d %d %d %d  %d %d %d  %d %d %d\n", PVAMD_MESH_PATH_NONE, PVAMD_MESH_PATH_LISTED, PVAMD_MESH_PATH_SCAN,
+             PVAMD_MESH_PATH_SCAN_HEAVY, PVAMD_MESH_ORDER_GIVEN, PVAMD_MESH_ORDER_INSIDE, PVAMD_MESH_ORDER_SORT_CALL,
+             PVAMD_ORDER_KERNEL_SMALL, PVAMD_ORDER_KERNEL_COUNTING, PVAMD_ORDER_KERNEL_RADIX);
       return 0; }'''
     exe = str(tmp_path / "pvamd_layout")
     subprocess.run(["gcc", "-x", "c", "-", "-I", os.path.join(ROOT, "include"), "-o", exe], input=src.encode(), check=True)
@@ -63,7 +69,13 @@ def test_struct_layouts_match_the_header(tmp_path):
     G, M = _lib.GridDesc, _lib.MeshDesc
     assert [int(x) for x in out[:7]] == [ctypes.sizeof(G), G.dres.offset, G.fmin.offset, G.bb_min.offset, G.shape.offset,
                                          G.index_f64.offset, G.oob_mode.offset]
-    assert [int(x) for x in out[7:]] == [ctypes.sizeof(M), M.F.offset, M.ray_dir.offset]
+    assert [int(x) for x in out[7:10]] == [ctypes.sizeof(M), M.F.offset, M.ray_dir.offset]
+    Pl = _lib.MeshPlan
+    assert [int(x) for x in out[10:18]] == [ctypes.sizeof(Pl)] + [getattr(Pl, name).offset for name, _ in Pl._fields_]
+    assert [name for name, _ in Pl._fields_] == ["path", "order", "groups", "slots", "scan_waves", "parts", "part_waves"]
+    assert [int(x) for x in out[18:]] == [_lib.MESH_PATH_NONE, _lib.MESH_PATH_LISTED, _lib.MESH_PATH_SCAN, _lib.MESH_PATH_SCAN_HEAVY,
+                                          _lib.MESH_ORDER_GIVEN, _lib.MESH_ORDER_INSIDE, _lib.MESH_ORDER_SORT_CALL,
+                                          _lib.ORDER_KERNEL_SMALL, _lib.ORDER_KERNEL_COUNTING, _lib.ORDER_KERNEL_RADIX]
 
 
 def test_oracle_grid_layout_is_one_definition(tmp_path):

@@ -5,7 +5,7 @@ import torch
 
 import pytorch_volumetric_amd as pv
 from oracle import oracle
-from pytorch_volumetric_amd import mesh_io
+from pytorch_volumetric_amd import _lib, mesh_io
 from pytorch_volumetric_amd import transforms as tf
 from tests import helpers as H
 
@@ -150,6 +150,9 @@ def test_c5_shape_sphere_mesh_chamfer_slice_matches_analytic():
     m = mesh_io.uv_sphere_mesh(0.1, 250, 200)
     assert m.faces.shape[0] == 99_500
     obj = pv.MeshObjectFactory(mesh=m)
+    plan = _lib.chamfer_mesh_plan(4096, 1, obj.num_faces, True)  # few groups: the widest scan, heavy groups handed over
+    assert plan.path == _lib.MESH_PATH_SCAN_HEAVY and plan.scan_waves == max(
+        _lib.chamfer_mesh_plan(n, 1, obj.num_faces, True).scan_waves for n in (1, 4096, 1 << 21))
     pts = H.uniform_points(4096, [-0.15] * 3, [0.15] * 3, seed=0)
     W = torch.eye(4).unsqueeze(0)
     err = pv.batch_chamfer_dist(W, pts, obj, scale=1.0)
@@ -163,6 +166,9 @@ def test_full_size_c5_properties():
     r = 0.1
     obj = pv.MeshObjectFactory(mesh=mesh_io.uv_sphere_mesh(r, 250, 200))
     N = 1 << 21
+    plan = _lib.chamfer_mesh_plan(N, 1, obj.num_faces, True)  # many groups: the narrowest scan this mesh gets, heavy groups handed over
+    assert plan.path == _lib.MESH_PATH_SCAN_HEAVY and plan.parts > 1 and plan.scan_waves == min(
+        _lib.chamfer_mesh_plan(n, 1, obj.num_faces, True).scan_waves for n in (1, 4096, N))
     pts = H.uniform_points(N, [-0.15] * 3, [0.15] * 3, seed=2).cuda()
     W = torch.eye(4).unsqueeze(0).cuda()
     e1 = pv.batch_chamfer_dist(W, pts, obj, scale=1.0)
@@ -190,6 +196,10 @@ def test_flat_call_equals_the_per_transform_call(monkeypatch):
     T = H.random_rigid(40, seed=1, trans=0.05)
     W = torch.einsum("bij,pjk->bpik", tf.rigid_inverse(T), H.random_rigid(30, seed=2, trans=0.05)).reshape(-1, 4, 4)
     assert chamfer.flat_call_pays(W.shape[0], 500)
+    # the drill has too few tiles to hand over: one scan either way, over all the points as one row or over 500 per transform
+    flat_plan = _lib.chamfer_mesh_plan(W.shape[0] * 500, 1, obj.num_faces, True)
+    rows_plan = _lib.chamfer_mesh_plan(500, W.shape[0], obj.num_faces, True)
+    assert flat_plan.path == rows_plan.path == _lib.MESH_PATH_SCAN and flat_plan.groups > rows_plan.groups == 8
     flat = pv.batch_chamfer_dist(W, pts, obj).double()
     monkeypatch.setattr(chamfer, "FLAT_MAX_POINTS_PER_TRANSFORM", 0)
     assert not chamfer.flat_call_pays(W.shape[0], 500)
@@ -200,3 +210,47 @@ def test_flat_call_equals_the_per_transform_call(monkeypatch):
     # and through the caller: the (B, P) matrix of pairwise_distance_chamfer
     m = pv.pairwise_distance_chamfer(T[:7], obj_factory=obj, model_points_eval=pts)
     assert m.shape == (7, 7) and torch.allclose(m.diagonal(), torch.zeros(7), atol=1e-3)
+
+
+def test_every_plan_of_the_mesh_chamfer_matches_the_oracle():
+    """pvamd_chamfer_mesh_plan scanned over the number of transforms (1 .. 5000 rows of 101 points: two groups, the second
+    ragged -- the scan width follows groups x rows, so the rows reach every width with few points) for the drill and the
+    many-tile sphere, with and without scratch: every distinct (path, scan width, part-block width) at the fewest rows that
+    reach it and at 37 more, so the test follows the thresholds when they are retuned.  The transforms cycle through four
+    poses, so the oracle's four sums are the reference of every row of every case.  Every point's distance is the oracle's
+    float32 number; a sum of N non-negative float64 terms in another order differs by at most N x 2^-52 relative."""
+    import ctypes
+    lib = _lib.load()
+    N, top = 101, 5000
+    g = torch.Generator().manual_seed(7)
+    centre = (torch.rand(N, 3, generator=g) - 0.5) * 0.02  # the sphere: about equidistant to all of it -- heavy groups
+    poses = H.random_rigid(4, seed=3, trans=0.004)
+    drill = pv.MeshObjectFactory(H.mesh_path("ycb_power_drill.npz"))
+    sphere = pv.MeshObjectFactory(mesh=mesh_io.uv_sphere_mesh(0.1, 150, 120))
+    bb = drill.bounding_box(padding_ratio=0.3)
+    union, cases = set(), 0
+    for obj, pts in ((drill, H.uniform_points(N, bb[:, 0], bb[:, 1], seed=4)), (sphere, centre)):
+        ref = oracle.chamfer_mesh(H.oracle_mesh_from_factory(obj), poses.numpy(), pts.numpy(), scale=1000.0)
+        seen = {}
+        for has_scratch in (False, True):
+            for rows in range(1, top + 1):
+                seen.setdefault((has_scratch,) + H.plan_key(_lib.chamfer_mesh_plan(N, rows, obj.num_faces, has_scratch)), rows)
+        dev = pts.cuda().contiguous()
+        desc = obj._mesh_desc()
+        W = poses.repeat((top + 37 + 3) // 4, 1, 1).cuda().contiguous()
+        scratch = _lib.scratch_buffer(_lib.mesh_scratch_bytes(N), dev.device)
+        for (has_scratch, path, order, scan_waves, part_waves), first in sorted(seen.items()):
+            union.add((path, scan_waves, part_waves))
+            assert order == _lib.MESH_ORDER_GIVEN
+            for rows in (first, first + 37):
+                assert (has_scratch,) + H.plan_key(_lib.chamfer_mesh_plan(N, rows, obj.num_faces, has_scratch)) == \
+                    (has_scratch, path, order, scan_waves, part_waves), (obj.num_faces, rows)
+                sums = torch.empty((rows,), dtype=torch.float64, device="cuda")
+                _lib.check(lib.pvamd_chamfer_mesh(ctypes.byref(desc), _lib.ptr(W), rows, _lib.ptr(dev), None, N, 1000.0, _lib.ptr(sums),
+                                                  _lib.ptr(scratch if has_scratch else None), _lib.stream_ptr()), "pvamd_chamfer_mesh")
+                want = np.tile(ref, (rows + 3) // 4)[:rows]
+                assert np.allclose(sums.cpu().numpy(), want, rtol=N * 2.0 ** -52, atol=0), (obj.num_faces, rows, has_scratch)
+                cases += 1
+    paths, scans, part_blocks = (set(x) for x in zip(*union))
+    assert paths == {_lib.MESH_PATH_SCAN, _lib.MESH_PATH_SCAN_HEAVY} and scans == {2, 4, 8} and part_blocks == {0, 4}, union
+    assert cases >= 16, cases

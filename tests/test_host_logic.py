@@ -645,3 +645,58 @@ def test_composed_kernel_choice_is_reported_and_grouping_follows_it():
     assert comp._grouping_pays(1, chunk, 0) and not comp._grouping_pays(200, chunk - 1, 0) and not comp._grouping_pays(200, chunk, 1)
     comp.group_points = False
     assert not comp._grouping_pays(200, 1 << 18, 0)
+
+
+def test_mesh_launch_plan_and_sort_choice_are_reported():
+    """pvamd_mesh_query_plan / pvamd_chamfer_mesh_plan / pvamd_morton_order_kernel / pvamd_morton_order_bits: the library's own
+    statement of the launches behind the mesh query, the mesh chamfer and the spatial sort, at the regimes the header and
+    DESIGN.md 3.3 name.  Host-side and pure: no GPU."""
+    _lib = pv._lib
+    lib = _lib.load()
+    LISTED, SCAN, HEAVY = _lib.MESH_PATH_LISTED, _lib.MESH_PATH_SCAN, _lib.MESH_PATH_SCAN_HEAVY
+    GIVEN, INSIDE, SORT_CALL = _lib.MESH_ORDER_GIVEN, _lib.MESH_ORDER_INSIDE, _lib.MESH_ORDER_SORT_CALL
+    fields = lambda p: (p.path, p.order, p.groups, p.slots, p.scan_waves, p.parts, p.part_waves)
+    drill, sphere, box = 15_728, 35_700, 12  # 62 tiles, 140 tiles, one tile
+    # C1: 10,000 points on the drill.  With the scratch every one of its 157 groups is listed, 1.5 tiles to a block of four
+    # waves, the order from inside the first launch; without, one scan of the widest workgroups over the caller's order
+    assert fields(_lib.mesh_query_plan(10_000, drill, True, True)) == (LISTED, INSIDE, 157, 157, 0, 42, 4)
+    assert fields(_lib.mesh_query_plan(10_000, drill, True, False)) == (LISTED, GIVEN, 157, 157, 0, 42, 4)
+    assert fields(_lib.mesh_query_plan(10_000, drill, False, False)) == (SCAN, GIVEN, 157, 157, 8, 0, 0)
+    # a 12-face box: one tile, nothing to spread -- one wave per group; an unordered call sorts in front
+    assert fields(_lib.mesh_query_plan(5000, box, True, True)) == (SCAN, SORT_CALL, 79, 79, 1, 0, 0)
+    assert fields(_lib.mesh_query_plan(5000, box, False, False)) == (SCAN, GIVEN, 79, 79, 1, 0, 0)
+    # 8192 groups is what the scratch lists; one point more and it is the scan -- handing heavy groups over from 128 tiles on
+    assert fields(_lib.mesh_query_plan(524_288, drill, True)) == (LISTED, GIVEN, 8192, 8192, 0, 4, 2)
+    assert fields(_lib.mesh_query_plan(524_289, drill, True)) == (SCAN, GIVEN, 8193, 8192, 2, 0, 0)
+    assert fields(_lib.mesh_query_plan(524_289, sphere, True)) == (HEAVY, GIVEN, 8193, 8192, 2, 32, 4)
+    assert fields(_lib.mesh_query_plan(524_289, sphere, False)) == (SCAN, GIVEN, 8193, 8192, 8, 0, 0)
+    # exactly 128 tiles: hands over with a scratch (>= 128); without one, its waves follow the group count (8 only ABOVE 128)
+    assert fields(_lib.mesh_query_plan(1 << 21, 128 * 256, True)) == (HEAVY, GIVEN, 32768, 8192, 2, 32, 4)
+    assert _lib.mesh_query_plan(1 << 21, 128 * 256, False).scan_waves == 2 and _lib.mesh_query_plan(1 << 21, 128 * 256 + 1, False).scan_waves == 8
+    # the chamfer has no listed path; its scan width follows groups x rows
+    assert fields(_lib.chamfer_mesh_plan(1 << 21, 1, 99_500, True)) == (HEAVY, GIVEN, 32768, 8192, 2, 32, 4)  # C5
+    assert fields(_lib.chamfer_mesh_plan(4096, 1, 99_500, False)) == (SCAN, GIVEN, 64, 64, 8, 0, 0)
+    assert _lib.chamfer_mesh_plan(500, 10_000, drill, True).scan_waves == 2 and _lib.chamfer_mesh_plan(500, 1, drill, True).scan_waves == 8
+    # nothing to launch
+    assert fields(_lib.mesh_query_plan(0, drill, True)) == fields(_lib.chamfer_mesh_plan(0, 3, drill, True)) == (0,) * 7
+    assert fields(_lib.chamfer_mesh_plan(100, 0, drill, True)) == fields(_lib.chamfer_mesh_plan(100, 3, 0, True)) == (0,) * 7
+    assert _lib.MESH_PATH_NONE == 0
+    # what the entry points refuse
+    import ctypes
+    plan = _lib.MeshPlan()
+    ref = ctypes.byref(plan)
+    small = _lib.mesh_small_points()
+    for args in ((-1, drill, 1, 0), (100, -1, 1, 0), (100, (1 << 26) + 1, 1, 0), (small + 1, drill, 1, 1), (64 << 31, drill, 0, 0)):
+        assert lib.pvamd_mesh_query_plan(*args, ref) == _lib.E_SHAPE, args
+    assert lib.pvamd_mesh_query_plan(small, drill, 1, 1, ref) == 0 and lib.pvamd_mesh_query_plan(100, 1 << 26, 0, 0, ref) == 0
+    for args in ((-1, 1, drill, 1), (100, -1, drill, 1), (100, 1, -1, 1), (100, 1, (1 << 26) + 1, 1)):
+        assert lib.pvamd_chamfer_mesh_plan(*args, ref) == _lib.E_SHAPE, args
+    assert lib.pvamd_mesh_query_plan(100, drill, 1, 0, None) == -1 and lib.pvamd_chamfer_mesh_plan(100, 1, drill, 1, None) == -1
+    # the sort: one workgroup while it holds the points (and then 16^3 cells), counting, radix; E_SHAPE beyond int32
+    assert [lib.pvamd_morton_order_kernel(P) for P in (0, 1, small, 10_000, 100_000, 1 << 21)] == [
+        _lib.ORDER_KERNEL_SMALL] * 4 + [_lib.ORDER_KERNEL_COUNTING, _lib.ORDER_KERNEL_RADIX]
+    assert [lib.pvamd_morton_order_bits(P) for P in (1, 10_000, 20_000, 100_000, 1 << 20)] == [12, 12, 15, 18, 21]
+    assert lib.pvamd_morton_order_kernel(small + 1) != _lib.ORDER_KERNEL_SMALL  # an unordered query never outgrows the one workgroup
+    for P in (-1, 1 << 31):
+        assert lib.pvamd_morton_order_kernel(P) == lib.pvamd_morton_order_bits(P) == _lib.E_SHAPE
+    assert lib.pvamd_morton_order_kernel((1 << 31) - 1) == _lib.ORDER_KERNEL_RADIX

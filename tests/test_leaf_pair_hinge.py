@@ -97,7 +97,7 @@ def test_abi_mirrors():
     lib = _lib.load()
     for name in NAMES:
         assert name in _lib.SIGNATURES and hasattr(lib, name)
-    assert _lib.ABI_VERSION == 15
+    assert _lib.ABI_VERSION == 16
     # every set within one 4096-point chunk: the single-pass forward needs no scratch
     assert _lib.leaf_pair_hinge_scratch_bytes(42, 200, 4096, False, False) == 0
     assert _lib.leaf_pair_hinge_scratch_bytes(42, 200, 4097, False, False) == 16 * 42 * 200 * 2

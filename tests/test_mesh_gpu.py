@@ -6,7 +6,7 @@ import torch
 
 import pytorch_volumetric_amd as pv
 from oracle import oracle
-from pytorch_volumetric_amd import mesh_io
+from pytorch_volumetric_amd import _lib, mesh_io
 from tests import helpers as H
 
 pytestmark = pytest.mark.gpu
@@ -14,6 +14,14 @@ pytestmark = pytest.mark.gpu
 
 def factory(name, **kw):
     return pv.MeshObjectFactory(H.mesh_path(name), **kw)
+
+
+def plan_of(obj, n):
+    """The launch plan the library reports (pvamd_mesh_query_plan) for the call object_frame_closest_point makes for n points
+    that come without an order: with the scratch unless tile_split is off, and through pvamd_mesh_query_unordered while the
+    points fit it."""
+    split = getattr(obj, "tile_split", True)
+    return _lib.mesh_query_plan(n, obj.num_faces, split, split and n <= _lib.mesh_small_points())
 
 
 def grid_sample(obj, n, seed, res=0.002, pad=0.01):
@@ -64,20 +72,46 @@ def test_c1_drill_10k_grid_points_match_oracle(tile_split):
     obj = factory("ycb_power_drill.npz")
     obj.tile_split = tile_split
     assert obj.num_faces == 15728
+    plan = plan_of(obj, 10_000)
+    if tile_split:  # every group listed, the order worked out inside the first launch
+        assert (plan.path, plan.order) == (_lib.MESH_PATH_LISTED, _lib.MESH_ORDER_INSIDE) and plan.parts > 1 and plan.scan_waves == 0
+    else:
+        assert (plan.path, plan.order) == (_lib.MESH_PATH_SCAN, _lib.MESH_ORDER_GIVEN) and plan.parts == 0 and plan.scan_waves > 1
     pts = grid_sample(obj, 10_000, seed=0)
     d = assert_query_matches(obj, pts, seed=0)
     assert 0.05 < (d < 0).mean() < 0.9
 
 
-@pytest.mark.parametrize("n", [1, 63, 64, 65, 1000, 4100, 12_000, 16_500, 40_000, 131_072, 300_000, 524_288, 524_289])
+GROUP_COUNT_SIZES = [1, 63, 64, 65, 1000, 4100, 12_000, 16_500, 40_000, 131_072, 300_000, 524_288, 524_289]
+
+
+@pytest.mark.parametrize("n", GROUP_COUNT_SIZES)
 def test_tile_split_path_for_every_group_count(n):
-    """Partial last group, a single point, every tiles-per-block rule of the two-launch path (1 / 1.5 / 3 / groups / 512 tiles
-    per block, four and two waves per block), counts on both sides of the 8192 groups where it hands over to the single launch,
-    and every waves-per-group choice of the latter."""
+    """Partial last group, a single point, every tiles-per-block rule of the listed path (1 / 1.5 / 3 / groups / 512 tiles per
+    block: five different numbers of parts on the drill), four and two waves per block, the order worked out inside and by
+    the caller, and counts on both sides of the number of groups the scratch has slots for, beyond which it is the single
+    scan (at these counts: of two waves per group; the other scan widths are in test_every_plan_of_the_mesh_query_...)."""
     obj = factory("ycb_power_drill.npz")
+    plan = plan_of(obj, n)
+    listed = plan.groups <= plan.slots  # 64 tiles is enough for the listed path at every group count: the scratch decides
+    assert plan.path == (_lib.MESH_PATH_LISTED if listed else _lib.MESH_PATH_SCAN)
+    assert plan.order == (_lib.MESH_ORDER_INSIDE if n <= _lib.mesh_small_points() else _lib.MESH_ORDER_GIVEN)
+    assert (plan.parts > 0 and plan.part_waves > 0 and plan.scan_waves == 0) if listed else (plan.parts == 0 and plan.scan_waves > 0)
     bb = obj.bounding_box(padding_ratio=0.3)
     pts = H.uniform_points(n, bb[:, 0], bb[:, 1], seed=100 + n)
     assert_query_matches(obj, pts, seed=n, oracle_points=40_000)
+
+
+def test_the_group_count_list_reaches_what_its_docstring_says():
+    """The size list of test_tile_split_path_for_every_group_count, through the export: both paths, both order sources of the
+    listed path, both part-block widths and at least five different numbers of parts (the tiles-per-block rules)."""
+    obj = factory("ycb_power_drill.npz")
+    plans = [plan_of(obj, n) for n in GROUP_COUNT_SIZES]
+    listed = [p for p in plans if p.path == _lib.MESH_PATH_LISTED]
+    assert {p.path for p in plans} == {_lib.MESH_PATH_LISTED, _lib.MESH_PATH_SCAN}
+    assert {p.order for p in listed} == {_lib.MESH_ORDER_INSIDE, _lib.MESH_ORDER_GIVEN}
+    assert len({p.part_waves for p in listed}) == 2 and len({p.parts for p in listed}) >= 5
+    assert plans[-2].path == _lib.MESH_PATH_LISTED and plans[-1].path == _lib.MESH_PATH_SCAN  # one point apart
 
 
 def test_cube_closed_form():
@@ -267,22 +301,33 @@ def test_large_sphere_mesh_distance_close_to_analytic():
     assert ((val.cpu() < 0) == (ref < -1e-3))[ref.abs() > 1e-3].all()
 
 
-@pytest.mark.parametrize("n,slices", [(300, 16), (70_000, 16), (300_000, 4)])
-def test_every_slice_configuration_matches_oracle(n, slices):
-    """The kernel picks 16, 8 or 4 waves per 64-point group from the point count and the mesh size (8: many points AND
-    more than 128 tiles, covered by the sphere / chamfer tests); unsorted (n < 2048) and Morton-sorted processing
-    orders are both covered.  All must reproduce the plain double loop bit for bit."""
+@pytest.mark.parametrize("n", [300, 70_000, 300_000])
+def test_a_mesh_of_two_tiles_is_scanned_whatever_the_point_count(n):
+    """probe.obj has 338 faces: two tiles, too few for the listed path, so every point count is one scan launch, and of as many
+    waves per 64-point group as the mesh has tiles.  An order worked out by a sort call in front (n within the unordered
+    entry point), the caller's Morton order beyond.  All must reproduce the plain double loop bit for bit.  (Every scan width
+    the library has, on meshes with the tiles for it: test_every_plan_of_the_mesh_query_matches_the_oracle_bitwise.)"""
     obj = factory("probe.obj")
+    plan = plan_of(obj, n)
+    tiles = _lib.tiles_floats(obj.num_faces) // _lib.tiles_floats(1)
+    assert tiles == 2 and (plan.path, plan.scan_waves, plan.parts) == (_lib.MESH_PATH_SCAN, tiles, 0)
+    assert plan.order == (_lib.MESH_ORDER_SORT_CALL if n <= _lib.mesh_small_points() else _lib.MESH_ORDER_GIVEN)
     bb = obj.bounding_box(padding_ratio=0.5)
     pts = H.uniform_points(n, bb[:, 0], bb[:, 1], seed=n)
     assert_query_matches(obj, pts, seed=n)
 
 
 def test_eight_wave_configuration_on_a_mesh_of_many_tiles():
-    """Many points AND more than 128 tiles (> 32,768 triangles) -> 8 waves per point group.  The oracle checks a prefix
+    """More than 128 tiles (> 32,768 triangles) and no scratch to hand heavy groups over with -> the scan with the most waves
+    per point group the library has, whatever the point count.  (With the scratch, 2^18 points are 4096 groups, which it has
+    slots for: the listed path, covered in test_heavy_point_groups_... and the plan scan below.)  The oracle checks a prefix
     of the batch (points are independent; the jitter is indexed by global point id)."""
     obj = pv.MeshObjectFactory(mesh=mesh_io.uv_sphere_mesh(0.1, 150, 120, scale=(1.0, 0.7, 1.3)))
     assert obj.num_faces > 128 * 256
+    obj.tile_split = False
+    plan = plan_of(obj, 1 << 18)
+    widest = max(plan_of(obj, n).scan_waves for n in (1, 1 << 12, 1 << 18, 1 << 22))
+    assert (plan.path, plan.order, plan.scan_waves) == (_lib.MESH_PATH_SCAN, _lib.MESH_ORDER_GIVEN, widest) and widest == 8
     pts = H.uniform_points(1 << 18, [-0.16] * 3, [0.16] * 3, seed=8)
     obj.jitter_seed = 5
     res = obj.object_frame_closest_point(pts.cuda(), compute_normal=True)
@@ -295,14 +340,22 @@ def test_eight_wave_configuration_on_a_mesh_of_many_tiles():
 
 
 def test_heavy_point_groups_are_handed_over_with_the_same_bits():
-    """A sphere mesh of more than 128 tiles and points around its centre -- about equidistant to the whole surface: such
-    point groups are handed over to a second launch that spreads their tiles over many workgroups (scratch given), or walk
-    the mesh on their own 8 waves (scratch withheld).  Same bits either way, and the oracle's on a slice that contains
-    centre points.  The chamfer entry point reports how many groups it handed over."""
+    """A sphere mesh of more than 128 tiles and points around its centre -- about equidistant to the whole surface.  The
+    query, 2^17 points: with the scratch every group is listed and its tiles spread over many workgroups (2048 groups: the
+    scratch has slots for all; the hand-over of only the heavy groups, for a query of more groups than slots, is in the
+    plan scan below); without it each group walks the mesh on its own 8 waves.  Same bits either way, and the oracle's on
+    a slice that contains centre points.  The chamfer: with the scratch the scan hands its heavy groups over to a second
+    launch and reports how many it listed; without it, the plain scan."""
     import ctypes
-    from pytorch_volumetric_amd import _lib
     obj = pv.MeshObjectFactory(mesh=mesh_io.uv_sphere_mesh(0.1, 150, 120))
     assert obj.num_faces > 128 * 256
+    for split, path in ((True, _lib.MESH_PATH_LISTED), (False, _lib.MESH_PATH_SCAN)):
+        obj.tile_split = split
+        for n in (1 << 17, 140_000):
+            assert plan_of(obj, n).path == path and plan_of(obj, n).order == _lib.MESH_ORDER_GIVEN
+    for rows, n in ((2, 1 << 17), (1, 9000 * 64)):
+        assert _lib.chamfer_mesh_plan(n, rows, obj.num_faces, True).path == _lib.MESH_PATH_SCAN_HEAVY
+        assert _lib.chamfer_mesh_plan(n, rows, obj.num_faces, False).path == _lib.MESH_PATH_SCAN
     g = torch.Generator().manual_seed(3)
     centre = (torch.rand(4096, 3, generator=g) - 0.5) * 0.02
     pts = torch.cat((centre[:700], H.uniform_points((1 << 17) - 4096, [-0.15] * 3, [0.15] * 3, seed=9), centre[700:])).float()
@@ -341,13 +394,89 @@ def test_heavy_point_groups_are_handed_over_with_the_same_bits():
     for k, sc in enumerate((None, scratch)):
         _lib.check(lib.pvamd_chamfer_mesh(ctypes.byref(desc), _lib.ptr(W), 1, _lib.ptr(many), _lib.ptr(order), many.shape[0],
                                           1000.0, _lib.ptr(one[k]), _lib.ptr(sc), _lib.stream_ptr()), "pvamd_chamfer_mesh")
-    assert int(scratch.view(torch.int32)[0].item()) > 8192  # 9000 groups still get the floor of 8192 slots:
-    assert _lib.mesh_scratch_bytes(many.shape[0]) == _lib.mesh_scratch_bytes(8192 * 64)
+    slots = _lib.chamfer_mesh_plan(many.shape[0], 1, obj.num_faces, True).slots
+    assert int(scratch.view(torch.int32)[0].item()) > slots  # 9000 groups still get the floor of 8192 slots:
+    assert slots == 8192 and _lib.mesh_scratch_bytes(many.shape[0]) == _lib.mesh_scratch_bytes(slots * 64)
     assert torch.allclose(one[0], one[1], rtol=1e-12, atol=0)
     obj.tile_split = True
     a_ = obj.object_frame_closest_point(many[:140_000]).distance.clone()
     obj.tile_split = False
     assert torch.equal(a_, obj.object_frame_closest_point(many[:140_000]).distance)
+
+
+def _query_plans(F, top):
+    """{(has_scratch, unordered) + helpers.plan_key: smallest point count that reaches it}, from pvamd_mesh_query_plan at the
+    first point count of every group count up to `top` points (the plan depends on the points through their group count)."""
+    seen = {}
+    for has_scratch in (False, True):
+        for unordered in (False, True):
+            for first in range(1, min(top, _lib.mesh_small_points() if unordered else top) + 1, 64):
+                key = (has_scratch, unordered) + H.plan_key(_lib.mesh_query_plan(first, F, has_scratch, unordered))
+                seen.setdefault(key, first)
+    return seen
+
+
+def _run_query(obj, pts, has_scratch, unordered, seed):
+    """pvamd_mesh_query / pvamd_mesh_query_unordered as the plan was asked for; ordered = the caller's Hilbert order."""
+    import ctypes
+    lib = _lib.load()
+    P = pts.shape[0]
+    out = [torch.empty((P, 3), device="cuda"), torch.empty((P,), device="cuda"), torch.empty((P, 3), device="cuda"),
+           torch.empty((P,), dtype=torch.int32, device="cuda"), torch.empty((P, 3), device="cuda")]
+    scratch = _lib.scratch_buffer(_lib.mesh_scratch_bytes(P), pts.device) if has_scratch else None
+    desc = obj._mesh_desc()
+    if unordered:
+        order = torch.empty((P,), dtype=torch.int32, device="cuda")
+        _lib.check(lib.pvamd_mesh_query_unordered(ctypes.byref(desc), _lib.ptr(pts), P, ctypes.c_uint64(seed), 0, *map(_lib.ptr, out),
+                                                  _lib.ptr(order), _lib.ptr(scratch), _lib.stream_ptr()), "pvamd_mesh_query_unordered")
+        assert torch.equal(torch.sort(order).values, torch.arange(P, dtype=torch.int32, device="cuda"))  # the order used
+    else:
+        order = _lib.morton_order(pts, min_points=0)
+        _lib.check(lib.pvamd_mesh_query(ctypes.byref(desc), _lib.ptr(pts), _lib.ptr(order), P, ctypes.c_uint64(seed), 0,
+                                        *map(_lib.ptr, out), _lib.ptr(scratch), _lib.stream_ptr()), "pvamd_mesh_query")
+    return out
+
+
+def test_every_plan_of_the_mesh_query_matches_the_oracle_bitwise():
+    """pvamd_mesh_query_plan scanned up to 2^20 points for the drill (62 tiles), the many-tile sphere (140) and the 12-face
+    box (one tile: the only way to the one-wave scan), with and without scratch, ordered and unordered: every distinct
+    (path, order source, scan width, part-block width) at the smallest point count that reaches it and at that + 37, so the
+    test follows the thresholds when they are retuned.  The jitter is indexed by global point id and every size is a prefix
+    of one pool per mesh, so ONE oracle run over the pool's first 4096 points is the reference of every case: bit for bit.
+    The sphere's pool starts with points around its centre -- groups that the heavy path hands over."""
+    PREFIX, TOP, seed = 4096, 1 << 20, 13
+    g = torch.Generator().manual_seed(5)
+    centre = (torch.rand(700, 3, generator=g) - 0.5) * 0.02
+    drill, box = factory("ycb_power_drill.npz"), factory("box_template.obj")
+    sphere = pv.MeshObjectFactory(mesh=mesh_io.uv_sphere_mesh(0.1, 150, 120))
+    bb = drill.bounding_box(padding_ratio=0.3)
+    meshes = [(drill, None, bb[:, 0], bb[:, 1]), (sphere, centre, [-0.15] * 3, [0.15] * 3), (box, None, [-2.5] * 3, [2.5] * 3)]
+    union, cases = set(), 0
+    for obj, lead, lo, hi in meshes:
+        plans = _query_plans(obj.num_faces, TOP)
+        need = max(plans.values()) + 37
+        pool = H.uniform_points(need, lo, hi, seed=21)
+        if lead is not None:
+            pool[:len(lead)] = lead
+        ref = oracle.mesh_query(H.oracle_mesh_from_factory(obj), pool[:PREFIX].numpy(), seed=seed)
+        dev = pool.cuda().contiguous()
+        for (has_scratch, unordered, path, order, scan_waves, part_waves), first in sorted(plans.items()):
+            union.add((path, order, scan_waves, part_waves))
+            for P in (first, first + 37):
+                if unordered and P > _lib.mesh_small_points():
+                    continue
+                assert (has_scratch, unordered) + H.plan_key(_lib.mesh_query_plan(P, obj.num_faces, has_scratch, unordered)) == \
+                    (has_scratch, unordered, path, order, scan_waves, part_waves), (obj.num_faces, P)
+                got = _run_query(obj, dev[:P], has_scratch, unordered, seed)
+                n = min(P, PREFIX)
+                for a, b, what in zip(got, ref, ("closest", "distance", "gradient", "face", "normal")):
+                    assert np.array_equal(a[:n].cpu().numpy(), b[:n], equal_nan=True), (what, obj.num_faces, P, has_scratch, unordered)
+                cases += 1
+    paths, orders, scans, part_blocks = (set(x) for x in zip(*union))
+    assert paths == {_lib.MESH_PATH_LISTED, _lib.MESH_PATH_SCAN, _lib.MESH_PATH_SCAN_HEAVY}
+    assert orders == {_lib.MESH_ORDER_GIVEN, _lib.MESH_ORDER_INSIDE, _lib.MESH_ORDER_SORT_CALL}
+    assert scans - {0} == {1, 2, 4, 8} and part_blocks - {0} == {2, 4}, union
+    assert cases >= 30, cases
 
 
 def test_culling_is_exact_for_far_and_degenerate_queries():

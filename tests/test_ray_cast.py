@@ -31,8 +31,8 @@ def test_abi_mirrors_and_status_codes_match_the_header():
     text = open(os.path.join(ROOT, "include", "pvamd.h")).read()
     for name, code in (("MISS", 0), ("HIT", 1), ("MAX_STEPS", 2), ("INVALID", 3)):
         assert re.search(rf"#define\s+PVAMD_RAY_{name}\s+{code}\b", text), name
-    assert re.search(r"#define\s+PVAMD_ABI_VERSION\s+15\b", text)
-    assert _lib.ABI_VERSION == 15
+    assert re.search(r"#define\s+PVAMD_ABI_VERSION\s+16\b", text)
+    assert _lib.ABI_VERSION == 16
     code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     for name in SYMBOLS:
         m = re.search(rf"\bint\s+{name}\s*\(([^)]*)\)\s*;", code)

@@ -33,7 +33,7 @@ def test_symbols_are_bound_and_declared_and_the_abi_number_stays():
         assert name in _lib.SIGNATURES and hasattr(lib, name)
         assert re.search(r"\b" + name + r"\s*\(", header), name
     assert "Chamfer normal equations" in open(os.path.join(ROOT, "include", "pvamd.h")).read()
-    assert lib.pvamd_abi_version() == 15 == _lib.ABI_VERSION
+    assert lib.pvamd_abi_version() == 16 == _lib.ABI_VERSION
 
 
 def test_scratch_bytes_mirror():

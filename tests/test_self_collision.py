@@ -194,7 +194,7 @@ def test_abi_mirrors():
                  "pvamd_leaf_pair_distance", "pvamd_leaf_pair_distance_f64", "pvamd_leaf_pair_distance_backward",
                  "pvamd_leaf_pair_distance_backward_f64"):
         assert name in _lib.SIGNATURES and hasattr(lib, name)
-    assert _lib.ABI_VERSION == 15
+    assert _lib.ABI_VERSION == 16
     # the common case: every set within one 4096-point chunk -> the single-pass forward needs no scratch
     assert _lib.leaf_pair_scratch_bytes(42, 200, 256, False, False) == 0
     assert _lib.leaf_pair_scratch_bytes(42, 200, 4097, False, False) == 16 * 42 * 200 * 2

@@ -1,4 +1,5 @@
-"""-m gpu: pvamd_morton_order -- the seven-launch counting sort and, from 786,432 points (3 << 18), the hand-written LSD radix sort -- that
+"""-m gpu: pvamd_morton_order -- one workgroup for few points, the seven-launch counting sort and, for many, the hand-written LSD radix
+sort; pvamd_morton_order_kernel says which at every size and pvamd_morton_order_bits on how many key bits -- that
 gives the mesh kernels and the bucketed composed path their spatial processing order (replaces torch.argsort of Morton keys,
 VERDICT r1 item 8; no library sort since round 5)."""
 import numpy as np
@@ -49,8 +50,35 @@ def curve_cells(pts, bits):
     return key
 
 
-@pytest.mark.parametrize("P", [1, 5, 300, 10_000, 16_384, 16_385, 65_535, 65_536, 262_144, (1 << 20) + 77, (3 << 18) - 1, (3 << 18) + 77, (3 << 19) - 1,
-                               (3 << 19) + 77, 1 << 21, (1 << 22) + 4095, 9_000_001])
+def _kernel_boundaries(top=1 << 24):
+    """Point counts either side of every change of pvamd_morton_order_kernel or pvamd_morton_order_bits up to `top` (scan in
+    steps of 4096, bisect inside a step), so the tests follow the thresholds when they are retuned."""
+    lib = _lib.load()
+    what = lambda p: (int(lib.pvamd_morton_order_kernel(p)), int(lib.pvamd_morton_order_bits(p)))
+    sizes, prev = set(), 1
+    for p in range(4096, top + 1, 4096):
+        if what(p) != what(prev):
+            a, b = prev, p
+            while b - a > 1:  # what(a) == what(prev) != what(b)
+                m = (a + b) // 2
+                a, b = (m, b) if what(m) == what(prev) else (a, m)
+            sizes.update({a, b})
+        prev = p
+    return sizes
+
+
+SIZES = sorted({1, 5, 300, 10_000, 16_384, 16_385, 65_535, 65_536, 262_144, (1 << 20) + 77, (3 << 18) - 1, (3 << 18) + 77, (3 << 19) - 1,
+                (3 << 19) + 77, 1 << 21, (1 << 22) + 4095, 9_000_001} | _kernel_boundaries())
+
+
+def test_the_size_list_has_every_sort_and_every_number_of_key_bits():
+    lib = _lib.load()
+    assert {int(lib.pvamd_morton_order_kernel(P)) for P in SIZES} == {_lib.ORDER_KERNEL_SMALL, _lib.ORDER_KERNEL_COUNTING, _lib.ORDER_KERNEL_RADIX}
+    assert len({int(lib.pvamd_morton_order_bits(P)) for P in SIZES}) == 4
+    assert len(_kernel_boundaries()) >= 8  # four changes (one workgroup / 2^15 / 2^18 cells / radix / 2^21 cells), two sides each
+
+
+@pytest.mark.parametrize("P", SIZES)
 def test_order_is_a_permutation_that_walks_the_cells_along_the_hilbert_curve(P):
     pts = H.uniform_points(P, [-0.7, -0.7, -0.2], [0.7, 0.7, 1.5], seed=P).cuda()
     order, inv, spts = _lib.morton_order(pts, min_points=0, want_inverse=True, want_sorted=True)
@@ -58,10 +86,11 @@ def test_order_is_a_permutation_that_walks_the_cells_along_the_hilbert_curve(P):
     assert np.array_equal(np.sort(o), np.arange(P))
     assert np.array_equal(inv.cpu().numpy()[o], np.arange(P))
     assert torch.equal(spts, pts[order.long()])
-    cells = curve_cells(pts.cpu().numpy(), 21 if P >= (1 << 20) else (18 if P >= (1 << 16) else (15 if P > 16384 else 12)))
+    lib = _lib.load()
+    cells = curve_cells(pts.cpu().numpy(), lib.pvamd_morton_order_bits(P))
     walked = cells[o]
     assert (np.diff(walked) >= 0).all()  # cells in curve order; inside a cell any order ...
-    if P >= (3 << 18):  # ... except from 786,432 points on (a stable radix sort of (cell, index) pairs, csrc/sort.hip): index order
+    if lib.pvamd_morton_order_kernel(P) == _lib.ORDER_KERNEL_RADIX:  # ... except in the stable radix sort of (cell, index) pairs (csrc/sort.hip): index order
         same = np.diff(walked) == 0
         assert (np.diff(o)[same] > 0).all()
 
@@ -95,7 +124,8 @@ def test_degenerate_clouds():
     line[:, 0] = torch.linspace(0, 1, 4096)
     o = _lib.morton_order(line.cuda(), min_points=0).cpu().numpy()
     assert np.array_equal(np.sort(o), np.arange(4096))
-    assert np.abs(np.diff(line[o, 0].numpy())).mean() < 2.0 / 15  # neighbours stay neighbours (16 cells per axis here)
+    per_axis = 1 << (_lib.load().pvamd_morton_order_bits(4096) // 3)  # cells per axis of the sort that 4096 points get
+    assert np.abs(np.diff(line[o, 0].numpy())).mean() < 2.0 / (per_axis - 1)  # neighbours stay neighbours
 
 
 def test_mesh_query_bits_do_not_depend_on_the_processing_order():
@@ -109,9 +139,11 @@ def test_mesh_query_bits_do_not_depend_on_the_processing_order():
 
 
 def test_radix_sort_is_deterministic_and_handles_clustered_keys():
-    """From 786,432 points on: the same permutation on every run (stable passes, no atomics in the ranking), also when almost
+    """The radix sort: the same permutation on every run (stable passes, no atomics in the ranking), also when almost
     every point shares one cell (one digit run holds nearly the whole tile) and when the cloud is a few clusters."""
-    P = (3 << 18) + 12_345
+    lib = _lib.load()
+    P = next(p for p in _kernel_boundaries() if lib.pvamd_morton_order_kernel(p) == _lib.ORDER_KERNEL_RADIX) + 12_345
+    assert lib.pvamd_morton_order_kernel(P) == _lib.ORDER_KERNEL_RADIX
     g = torch.Generator().manual_seed(3)
     same = torch.full((P, 3), 0.5)
     same[:1000] = torch.rand(1000, 3, generator=g)  # bounds stay the unit box; everything else in ONE cell
@@ -123,6 +155,6 @@ def test_radix_sort_is_deterministic_and_handles_clustered_keys():
         assert torch.equal(a, b)
         o = a.cpu().numpy()
         assert np.array_equal(np.sort(o), np.arange(P))
-        cells = curve_cells(pts.cpu().numpy(), 21 if P >= (1 << 20) else 18)[o]
+        cells = curve_cells(pts.cpu().numpy(), lib.pvamd_morton_order_bits(P))[o]
         assert (np.diff(cells) >= 0).all()
         assert (np.diff(o)[np.diff(cells) == 0] > 0).all()
