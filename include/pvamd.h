@@ -866,6 +866,54 @@ int pvamd_composed_ray_cast_f64(const pvamd_grid_t* grids, int32_t S, const doub
                                 const double* directions, int64_t R, int32_t mode, double t_min, double t_max, double eps,
                                 double step_scale, int32_t max_steps, double* out_t, uint8_t* out_status, double* out_val,
                                 double* out_grad, int32_t* out_steps, void* stream);
+
+/* ---- Ray casting: gradient of the hit distance (ray_cast(..., differentiable=True)) ----
+ * The derivative of out_t of "Ray casting" w.r.t. the origins, the directions and, for a composition, the transforms, under the
+ * surface-normal linearisation at the hit point -- the model "Chamfer normal equations" takes: the gradient a cache record
+ * stores is the first-order model of the surface.  It is NOT the derivative of the step loop: that would need every step's
+ * state and is zero at every in-range point of a nearest grid.  Decisions are held fixed: status, step count, winning leaf.
+ *  1. Per (configuration a, ray i): t = out_t, x = o_i + t d_i, n = out_grad (the gradient the forward returned at x).  The model
+ *     is val(x + delta) = v + n . delta, and t is the root of val(o + t d) = const.
+ *  2. Every term is formed in float64 from the T inputs, every product and sum rounded separately, left to right.
+ *     c = n0 d0 + n1 d1 + n2 d2.  The pair contributes only when status == PVAMD_RAY_HIT, c < 0 and c is finite; a miss, a
+ *     max-steps ray, an invalid ray and a hit whose normal does not face the ray (c >= 0: a ray that starts inside and points
+ *     outward) contribute exactly zero to every output.  With w = -up[a][i] / c (up: the upstream of out_t):
+ *         dorigins_i    += w n
+ *         ddirections_i += (w t) n
+ *     A grazing hit (c -> 0-) gives a large gradient by construction; weighting it is the caller's job.
+ *  3. A composition: s the winning leaf at x, M = tf[s*A + a] (rigid), gamma_r = M[r][0] n0 + M[r][1] n1 + M[r][2] n2 (the
+ *     leaf-frame record gradient: the forward returned n = L^T gamma), x_j = o_j + t d_j in float64:
+ *         dtf[s*A + a][r][j] += (w gamma_r) x_j   (j < 3)
+ *         dtf[s*A + a][r][3] += w gamma_r
+ *     Row 3 of every dtf matrix is zero and leaves that win nowhere get exactly zero rows.  (v, n, s) are recomputed at the
+ *     forward's own p (o + t d rounded in T as in "Ray casting" 2) with the forward's statements: the forward's bits, so no leaf
+ *     ids are stored.
+ *  4. Sums: dorigins / ddirections [R][3] sum over the configurations, dtf [S*A][4][4] over the rays, in float64, in an order
+ *     that depends only on (S, A, R), each rounded once to T.  dorigins / ddirections: in configuration order within a split of
+ *     aper consecutive configurations, then the splits in split order, where with nchunks = ceil(R / PVAMD_RAY_BACKWARD_CHUNK)
+ *     and want = min(A, ceil(2048 / nchunks)): aper = ceil(A / want).  dtf: a wave butterfly over 64 consecutive rays, the four
+ *     waves of a PVAMD_RAY_BACKWARD_CHUNK-ray chunk in wave order, then the chunks in chunk order.  No float atomics: two calls
+ *     give the same bits.  No device -> host synchronisation, no allocation: capturable in a graph.
+ * Argument errors return before any launch.  Any of dorigins, ddirections, dtf may be NULL (not wanted).
+ * pvamd_cached_ray_cast_backward / _f64: one grid; elementwise, no lookup, no scratch.  directions, grad (the forward's out_grad)
+ *   [R][3]; t, status, up [R]; dorigins, ddirections [R][3].  The origins do not enter: x appears in no term.  0 <= R.
+ * pvamd_composed_ray_cast_backward / _f64: t, status, up [A][R]; dtf [S*A][4][4].  1 <= S <= 64, 0 <= A, 0 <= R (A = 0 or R = 0
+ *   writes zeros).  scratch: device, pvamd_ray_cast_backward_scratch_bytes(S, A, R, is_f64) bytes, 16-byte aligned: 12 float64
+ *   per (chunk, leaf, configuration), then 6 float64 per (split, ray) when there is more than one split.  That function is the
+ *   definition (the launch plan decides the size; the partials are float64 for either T); there is no macro.                    */
+#define PVAMD_RAY_BACKWARD_CHUNK 256 /* rays per slab row */
+int64_t pvamd_ray_cast_backward_scratch_bytes(int32_t S, int32_t A, int64_t R, int32_t is_f64);
+int pvamd_cached_ray_cast_backward(const float* directions, int64_t R, const float* t, const uint8_t* status, const float* grad,
+                                   const float* up, float* dorigins, float* ddirections, void* stream);
+int pvamd_cached_ray_cast_backward_f64(const double* directions, int64_t R, const double* t, const uint8_t* status,
+                                       const double* grad, const double* up, double* dorigins, double* ddirections, void* stream);
+int pvamd_composed_ray_cast_backward(const pvamd_grid_t* grids, int32_t S, const float* tf, int32_t A, const float* origins,
+                                     const float* directions, int64_t R, int32_t mode, const float* t, const uint8_t* status,
+                                     const float* up, float* dorigins, float* ddirections, float* dtf, void* scratch, void* stream);
+int pvamd_composed_ray_cast_backward_f64(const pvamd_grid_t* grids, int32_t S, const double* tf, int32_t A, const double* origins,
+                                         const double* directions, int64_t R, int32_t mode, const double* t, const uint8_t* status,
+                                         const double* up, double* dorigins, double* ddirections, double* dtf, void* scratch,
+                                         void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -34,6 +34,7 @@ MOP_CHUNK = 4096  # PVAMD_MOP_CHUNK
 REG_CHUNK = 2048  # PVAMD_REG_CHUNK
 REG_SUMS = 28     # PVAMD_REG_SUMS: the row length of pvamd_chamfer_normal_eq's out_sums
 RAY_MISS, RAY_HIT, RAY_MAX_STEPS, RAY_INVALID = 0, 1, 2, 3  # PVAMD_RAY_*: the status codes of the ray-cast entry points
+RAY_BACKWARD_CHUNK = 256  # PVAMD_RAY_BACKWARD_CHUNK
 
 
 # Buffer sizes: the library's exported size functions are the definition (include/pvamd.h) -- what they report is what the
@@ -104,6 +105,13 @@ def leaf_pair_hinge_scratch_bytes(K, A, max_points, f64, backward):
     when a set holds more than one chunk (else none); the backward's dC slab of 12 values per pair, configuration and
     1024-point chunk, then dMs and dMt per pair and configuration."""
     return load().pvamd_leaf_pair_hinge_scratch_bytes(K, A, max_points, int(f64), int(backward))
+
+
+@_remembered
+def ray_cast_backward_scratch_bytes(S, A, R, f64):
+    """pvamd_ray_cast_backward_scratch_bytes: 12 float64 per ray chunk, leaf and configuration, then 6 float64 per configuration
+    split and ray when the plan splits the configurations."""
+    return load().pvamd_ray_cast_backward_scratch_bytes(S, A, R, int(f64))
 
 
 @_remembered
@@ -359,6 +367,12 @@ SIGNATURES = {
     "pvamd_cached_ray_cast_f64": (ctypes.c_int, [ctypes.POINTER(GridDesc), ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "pvamd_composed_ray_cast": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "pvamd_composed_ray_cast_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    # ray_cast(..., differentiable=True) (include/pvamd.h "Ray casting: gradient of the hit distance")
+    "pvamd_ray_cast_backward_scratch_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32]),
+    "pvamd_cached_ray_cast_backward": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "pvamd_cached_ray_cast_backward_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "pvamd_composed_ray_cast_backward": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "pvamd_composed_ray_cast_backward_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
 }
 
 E_SHAPE = -2  # PVAMD_E_SHAPE (include/pvamd.h)

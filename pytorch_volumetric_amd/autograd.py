@@ -326,6 +326,107 @@ def leaf_pair_hinge(composed, plan, margin, power, mode):
     return LeafPairHinge(val, cnt)
 
 
+# ---------------------------------------------------------------- ray_cast(..., differentiable=True)
+# (include/pvamd.h "Ray casting: gradient of the hit distance")
+def ray_hit_vjp_torch(d, t, status, n, up):
+    """The contract's formula for the rays in float64 torch: directions d (..., 3), the forward's t, status and gradients n, the
+    upstream up of t -> (w n, (w t) n), exact zeros where the pair does not contribute.  Not summed over anything."""
+    d, t, n, up = (x.to(torch.float64) for x in (d, t, n, up))
+    c = n[..., 0] * d[..., 0] + n[..., 1] * d[..., 1] + n[..., 2] * d[..., 2]
+    on = (status == _lib.RAY_HIT) & (c < 0) & torch.isfinite(c)
+    w = torch.where(on, -up / torch.where(on, c, torch.ones_like(c)), torch.zeros_like(c))
+    zero = torch.zeros_like(n)
+    return (torch.where(on.unsqueeze(-1), w.unsqueeze(-1) * n, zero),
+            torch.where(on.unsqueeze(-1), (w * t).unsqueeze(-1) * n, zero))
+
+
+class RayHitDistance(torch.autograd.Function):
+    """The generic ray cast's t with its gradient: forward returns the bits of the torch march's t, backward is the contract's
+    formula in float64 torch (any SDF, any floating dtype; not a hot path).  origins / directions: the caller's tensors expanded
+    to the rays' shape; d, t, status, n: the flat (R, ...) results of the march."""
+
+    @staticmethod
+    def forward(ctx, origins, directions, d, t, status, n):
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(origins, directions, d, t, status, n)
+        return t.clone()
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, up):
+        origins, directions, d, t, status, n = ctx.saved_tensors
+        if up is None:
+            return None, None, None, None, None, None
+        go, gd = ray_hit_vjp_torch(d, t, status, n, up.detach().to(t.device))
+        return (go.reshape(origins.shape).to(device=origins.device, dtype=origins.dtype) if ctx.needs_input_grad[0] else None,
+                gd.reshape(directions.shape).to(device=directions.device, dtype=directions.dtype) if ctx.needs_input_grad[1] else None,
+                None, None, None, None)
+
+
+class RayCastQuery(torch.autograd.Function):
+    """Forward: the fused ray cast (CachedSDF / ComposedSDF._ray_cast_fused: the usual kernels, the usual bits).  Backward:
+    pvamd_cached_ray_cast_backward / pvamd_composed_ray_cast_backward (csrc/ray_cast_backward.hip) from the forward's t, status
+    and gradients; a composition recomputes the winning leaf in the kernel.  origins / directions: the caller's tensors expanded
+    to the rays' shape (torch's expand backward sums a shared origin); tfm: a composition's stack, else None."""
+
+    @staticmethod
+    def forward(ctx, sdf, origins, directions, tfm, o, d, lead, dtype, args):
+        ctx.set_materialize_grads(False)
+        res, kept = sdf._ray_cast_fused(o, d, lead, dtype, args)
+        ctx.kept, ctx.lead = kept, lead
+        # the flat rays and the stack the kernels read may alias the inputs, and the results are views of the kernels' buffers:
+        # saving them lets torch raise on an in-place write between forward and backward
+        ctx.save_for_backward(origins, directions, tfm, kept["out"][0], kept["out"][1], kept["out"][3])
+        ctx.mark_non_differentiable(res.status, res.values, res.gradients, res.steps)
+        return tuple(res)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dt, *_):
+        if dt is None:  # nothing flows back
+            return (None,) * 9
+        origins, directions, tfm = ctx.saved_tensors[:3]  # and the version check of everything saved
+        need_o, need_d, need_tf = ctx.needs_input_grad[1:4]
+        kept = ctx.kept
+        o, d, (t, status, _, grad, _) = kept["o"], kept["d"], kept["out"]
+        R, dev, dtype = o.shape[0], o.device, o.dtype
+        f64 = dtype == torch.float64
+        go = torch.empty((R, 3), dtype=dtype, device=dev) if need_o else None
+        gd = torch.empty((R, 3), dtype=dtype, device=dev) if need_d else None
+        gtf = None
+        if "tfd" not in kept:
+            up = _upstream(dt, dev, dtype, (R,))
+            name = "pvamd_cached_ray_cast_backward" + ("_f64" if f64 else "")
+            with _lib.on_device(dev):
+                _lib.check(getattr(_lib.load(), name)(_lib.ptr(d), R, _lib.ptr(t), _lib.ptr(status), _lib.ptr(grad), _lib.ptr(up),
+                                                      _lib.ptr(go), _lib.ptr(gd), _lib.stream_ptr()), name)
+        else:
+            S, A = kept["S"], kept["A"]
+            up = _upstream(dt, dev, dtype, (A, R))
+            gtf = torch.empty((S * A, 4, 4), dtype=dtype, device=dev) if need_tf else None
+            name = "pvamd_composed_ray_cast_backward" + ("_f64" if f64 else "")
+            with _lib.on_device(dev):
+                scratch = _lib.scratch_buffer(max(_lib.ray_cast_backward_scratch_bytes(S, A, R, f64), 16), dev)
+                _lib.check(getattr(_lib.load(), name)(_lib.ptr(kept["grids"]), S, _lib.ptr(kept["tfd"]), A, _lib.ptr(o), _lib.ptr(d), R,
+                                                      _lib.LEAF_MODES[kept["mode"]], _lib.ptr(t), _lib.ptr(status), _lib.ptr(up),
+                                                      _lib.ptr(go), _lib.ptr(gd), _lib.ptr(gtf), _lib.ptr(scratch),
+                                                      _lib.stream_ptr()), name)
+        return (None,
+                go.reshape(*ctx.lead, 3).to(device=origins.device, dtype=origins.dtype) if need_o else None,
+                gd.reshape(*ctx.lead, 3).to(device=directions.device, dtype=directions.dtype) if need_d else None,
+                gtf.to(device=tfm.device, dtype=tfm.dtype) if need_tf else None,
+                None, None, None, None, None)
+
+
+def ray_cast(sdf, graph, o, d, lead, dtype, args):
+    """sdf.ray_cast through RayCastQuery: graph = (origins, directions) expanded to the rays' shape, still attached."""
+    from pytorch_volumetric_amd.sdf import RayCast
+    tfm = getattr(sdf, "_tf_matrix", None)
+    if tfm is not None and len(sdf.sdfs) > MAX_LEAVES:
+        raise _lib.PvamdError(f"gradients through a composition need at most {MAX_LEAVES} leaves, this one has {len(sdf.sdfs)}")
+    return RayCast(*RayCastQuery.apply(sdf, graph[0], graph[1], tfm, o, d, lead, dtype, args))
+
+
 def pair_transforms_torch(stack, pairs):
     """The pair transforms of include/pvamd.h "Leaf-pair distance" 1 in torch (any dtype, differentiable): stack (S, A, 4, 4),
     pairs (K, 2) -> (K, A, 4, 4).  Rounding aside (torch's matmul does not promise the kernel's fma order), the same C."""

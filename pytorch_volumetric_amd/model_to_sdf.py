@@ -283,12 +283,15 @@ class RobotSDF(sdf.ObjectFrameSDF):
         margin.  Differentiable w.r.t. q when set_joint_configuration was given a q that requires grad, as __call__ is."""
         return self.sdf.hinge_over_points(points, margin, power=power, per_leaf=per_leaf)
 
-    def ray_cast(self, origins, directions, t_min=0., t_max=math.inf, hit_tolerance=1e-3, step_scale=1., max_steps=128):
+    def ray_cast(self, origins, directions, t_min=0., t_max=math.inf, hit_tolerance=1e-3, step_scale=1., max_steps=128,
+                 differentiable=False):
         """ComposedSDF.ray_cast under the current joint configuration: per configuration and ray (rays in the robot frame, shared
         by the configurations) where the ray first meets the robot -- a depth or lidar sensor simulated against every
-        configuration at once.  The result carries no autograd graph."""
+        configuration at once.  The result carries no autograd graph unless differentiable=True: then t is differentiable
+        w.r.t. the rays and, when set_joint_configuration was given a q that requires grad, w.r.t. q (the surface-normal
+        linearisation at the hit point; include/pvamd.h "Ray casting: gradient of the hit distance")."""
         return self.sdf.ray_cast(origins, directions, t_min=t_min, t_max=t_max, hit_tolerance=hit_tolerance,
-                                 step_scale=step_scale, max_steps=max_steps)
+                                 step_scale=step_scale, max_steps=max_steps, differentiable=differentiable)
 
     def set_self_collision_points(self, points=None, num_points=256, seed=0):
         """The point set of each leaf that self_collision_distance moves against the other leaves' SDFs.

@@ -134,6 +134,21 @@ def _ray_inputs(origins, directions):
     return origins.detach().expand(shape), directions.detach().expand(shape), tuple(shape[:-1]), dtype
 
 
+def _ray_graph(differentiable, origins, directions, lead, tf_grad=False):
+    """Whether a ray cast keeps an autograd graph (include/pvamd.h "Ray casting: gradient of the hit distance"): None -- today's
+    path -- unless differentiable is True, grad mode is on and the origins, the directions or (tf_grad) a composition's
+    transforms require grad; else (origins, directions) expanded to the rays' shape lead + (3,), still attached."""
+    if not isinstance(differentiable, bool):
+        raise TypeError(f"differentiable must be True or False, got {differentiable!r}")
+    if not (differentiable and torch.is_grad_enabled()):
+        return None
+    origins = origins if torch.is_tensor(origins) else torch.as_tensor(origins)
+    directions = directions if torch.is_tensor(directions) else torch.as_tensor(directions)
+    if not (origins.requires_grad or directions.requires_grad or tf_grad):
+        return None
+    return origins.expand(*lead, 3), directions.expand(*lead, 3)
+
+
 def _ray_outputs(shape, dtype, dev):
     """(t, status, values, gradients, steps) buffers of the ray-cast entry points, in the C ABI's argument order."""
     return (torch.empty(shape, dtype=dtype, device=dev), torch.empty(shape, dtype=torch.uint8, device=dev),
@@ -452,7 +467,8 @@ class ObjectFrameSDF(abc.ABC):
         sdf_values, _ = self.__call__(points_in_object_frame)
         return sdf_values > surface_level
 
-    def ray_cast(self, origins, directions, t_min=0., t_max=math.inf, hit_tolerance=1e-3, step_scale=1., max_steps=128):
+    def ray_cast(self, origins, directions, t_min=0., t_max=math.inf, hit_tolerance=1e-3, step_scale=1., max_steps=128,
+                 differentiable=False):
         """Sphere tracing: where each ray origins + t * directions first meets the surface (include/pvamd.h "Ray casting").
 
         :param origins, directions: (..., 3), broadcast against each other and promoted to one dtype (the dtype and device rules
@@ -466,21 +482,32 @@ class ObjectFrameSDF(abc.ABC):
             the last evaluated point (t_min when none was), values / gradients are the bits __call__ returns there (NaN when none
             was), status is uint8 (RAY_MISS, RAY_HIT, RAY_MAX_STEPS, RAY_INVALID: the query returned NaN), steps int32.  Each real
             scalar is rounded once to the rays' dtype, and every product and sum is rounded separately in it.  No rays give empty
-            results.  The result carries no autograd graph: rays that require grad are accepted and detached.
+            results.
+        :param differentiable: must be a bool.  False (the default), grad mode off or nothing that requires grad: the result
+            carries no autograd graph, and rays that require grad are accepted and detached.  True with origins or directions
+            that require grad: t -- and only t -- gains a grad_fn, every output keeping the bits of the non-differentiable call.
+            The gradient is the surface-normal linearisation at the hit point (include/pvamd.h "Ray casting: gradient of the hit
+            distance"), not autograd through the loop: with n = gradients and c = n . d, a ray with status RAY_HIT and c < 0
+            gives dt/do = -n / c and dt/dd = -t n / c, every other ray exactly zero.  A grazing hit (c -> 0-) gives a large
+            gradient by construction; weighting it is the caller's job.  Double backward is not supported.
 
         This is the loop in torch around __call__ -- every SDF has it; it is not a hot path and synchronises once per step.
         CachedSDF and ComposedSDF run it as one HIP kernel where they can (csrc/ray_cast.hip)."""
         args = _ray_args(t_min, t_max, hit_tolerance, step_scale, max_steps)
         o, d, lead, dtype = _ray_inputs(origins, directions)
-        return self._ray_cast_generic(o, d, lead, dtype, args)
+        return self._ray_cast_generic(o, d, lead, dtype, args, _ray_graph(differentiable, origins, directions, lead))
 
-    def _ray_cast_generic(self, o, d, lead, dtype, args):
-        """ray_cast after the argument checks: the torch loop around __call__ on the rays' own device."""
+    def _ray_cast_generic(self, o, d, lead, dtype, args, graph=None):
+        """ray_cast after the argument checks: the torch loop around __call__ on the rays' own device.  graph (_ray_graph): t
+        leaves with the contract's gradient w.r.t. the rays attached, its bits unchanged."""
         dev = o.device if o.device.type != "cpu" else d.device
         o = o.reshape(-1, 3).to(device=dev, dtype=dtype)
         d = d.reshape(-1, 3).to(device=dev, dtype=dtype)
         with torch.no_grad():
             t, status, v, g, steps = _ray_march(self.__call__, o, d, *args)
+        if graph is not None:
+            from pytorch_volumetric_amd import autograd
+            t = autograd.RayHitDistance.apply(graph[0], graph[1], d, t, status, g)
         return RayCast(t.reshape(lead), status.reshape(lead), v.reshape(lead), g.reshape(*lead, 3), steps.reshape(lead))
 
     def get_voxel_view(self, voxels=None, dtype=torch.float, device='cpu'):
@@ -918,22 +945,34 @@ class CachedSDF(ObjectFrameSDF):
                        name)
         return val, grad, oob
 
-    def ray_cast(self, origins, directions, t_min=0., t_max=math.inf, hit_tolerance=1e-3, step_scale=1., max_steps=128):
+    def ray_cast(self, origins, directions, t_min=0., t_max=math.inf, hit_tolerance=1e-3, step_scale=1., max_steps=128,
+                 differentiable=False):
         """ObjectFrameSDF.ray_cast (arguments, results and contract there; include/pvamd.h "Ray casting") against this cache, in the
         cache's interpolation.  A 3-D BOUNDING_BOX cache with float32 or float64 rays is ONE kernel launch (csrc/ray_cast.hip:
         a lane per ray, the whole march in registers, nothing but the results written) with nothing that synchronises with the
         host, so it can be captured in a graph; LOOKUP_GT_SDF caches and other dtypes run the torch loop around __call__.
-        Planar caches raise.  Results are returned on this cache's device; they carry no autograd graph.
+        Planar caches raise.  Results are returned on this cache's device; they carry no autograd graph unless differentiable=True
+        and a ray input requires grad: then t carries the gradient of the hit distance, and on the one-kernel path its backward
+        is one elementwise kernel (csrc/ray_cast_backward.hip) from the forward's own t, status and gradients.
 
         A nearest cache is piecewise constant -- one voxel-centre sample per voxel -- so the march can overshoot the surface
         by up to half a voxel diagonal: interpolation="trilinear" or step_scale < 1 is the remedy."""
         args = _ray_args(t_min, t_max, hit_tolerance, step_scale, max_steps)
         o, d, lead, dtype = _ray_inputs(origins, directions)
+        graph = _ray_graph(differentiable, origins, directions, lead)
         if self._dim != 3:
             raise ValueError("ray_cast needs a 3-D cache, this one is planar")
         if self.out_of_bounds_strategy != OutOfBoundsStrategy.BOUNDING_BOX or self.debug_check_sdf or \
                 dtype not in (torch.float32, torch.float64):
-            return self._ray_cast_generic(o, d, lead, dtype, args)
+            return self._ray_cast_generic(o, d, lead, dtype, args, graph)
+        if graph is not None:
+            from pytorch_volumetric_amd import autograd
+            return autograd.ray_cast(self, graph, o, d, lead, dtype, args)
+        return self._ray_cast_fused(o, d, lead, dtype, args)[0]
+
+    def _ray_cast_fused(self, o, d, lead, dtype, args):
+        """One pvamd_cached_ray_cast[_f64] call.  Returns the RayCast, then what the backward needs: the flat rays the kernel read
+        and its five output buffers."""
         dev = self._packed.device
         o = o.reshape(-1, 3).to(device=dev, dtype=dtype).contiguous()
         d = d.reshape(-1, 3).to(device=dev, dtype=dtype).contiguous()
@@ -943,7 +982,7 @@ class CachedSDF(ObjectFrameSDF):
         with _lib.on_device(dev):
             _lib.check(getattr(_lib.load(), name)(ctypes.byref(self._grid_desc()), _lib.LEAF_MODES[self.interpolation], _lib.ptr(o),
                                                   _lib.ptr(d), R, *args, *map(_lib.ptr, out), _lib.stream_ptr()), name)
-        return _ray_result(out, lead, self.device)
+        return _ray_result(out, lead, self.device), {"o": o, "d": d, "out": out}
 
     def outside_surface(self, points_in_object_frame, surface_level=0):
         """sdf.py:593-602 (trilinear caches: the interpolated value > surface_level in range, True out of range)"""
@@ -1501,14 +1540,23 @@ class ComposedSDF(ObjectFrameSDF):
         return MinOverPoints(v.reshape(batch), idx.reshape(batch), g.reshape(*batch, 3))
 
     # ---- ray casting ----
-    def ray_cast(self, origins, directions, t_min=0., t_max=math.inf, hit_tolerance=1e-3, step_scale=1., max_steps=128):
+    def ray_cast(self, origins, directions, t_min=0., t_max=math.inf, hit_tolerance=1e-3, step_scale=1., max_steps=128,
+                 differentiable=False):
         """ObjectFrameSDF.ray_cast (arguments and contract there; include/pvamd.h "Ray casting") against the composition under every
         configuration: the rays are given in the composition's object frame and shared by all configurations.
 
         :return: RayCast(t, status, values, gradients, steps) of shapes B + (...) (gradients B + (..., 3)), B the transform batch
             shape (() without one) and (...) the broadcast shape of origins and directions without its last dimension.  Row a is,
-            bit for bit, the loop over configuration a alone, with the values and gradients __call__ returns.  The result carries
-            no autograd graph: rays (and transforms) that require grad are accepted and detached.
+            bit for bit, the loop over configuration a alone, with the values and gradients __call__ returns.  Without
+            differentiable=True the result carries no autograd graph: rays (and transforms) that require grad are accepted and
+            detached.
+        :param differentiable: True, with grad mode on and origins, directions or the transforms (a RobotSDF's joint values)
+            requiring grad: t gains a grad_fn, with the same bits (ObjectFrameSDF.ray_cast; include/pvamd.h "Ray casting: gradient
+            of the hit distance").  The rays' gradients sum over the configurations; the winning leaf s's transform M gets
+            dM[:3, :3] = w gamma x^T and dM[:3, 3] = w gamma per contributing pair (gamma = M[:3, :3] n, w = -upstream / c), summed
+            over the rays.  Fused compositions run one HIP backward (csrc/ray_cast_backward.hip: fixed-order float64 sums, bitwise
+            reproducible, at most 64 leaves).  Any other composition differentiates w.r.t. the rays only and raises ValueError
+            when its transforms require grad.
 
         Fused compositions (_fused_mode(): every leaf a BOUNDING_BOX CachedSDF of one interpolation, rigid transforms) with float32
         or float64 rays run ONE kernel (csrc/ray_cast.hip: a lane per configuration and ray) that writes nothing but the results
@@ -1520,9 +1568,20 @@ class ComposedSDF(ObjectFrameSDF):
         if self._tf_matrix is None:
             raise ValueError("ray_cast needs the transforms to be set")
         batch = tuple(self.tsf_batch) if self.tsf_batch is not None else ()
+        graph = _ray_graph(differentiable, origins, directions, lead, self._tf_grad)
         mode = self._fused_mode()
         if mode is None or dtype not in (torch.float32, torch.float64):
-            return self._ray_cast_per_configuration(o, d, lead, dtype, args, batch)
+            return self._ray_cast_per_configuration(o, d, lead, dtype, args, batch, graph)
+        if graph is not None:
+            from pytorch_volumetric_amd import autograd
+            return autograd.ray_cast(self, graph, o, d, lead, dtype, args)
+        return self._ray_cast_fused(o, d, lead, dtype, args)[0]
+
+    def _ray_cast_fused(self, o, d, lead, dtype, args):
+        """One pvamd_composed_ray_cast[_f64] call.  Returns the RayCast, then what the backward needs: the flat rays and the stack
+        the kernel read, the leaf descriptors and the five output buffers."""
+        batch = tuple(self.tsf_batch) if self.tsf_batch is not None else ()
+        mode = self._fused_mode()
         S, A = len(self.sdfs), math.prod(batch)
         dev = self._owner_device()
         o = o.reshape(-1, 3).to(device=dev, dtype=dtype).contiguous()
@@ -1535,18 +1594,26 @@ class ComposedSDF(ObjectFrameSDF):
             grids = self._leaf_grids(dev)
             _lib.check(getattr(_lib.load(), name)(_lib.ptr(grids), S, _lib.ptr(tfd), A, _lib.ptr(o), _lib.ptr(d), R,
                                                   _lib.LEAF_MODES[mode], *args, *map(_lib.ptr, out), _lib.stream_ptr()), name)
-        return _ray_result(out, batch + lead, self.sdfs[0].device)  # leaves return on their own device (sdf.py:546)
+        # leaves return on their own device (sdf.py:546)
+        return _ray_result(out, batch + lead, self.sdfs[0].device), {"o": o, "d": d, "out": out, "tfd": tfd, "grids": grids,
+                                                                      "S": S, "A": A, "mode": mode}
 
-    def _ray_cast_per_configuration(self, o, d, lead, dtype, args, batch):
+    def _ray_cast_per_configuration(self, o, d, lead, dtype, args, batch, graph=None):
         """Compositions the kernel does not serve (other leaves, mixed modes, non-rigid transforms, other dtypes): the torch loop
-        around __call__ for each configuration's own composition -- not a hot path."""
+        around __call__ for each configuration's own composition -- not a hot path.  graph (_ray_graph): the rays get the
+        gradient of the hit distance, summed over the configurations by torch; transforms that require grad raise, since their
+        gradient would be dropped without a word."""
+        if graph is not None and self._tf_grad:
+            raise ValueError("ray_cast(differentiable=True): this composition is not served by the fused kernels (mixed or generic "
+                             "leaves, non-rigid transforms or another dtype), so its transforms get no gradient; detach them or "
+                             "use a fused composition")
         S, A = len(self.sdfs), math.prod(batch)
         stack = self._tf_matrix.detach().reshape(S, A, 4, 4)
         rows = []
         for a in range(A):
             one = ComposedSDF(self.sdfs, None)
             one.set_transforms(stack[:, a], known_rigid=self._rigid)
-            rows.append(one._ray_cast_generic(o, d, lead, dtype, args))
+            rows.append(one._ray_cast_generic(o, d, lead, dtype, args, graph))
         if not rows:
             dev = o.device if o.device.type != "cpu" else d.device
             return _ray_result(_ray_outputs(batch + lead, dtype, dev), batch + lead, dev)
