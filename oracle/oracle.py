@@ -323,11 +323,14 @@ class OracleJoint(ctypes.Structure):
 
 def chain_fk(joint_table, q, n_leaves):
     """joint_table: bytes of F pvamd_joint_t records (Chain.joint_table()); q: [A,M] float32.
-    Returns (world [F,A,3,4], link_world [S*A,4,4])."""
+    Returns (world [F,A,3,4], link_world [S*A,4,4], sin q, cos q).  A comes from q's leading dimensions, not from its size: a
+    robot of fixed joints only has M == 0 and still A configurations."""
     F = len(joint_table) // ctypes.sizeof(OracleJoint)
     joints = (OracleJoint * F).from_buffer_copy(joint_table)
-    q = _f32(q).reshape(-1, max(1, np.asarray(q).shape[-1]))
-    A, M = q.shape
+    q = np.atleast_2d(_f32(q))
+    M = q.shape[-1]
+    A = int(np.prod(q.shape[:-1]))
+    q = q.reshape(A, M)
     sq, cq = np.sin(q).astype(np.float32), np.cos(q).astype(np.float32)
     world = np.zeros((F, A, 12), np.float32)
     link_world = np.zeros((max(1, n_leaves) * A, 4, 4), np.float32)
