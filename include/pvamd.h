@@ -15,6 +15,9 @@
  *     synchronising; nothing is allocated or freed; no static mutable state (re-entrant).
  *   - 4x4 transforms are row-major, column-vector convention: x' = M[:3,:3] x + M[:3,3]
  *     (chamfer.py:14, tests/test_model_to_sdf.py:277-279).
+ *   - the Python binding is read from these declarations (pytorch_volumetric_amd/_header.py), and three parameter names carry
+ *     meaning there: `pvamd_grid_t* grid`, `pvamd_mesh_t* mesh` and `pvamd_mesh_plan_t* plan_out` are HOST structs; a pointer
+ *     under any other name (`grids`, `joints`, ...) is bound as a raw address.  One declaration per `;`, every parameter named.
  */
 #ifndef PVAMD_H
 #define PVAMD_H

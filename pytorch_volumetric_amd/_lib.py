@@ -9,32 +9,10 @@ import os
 
 import torch
 
+from pytorch_volumetric_amd import _header
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PVAMD_LIB") or os.path.join(_HERE, "csrc", "libpvamd.so")  # PVAMD_LIB: A/B builds (tools/)
-
-ABI_VERSION = 16
-OOB_LOOKUP_GT_SDF = 0
-OOB_BOUNDING_BOX = 1
-COMPOSED_INLINE_EXACT = 1
-COMPOSED_FORCE_PER_LANE = 2
-COMPOSED_FORCE_WAVE_TILE = 4
-COMPOSED_OUT_PACKED = 32
-COMPOSED_NO_GROUPING = 64
-COMPOSED_FORCE_FUSED = 128
-CO_KERNEL_PER_LANE, CO_KERNEL_WAVE_TILE, CO_KERNEL_FUSED = 0, 1, 2  # PVAMD_CO_KERNEL_* (include/pvamd.h)
-ORDER_KERNEL_SMALL, ORDER_KERNEL_COUNTING, ORDER_KERNEL_RADIX = 0, 1, 2  # PVAMD_ORDER_KERNEL_*
-MESH_PATH_NONE, MESH_PATH_LISTED, MESH_PATH_SCAN, MESH_PATH_SCAN_HEAVY = 0, 1, 2, 3  # PVAMD_MESH_PATH_*
-MESH_ORDER_GIVEN, MESH_ORDER_INSIDE, MESH_ORDER_SORT_CALL = 0, 1, 2  # PVAMD_MESH_ORDER_*
-RULE_VALID_ON_INDEX = 1
-RULE_ROUND_HALF_AWAY = 2
-RULE_ROUND_FLOOR_HALF = 4
-RULE_RES_F64 = 8
-LEAF_MODES = {"nearest": 0, "trilinear": 1}  # PVAMD_LEAF_NEAREST / PVAMD_LEAF_TRILINEAR
-MOP_CHUNK = 4096  # PVAMD_MOP_CHUNK
-REG_CHUNK = 2048  # PVAMD_REG_CHUNK
-REG_SUMS = 28     # PVAMD_REG_SUMS: the row length of pvamd_chamfer_normal_eq's out_sums
-RAY_MISS, RAY_HIT, RAY_MAX_STEPS, RAY_INVALID = 0, 1, 2, 3  # PVAMD_RAY_*: the status codes of the ray-cast entry points
-RAY_BACKWARD_CHUNK = 256  # PVAMD_RAY_BACKWARD_CHUNK
 
 
 # Buffer sizes: the library's exported size functions are the definition (include/pvamd.h) -- what they report is what the
@@ -203,187 +181,61 @@ class JointDesc(ctypes.Structure):
                 ("origin", ctypes.c_float * 12)]
 
 
-# name -> (restype, argtypes); the test-suite checks every one of these is exported by the .so and declared in
-# include/pvamd.h
-SIGNATURES = {
-    "pvamd_abi_version": (ctypes.c_int, []),
-    "pvamd_build_info": (ctypes.c_char_p, []),
-    "pvamd_device_count": (ctypes.c_int, []),
-    "pvamd_grid_finalize": (ctypes.c_int, [ctypes.POINTER(GridDesc)]),
-    "pvamd_pack_grid": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
-                                       ctypes.c_void_p]),
-    "pvamd_cached_query": (ctypes.c_int, [ctypes.POINTER(GridDesc), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
-                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_cached_outside": (ctypes.c_int, [ctypes.POINTER(GridDesc), ctypes.c_void_p, ctypes.c_int64,
-                                            ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_voxel_index": (ctypes.c_int, [ctypes.POINTER(GridDesc), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
-                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_cached_query_f64": (ctypes.c_int, [ctypes.POINTER(GridDesc), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
-                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_cached_outside_f64": (ctypes.c_int, [ctypes.POINTER(GridDesc), ctypes.c_void_p, ctypes.c_int64,
-                                                ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_voxel_index_f64": (ctypes.c_int, [ctypes.POINTER(GridDesc), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
-                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_composed_query": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
-                                            ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
-                                            ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]),
-    "pvamd_composed_query_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
-                                                ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
-                                                ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_composed_query_packed": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
-                                                   ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32,
-                                                   ctypes.c_void_p]),
-    "pvamd_unpack_records": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
-                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_composed_query_bucketed": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
-                                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
-                                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
-                                                     ctypes.c_void_p]),
-    "pvamd_cached_query_kernel": (ctypes.c_int, [ctypes.c_int64]),
-    "pvamd_composed_query_kernel": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int64, ctypes.c_int32]),
-    "pvamd_group_chunk_points": (ctypes.c_int64, []),
-    "pvamd_group_scratch_bytes": (ctypes.c_int64, [ctypes.c_int64]),
-    "pvamd_group_points": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_composed_query_grouped": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
-                                                    ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
-                                                    ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]),
-    "pvamd_transform_points": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64,
-                                              ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_compose_merge": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
-                                           ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                           ctypes.c_void_p]),
-    "pvamd_voxel_gather_f32": (ctypes.c_int, [ctypes.POINTER(GridDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                                              ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_voxel_gather_u8": (ctypes.c_int, [ctypes.POINTER(GridDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                                             ctypes.c_uint8, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_voxel_scatter_f32": (ctypes.c_int, [ctypes.POINTER(GridDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                               ctypes.c_float, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_voxel_scatter_u8": (ctypes.c_int, [ctypes.POINTER(GridDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                              ctypes.c_uint8, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_points_aabb": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_morton_keys": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
-                                         ctypes.c_void_p]),
-    "pvamd_morton_order": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
-                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_morton_order_scratch_bytes": (ctypes.c_int64, [ctypes.c_int64]),
-    "pvamd_morton_order_kernel": (ctypes.c_int, [ctypes.c_int64]),
-    "pvamd_morton_order_bits": (ctypes.c_int, [ctypes.c_int64]),
-    "pvamd_mesh_query_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(MeshPlan)]),
-    "pvamd_chamfer_mesh_plan": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(MeshPlan)]),
-    "pvamd_mesh_rec_floats": (ctypes.c_int64, [ctypes.c_int32]),
-    "pvamd_mesh_tiles_floats": (ctypes.c_int64, [ctypes.c_int32]),
-    "pvamd_mesh_small_points": (ctypes.c_int64, []),
-    "pvamd_mesh_scratch_bytes": (ctypes.c_int64, [ctypes.c_int64]),
-    "pvamd_mesh_prepare": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_float,
-                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_mesh_query": (ctypes.c_int, [ctypes.POINTER(MeshDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                                        ctypes.c_uint64,
-                                        ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_mesh_query_unordered": (ctypes.c_int, [ctypes.POINTER(MeshDesc), ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64,
-                                                  ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                  ctypes.c_void_p]),
-    "pvamd_cache_build": (ctypes.c_int, [ctypes.POINTER(MeshDesc), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
-                                         ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
-                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_sample_surface": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64,
-                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_chamfer_mesh": (ctypes.c_int, [ctypes.POINTER(MeshDesc), ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
-                                          ctypes.c_void_p, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
-                                          ctypes.c_void_p]),
-    "pvamd_chamfer_mesh_flat": (ctypes.c_int, [ctypes.POINTER(MeshDesc), ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
-                                               ctypes.c_int64, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_chamfer_grid": (ctypes.c_int, [ctypes.POINTER(GridDesc), ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
-                                          ctypes.c_int64, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_chain_fk": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                      ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_pairwise_min_reduce": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
-                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_configure_chain": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
-                                             ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                             ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_transform_stack": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
-                                             ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_cached_query_backward": (ctypes.c_int, [ctypes.POINTER(GridDesc), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
-                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_cached_query_backward_f64": (ctypes.c_int, [ctypes.POINTER(GridDesc), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
-                                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_composed_backward_scratch_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32]),
-    "pvamd_composed_query_backward": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
-                                                     ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
-                                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                     ctypes.c_void_p]),
-    "pvamd_composed_query_backward_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
-                                                         ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
-                                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                         ctypes.c_void_p]),
-    "pvamd_chamfer_grid_backward": (ctypes.c_int, [ctypes.POINTER(GridDesc), ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
-                                                   ctypes.c_int64, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p,
-                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    # interpolation="trilinear" (include/pvamd.h "Interpolated queries")
-    "pvamd_cached_query_interp": (ctypes.c_int, [ctypes.POINTER(GridDesc), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_cached_query_interp_f64": (ctypes.c_int, [ctypes.POINTER(GridDesc), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_composed_query_interp": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_composed_query_interp_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_cached_query_interp_backward": (ctypes.c_int, [ctypes.POINTER(GridDesc), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_cached_query_interp_backward_f64": (ctypes.c_int, [ctypes.POINTER(GridDesc), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_composed_query_interp_backward": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_composed_query_interp_backward_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    # ComposedSDF.min_over_points (include/pvamd.h "Minimum over points")
-    "pvamd_min_over_points_scratch_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32]),
-    "pvamd_min_over_points_backward_scratch_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
-    "pvamd_composed_min_over_points": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_composed_min_over_points_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_composed_min_over_points_backward": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_composed_min_over_points_backward_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    # ComposedSDF.leaf_pair_distance (include/pvamd.h "Leaf-pair distance")
-    "pvamd_leaf_pair_scratch_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]),
-    "pvamd_leaf_pair_transforms": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_leaf_pair_transforms_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_leaf_pair_distance": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_leaf_pair_distance_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_leaf_pair_distance_backward": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_leaf_pair_distance_backward_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    # ComposedSDF.leaf_pair_hinge (include/pvamd.h "Leaf-pair hinge")
-    "pvamd_leaf_pair_hinge_scratch_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]),
-    "pvamd_leaf_pair_hinge": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_leaf_pair_hinge_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_double, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_leaf_pair_hinge_backward": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_leaf_pair_hinge_backward_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_double, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    # ComposedSDF.hinge_over_points (include/pvamd.h "Hinge penalty over points")
-    "pvamd_hinge_over_points_scratch_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32]),
-    "pvamd_hinge_over_points_backward_scratch_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]),
-    "pvamd_composed_hinge_over_points": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_composed_hinge_over_points_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_composed_hinge_over_points_backward": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_composed_hinge_over_points_backward_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    # chamfer_normal_equations / refine_poses (include/pvamd.h "Chamfer normal equations")
-    "pvamd_chamfer_normal_eq_scratch_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int64]),
-    "pvamd_chamfer_normal_eq": (ctypes.c_int, [ctypes.POINTER(GridDesc), ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_pose_lm_step": (ctypes.c_int, [ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_void_p]),
-    # CachedSDF / ComposedSDF.ray_cast (include/pvamd.h "Ray casting")
-    "pvamd_cached_ray_cast": (ctypes.c_int, [ctypes.POINTER(GridDesc), ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_cached_ray_cast_f64": (ctypes.c_int, [ctypes.POINTER(GridDesc), ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_composed_ray_cast": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_composed_ray_cast_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    # ray_cast(..., differentiable=True) (include/pvamd.h "Ray casting: gradient of the hit distance")
-    "pvamd_ray_cast_backward_scratch_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32]),
-    "pvamd_cached_ray_cast_backward": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_cached_ray_cast_backward_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_composed_ray_cast_backward": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "pvamd_composed_ray_cast_backward_f64": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-}
-
-E_SHAPE = -2  # PVAMD_E_SHAPE (include/pvamd.h)
-_ERRORS = {-1: "a required pointer is NULL", -2: "a size/shape argument is out of range",
-           -3: "a pointer is misaligned", -4: "unknown enum value"}
-
-_lib = None
-
-
 class PvamdError(RuntimeError):
     pass
+
+
+# The binding is read from include/pvamd.h, the one definition of the C ABI (_header.py states the rules).  SIGNATURES: name ->
+# (restype, argtypes) of every declaration; scalars map to their ctypes scalar and pointers to c_void_p, except the host structs
+# passed with byref -- `pvamd_grid_t* grid`, `pvamd_mesh_t* mesh`, `pvamd_mesh_plan_t* plan_out` -- which map to POINTER of the
+# mirror above.  H: the header's integer #defines.  The test-suite checks that every entry is exported by the .so and that
+# the mirrors have the header's layout.
+try:
+    SIGNATURES, H = _header.read({"GridDesc": GridDesc, "MeshDesc": MeshDesc, "MeshPlan": MeshPlan})
+except OSError as e:
+    raise PvamdError(f"{_header.HEADER_PATH} cannot be read ({e}): the binding of libpvamd.so is read from the header that "
+                     f"the library was built from, and there is no second copy of it") from e
+
+ABI_VERSION = H["PVAMD_ABI_VERSION"]  # of the header in this tree: load() compares it with the .so's
+OOB_LOOKUP_GT_SDF = H["PVAMD_OOB_LOOKUP_GT_SDF"]
+OOB_BOUNDING_BOX = H["PVAMD_OOB_BOUNDING_BOX"]
+COMPOSED_INLINE_EXACT = H["PVAMD_COMPOSED_INLINE_EXACT"]
+COMPOSED_FORCE_PER_LANE = H["PVAMD_COMPOSED_FORCE_PER_LANE"]
+COMPOSED_FORCE_WAVE_TILE = H["PVAMD_COMPOSED_FORCE_WAVE_TILE"]
+COMPOSED_OUT_PACKED = H["PVAMD_COMPOSED_OUT_PACKED"]
+COMPOSED_NO_GROUPING = H["PVAMD_COMPOSED_NO_GROUPING"]
+COMPOSED_FORCE_FUSED = H["PVAMD_COMPOSED_FORCE_FUSED"]
+CO_KERNEL_PER_LANE = H["PVAMD_CO_KERNEL_PER_LANE"]
+CO_KERNEL_WAVE_TILE = H["PVAMD_CO_KERNEL_WAVE_TILE"]
+CO_KERNEL_FUSED = H["PVAMD_CO_KERNEL_FUSED"]
+ORDER_KERNEL_SMALL = H["PVAMD_ORDER_KERNEL_SMALL"]
+ORDER_KERNEL_COUNTING = H["PVAMD_ORDER_KERNEL_COUNTING"]
+ORDER_KERNEL_RADIX = H["PVAMD_ORDER_KERNEL_RADIX"]
+MESH_PATH_NONE = H["PVAMD_MESH_PATH_NONE"]
+MESH_PATH_LISTED = H["PVAMD_MESH_PATH_LISTED"]
+MESH_PATH_SCAN = H["PVAMD_MESH_PATH_SCAN"]
+MESH_PATH_SCAN_HEAVY = H["PVAMD_MESH_PATH_SCAN_HEAVY"]
+MESH_ORDER_GIVEN = H["PVAMD_MESH_ORDER_GIVEN"]
+MESH_ORDER_INSIDE = H["PVAMD_MESH_ORDER_INSIDE"]
+MESH_ORDER_SORT_CALL = H["PVAMD_MESH_ORDER_SORT_CALL"]
+RULE_VALID_ON_INDEX = H["PVAMD_RULE_VALID_ON_INDEX"]
+RULE_ROUND_HALF_AWAY = H["PVAMD_RULE_ROUND_HALF_AWAY"]
+RULE_ROUND_FLOOR_HALF = H["PVAMD_RULE_ROUND_FLOOR_HALF"]
+RULE_RES_F64 = H["PVAMD_RULE_RES_F64"]
+LEAF_MODES = {"nearest": H["PVAMD_LEAF_NEAREST"], "trilinear": H["PVAMD_LEAF_TRILINEAR"]}
+MOP_CHUNK = H["PVAMD_MOP_CHUNK"]
+REG_CHUNK = H["PVAMD_REG_CHUNK"]
+REG_SUMS = H["PVAMD_REG_SUMS"]  # the row length of pvamd_chamfer_normal_eq's out_sums
+RAY_MISS = H["PVAMD_RAY_MISS"]  # RAY_*: the status codes of the ray-cast entry points
+RAY_HIT = H["PVAMD_RAY_HIT"]
+RAY_MAX_STEPS = H["PVAMD_RAY_MAX_STEPS"]
+RAY_INVALID = H["PVAMD_RAY_INVALID"]
+RAY_BACKWARD_CHUNK = H["PVAMD_RAY_BACKWARD_CHUNK"]
+E_SHAPE = H["PVAMD_E_SHAPE"]
+_ERRORS = {H["PVAMD_E_NULL"]: "a required pointer is NULL", H["PVAMD_E_SHAPE"]: "a size/shape argument is out of range",
+           H["PVAMD_E_ALIGN"]: "a pointer is misaligned", H["PVAMD_E_MODE"]: "unknown enum value"}
+
+_lib = None
 
 
 def load():

@@ -7,10 +7,13 @@
 #include <c10/hip/HIPStream.h>
 #include <c10/hip/HIPFunctions.h>
 
+#include "pvamd.h"
+
 namespace {
 
-using cached_fn = int (*)(const void*, const float*, int64_t, float*, float*, uint8_t*, void*);
-using composed_fn = int (*)(const void*, int32_t, const float*, int32_t, const float*, int64_t, float*, float*, int32_t*, int32_t, void*);
+// the types of the two entry points, from their declarations: a call below that disagrees with the ABI does not compile
+using cached_fn = decltype(&pvamd_cached_query);
+using composed_fn = decltype(&pvamd_composed_query);
 
 inline bool takes(const at::Tensor& t, int64_t dev) {
     return t.scalar_type() == at::kFloat && t.is_cuda() && t.get_device() == dev && t.is_contiguous();
@@ -35,7 +38,7 @@ py::object cached_call(int64_t fn, int64_t desc, int64_t dev, const at::Tensor& 
         py::gil_scoped_release nogil;  // like the ctypes call this replaces: other host threads keep running during the launch
         val = at::empty(p.sizes().slice(0, p.dim() - 1), p.options());
         grad = at::empty_like(p);
-        rc = reinterpret_cast<cached_fn>(fn)(reinterpret_cast<const void*>(desc), p.data_ptr<float>(), val.numel(), val.data_ptr<float>(),
+        rc = reinterpret_cast<cached_fn>(fn)(reinterpret_cast<const pvamd_grid_t*>(desc), p.data_ptr<float>(), val.numel(), val.data_ptr<float>(),
                                              grad.data_ptr<float>(), nullptr, c10::hip::getCurrentHIPStream(dev).stream());
     }
     if (rc != 0) fail("pvamd_cached_query", rc);
@@ -50,7 +53,7 @@ bool cached_into(int64_t fn, int64_t desc, int64_t dev, const at::Tensor& p, con
     int rc;
     {
         py::gil_scoped_release nogil;
-        rc = reinterpret_cast<cached_fn>(fn)(reinterpret_cast<const void*>(desc), p.data_ptr<float>(), P, val.data_ptr<float>(),
+        rc = reinterpret_cast<cached_fn>(fn)(reinterpret_cast<const pvamd_grid_t*>(desc), p.data_ptr<float>(), P, val.data_ptr<float>(),
                                              grad.data_ptr<float>(), nullptr, c10::hip::getCurrentHIPStream(dev).stream());
     }
     if (rc != 0) fail("pvamd_cached_query", rc);
@@ -78,7 +81,7 @@ py::object composed_call(int64_t fn, int64_t grids, int64_t S, int64_t tf, int64
         py::gil_scoped_release nogil;
         val = at::empty(vs, p.options());
         grad = at::empty(gs, p.options());
-        rc = reinterpret_cast<composed_fn>(fn)(reinterpret_cast<const void*>(grids), (int32_t)S, reinterpret_cast<const float*>(tf), (int32_t)A,
+        rc = reinterpret_cast<composed_fn>(fn)(reinterpret_cast<const pvamd_grid_t*>(grids), (int32_t)S, reinterpret_cast<const float*>(tf), (int32_t)A,
                                                p.data_ptr<float>(), P, val.data_ptr<float>(), grad.data_ptr<float>(), nullptr, (int32_t)flags,
                                                c10::hip::getCurrentHIPStream(dev).stream());
     }

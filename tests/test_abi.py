@@ -7,7 +7,7 @@ import subprocess
 import pytest
 
 import pytorch_volumetric_amd as pv
-from pytorch_volumetric_amd import _lib
+from pytorch_volumetric_amd import _header, _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "pvamd.h")
@@ -45,37 +45,198 @@ def test_no_library_kernels_inside_the_shared_object():
     assert "#include <rocprim" not in src
 
 
+STRUCT_MIRRORS = {"pvamd_grid_t": _lib.GridDesc, "pvamd_mesh_t": _lib.MeshDesc, "pvamd_mesh_plan_t": _lib.MeshPlan,
+                  "pvamd_joint_t": _lib.JointDesc}
+
+
 def test_struct_layouts_match_the_header(tmp_path):
-    """Compile a tiny C program against the header and compare sizeof/offsetof with the ctypes mirrors."""
+    """Compile a tiny C program against the header and compare sizeof, and offsetof and size of every field, with the four
+    ctypes mirrors.  The program is generated from the mirrors' _fields_: a field the header does not have fails to compile, one
+    the mirror lacks moves a later offset or the size."""
+    prints = []
+    for ctype, mirror in STRUCT_MIRRORS.items():
+        prints.append(f'printf("%zu", sizeof({ctype}));')
+        prints += [f'printf(" %zu %zu", offsetof({ctype}, {name}), sizeof((({ctype}*)0)->{name}));' for name, _ in mirror._fields_]
+        prints.append(r'printf("\n");')
     src = r'''
     #include <stdio.h>
     #include <stddef.h>
     #include "pvamd.h"
     int main(void) {
-      printf("%zu %zu %zu %zu %zu %zu %zu\n", sizeof(pvamd_grid_t), offsetof(pvamd_grid_t, dres), offsetof(pvamd_grid_t, fmin),
-             offsetof(pvamd_grid_t, bb_min), offsetof(pvamd_grid_t, shape), offsetof(pvamd_grid_t, index_f64),
-             offsetof(pvamd_grid_t, oob_mode));
-      printf("%zu %zu %zu\n", sizeof(pvamd_mesh_t), offsetof(pvamd_mesh_t, F), offsetof(pvamd_mesh_t, ray_dir));
-      printf("%zu %zu %zu %zu %zu %zu %zu %zu\n", sizeof(pvamd_mesh_plan_t), offsetof(pvamd_mesh_plan_t, path),
-             offsetof(pvamd_mesh_plan_t, order), offsetof(pvamd_mesh_plan_t, groups), offsetof(pvamd_mesh_plan_t, slots),
-             offsetof(pvamd_mesh_plan_t, scan_waves), offsetof(pvamd_mesh_plan_t, parts), offsetof(pvamd_mesh_plan_t, part_waves));
+      STRUCTS
       printf("%d %d %d %d  %d %d %d  %d %d %d\n", PVAMD_MESH_PATH_NONE, PVAMD_MESH_PATH_LISTED, PVAMD_MESH_PATH_SCAN,
              PVAMD_MESH_PATH_SCAN_HEAVY, PVAMD_MESH_ORDER_GIVEN, PVAMD_MESH_ORDER_INSIDE, PVAMD_MESH_ORDER_SORT_CALL,
              PVAMD_ORDER_KERNEL_SMALL, PVAMD_ORDER_KERNEL_COUNTING, PVAMD_ORDER_KERNEL_RADIX);
-      return 0; }'''
+      return 0; }'''.replace("STRUCTS", "\n      ".join(prints))
     exe = str(tmp_path / "pvamd_layout")
     subprocess.run(["gcc", "-x", "c", "-", "-I", os.path.join(ROOT, "include"), "-o", exe], input=src.encode(), check=True)
-    out = subprocess.run([exe], capture_output=True, check=True).stdout.decode().split()
-    G, M = _lib.GridDesc, _lib.MeshDesc
-    assert [int(x) for x in out[:7]] == [ctypes.sizeof(G), G.dres.offset, G.fmin.offset, G.bb_min.offset, G.shape.offset,
-                                         G.index_f64.offset, G.oob_mode.offset]
-    assert [int(x) for x in out[7:10]] == [ctypes.sizeof(M), M.F.offset, M.ray_dir.offset]
+    out = [[int(x) for x in line.split()] for line in subprocess.run([exe], capture_output=True, check=True).stdout.decode().splitlines()]
+    assert len(out) == len(STRUCT_MIRRORS) + 1
+    for (ctype, mirror), row in zip(STRUCT_MIRRORS.items(), out):
+        want = [ctypes.sizeof(mirror)]
+        for name, _ in mirror._fields_:
+            want += [getattr(mirror, name).offset, getattr(mirror, name).size]
+        assert row == want, ctype
+    assert [len(mirror._fields_) for mirror in STRUCT_MIRRORS.values()] == [22, 8, 7, 7]
     Pl = _lib.MeshPlan
-    assert [int(x) for x in out[10:18]] == [ctypes.sizeof(Pl)] + [getattr(Pl, name).offset for name, _ in Pl._fields_]
     assert [name for name, _ in Pl._fields_] == ["path", "order", "groups", "slots", "scan_waves", "parts", "part_waves"]
-    assert [int(x) for x in out[18:]] == [_lib.MESH_PATH_NONE, _lib.MESH_PATH_LISTED, _lib.MESH_PATH_SCAN, _lib.MESH_PATH_SCAN_HEAVY,
-                                          _lib.MESH_ORDER_GIVEN, _lib.MESH_ORDER_INSIDE, _lib.MESH_ORDER_SORT_CALL,
-                                          _lib.ORDER_KERNEL_SMALL, _lib.ORDER_KERNEL_COUNTING, _lib.ORDER_KERNEL_RADIX]
+    assert out[-1] == [_lib.MESH_PATH_NONE, _lib.MESH_PATH_LISTED, _lib.MESH_PATH_SCAN, _lib.MESH_PATH_SCAN_HEAVY,
+                       _lib.MESH_ORDER_GIVEN, _lib.MESH_ORDER_INSIDE, _lib.MESH_ORDER_SORT_CALL,
+                       _lib.ORDER_KERNEL_SMALL, _lib.ORDER_KERNEL_COUNTING, _lib.ORDER_KERNEL_RADIX]
+
+
+HOST_MIRRORS = {"GridDesc": _lib.GridDesc, "MeshDesc": _lib.MeshDesc, "MeshPlan": _lib.MeshPlan}
+SYNTHETIC_HEADER = r"""
+/* a comment that mentions pvamd_not_declared( and
+ * #define PVAMD_IN_COMMENT 5 */
+#ifndef SYNTHETIC_H
+#define SYNTHETIC_H
+#include <stdint.h>
+#ifdef __cplusplus
+extern "C" {
+#endif
+#define PVAMD_PLAIN 16
+#define PVAMD_ZERO 0   /* a trailing comment */
+#define PVAMD_PAREN (7)
+#define PVAMD_NEG_PAREN (-3)  /* a comment that
+                                 runs over two lines */
+#define PVAMD_NEG_BARE -4
+  #  define PVAMD_INDENTED 9
+#define PVAMD_FUNCTION_LIKE(F) ((F) + 1)
+#define PVAMD_EXPRESSION (3 << 18)
+#define PVAMD_REAL 1.5
+#define PVAMD_HEX 0x10
+#define PVAMD_TEXT "16"
+#define PVAMD_HALF_OPEN (8
+#define PVAMD_EMPTY
+#define PVAMD_CONTINUED(a, b) \
+    ((a) + \
+     pvamd_in_a_macro(b))
+typedef struct pvamd_grid { const float* vox; int32_t shape[3]; } pvamd_grid_t;
+int pvamd_no_arguments(void);
+const char* pvamd_text(void);
+int64_t pvamd_scalars(int a, int32_t b, int64_t c, uint64_t d, uint8_t e, float f, double g);
+int pvamd_over_lines(const float* points, void *stream,
+                     int64_t * out_index,   /* a comment between parameters */
+                     uint8_t*out_flags);
+int pvamd_host_structs(const pvamd_grid_t* grid, pvamd_mesh_t* mesh, pvamd_mesh_plan_t* plan_out);
+int pvamd_device_arrays(const pvamd_grid_t* grids, const pvamd_mesh_t* meshes, pvamd_mesh_plan_t* plan, const pvamd_joint_t* joints,
+                        const float* grid);
+#ifdef __cplusplus
+}
+#endif
+#endif
+"""
+
+
+def test_header_reader_maps_each_rule_on_a_synthetic_header():
+    """_header.parse on a header written for it: one declaration per rule, and the #defines it keeps and ignores."""
+    c = ctypes
+    declarations, defines = _header.parse(SYNTHETIC_HEADER, HOST_MIRRORS)
+    assert list(declarations.items()) == [
+        ("pvamd_no_arguments", (c.c_int, [])),
+        ("pvamd_text", (c.c_char_p, [])),
+        ("pvamd_scalars", (c.c_int64, [c.c_int, c.c_int32, c.c_int64, c.c_uint64, c.c_uint8, c.c_float, c.c_double])),
+        ("pvamd_over_lines", (c.c_int, [c.c_void_p] * 4)),
+        ("pvamd_host_structs", (c.c_int, [c.POINTER(_lib.GridDesc), c.POINTER(_lib.MeshDesc), c.POINTER(_lib.MeshPlan)])),
+        # the same types under other names, and another type under a host struct's name: raw addresses
+        ("pvamd_device_arrays", (c.c_int, [c.c_void_p] * 5)),
+    ]
+    assert defines == {"PVAMD_PLAIN": 16, "PVAMD_ZERO": 0, "PVAMD_PAREN": 7, "PVAMD_NEG_PAREN": -3, "PVAMD_NEG_BARE": -4,
+                       "PVAMD_INDENTED": 9}
+    assert sorted(_header.HOST_STRUCTS) == [("pvamd_grid_t", "grid"), ("pvamd_mesh_plan_t", "plan_out"), ("pvamd_mesh_t", "mesh")]
+
+
+@pytest.mark.parametrize("line", [
+    "int pvamd_refused(foo_t a);",                          # an unknown scalar type
+    "int pvamd_refused(unsigned int a);",
+    "void pvamd_refused(int a);",                           # an unknown return type
+    "const float* pvamd_refused(int a);",
+    "int pvamd_refused(const float*, int64_t P);",          # a parameter without a name
+    "int pvamd_refused(const float* points, int64_t);",
+    "int pvamd_refused();",
+    "int pvamd_refused(float** rows);",
+    "int pvamd_refused(float rows[3]);",
+    "int pvamd_refused(int (*callback)(int), void* stream);",  # a function-pointer parameter
+    "int pvamd_refused(int a)",                             # no semicolon: runs into the next declaration
+    "static inline int pvamd_refused(int a) { return a; }",
+    "int (*pvamd_refused)(int a);",
+    "typedef int pvamd_refused(int a);",
+    "int pvamd_no_arguments(int a);",                       # a second declaration of a name
+    "typedef struct { int (*member)(int); int pvamd_refused(int); } odd_t;",
+])
+def test_header_reader_refuses_what_it_cannot_map(line):
+    """No declaration is ever skipped: whatever is not `type pvamd_name(parameters);` under the rules raises, naming it."""
+    name = "pvamd_no_arguments" if "pvamd_no_arguments" in line else "pvamd_refused"
+    text = SYNTHETIC_HEADER.replace("int pvamd_no_arguments(void);", line + "\nint pvamd_no_arguments(void);")
+    assert text != SYNTHETIC_HEADER
+    with pytest.raises(ValueError, match=name):
+        _header.parse(text, HOST_MIRRORS)
+
+
+def test_missing_header_is_a_loud_error_without_a_fallback_table(tmp_path, monkeypatch):
+    """The binding executed with no header to read raises PvamdError naming the path it expected."""
+    import importlib.util
+    assert os.path.samefile(_header.HEADER_PATH, HEADER)
+    missing = str(tmp_path / "include" / "pvamd.h")
+    monkeypatch.setattr(_header, "HEADER_PATH", missing)
+    with pytest.raises(OSError):
+        _header.read(HOST_MIRRORS)
+    spec = importlib.util.spec_from_file_location("pvamd_lib_without_header", _lib.__file__)  # a second copy: _lib itself stays
+    with pytest.raises(RuntimeError, match=re.escape(missing)) as e:
+        spec.loader.exec_module(importlib.util.module_from_spec(spec))
+    assert type(e.value).__name__ == "PvamdError"
+
+
+def test_binding_is_the_header_read_with_pins_on_what_must_not_move():
+    """_lib.SIGNATURES is what the reader makes of include/pvamd.h; the entries whose types a caller's arguments depend on are
+    pinned literally, so that a change of the rules cannot move them unnoticed."""
+    c = ctypes
+    declarations, defines = _header.read(HOST_MIRRORS)
+    assert _lib.SIGNATURES == declarations and _lib.H == defines and len(declarations) >= 102
+    S = _lib.SIGNATURES
+    assert S["pvamd_cached_query"] == (c.c_int, [c.POINTER(_lib.GridDesc), c.c_void_p, c.c_int64, c.c_void_p, c.c_void_p, c.c_void_p,
+                                                 c.c_void_p])
+    assert S["pvamd_composed_query"][1][0] is c.c_void_p and len(S["pvamd_composed_query"][1]) == 11
+    assert S["pvamd_grid_finalize"] == (c.c_int, [c.POINTER(_lib.GridDesc)])
+    assert S["pvamd_mesh_query"][1][0] == c.POINTER(_lib.MeshDesc)
+    assert S["pvamd_mesh_query_plan"][1] == [c.c_int64, c.c_int32, c.c_int32, c.c_int32, c.POINTER(_lib.MeshPlan)]
+    assert S["pvamd_chamfer_mesh_plan"][1][-1] == c.POINTER(_lib.MeshPlan)
+    assert S["pvamd_chain_fk"][1][0] is c.c_void_p and S["pvamd_configure_chain"][1][0] is c.c_void_p  # joints: a device array
+    at = S["pvamd_leaf_pair_hinge"][1].index(c.c_float)
+    assert at == 10 and S["pvamd_leaf_pair_hinge_f64"][1][at] is c.c_double
+    assert c.c_double not in S["pvamd_leaf_pair_hinge"][1] and c.c_float not in S["pvamd_leaf_pair_hinge_f64"][1]
+    for name in ("pvamd_leaf_pair_hinge_backward", "pvamd_composed_hinge_over_points", "pvamd_composed_hinge_over_points_backward"):
+        margin = [i for i, t in enumerate(S[name][1]) if t is c.c_float]
+        assert len(margin) == 1 and [i for i, t in enumerate(S[name + "_f64"][1]) if t is c.c_double] == margin, name
+    assert S["pvamd_build_info"] == (c.c_char_p, [])
+    sizes = [name for name in S if name.endswith("_scratch_bytes")]
+    assert len(sizes) >= 12 and all(S[name][0] is c.c_int64 for name in sizes), sizes
+    assert all(restype in (c.c_int, c.c_int64, c.c_char_p) for restype, _ in S.values())
+
+
+def test_binding_copies_no_value_the_header_defines():
+    """The source of _lib.py assigns no integer literal to a name the header defines as PVAMD_<name> (nor inside LEAF_MODES and
+    the keys of _ERRORS): each is looked up in the header that was read, so the value cannot drift from it."""
+    import ast
+    import inspect
+    mirrored = {}
+    for node in ast.parse(inspect.getsource(_lib)).body:
+        if not isinstance(node, ast.Assign):
+            continue
+        names = [n.id for target in node.targets for n in ast.walk(target) if isinstance(n, ast.Name)]
+        literals = [k.value for k in ast.walk(node.value) if isinstance(k, ast.Constant) and type(k.value) is int]
+        for name in names:
+            if "PVAMD_" + name in _lib.H or name in ("LEAF_MODES", "_ERRORS"):
+                assert not literals, (name, literals)
+                mirrored[name] = getattr(_lib, name)
+    assert len(mirrored) >= 37, sorted(mirrored)
+    for name, value in mirrored.items():
+        if name not in ("LEAF_MODES", "_ERRORS"):
+            assert value == _lib.H["PVAMD_" + name], name
+    assert mirrored["LEAF_MODES"] == {"nearest": _lib.H["PVAMD_LEAF_NEAREST"], "trilinear": _lib.H["PVAMD_LEAF_TRILINEAR"]}
+    assert sorted(mirrored["_ERRORS"]) == sorted(v for k, v in _lib.H.items() if k.startswith("PVAMD_E_"))
+    assert _lib.ABI_VERSION == _lib.H["PVAMD_ABI_VERSION"] == 16 and _lib.E_SHAPE == -2 and _lib.RAY_HIT == 1
 
 
 def test_oracle_grid_layout_is_one_definition(tmp_path):
