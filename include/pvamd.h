@@ -917,6 +917,40 @@ int pvamd_composed_ray_cast_backward_f64(const pvamd_grid_t* grids, int32_t S, c
                                          const double* directions, int64_t R, int32_t mode, const double* t, const uint8_t* status,
                                          const double* up, double* dorigins, double* ddirections, double* dtf, void* scratch,
                                          void* stream);
+
+/* ---- Distance transform (SDF from voxel occupancy) ----
+ * The exact Euclidean distance transform of an occupancy grid, fused with the statements that turn it into the packed (val, gx,
+ * gy, gz) records of a cached voxel grid (pvamd_grid_t.vox): the producer for scenes that are observed as voxels, not given as
+ * a mesh.  Replaces nothing in the reference: its VoxelGrid (voxel.py:42-103) holds the occupancy and nothing there turns it
+ * into a distance field.
+ *  1. occupied: device uint8 [nx][ny][nz] in C order (x slowest, z fastest, the layout of the records), non-zero = occupied.
+ *     For voxel i = (x, y, z) the site class Q is: the occupied voxels when i is free; the free voxels when i is occupied and
+ *     is_signed = 1; {i} itself when i is occupied and is_signed = 0.
+ *  2. squared(i) = min over j in Q of |i - j|^2 in voxel units, exact in int32 (at most 3 * 2047^2 < 2^24).  site(i) = the
+ *     SMALLEST flat C-order index j = (jx * ny + jy) * nz + jz that attains it: the gradient depends on this tie rule.
+ *  3. With r = resolution and s = sqrtf((float)squared), each operation rounded on its own (correctly rounded sqrt and divide,
+ *     no contraction), j = site(i):
+ *       is_signed = 1, i free:      val = r * (s - 0.5f)         the surface lies on the voxel faces between the two classes,
+ *       is_signed = 1, i occupied:  val = -(r * (s - 0.5f))      half a voxel from either centre
+ *       is_signed = 0:              val = r * s                  an occupied voxel: +0.0, gradient zeros, site i
+ *       gradient component k:       (float)(i_k - j_k) / s for a free voxel, (float)(j_k - i_k) / s for an occupied one
+ *                                   (toward increasing val)
+ *  4. Empty Q (no occupied voxel; is_signed = 1 and no free voxel): squared = PVAMD_EDT_NO_SITE, site = -1, val = +INFINITY for a
+ *     free voxel and -INFINITY for an occupied one, gradient zeros.  These are ordinary results, reported without a
+ *     synchronisation.
+ *  5. Three line passes (z, y, x; the last fused with 3.) that keep one int32 per voxel and class in scratch; no sum ever
+ *     includes the no-site sentinel.  The line minima are found by an outward scan that stops once the offset alone exceeds the
+ *     best cost: the time grows with the distances in the grid, up to the line length per voxel and pass in empty space.
+ * Each axis in [1, 2048] and nx * ny * nz <= 2^31 - 1, else PVAMD_E_SHAPE; is_signed other than 0 / 1: PVAMD_E_MODE.
+ * records: device [n][4] float32, 16-byte aligned (n = nx * ny * nz).  sites, squared: device [n] int32, or NULL (not wanted).
+ * scratch: device, pvamd_distance_transform_scratch_bytes(nx, ny, nz, is_signed) bytes, 4-byte aligned; that function is the
+ * definition (0 for arguments the entry point refuses) and there is no macro.  Contents on return are unspecified.
+ * Stream-ordered, no allocation, no device -> host synchronisation, no atomics: capturable in a graph, and two calls give the
+ * same bits.                                                                                                                    */
+#define PVAMD_EDT_NO_SITE 2147483647  /* INT32_MAX: squared(i) when Q is empty */
+int64_t pvamd_distance_transform_scratch_bytes(int32_t nx, int32_t ny, int32_t nz, int32_t is_signed);
+int pvamd_distance_transform(const uint8_t* occupied, int32_t nx, int32_t ny, int32_t nz, float resolution, int32_t is_signed,
+                             float* records, int32_t* sites, int32_t* squared, void* scratch, void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -99,6 +99,12 @@ def chamfer_normal_eq_scratch_bytes(B, N):
 
 
 @_remembered
+def distance_transform_scratch_bytes(nx, ny, nz, signed):
+    """pvamd_distance_transform_scratch_bytes: one int32 per voxel, site class and line pass that hands on a state."""
+    return load().pvamd_distance_transform_scratch_bytes(nx, ny, nz, int(signed))
+
+
+@_remembered
 def composed_query_kernel(A, P, flags):
     """pvamd_composed_query_kernel: the kernel (CO_KERNEL_*) pvamd_composed_query launches for A configurations of P points."""
     return load().pvamd_composed_query_kernel(A, P, flags)
@@ -231,6 +237,7 @@ RAY_HIT = H["PVAMD_RAY_HIT"]
 RAY_MAX_STEPS = H["PVAMD_RAY_MAX_STEPS"]
 RAY_INVALID = H["PVAMD_RAY_INVALID"]
 RAY_BACKWARD_CHUNK = H["PVAMD_RAY_BACKWARD_CHUNK"]
+EDT_NO_SITE = H["PVAMD_EDT_NO_SITE"]  # DistanceTransform.squared where the site class is empty
 E_SHAPE = H["PVAMD_E_SHAPE"]
 _ERRORS = {H["PVAMD_E_NULL"]: "a required pointer is NULL", H["PVAMD_E_SHAPE"]: "a size/shape argument is out of range",
            H["PVAMD_E_ALIGN"]: "a pointer is misaligned", H["PVAMD_E_MODE"]: "unknown enum value"}

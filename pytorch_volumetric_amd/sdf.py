@@ -693,8 +693,11 @@ class CachedSDF(ObjectFrameSDF):
             coords, _ = get_coordinates_and_points_in_grid(self.resolution, self.ranges, get_points=False)
             dev_q = _lib.require_gpu()
             built = self._build_from_mesh(gt_sdf, coords, dev_q)
+            if built is None:
+                built = self._copy_from_occupancy(gt_sdf, self.resolution, self.ranges, coords, dev_q)
             if built is not None:
-                # a plain MeshSDF: centres, processing order, mesh kernel and packing in <= 3 launches (pvamd_cache_build);
+                # a plain MeshSDF: centres, processing order, mesh kernel and packing in <= 3 launches (pvamd_cache_build); an
+                # OccupancySDF over this very lattice: its records;
                 # `val` / `grad` are views of the packed records -- what the reference stores and pickles
                 val, grad = built[:, 0].reshape([len(coord) for coord in coords]), built[:, 1:4]
             else:
@@ -774,6 +777,15 @@ class CachedSDF(ObjectFrameSDF):
                                              ctypes.c_uint64(obj.jitter_seed), _lib.ptr(packed), _lib.ptr(pts), _lib.ptr(order),
                                              _lib.ptr(scratch), _lib.stream_ptr()), "pvamd_cache_build")
         return packed
+
+    @staticmethod
+    def _copy_from_occupancy(gt_sdf, resolution, ranges, coords, dev):
+        """The cache of an OccupancySDF whose lattice is the cache's own: a copy of the field's packed (n, 4) records as they are,
+        on `dev`.  None for any other ground truth or lattice (the field is then asked at every voxel centre)."""
+        from pytorch_volumetric_amd.occupancy import OccupancySDF
+        if not isinstance(gt_sdf, OccupancySDF) or not gt_sdf.same_lattice(resolution, ranges, [len(c) for c in coords]):
+            return None
+        return gt_sdf._records.to(device=dev, copy=True)
 
     _PLAN_ATTRS = frozenset(("device", "out_of_bounds_strategy", "debug_check_sdf", "_packed", "bb", "interpolation"))
 
