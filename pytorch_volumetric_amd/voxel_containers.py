@@ -132,11 +132,22 @@ class ValueRangeView:
         return out
 
     def __setitem__(self, pts, value):
+        per_point = _check_per_point(pts, value)
         if self._device_path(pts):
             return self._device_set(pts, value)
         ok = self.get_valid_values(pts)
-        per_point = torch.is_tensor(value) and value.dim() > 0
-        self.raw_data[self._flat(pts[ok])] = value[ok] if per_point else value
+        self.raw_data[self._flat(pts[ok])] = value.reshape(ok.shape)[ok] if per_point else value
+
+
+def _check_per_point(pts, value):
+    """Whether `value` holds one value per point (a tensor with dim() > 0): then the counts must agree, in any shape -- the
+    device kernel reads values[i] for every point i, the generic path indexes the values like the points' batch dimensions."""
+    if not (torch.is_tensor(value) and value.dim() > 0):
+        return False
+    npts = pts.numel() // pts.shape[-1] if pts.shape[-1] else 0
+    if value.numel() != npts:
+        raise ValueError(f"per-point values: {value.numel()} values for {npts} points")
+    return True
 
 
 class Voxels(abc.ABC):
@@ -212,6 +223,7 @@ class ExpandingVoxelGrid(VoxelGrid):
     """VoxelGrid whose range grows, in whole cells, to contain whatever is written to it."""
 
     def __setitem__(self, pts, value):
+        _check_per_point(pts, value)  # before the range grows: a refused write leaves the container as it was
         if pts.numel():
             lo, hi = _point_bounds(pts.reshape(-1, pts.shape[-1]))
             cells_below = np.ceil(np.maximum(self.range_per_dim[:, 0] - lo, 0) / self.resolution)

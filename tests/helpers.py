@@ -16,6 +16,13 @@ DRILL_BB = np.array([[-0.067981, 0.095006], [-0.041332, 0.081863], [-0.003716, 0
 
 mesh_path = workloads.mesh_path
 
+# The two launch bounds the kernels split their work at (tests/test_launch_bounds.py checks them against csrc/common.h and
+# lists the test that crosses each): stream_grid() caps a streaming grid at kNumCU * kMaxBlocksPerCU blocks of 256 lanes, so
+# a lane takes a second item only above STREAM_GRID_ITEMS items; gridDim.y holds at most GRID_Y_MAX configurations.
+STREAM_GRID_ITEMS = 256 * 8 * 256
+GRID_Y_MAX = 65535
+PAST_CAP = STREAM_GRID_ITEMS + 4099  # items: the first 4099 lanes of a capped streaming grid take a second one
+
 
 class AnalyticEllipsoidSDF:
     """A cheap closed-form stand-in for a mesh SDF: a sphere SDF in a stretched space (not a true distance, but

@@ -80,6 +80,70 @@ def test_chamfer_against_cached_sdf_matches_oracle():
         pv.batch_chamfer_dist(W, pts)
 
 
+PAST_CAP = H.PAST_CAP
+GRID_CHAMFER_CASES = [(H.GRID_Y_MAX + 2, 37),   # the host loop over slabs of 65535 transforms takes a second turn (of two rows)
+                      (1, PAST_CAP),            # more points than the capped grid has lanes
+                      (3, 200_000)]             # the cap is split over the transforms: 683 blocks per row
+
+
+@pytest.mark.parametrize("f64_range", [False, True], ids=["float32-range", "float64-range"])
+@pytest.mark.parametrize("B,N", GRID_CHAMFER_CASES)
+def test_chamfer_grid_past_the_slab_and_the_streaming_cap(B, N, f64_range):
+    """pvamd_chamfer_grid against the oracle's sequential sums.  Every term is the oracle's float32 number widened; a sum of N
+    non-negative float64 terms taken in another order differs by at most N x 2^-52 relative (the bound of
+    test_every_plan_of_the_mesh_chamfer_matches_the_oracle)."""
+    import ctypes
+    assert B > H.GRID_Y_MAX or (N + 255) // 256 > (H.STREAM_GRID_ITEMS // 256 + B - 1) // B
+    cached = pv.CachedSDF("ellipsoid", 0.01, H.padded_range(H.DRILL_BB, 0.05, as_numpy=f64_range), H.drill_like_gt(), device="cuda",
+                          cache_path=None)
+    assert cached._view.index_f64 == f64_range
+    lo, hi = H.DRILL_BB[:, 0] - 0.1, H.DRILL_BB[:, 1] + 0.1  # in range and out of it
+    pts = H.uniform_points(N, lo, hi, seed=N % 1000)
+    W = H.random_rigid(B, seed=B % 1000, trans=0.03)
+    sums = torch.full((B,), -7.0, dtype=torch.float64, device="cuda")  # the entry point zeroes its output itself
+    _lib.check(_lib.load().pvamd_chamfer_grid(ctypes.byref(cached._grid_desc()), _lib.ptr(W.cuda().contiguous()), B,
+                                              _lib.ptr(pts.cuda().contiguous()), N, 1000.0, _lib.ptr(sums), _lib.stream_ptr()),
+               "pvamd_chamfer_grid")
+    want = oracle.chamfer_grid(H.oracle_grid_from_cached(cached), W.numpy(), pts.numpy(), scale=1000.0)
+    got = sums.cpu().numpy()
+    assert (want > 0).all() and len(np.unique(want)) == B
+    assert np.allclose(got, want, rtol=N * 2.0 ** -52, atol=0), np.abs(got / want - 1).max()
+    for b in sorted({0, 1, B - 1} | ({H.GRID_Y_MAX - 1, H.GRID_Y_MAX, H.GRID_Y_MAX + 1} if B > H.GRID_Y_MAX else set())):
+        if b < B:
+            assert abs(got[b] / want[b] - 1) <= N * 2.0 ** -52, b
+    # and through the caller
+    if B <= 3:
+        err = pv.batch_chamfer_dist(W, pts, obj_sdf=cached)
+        assert np.allclose(err.double().cpu().numpy(), want / N, rtol=1e-6)
+
+
+@pytest.mark.parametrize("has_scratch", [False, True], ids=["no-scratch", "scratch"])
+def test_chamfer_mesh_takes_more_transforms_than_one_grid_dimension_holds(has_scratch):
+    """pvamd_chamfer_mesh walks its transforms in slabs of 65535 grid rows: two more than that, cycling through four poses, so the
+    oracle's four sums are the reference of every row (the construction and the bound of
+    test_every_plan_of_the_mesh_chamfer_matches_the_oracle)."""
+    import ctypes
+    lib = _lib.load()
+    rows, N = H.GRID_Y_MAX + 2, 37
+    obj = pv.MeshObjectFactory(H.mesh_path("box_template.obj"), scale=0.03)
+    poses = H.random_rigid(4, seed=3, trans=0.004)
+    pts = H.uniform_points(N, [-0.05] * 3, [0.05] * 3, seed=4)
+    ref = oracle.chamfer_mesh(H.oracle_mesh_from_factory(obj), poses.numpy(), pts.numpy(), scale=1000.0)
+    assert (ref > 0).all() and len(np.unique(ref)) == 4
+    dev = pts.cuda().contiguous()
+    desc = obj._mesh_desc()
+    W = poses.repeat((rows + 3) // 4, 1, 1)[:rows].cuda().contiguous()
+    scratch = _lib.scratch_buffer(_lib.mesh_scratch_bytes(N), dev.device) if has_scratch else None
+    sums = torch.full((rows,), -7.0, dtype=torch.float64, device="cuda")  # the entry point zeroes its output itself
+    _lib.check(lib.pvamd_chamfer_mesh(ctypes.byref(desc), _lib.ptr(W), rows, _lib.ptr(dev), None, N, 1000.0, _lib.ptr(sums),
+                                      _lib.ptr(scratch), _lib.stream_ptr()), "pvamd_chamfer_mesh")
+    got = sums.cpu().numpy()
+    want = np.tile(ref, (rows + 3) // 4)[:rows]
+    assert np.allclose(got, want, rtol=N * 2.0 ** -52, atol=0), int((~np.isclose(got, want, rtol=N * 2.0 ** -52, atol=0)).sum())
+    for b in (0, 1, H.GRID_Y_MAX - 1, H.GRID_Y_MAX, H.GRID_Y_MAX + 1):
+        assert abs(got[b] / want[b] - 1) <= N * 2.0 ** -52, b
+
+
 @pytest.mark.parametrize("mesh", ["probe.obj", "offset_wrench_nogrip.obj"])
 def test_plausible_diversity_properties(mesh):
     """tests/test_chamfer.py:85-130 of the reference, headless."""

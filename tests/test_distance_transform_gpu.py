@@ -77,6 +77,55 @@ def test_bit_for_bit_against_the_restatement(name, signed):
         assert (sites[plane] == np.ravel_multi_index((2, 3, 3), occ.shape)).all()  # the smaller flat index of the two
 
 
+# Past both launch caps (tests/test_launch_bounds.py): the y and x passes give a lane a second voxel above H.STREAM_GRID_ITEMS
+# voxels, and the z pass gives a wave a second line -- reusing its LDS bit set -- above H.STREAM_GRID_ITEMS / 64 lines.  The
+# restatement is O(voxels x sites), so these grids are nearly empty or nearly full: (name, shape, fraction, seed, signed).
+LARGE_GRIDS = [
+    ("100x100x70@0.1-signed", (100, 100, 70), 0.001, 51, True),    # 10,000 lines of two bit-set words with a 6-bit tail
+    ("100x100x70@0.1-unsigned", (100, 100, 70), 0.001, 51, False),
+    ("100x100x70@99.9-signed", (100, 100, 70), 0.999, 52, True),
+    ("128x128x36@0.1-signed", (128, 128, 36), 0.001, 53, True),    # 16,384 lines: every wave takes exactly two
+]
+
+
+@pytest.mark.parametrize("name,shape,fraction,seed,signed", LARGE_GRIDS, ids=[g[0] for g in LARGE_GRIDS])
+def test_bit_for_bit_past_the_launch_caps(name, shape, fraction, seed, signed):
+    lines = shape[0] * shape[1]
+    assert lines > H.STREAM_GRID_ITEMS // 64, "the z pass must take a second line per wave"
+    if shape[2] == 70:
+        assert lines * shape[2] > H.STREAM_GRID_ITEMS, "the y and x passes must take a second voxel per lane"
+    else:
+        assert lines == 2 * (H.STREAM_GRID_ITEMS // 64)
+    occ = ref.random_grid(shape, fraction, seed)
+    resolution = 0.037
+    want_rec, want_sites, want_sq = ref.transform(occ, resolution, signed)
+    rc, rec, sites, sq = c_entry(occ, resolution, signed)  # outputs pre-filled with -7: an unwritten tail fails below
+    assert rc == 0
+    assert np.array_equal(sq, want_sq), int((sq != want_sq).sum())
+    assert np.array_equal(sites, want_sites), int((sites != want_sites).sum())
+    assert np.array_equal(bits(rec), bits(want_rec)), int((bits(rec) != bits(want_rec)).any(axis=1).sum())
+    dt, rec2, sites2, sq2 = gpu_transform(occ, resolution, signed)  # and the Python layer hands the same bits on
+    assert np.array_equal(sq2, sq) and np.array_equal(sites2, sites) and np.array_equal(bits(rec2), bits(rec))
+
+
+def test_a_graph_replay_past_the_launch_caps_gives_the_eager_bits():
+    occ = torch.from_numpy(ref.random_grid((100, 100, 70), 0.001, 51)).cuda()
+    assert occ.numel() > H.STREAM_GRID_ITEMS and occ.shape[0] * occ.shape[1] > H.STREAM_GRID_ITEMS // 64
+    eager = pv.distance_transform(occ, resolution=0.037)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        captured = pv.distance_transform(occ, resolution=0.037)
+    for t in captured:
+        t.fill_(-7)
+    g.replay()
+    torch.cuda.synchronize()
+    for a, c in zip(eager, captured):
+        raw = (lambda t: t.view(torch.int32)) if a.dtype == torch.float32 else (lambda t: t)
+        assert torch.equal(raw(a), raw(c))
+    assert (eager.squared > 0).any()
+
+
 def test_input_dtypes_mean_the_same_occupancy():
     occ = ref.random_grid((6, 9, 70), 0.2, 21)
     base = gpu_transform(occ, 0.5, True)[1:]

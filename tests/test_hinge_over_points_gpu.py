@@ -11,8 +11,10 @@ import torch
 
 import pytorch_volumetric_amd as pv
 import workloads as W
+from tests import helpers as H
 from tests.test_interp_gpu import build_robot
-from tests.test_min_over_points_gpu import c3, c3_pts, deepest_voxel_centre, one_leaf, two_placements
+from tests.test_min_over_points_gpu import (EDGE_ROWS, c3, c3_pts, deepest_voxel_centre, many_configurations, one_leaf,
+                                            two_placements)
 
 pytestmark = pytest.mark.gpu
 
@@ -278,6 +280,36 @@ def test_composed_dpoints_dtf(cache, cache_tri, tri, dtype):
     comp.set_transforms(tfm, batch_dim=(A,))
 
 
+def test_per_leaf_dpoints_of_more_points_than_the_reduction_grids_have_lanes(cache_tri):
+    """The per-leaf backward adds the split rows up (reduce_splits_kernel) and then the leaves' terms (accumulate_kernel), both
+    streaming over P x 3 elements: past STREAM_GRID_ITEMS / 3 points a lane takes a second one.  A point's gradient depends on
+    no other point: the two halves, neither of which strides, give it within the bound test_composed_dpoints_dtf uses for
+    dpoints (the halves may split the configurations otherwise)."""
+    S, A, P = 2, 2, H.STREAM_GRID_ITEMS // 3 + 4099
+    assert P * 3 > H.STREAM_GRID_ITEMS and (P - P // 2) * 3 < H.STREAM_GRID_ITEMS
+    comp = pv.ComposedSDF([cache_tri] * S, None)
+    t = W.random_rigid(S * A, seed=33, trans=0.2).cuda().requires_grad_()
+    comp.set_transforms(t, batch_dim=(A,))
+    pts = c3_pts(P, seed=34)
+    wl = None
+
+    def grads(rows):
+        nonlocal wl
+        p = pts[rows].clone().requires_grad_()
+        res = comp.hinge_over_points(p, GRAD_MARGIN, per_leaf=True)
+        if wl is None:
+            wl = weights((A, S), 4, res.values)
+        return torch.autograd.grad((res.values * wl).sum(), (p, t))
+
+    dp, dt = grads(slice(0, P))
+    half = P // 2
+    (dpa, dta), (dpb, dtb) = grads(slice(0, half)), grads(slice(half, P))
+    halves = torch.cat((dpa, dpb))
+    scale = float(halves.abs().max())
+    assert scale > 0 and float((dp - halves).abs().max()) <= 1e-5 * scale
+    assert bool((dp[H.STREAM_GRID_ITEMS // 3:].abs().sum(dim=-1) > 0).any())
+
+
 # ---------------------------------------------------------------- the generic path
 def test_generic_fallback_same_contract(cache, cache_tri):
     pts = c3_pts(20_000, seed=12)
@@ -304,6 +336,28 @@ def test_generic_fallback_same_contract(cache, cache_tri):
     (rt,) = torch.autograd.grad(unfused(comp, ph, GRAD_MARGIN, 2).sum(), t)
     assert torch.equal(dt, rt) and float(dt.abs().max()) > 0
     comp.set_transforms(tfm, batch_dim=(2,))
+
+
+# ---------------------------------------------------------------- more configurations than gridDim.y holds
+@pytest.mark.parametrize("mode", ["f32-nearest", "f32-trilinear", "f64-nearest"])
+@pytest.mark.parametrize("per_leaf", [False, True], ids=["overall", "per_leaf"])
+def test_more_configurations_than_grid_rows(cache, cache_tri, mode, per_leaf):
+    """hop_partial_kernel wraps a += gridDim.y and reuses its LDS partials behind a trailing barrier: rows 65535.. are a block's
+    second turn."""
+    comp, few = many_configurations(cache_tri if mode == "f32-trilinear" else cache)
+    pts = c3_pts(5, seed=22).to(torch.float64 if mode == "f64-nearest" else torch.float32)
+    v = field(comp, pts, per_leaf)
+    m = margins(v)[1]
+    rows = list(EDGE_ROWS)
+    for power in (1, 2):
+        res, _ = check(comp, pts, m, power, per_leaf)  # every configuration against composed(points), summed exactly
+        counts = res.counts.cpu().numpy()
+        assert ((counts > 0) & (counts < 5)).any() and (counts == 0).any()  # the margin cuts through the rows
+        # the rows on either side of the wrap against a composition of those six configurations alone: no launch of it wraps
+        want, wcounts, bound = expected(field(few, pts, per_leaf), m, power)
+        got = res.values[rows].reshape(want.shape).cpu().numpy().astype(np.float64)
+        assert np.all(np.abs(got - want.astype(np.float64)) <= bound), (got, want)
+        assert np.array_equal(counts[rows].reshape(wcounts.shape), wcounts)
 
 
 # ---------------------------------------------------------------- memory, graph capture

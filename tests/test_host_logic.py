@@ -548,6 +548,38 @@ def test_voxel_containers_thin_port():
     assert vs.get_known_pos_and_values()[0].shape == (2, 3)
 
 
+def test_per_point_values_must_match_the_points():
+    """A tensor value with dim() > 0 is one value per point: any other count is a ValueError naming both counts, on the
+    generic path here as on the device path (tests/test_voxelgrid_gpu.py), and the storage stays as it was."""
+    P = 10
+    vg = pv.VoxelGrid(0.1, [(0.0, 1.0)] * 3)
+    pts = (torch.arange(P) * 0.1 + 0.01).unsqueeze(-1).repeat(1, 3)  # one voxel each
+    vg[pts] = torch.arange(1.0, P + 1)
+    before = vg.get_voxel_values().clone()
+    for shape in ((1,), (3,), (P + 1,)):
+        with pytest.raises(ValueError, match=rf"\b{shape[0]} values for {P} points"):
+            vg[pts] = torch.ones(shape)
+        with pytest.raises(ValueError, match=rf"\b{shape[0]} values for {P} points"):
+            vg[pts.reshape(2, 5, 3)] = torch.ones(shape)
+    assert torch.equal(vg.get_voxel_values(), before)
+    # what stays allowed: a 0-dim tensor, a python scalar, and values shaped like the points' batch dimensions
+    vg[pts] = torch.tensor(7.0)
+    assert (vg[pts] == 7).all()
+    vg[pts.reshape(2, 5, 3)] = torch.arange(1.0, P + 1).reshape(2, 5)
+    assert torch.equal(vg.get_voxel_values(), before)
+    # the count decides, not the shape: (P, 1) values are the P values, on this path as in the device path's reshape(-1)
+    vg[pts] = torch.full((P, 1), 9.0)
+    vg[pts] = torch.arange(1.0, P + 1).reshape(P, 1)
+    assert torch.equal(vg.get_voxel_values(), before)
+    # a growing grid refuses the write before it grows: range and storage stay as they were
+    ev = pv.ExpandingVoxelGrid(0.1, [(0.0, 1.0)] * 3)
+    ev[pts] = torch.arange(1.0, P + 1)
+    rng, shape, kept = ev.range_per_dim.copy(), ev.get_voxel_values().shape, ev.get_voxel_values().clone()
+    with pytest.raises(ValueError, match=rf"\b3 values for {P} points"):
+        ev[pts + 5.0] = torch.ones(3)
+    assert np.array_equal(ev.range_per_dim, rng) and ev.get_voxel_values().shape == shape and torch.equal(ev.get_voxel_values(), kept)
+
+
 def test_composed_surface_bounding_box_matches_the_reference_glue():
     """sdf.py:347-368 run verbatim (make_golden.py group B), including its choice of transforming only the min-row and
     max-row of each leaf box."""

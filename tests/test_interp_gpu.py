@@ -13,6 +13,7 @@ import torch
 import pytorch_volumetric_amd as pv
 import workloads as W
 from pytorch_volumetric_amd import _lib
+from tests import helpers as H
 from tests import interp_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -253,6 +254,27 @@ def test_composed_and_robot_forward_bit_exact(robot, robot_nearest):
     v64, _ = robot(pts[:-2].double())
     assert v64.dtype == torch.float64
     assert torch.allclose(v64.float(), val[:, :-2], atol=1e-5, rtol=1e-5)
+
+
+def test_composed_forward_with_more_configurations_than_grid_rows(tri):
+    """composed_interp_kernel takes the configuration from blockIdx.y and wraps a += gridDim.y: rows 65535.. are a block's second
+    turn.  Values, gradients and leaf ids of every configuration against interp_ref.c, and the rows on either side of the wrap
+    again by name."""
+    A = H.GRID_Y_MAX + 66
+    comp = pv.ComposedSDF([tri, tri], None)
+    comp.set_transforms(W.random_rigid(2 * A, seed=61, trans=0.2).cuda(), batch_dim=(A,))
+    pts = torch.cat((W.c3_points(4, seed=62), torch.tensor([[math.nan, 0, 0]], device="cuda")))
+    assert comp._fused_mode() == "trilinear"
+    rv, rg, rl = composed_ref_f32(comp.sdfs, comp._tf_matrix, pts)
+    val, grad = comp(pts)
+    assert val.shape == (A, 5) and grad.shape == (A, 5, 3)
+    _, _, leaf, _, _ = comp._interp_forward(pts, want_leaf=True)
+    val, grad, leaf = val.cpu().numpy(), grad.cpu().numpy(), leaf.cpu().numpy()
+    assert np.array_equal(val, rv, equal_nan=True) and np.array_equal(grad, rg, equal_nan=True) and np.array_equal(leaf, rl)
+    for a in (0, 1, H.GRID_Y_MAX - 1, H.GRID_Y_MAX, H.GRID_Y_MAX + 1, A - 1):
+        assert np.array_equal(val[a], rv[a], equal_nan=True) and np.array_equal(grad[a], rg[a], equal_nan=True), a
+        assert np.array_equal(leaf[a], rl[a]), a
+    assert len(np.unique(val[:, 0])) > 1000 and (rl == 0).any() and (rl == 1).any()  # the rows differ, both leaves answer
 
 
 def composed_abi_f64(comp, tfm, pts):

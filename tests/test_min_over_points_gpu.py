@@ -383,6 +383,36 @@ def test_peak_memory_c4(robot):
     assert res.values.shape == (A,)
 
 
+# ---------------------------------------------------------------- more configurations than gridDim.y holds
+MANY = H.GRID_Y_MAX + 66  # mop_partial_kernel wraps a += gridDim.y: rows 65535.. are a block's second turn, over the same LDS
+EDGE_ROWS = (0, 1, H.GRID_Y_MAX - 1, H.GRID_Y_MAX, H.GRID_Y_MAX + 1, MANY - 1)
+
+
+def many_configurations(leaf, seed=21):
+    """(the composition of two leaves under MANY configurations, the same leaves under the EDGE_ROWS configurations only)"""
+    tfm = W.random_rigid(2 * MANY, seed=seed, trans=0.2).reshape(2, MANY, 4, 4)
+    comp = pv.ComposedSDF([leaf] * 2, None)
+    comp.set_transforms(tfm.reshape(-1, 4, 4).cuda(), batch_dim=(MANY,))
+    few = pv.ComposedSDF([leaf] * 2, None)
+    few.set_transforms(tfm[:, list(EDGE_ROWS)].reshape(-1, 4, 4).cuda(), batch_dim=(len(EDGE_ROWS),))
+    return comp, few
+
+
+@pytest.mark.parametrize("mode", ["f32-nearest", "f32-trilinear", "f64-nearest"])
+@pytest.mark.parametrize("per_leaf", [False, True], ids=["overall", "per_leaf"])
+def test_more_configurations_than_grid_rows(cache, cache_tri, mode, per_leaf):
+    comp, few = many_configurations(cache_tri if mode == "f32-trilinear" else cache)
+    pts = c3_pts(5, seed=22).to(torch.float64 if mode == "f64-nearest" else torch.float32)
+    res = check(comp, pts, per_leaf)  # every configuration against __call__ + the restated rule
+    assert res.values.shape == ((MANY, 2) if per_leaf else (MANY,))
+    # and the rows on either side of the wrap against a composition of those six configurations alone: no launch of it wraps
+    ev, ei, eg = expected(few, pts, per_leaf)
+    rows = list(EDGE_ROWS)
+    assert np.array_equal(res.indices[rows].cpu().numpy(), ei)
+    assert same_bits(res.values[rows].cpu().numpy(), ev) and same_bits(res.gradients[rows].cpu().numpy(), eg)
+    assert len(np.unique(res.values.cpu().numpy())) > 1000  # the configurations do differ
+
+
 def test_graph_capture_single_stream(robot):
     robot.set_joint_configuration(W.c4_joint_configs(20, seed=50).cuda())
     pts = W.c4_points(50_000, seed=51)

@@ -17,6 +17,7 @@ import pytorch_volumetric_amd as pv
 import workloads as W
 from pytorch_volumetric_amd import _lib, mesh_io
 from tests import ray_backward_ref as RB
+from tests.helpers import STREAM_GRID_ITEMS
 from tests.test_min_over_points_gpu import same_bits
 
 pytestmark = pytest.mark.gpu
@@ -136,6 +137,46 @@ def test_cached(boxes, mode, dtype, R):
                 assert int(terms["on"].sum()) > R // 4
     if R >= 64:
         assert seen == {pv.RAY_MISS, pv.RAY_HIT, pv.RAY_MAX_STEPS, pv.RAY_INVALID}
+
+
+@pytest.mark.parametrize("mode,dtype", [("nearest", torch.float32), ("trilinear", torch.float64)], ids=["nearest-f32", "trilinear-f64"])
+def test_cached_with_more_rays_than_the_backward_grid_has_lanes(boxes, mode, dtype):
+    """cached_ray_cast_backward_kernel runs on a capped streaming grid of kRayBwdBlock lanes per block: past that many rays a lane
+    takes a second one.  The gradients of all the rays equal those of the same rays cast in two halves, neither of which
+    strides, bit for bit (a ray's gradient depends on no other ray), and the 10,000 rays around the first stride stay within the
+    bound of the float64 restatement."""
+    import os
+    import re
+    src = open(os.path.join(os.path.dirname(pv.__file__), "csrc", "ray_cast_backward.hip")).read()
+    assert re.search(r"constexpr\s+int\s+kRayBwdBlock\s*=\s*PVAMD_RAY_BACKWARD_CHUNK\s*;", src)
+    assert re.search(r"stream_grid\(R,\s*kRayBwdBlock\)", src)
+    first = STREAM_GRID_ITEMS // 256 * CHUNK  # rays the capped grid covers in one turn
+    R = first + 4099
+    cache = boxes[mode]
+    o, d = cached_rays(cache, R, dtype)
+    up = weights((R,), dtype, 77)
+
+    def gradients(rows):
+        og, dg = o[rows].clone().requires_grad_(), d[rows].clone().requires_grad_()
+        res = cache.ray_cast(og, dg, differentiable=True, **KW)
+        (res.t * up[rows]).sum().backward()
+        return res, og.grad, dg.grad
+
+    res, go, gd = gradients(slice(0, R))
+    half = R // 2
+    assert half < first
+    (_, go_a, gd_a), (_, go_b, gd_b) = gradients(slice(0, half)), gradients(slice(half, R))
+    assert same_bits(go.cpu().numpy(), torch.cat((go_a, go_b)).cpu().numpy())
+    assert same_bits(gd.cpu().numpy(), torch.cat((gd_a, gd_b)).cpu().numpy())
+    rows = slice(first - 5000, first + 5000)
+    terms = RB.pair_terms(o[rows], d[rows], res.t[rows], res.status[rows], res.gradients[rows], up[rows])
+    (ro, bo), (rd, bd) = RB.ray_reference(terms, dtype)
+    RB.assert_within(go[rows], ro, bo, "dorigins")
+    RB.assert_within(gd[rows], rd, bd, "ddirections")
+    on = terms["on"]
+    assert int(on[:5000].sum()) > 500 and int(on[5000:].sum()) > 400  # contributing rays on both sides of the stride
+    assert bool((go[rows].cpu()[~on] == 0).all()) and bool((gd[rows].cpu()[~on] == 0).all())
+    assert bool((go[first:].abs().sum(dim=-1) > 0).any())
 
 
 def test_box_face(boxes):

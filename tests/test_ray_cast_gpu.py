@@ -20,6 +20,7 @@ import torch
 import pytorch_volumetric_amd as pv
 import workloads as W
 from pytorch_volumetric_amd import _lib
+from tests.helpers import GRID_Y_MAX
 from tests.test_interp_gpu import build_robot
 from tests.test_min_over_points_gpu import same_bits
 
@@ -250,6 +251,43 @@ def test_bit_exact_full_fan(scenes, kind, mode, dtype):
     check(sc.sdf.ray_cast(o, d, t_max=T_MAX, max_steps=2), ref2)
     if kind != "cached":  # ... and it was the kernel that answered
         assert (sc.sdf.sdf if kind == "robot" else sc.sdf)._fused_mode() == mode
+
+
+# ---------------------------------------------------------------- more configurations than gridDim.y holds
+@pytest.mark.parametrize("dtype", DTYPES, ids=["f32", "f64"])
+@pytest.mark.parametrize("mode", MODES)
+def test_more_configurations_than_grid_rows(caches, mode, dtype):
+    """composed_ray_cast_kernel wraps a += gridDim.y: configurations 65535.. are a block's second turn.  The loop restated above
+    is one Python loop of up to 128 eager steps per configuration, far too slow for 65,601 of them, so it answers for the rows on
+    either side of the wrap and a sample of the others; EVERY configuration is compared with the same call over two halves of the
+    stack, neither of which wraps."""
+    A = GRID_Y_MAX + 66
+    edge = [0, 1, GRID_Y_MAX - 1, GRID_Y_MAX, GRID_Y_MAX + 1, A - 1]
+    c = caches[mode]
+    stack = W.random_rigid(2 * A, seed=31, trans=0.2).reshape(2, A, 4, 4)
+
+    def composition(rows):
+        comp = pv.ComposedSDF([c, c], None)
+        part = stack[:, rows]
+        comp.set_transforms(part.reshape(-1, 4, 4).cuda(), batch_dim=(part.shape[1],))
+        return comp
+
+    eye = np.array([0.5, 0.3, 0.15])
+    aims = np.array([[0.0, 0.0, 0.0], [0.1, -0.1, 0.1], [1.0, 0.6, 0.3]]) - eye  # two towards the leaves, one away from them
+    o = torch.from_numpy(np.broadcast_to(eye, (3, 3)).copy()).to(dtype).cuda()
+    d = torch.from_numpy(aims / np.linalg.norm(aims, axis=1, keepdims=True)).to(dtype).cuda()
+    res = composition(slice(None)).ray_cast(o, d, t_max=T_MAX)
+    assert res.t.shape == (A, 3) and res.gradients.shape == (A, 3, 3)
+    status = res.status.cpu().numpy()
+    assert (status == pv.RAY_HIT).sum() > 100 and (status == pv.RAY_MISS).sum() > 100
+    half = A // 2
+    parts = [composition(slice(0, half)).ray_cast(o, d, t_max=T_MAX), composition(slice(half, A)).ray_cast(o, d, t_max=T_MAX)]
+    assert equal_results(res, pv.RayCast(*(torch.cat(xy) for xy in zip(*parts))))
+    rows = edge + sorted(np.random.default_rng(5).choice(A, 18, replace=False).tolist())
+    ref = reference(f"many-{mode}", composition(rows), o, d)
+    assert {pv.RAY_MISS, pv.RAY_HIT} <= statuses(ref), statuses(ref)
+    check(pv.RayCast(*(x[rows] for x in res)), ref)
+    check(pv.RayCast(*(x[edge] for x in res)), tuple(x[:len(edge)] for x in ref))  # rows 0, 1, 65534, 65535, 65536 and A - 1
 
 
 @pytest.mark.parametrize("R", [1, 63, 64, 65, 257])
