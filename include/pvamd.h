@@ -240,6 +240,7 @@ int pvamd_voxel_scatter_u8(const pvamd_grid_t* grid, uint8_t* storage, const flo
 #define PVAMD_COMPOSED_FORCE_WAVE_TILE 4  /* testing / tuning: take the wave-tile kernel whatever the size                 */
 #define PVAMD_COMPOSED_NO_GROUPING 64   /* testing / tuning: never the chunk-grouped kernel (the round-5 kernels whatever the size) */
 #define PVAMD_COMPOSED_FORCE_FUSED 128  /* testing / tuning: the chunk-grouped kernel with the in-workgroup sort whenever P >= one chunk */
+#define PVAMD_COMPOSED_TILE_POINTS 256  /* points per wave tile: what the sorted / packed entry points below pad their points to */
 #define PVAMD_COMPOSED_OUT_PACKED 32  /* pvamd_composed_query_grouped only: out_val takes [A][P] (val, gx, gy, gz) records (16-byte aligned), out_grad NULL */
 int pvamd_composed_query(const pvamd_grid_t* grids, int32_t S, const float* tf, int32_t A,
                          const float* points, int64_t P,
@@ -265,11 +266,11 @@ int pvamd_composed_query_f64(const pvamd_grid_t* grids, int32_t S, const double*
 /* The glue of ComposedSDF.__call__ for leaves that are not cached grids (MeshSDF, SphereSDF, nested compositions;
  * sdf.py:392-433 around per-leaf queries), with the fused kernel's rounding so that both paths state the same numbers:
  * pvamd_transform_points: out[a][p] = tf[a] p (sdf.py:399).  tf: device [A][4][4] -- the A transforms of ONE leaf.
- *   points: device [P][3].  out: device [A][P][3].  A <= 65535.
+ *   points: device [P][3].  out: device [A][P][3].  Any P >= 0, any A >= 1.
  * pvamd_compose_merge: fold leaf s into the running first minimum (sdf.py:409,421): where leaf_val is smaller than
  *   best_val (or is NaN against a number; everywhere when first != 0) take it, with the gradient brought back to the
  *   object frame as L^T g (L = linear part of tf[a]; valid for any affine transform).  leaf_val / best_val: device [A][P].
- *   leaf_grad / best_grad: device [A][P][3].  best_leaf: device [A][P] int32 or NULL.                                  */
+ *   leaf_grad / best_grad: device [A][P][3].  best_leaf: device [A][P] int32 or NULL.  Any P >= 0, any A >= 1.        */
 int pvamd_transform_points(const float* tf, int32_t A, const float* points, int64_t P, float* out, void* stream);
 int pvamd_compose_merge(const float* tf, int32_t A, int64_t P, const float* leaf_val, const float* leaf_grad,
                         int32_t s, int32_t first, float* best_val, float* best_grad, int32_t* best_leaf, void* stream);
@@ -281,7 +282,7 @@ int pvamd_compose_merge(const float* tf, int32_t A, int64_t P, const float* leaf
  * pass writes out_val / out_grad in the CALLER's point order: out[a][j] = record[a][inv[j]].  Same results, bit for
  * bit, as pvamd_composed_query on the unsorted points.
  * sorted_points: device [Pp][3], the P points in processing order followed by Pp - P copies of any of them (Pp a
- * multiple of 256, 16-byte aligned).  inv: device [P] int32, position of caller point j in sorted_points.
+ * multiple of PVAMD_COMPOSED_TILE_POINTS, 16-byte aligned).  inv: device [P] int32, position of caller point j in sorted_points.
  * scratch: device, A * Pp * 16 bytes, 16-byte aligned.  out_val: device [A][P].  out_grad: device [A][P][3].       */
 int pvamd_composed_query_bucketed(const pvamd_grid_t* grids, int32_t S, const float* tf, int32_t A,
                                   const float* sorted_points, const int32_t* inv, int64_t P, int64_t Pp,
@@ -310,7 +311,7 @@ int pvamd_composed_query_grouped(const pvamd_grid_t* grids, int32_t S, const flo
  * (model_to_sdf.py:117-125 -> sdf.py:392-433) sharded over GPUs runs on each rank's slice of the points, gathers ONE
  * buffer of records instead of val and grad, then unpacks straight into the reference's (A, P) / (A, P, 3) layout:
  * pvamd_composed_query_packed: out_rec[a][k] = (val, gx, gy, gz) of configuration a at points[k].  points: device [Pp][3],
- *   Pp a multiple of 256, at most 2^24 * 4.  out_rec: device, A * Pp * 16 bytes, 16-byte aligned.  Any A.
+ *   Pp a multiple of PVAMD_COMPOSED_TILE_POINTS, at most 2^24 * 4.  out_rec: device, A * Pp * 16 bytes, 16-byte aligned.  Any A.
  * pvamd_unpack_records: out_val[a][j] / out_grad[a][j] = rec[a * stride + index[j]] for j < P (index[j] may point
  *   anywhere in the buffer, e.g. into another rank's slab).  rec: device float4 records.  index: device [P] int32.   */
 int pvamd_composed_query_packed(const pvamd_grid_t* grids, int32_t S, const float* tf, int32_t A, const float* points,

@@ -211,6 +211,7 @@ COMPOSED_FORCE_WAVE_TILE = H["PVAMD_COMPOSED_FORCE_WAVE_TILE"]
 COMPOSED_OUT_PACKED = H["PVAMD_COMPOSED_OUT_PACKED"]
 COMPOSED_NO_GROUPING = H["PVAMD_COMPOSED_NO_GROUPING"]
 COMPOSED_FORCE_FUSED = H["PVAMD_COMPOSED_FORCE_FUSED"]
+TILE_POINTS = H["PVAMD_COMPOSED_TILE_POINTS"]  # the bucketed and packed composed queries take whole tiles of points
 CO_KERNEL_PER_LANE = H["PVAMD_CO_KERNEL_PER_LANE"]
 CO_KERNEL_WAVE_TILE = H["PVAMD_CO_KERNEL_WAVE_TILE"]
 CO_KERNEL_FUSED = H["PVAMD_CO_KERNEL_FUSED"]
@@ -413,6 +414,11 @@ def mesh_small_points():
     if _mesh_small is None:
         _mesh_small = int(load().pvamd_mesh_small_points())
     return _mesh_small
+
+
+def whole_tiles(P):
+    """P rounded up to whole tiles of TILE_POINTS: the Pp of pvamd_composed_query_bucketed and pvamd_composed_query_packed."""
+    return -(-P // TILE_POINTS) * TILE_POINTS
 
 
 def group_points(flat):

@@ -109,10 +109,8 @@ def chamfer_partial_sums(W, points, obj_factory, obj_sdf, scale):
                 # B * N points once, walk them in ONE spatial order (the 64 points of a wave are then neighbours in space,
                 # whichever transform they came from) and let every point add to its own transform's sum
                 x = torch.empty((B, N, 3), dtype=torch.float32, device=dev)
-                for b0 in range(0, B, 65535):  # the transform kernel carries the transform in a grid dimension
-                    nb = min(65535, B - b0)
-                    _lib.check(lib.pvamd_transform_points(_lib.ptr(Wd[b0:b0 + nb]), nb, _lib.ptr(pts), N, _lib.ptr(x[b0:b0 + nb]),
-                                                          _lib.stream_ptr()), "pvamd_transform_points")
+                _lib.check(lib.pvamd_transform_points(_lib.ptr(Wd), B, _lib.ptr(pts), N, _lib.ptr(x), _lib.stream_ptr()),
+                           "pvamd_transform_points")
                 flat = x.view(-1, 3)
                 order = _lib.morton_order(flat)
                 scratch = _lib.scratch_buffer(_lib.mesh_scratch_bytes(B * N), dev)

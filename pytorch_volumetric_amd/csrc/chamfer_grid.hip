@@ -116,13 +116,12 @@ extern "C" int pvamd_chamfer_grid(const pvamd_grid_t* grid, const float* W, int3
     if (N == 0) return (int)hipGetLastError();
     if (!W || !points) return PVAMD_E_NULL;
     const int64_t need = (N + 255) / 256;
-    for (int32_t b0 = 0; b0 < B; b0 += 65535) {
-        const int32_t nb = (B - b0) < 65535 ? (B - b0) : 65535;
+    for_row_slabs(B, [&](int32_t b0, int32_t nb) {
         const int64_t cap = ((int64_t)kNumCU * kMaxBlocksPerCU + nb - 1) / nb;
         const unsigned gx = (unsigned)(need < cap ? need : (cap < 1 ? 1 : cap));
         if (grid->index_f64) hipLaunchKernelGGL((chamfer_grid_kernel<true>), dim3(gx, nb), dim3(256), 0, s, *grid, W + 16 * (int64_t)b0, points, N, scale, out_sum + b0);
         else hipLaunchKernelGGL((chamfer_grid_kernel<false>), dim3(gx, nb), dim3(256), 0, s, *grid, W + 16 * (int64_t)b0, points, N, scale, out_sum + b0);
-    }
+    });
     return (int)hipGetLastError();
 }
 

@@ -36,8 +36,20 @@ typedef float f32x4_u __attribute__((ext_vector_type(4), aligned(4)));
 
 constexpr int kNumCU = 256;         // MI355X: 8 XCDs x 32 CUs
 constexpr int kMaxBlocksPerCU = 8;  // memory-bound kernels: cap the grid at 256 CU x 8 and grid-stride the rest
+constexpr int kMaxGridRows = 65535; // gridDim.y and gridDim.z of a HIP launch hold no more
 
 static inline bool aligned_to(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
+
+// gridDim.y (or .z) of a kernel that wraps its row (a += gridDim.y): n, at least 1 and at most kMaxGridRows
+static inline unsigned grid_rows(int64_t n) { return (unsigned)(n < 1 ? 1 : (n < kMaxGridRows ? n : kMaxGridRows)); }
+
+// fn(first, count) for consecutive slabs of at most kMaxGridRows rows that cover [0, rows): the launches of a kernel that takes
+// its row from blockIdx.y and does not wrap.  Counted in 64 bits: rows near INT32_MAX do not overflow.
+template <typename F>
+static inline void for_row_slabs(int32_t rows, F fn) {
+    for (int64_t first = 0; first < rows; first += kMaxGridRows)
+        fn((int32_t)first, (int32_t)(rows - first < kMaxGridRows ? rows - first : kMaxGridRows));
+}
 
 // grid size for a streaming kernel over n items with `block` threads
 static inline unsigned stream_grid(int64_t n, int block) {
@@ -48,14 +60,12 @@ static inline unsigned stream_grid(int64_t n, int block) {
 
 // gridDim.y of a kernel that takes the configuration as blockIdx.x (any count: one launch for any A) and grid-strides over
 // `need` rows of work per configuration in y: up to ~65536 blocks in total, split over the A configurations (about one
-// 256-point tile per wave in the composed query), at least 1 and at most the 65535 HIP allows.  (Sweep on C4, 200 x 262,144:
+// 256-point tile per wave in the composed query), at least 1 and at most kMaxGridRows.  (Sweep on C4, 200 x 262,144:
 // 1024 blocks 1.40 ms, 4096 1.17, 8192 1.13, 32768 1.09, 65536 1.08 -- the hardware dispatcher balances better than a
 // grid-stride loop over unequal tiles.)
 static inline unsigned config_rows(int32_t A, int64_t need) {
-    int64_t cap = ((int64_t)65536 + A - 1) / A;
-    if (cap > 65535) cap = 65535;
-    const int64_t rows = need < cap ? need : cap;
-    return (unsigned)(rows < 1 ? 1 : rows);
+    const int64_t cap = ((int64_t)65536 + A - 1) / A;
+    return grid_rows(need < cap ? need : cap);
 }
 
 static inline int check_grid(const pvamd_grid_t& g, bool need_vox = true) {

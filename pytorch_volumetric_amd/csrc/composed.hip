@@ -238,6 +238,7 @@ PVAMD_DEV uint64_t tile_leaf_mask(const float (*cull)[8], int S, int lane, const
 // through a wave-private LDS slice (same scheme as cached_query_wave, see cached.hip).
 constexpr int kWavesPerBlock = 4;
 constexpr int kTilePoints = 256;
+static_assert(kTilePoints == PVAMD_COMPOSED_TILE_POINTS, "callers pad their points to the header's tile");
 // fewer (tile, configuration) pairs than this: the one-point-per-lane kernel.  A tile is one wave's work and the chip
 // holds 6,144-8,192 waves: below ~4 rounds of them the last, partly filled round costs more than the tile machinery saves
 // (README case, 200 x 15,251 points = 12,000 tiles: per-lane 0.076 / 0.061 ms on 21 MB / 100 KB link grids against 0.104 /
@@ -1307,7 +1308,7 @@ extern "C" int pvamd_composed_query_packed(const pvamd_grid_t* grids, int32_t S,
     const int64_t ntiles = Pp / kTilePoints;
     const int64_t tile_blocks = (ntiles + kWavesPerBlock - 1) / kWavesPerBlock;
     // gridDim.y of the query kernel = tile blocks (the configuration is blockIdx.x: any A)
-    if (tile_blocks > 65535) return PVAMD_E_SHAPE;  // > 67 M points per call: use the direct entry point
+    if (tile_blocks > kMaxGridRows) return PVAMD_E_SHAPE;  // > 67 M points per call: use the direct entry point
     // large, gather-bound grids (the inline-exact hint): the round-3 loop; else the split loop
     if (flags & PVAMD_COMPOSED_INLINE_EXACT)
         hipLaunchKernelGGL((composed_query_wave<kPointsPerPass, true, 0>), dim3(A, (unsigned)tile_blocks),
@@ -1455,21 +1456,27 @@ extern "C" int pvamd_composed_query_grouped(const pvamd_grid_t* grids, int32_t S
 
 extern "C" int pvamd_transform_points(const float* tf, int32_t A, const float* points, int64_t P, float* out,
                                       void* stream) {
-    if (A < 1 || A > 65535 || P < 0) return PVAMD_E_SHAPE;
+    if (A < 1 || P < 0) return PVAMD_E_SHAPE;
     if (P == 0) return 0;
     if (!tf || !points || !out) return PVAMD_E_NULL;
-    hipLaunchKernelGGL(transform_points_kernel, dim3(stream_grid(P, 256), A), dim3(256), 0, (hipStream_t)stream, tf, points,
-                       P, out);
+    for_row_slabs(A, [&](int32_t a0, int32_t n) {  // the configuration is blockIdx.y
+        hipLaunchKernelGGL(transform_points_kernel, dim3(stream_grid(P, 256), n), dim3(256), 0, (hipStream_t)stream,
+                           tf + 16 * (int64_t)a0, points, P, out + 3 * (a0 * P));
+    });
     return (int)hipGetLastError();
 }
 
 extern "C" int pvamd_compose_merge(const float* tf, int32_t A, int64_t P, const float* leaf_val, const float* leaf_grad,
                                    int32_t s, int32_t first, float* best_val, float* best_grad, int32_t* best_leaf,
                                    void* stream) {
-    if (A < 1 || A > 65535 || P < 0 || s < 0) return PVAMD_E_SHAPE;
+    if (A < 1 || P < 0 || s < 0) return PVAMD_E_SHAPE;
     if (P == 0) return 0;
     if (!tf || !leaf_val || !leaf_grad || !best_val || !best_grad) return PVAMD_E_NULL;
-    hipLaunchKernelGGL(compose_merge_kernel, dim3(stream_grid(P, 256), A), dim3(256), 0, (hipStream_t)stream, tf, P,
-                       leaf_val, leaf_grad, s, first, best_val, best_grad, best_leaf);
+    for_row_slabs(A, [&](int32_t a0, int32_t n) {
+        const int64_t o = a0 * P;  // the slab's first element of the [A][P] arrays
+        hipLaunchKernelGGL(compose_merge_kernel, dim3(stream_grid(P, 256), n), dim3(256), 0, (hipStream_t)stream,
+                           tf + 16 * (int64_t)a0, P, leaf_val + o, leaf_grad + 3 * o, s, first, best_val + o, best_grad + 3 * o,
+                           best_leaf ? best_leaf + o : nullptr);
+    });
     return (int)hipGetLastError();
 }

@@ -87,7 +87,7 @@ static void hop_launch(const pvamd_grid_t* grids, int S, const T* tf, int A, con
     const int64_t nchunks = (P + PVAMD_MOP_CHUNK - 1) / PVAMD_MOP_CHUNK;
     const int Z = per_leaf ? S : 1;
     const int64_t npairs = (int64_t)A * Z;
-    hipLaunchKernelGGL((hop_partial_kernel<T, INTERP>), dim3((unsigned)nchunks, (unsigned)(A < 65535 ? A : 65535), (unsigned)Z),
+    hipLaunchKernelGGL((hop_partial_kernel<T, INTERP>), dim3((unsigned)nchunks, grid_rows(A), (unsigned)Z),
                        dim3(kHopBlock), 0, st, grids, S, tf, A, points, P, per_leaf, m, power, nchunks, part);
     hipLaunchKernelGGL(hop_finish_kernel<T>, dim3((unsigned)(npairs < 0x7fffffff ? npairs : 0x7fffffff)), dim3(64), 0, st, npairs,
                        nchunks, part, out_val, out_count);
@@ -96,7 +96,7 @@ static void hop_launch(const pvamd_grid_t* grids, int S, const T* tf, int A, con
 template <typename T>
 static int hinge_over_points(const pvamd_grid_t* grids, int32_t S, const T* tf, int32_t A, const T* points, int64_t P, int32_t mode,
                              int32_t per_leaf, T margin, int32_t power, T* out_val, int64_t* out_count, void* scratch, void* stream) {
-    if (S < 1 || A < 1 || P < 1 || (per_leaf && S > 65535) || (P + PVAMD_MOP_CHUNK - 1) / PVAMD_MOP_CHUNK > 0x7fffffff)
+    if (S < 1 || A < 1 || P < 1 || (per_leaf && S > kMaxGridRows) || (P + PVAMD_MOP_CHUNK - 1) / PVAMD_MOP_CHUNK > 0x7fffffff)
         return PVAMD_E_SHAPE;
     if ((mode != PVAMD_LEAF_NEAREST && mode != PVAMD_LEAF_TRILINEAR) || (per_leaf != 0 && per_leaf != 1) ||
         (power != 1 && power != 2))

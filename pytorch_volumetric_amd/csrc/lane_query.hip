@@ -246,11 +246,11 @@ extern "C" int pvamd_composed_query_interp(const pvamd_grid_t* grids, int32_t S,
                                            int64_t P, float* out_val, float* out_grad, int32_t* out_leaf, void* stream) {
     if (int e = check_composed<float>(grids, S, tf, A, points, P, out_val, out_grad)) return e;
     if (P == 0) return 0;
-    // point blocks in x (as many as the points need, at most the 2^31 - 1 HIP allows), configurations in y (at most 65535; more
+    // point blocks in x (as many as the points need, at most the 2^31 - 1 HIP allows), configurations in y (grid_rows; more
     // are strided)
     int64_t bx = (P + kLaneBlock - 1) / kLaneBlock;
     if (bx > 0x7fffffff) bx = 0x7fffffff;
-    hipLaunchKernelGGL(composed_interp_kernel, dim3((unsigned)bx, (unsigned)(A < 65535 ? A : 65535)), dim3(kLaneBlock), 0,
+    hipLaunchKernelGGL(composed_interp_kernel, dim3((unsigned)bx, grid_rows(A)), dim3(kLaneBlock), 0,
                        (hipStream_t)stream, grids, S, tf, A, points, P, out_val, out_grad, out_leaf);
     return (int)hipGetLastError();
 }

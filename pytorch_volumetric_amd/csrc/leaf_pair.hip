@@ -363,7 +363,7 @@ static void lp_launch(const pvamd_grid_t* grids, int S, const T* C, int A, const
     // configurations per workgroup: enough workgroups to fill the chip (a few thousand), then each loops over its configurations
     // so that a set's points are read from L2 for many a
     const int64_t want = (4096 + (int64_t)K * nchunks - 1) / ((int64_t)K * nchunks);
-    const unsigned ay = (unsigned)(A < want ? A : (want < 65535 ? want : 65535));
+    const unsigned ay = grid_rows(A < want ? A : want);
     const dim3 grd((unsigned)nchunks, ay, (unsigned)K);
     if (nchunks == 1) {
         hipLaunchKernelGGL((lp_partial_kernel<T, INTERP, true>), grd, dim3(kLpBlock), 0, st, grids, S, C, A, points, npoints, table, K,
@@ -381,7 +381,7 @@ template <typename T>
 static int leaf_pair_distance(const pvamd_grid_t* grids, int32_t S, const T* C, int32_t A, const T* points, int64_t npoints,
                               const int64_t* table, int32_t K, int64_t max_points, int32_t mode, T* out_val, T* out_grad,
                               int64_t* out_index, void* scratch, void* stream) {
-    if (max_points < 1 || max_points > npoints || max_points > (int64_t)0xfffffffe || K > 65535) return PVAMD_E_SHAPE;
+    if (max_points < 1 || max_points > npoints || max_points > (int64_t)0xfffffffe || K > kMaxGridRows) return PVAMD_E_SHAPE;
     if (int e = lp_check<T>(grids, S, C, A, points, npoints, table, K, mode)) return e;
     if (K == 0) return 0;
     const int64_t nchunks = lp_plan(K, A, max_points, sizeof(T), false, false).nchunks;
@@ -646,7 +646,7 @@ __global__ __launch_bounds__(256) void lph_pair_vjp_kernel(int S, const T* __res
 template <typename T>
 static int lph_check(const pvamd_grid_t* grids, int32_t S, const T* C, int32_t A, const T* points, int64_t npoints,
                      const int64_t* table, int32_t K, int64_t max_points, int32_t mode, int32_t power) {
-    if (max_points < 1 || max_points > npoints || max_points > (int64_t)0xfffffffe || K > 65535) return PVAMD_E_SHAPE;
+    if (max_points < 1 || max_points > npoints || max_points > (int64_t)0xfffffffe || K > kMaxGridRows) return PVAMD_E_SHAPE;
     if (S < 1 || A < 1 || K < 0) return PVAMD_E_SHAPE;
     if (power != 1 && power != 2) return PVAMD_E_MODE;
     return lp_check<T>(grids, S, C, A, points, npoints, table, K, mode);
@@ -657,7 +657,7 @@ static void lph_launch(const pvamd_grid_t* grids, int S, const T* C, int A, cons
                        int K, int64_t nchunks, T m, int power, T* out_val, int64_t* out_count, HopPart* part, hipStream_t st) {
     // lp_launch's geometry: a few thousand workgroups, each looping over its configurations
     const int64_t want = (4096 + (int64_t)K * nchunks - 1) / ((int64_t)K * nchunks);
-    const unsigned ay = (unsigned)(A < want ? A : (want < 65535 ? want : 65535));
+    const unsigned ay = grid_rows(A < want ? A : want);
     const dim3 grd((unsigned)nchunks, ay, (unsigned)K);
     if (nchunks == 1) {
         hipLaunchKernelGGL((lph_partial_kernel<T, INTERP, true>), grd, dim3(kHopBlock), 0, st, grids, S, C, A, points, npoints, table,

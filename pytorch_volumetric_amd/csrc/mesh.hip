@@ -1487,7 +1487,7 @@ static MeshPlan mesh_query_plan(int64_t P, int F, bool has_scratch, bool unorder
     // (in halves of a tile)
     const int half_tiles = groups <= 64 ? 2 : (groups <= 256 ? 3 : (groups < 2048 ? 6 : (int)(groups / 256)));
     int parts = (2 * ntiles + half_tiles - 1) / half_tiles;
-    if (parts > 65535) parts = 65535;  // gridDim.y (a mesh of more than 16.7 M triangles)
+    if (parts > kMaxGridRows) parts = kMaxGridRows;  // gridDim.y (a mesh of more than 16.7 M triangles)
     if (has_scratch && groups <= pl.slots && parts >= kMinParts) {
         pl.path = PVAMD_MESH_PATH_LISTED;
         pl.parts = parts;
@@ -1691,9 +1691,7 @@ static int launch_chamfer_mesh(const pvamd_mesh_t* mesh, const float* W, int32_t
     const bool heavy = plan.path == PVAMD_MESH_PATH_SCAN_HEAVY;
     const HandOver ho = hand_over(heavy ? scratch : nullptr, plan.slots);
     if (heavy) hipLaunchKernelGGL(hand_over_none_kernel, dim3(1), dim3(1), 0, s, ho);
-    // y-dimension of a HIP grid is limited to 65535: walk B in slabs
-    for (int32_t b0 = 0; b0 < ny; b0 += 65535) {
-        const int32_t nb = (ny - b0) < 65535 ? (ny - b0) : 65535;
+    for_row_slabs(ny, [&](int32_t b0, int32_t nb) {
         const dim3 grid((unsigned)plan.groups, nb);
         switch (plan.scan_waves) {
             case 8: hipLaunchKernelGGL((chamfer_mesh_kernel<8>), grid, dim3(512), 0, s, m, order, W, b0, points, N, scale, out_sum, ho, per); break;
@@ -1701,7 +1699,7 @@ static int launch_chamfer_mesh(const pvamd_mesh_t* mesh, const float* W, int32_t
             case 2: hipLaunchKernelGGL((chamfer_mesh_kernel<2>), grid, dim3(128), 0, s, m, order, W, b0, points, N, scale, out_sum, ho, per); break;
             default: hipLaunchKernelGGL((chamfer_mesh_kernel<1>), grid, dim3(64), 0, s, m, order, W, b0, points, N, scale, out_sum, ho, per); break;
         }
-    }
+    });
     if (heavy) {
         launch_heavy_parts<false>(m, 0, ho, plan, s);
         hipLaunchKernelGGL(chamfer_finish_kernel, dim3(list_blocks(ho.cap)), dim3(64), 0, s, m, order, W, points, N, scale, ho, out_sum, per);

@@ -192,7 +192,7 @@ __global__ __launch_bounds__(256) void mop_scatter_kernel(const int64_t* __restr
 
 template <typename T>
 static int mop_check(const pvamd_grid_t* grids, int S, const T* tf, int A, const T* points, int64_t P, int mode, int per_leaf) {
-    if (S < 1 || A < 1 || P < 1 || P > (int64_t)0xfffffffe || (per_leaf && S > 65535)) return PVAMD_E_SHAPE;
+    if (S < 1 || A < 1 || P < 1 || P > (int64_t)0xfffffffe || (per_leaf && S > kMaxGridRows)) return PVAMD_E_SHAPE;
     if (mode != PVAMD_LEAF_NEAREST && mode != PVAMD_LEAF_TRILINEAR) return PVAMD_E_MODE;
     if (per_leaf != 0 && per_leaf != 1) return PVAMD_E_MODE;
     if (!grids || !tf || !points) return PVAMD_E_NULL;
@@ -206,7 +206,7 @@ static void mop_launch(const pvamd_grid_t* grids, int S, const T* tf, int A, con
     const int64_t nchunks = (P + PVAMD_MOP_CHUNK - 1) / PVAMD_MOP_CHUNK;
     const int Z = per_leaf ? S : 1;
     const int64_t npairs = (int64_t)A * Z;
-    hipLaunchKernelGGL((mop_partial_kernel<T, INTERP>), dim3((unsigned)nchunks, (unsigned)(A < 65535 ? A : 65535), (unsigned)Z),
+    hipLaunchKernelGGL((mop_partial_kernel<T, INTERP>), dim3((unsigned)nchunks, grid_rows(A), (unsigned)Z),
                        dim3(kMopBlock), 0, st, grids, S, tf, A, points, P, per_leaf, nchunks, part);
     hipLaunchKernelGGL((mop_finish_kernel<T, INTERP>), dim3((unsigned)(npairs < 0x7fffffff ? npairs : 0x7fffffff)), dim3(64), 0, st,
                        grids, S, tf, A, points, P, per_leaf, nchunks, part, out_val, out_grad, out_index, out_leaf);

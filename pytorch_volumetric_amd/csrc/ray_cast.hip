@@ -185,7 +185,7 @@ static int composed_ray_cast(const pvamd_grid_t* grids, int32_t S, const T* tf, 
     if (!aligned_to(grids, 8) || !aligned_to(tf, sizeof(T))) return PVAMD_E_ALIGN;
     if (int e = ray_buffers<T>(origins, directions, out)) return e;
     hipStream_t st = (hipStream_t)stream;
-    const dim3 grd((unsigned)blocks, (unsigned)(A < 65535 ? A : 65535));
+    const dim3 grd((unsigned)blocks, grid_rows(A));
     if (mode == PVAMD_LEAF_TRILINEAR)
         hipLaunchKernelGGL((composed_ray_cast_kernel<T, true>), grd, dim3(kRayBlock), 0, st, grids, S, tf, A, origins, directions, R,
                            rp, out);

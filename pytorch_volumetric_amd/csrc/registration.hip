@@ -237,7 +237,7 @@ extern "C" int pvamd_chamfer_normal_eq(const pvamd_grid_t* grid, int32_t mode, c
     const int64_t nchunks = (N + PVAMD_REG_CHUNK - 1) / PVAMD_REG_CHUNK;
     double* slab = (double*)scratch;
     int64_t* slab_count = (int64_t*)(slab + nchunks * (int64_t)B * kRegSums);
-    const dim3 grid_dim((unsigned)nchunks, (unsigned)(B < 65535 ? B : 65535));
+    const dim3 grid_dim((unsigned)nchunks, grid_rows(B));
     if (mode == PVAMD_LEAF_TRILINEAR)
         hipLaunchKernelGGL((reg_partial_kernel<true>), grid_dim, dim3(kRegBlock), 0, st, *grid, W, B, points, N, nchunks, slab,
                            slab_count);

@@ -175,12 +175,12 @@ class ShardedSDF:
         if self.compute_device is not None and torch.device(self.compute_device).type != "cuda":
             return None
         A = math.prod(inner.tsf_batch) if inner.tsf_batch is not None else 1
-        Pp = -(-chunk // 256) * 256
+        Pp = _lib.whole_tiles(chunk)
         if world * A * Pp >= 2 ** 31:  # the unpack kernel indexes records with int32
             return None
         self.last_path = "packed"
         mine = flat[start:stop].to(dev)
-        if mine.shape[0] < Pp:  # whole 256-point tiles: pad with copies of a point (their records are never unpacked)
+        if mine.shape[0] < Pp:  # whole tiles: pad with copies of a point (their records are never unpacked)
             mine = torch.cat((mine, flat[:1].to(dev).expand(Pp - mine.shape[0], 3)), dim=0)
         rec = inner.query_packed(mine.contiguous())
         gathered = torch.empty((world, A, Pp, 4), dtype=torch.float32, device=dev)

@@ -105,10 +105,8 @@ class _Evaluator:
             return
         # any other object: transform with the kernel's statements, query the object, the same sums in float64 in torch
         x = torch.empty((self.B, self.N, 3), dtype=torch.float32, device=self.dev)
-        for b0 in range(0, self.B, 65535):  # the transform kernel carries the transform in a grid dimension
-            nb = min(65535, self.B - b0)
-            _lib.check(lib.pvamd_transform_points(_lib.ptr(W32[b0:b0 + nb]), nb, _lib.ptr(self.pts), self.N, _lib.ptr(x[b0:b0 + nb]),
-                                                  _lib.stream_ptr()), "pvamd_transform_points")
+        _lib.check(lib.pvamd_transform_points(_lib.ptr(W32), self.B, _lib.ptr(self.pts), self.N, _lib.ptr(x), _lib.stream_ptr()),
+                   "pvamd_transform_points")
         with torch.no_grad():
             v, n = self.obj_sdf(x)
         v = v.detach().to(device=self.dev, dtype=torch.float64).reshape(self.B, self.N)

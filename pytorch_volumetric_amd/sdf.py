@@ -1051,6 +1051,7 @@ class PreparedPoints:
 # instruction-bound, larger ones gather-bound.
 _XCD_L2_BYTES = 4 << 20
 _INLINE_EXACT = _lib.COMPOSED_INLINE_EXACT
+_TILE_POINTS = _lib.TILE_POINTS
 # Regrouping under group_points "auto" (ComposedSDF._grouping_pays): wherever the library itself would launch its wave-tile
 # kernel were regrouping off -- asked of the library (remembered per shape), not restated here.
 _composed_kernel, _NO_GROUPING, _WAVE_TILE = _lib.composed_query_kernel, _lib.COMPOSED_NO_GROUPING, _lib.CO_KERNEL_WAVE_TILE
@@ -1232,7 +1233,7 @@ class ComposedSDF(ObjectFrameSDF):
         in L2 whatever the order, so it is not sorted; a 64^3 grid in grid order (2.3 ms direct, 1.5 ms bucketed) fills
         the volume and is (tools/coherent_probe.py, profiles/r03_probes.txt)."""
         if self.bucket_points != "auto":
-            return bool(self.bucket_points) and P >= 256
+            return bool(self.bucket_points) and P >= _TILE_POINTS
         if not self._fusable():
             return False
         self._leaf_grids(self._owner_device())  # derives _query_flags from the grid sizes
@@ -1336,7 +1337,7 @@ class ComposedSDF(ObjectFrameSDF):
             flags = self._query_flags
             # the arithmetic half of _bucketing_pays, inline (its footprint probe waits in the general path)
             sort = (flags & _INLINE_EXACT and A >= _SORT_MIN_CONFIGS and P >= _SORT_MIN_POINTS and
-                    A * P * 16 <= _SORT_MAX_RECORD_BYTES) if bp == "auto" else (bool(bp) and P >= 256)
+                    A * P * 16 <= _SORT_MAX_RECORD_BYTES) if bp == "auto" else (bool(bp) and P >= _TILE_POINTS)
             if P > 0 and not sort:
                 dev = plan[0]
                 tfd = self._tf_dev
@@ -1395,8 +1396,8 @@ class ComposedSDF(ObjectFrameSDF):
                     # one spatial sort (Hilbert curve) of the shared point set, amortised over the A configurations; the kernel then
                     # sees spatially compact wave tiles and a second pass restores the caller's point order
                     _, inv, spts = _lib.morton_order(flat, min_points=0, want_inverse=True, want_sorted=True)
-                    Pp = -(-P // 256) * 256
-                    if Pp != P:  # whole 256-point tiles: pad with copies of the last point (never read back)
+                    Pp = _lib.whole_tiles(P)
+                    if Pp != P:  # whole tiles: pad with copies of the last point (never read back)
                         spts = torch.cat((spts, spts[-1:].expand(Pp - P, 3))).contiguous()
                     scratch = torch.empty((A, Pp, 4), dtype=torch.float32, device=dev)
                     _lib.check(lib.pvamd_composed_query_bucketed(_lib.ptr(grids), S, _lib.ptr(self._tf_device(dev)), A,
@@ -2015,7 +2016,7 @@ class ComposedSDF(ObjectFrameSDF):
             raise ValueError("prepare_points needs at least one point")
         with _lib.on_device(flat.device):
             order, inv, spts = _lib.morton_order(flat, min_points=0, want_inverse=True, want_sorted=True)
-            Pp = -(-P // 256) * 256
+            Pp = _lib.whole_tiles(P)
             padded = spts if Pp == P else torch.cat((spts, spts[-1:].expand(Pp - P, 3))).contiguous()
         return PreparedPoints(flat, order, inv, spts, padded, tuple(lead), dtype)
 
@@ -2067,7 +2068,7 @@ class ComposedSDF(ObjectFrameSDF):
 
     def query_packed(self, points, out=None):
         """Fused query that leaves one (val, gx, gy, gz) record per (configuration, point): (A, P, 4) fp32 for contiguous
-        fp32 (P, 3) GPU points, P a multiple of 256.  What a query sharded over GPUs gathers (one buffer instead of two,
+        fp32 (P, 3) GPU points, P a multiple of _lib.TILE_POINTS.  What a query sharded over GPUs gathers (one buffer instead of two,
         unpacked straight into the final layout: dist.ShardedSDF); same bits as __call__."""
         _require_nearest(self, "query_packed")
         if not self._fusable():
@@ -2075,8 +2076,8 @@ class ComposedSDF(ObjectFrameSDF):
         A = math.prod(self.tsf_batch) if self.tsf_batch is not None else 1
         P = points.shape[0]
         if not (points.is_cuda and points.dtype == torch.float32 and points.is_contiguous() and points.shape == (P, 3)) \
-                or P % 256 != 0 or P == 0:
-            raise ValueError("query_packed needs contiguous fp32 (P,3) points on the GPU, P a positive multiple of 256")
+                or P % _TILE_POINTS != 0 or P == 0:
+            raise ValueError(f"query_packed needs contiguous fp32 (P,3) points on the GPU, P a positive multiple of {_TILE_POINTS}")
         dev = points.device
         if dev != self._owner_device():
             raise _lib.PvamdError(f"query_packed: the leaf grids live on {self._owner_device()}; points are on {dev}")
@@ -2219,36 +2220,30 @@ class ComposedSDF(ObjectFrameSDF):
         m = self._tf_device(dev).reshape(S, A, 4, 4)
         best_v = torch.empty((A, P), dtype=torch.float32, device=dev)
         best_g = torch.empty((A, P, 3), dtype=torch.float32, device=dev)
-        slab = 65535  # the glue kernels carry the configuration in a grid dimension; the reference takes any batch
         # MeshSDF leaves want their points in a spatial order; every leaf sees a rigid image of the SAME points, so ONE spatial
         # order of the object-frame points (repeated per configuration) serves all of them instead of a sort per leaf
-        shared = None
-        if any(isinstance(s, MeshSDF) for s in self.sdfs) and getattr(self, "_rigid", True):
+        order = None
+        if any(isinstance(s, MeshSDF) for s in self.sdfs) and getattr(self, "_rigid", True) and A * P < 2 ** 31:
             with _lib.on_device(dev):
-                shared = _lib.morton_order(flat)
-        for a0 in range(0, A, slab):
-            An = min(slab, A - a0)
-            x = torch.empty((An, P, 3), dtype=torch.float32, device=dev)
-            order = None
-            if shared is not None and An * P < 2 ** 31:
-                order = shared if An == 1 else (shared.unsqueeze(0) + (torch.arange(An, device=dev, dtype=torch.int32) * P).unsqueeze(1)).reshape(-1)
-            bv, bg = best_v[a0:a0 + An], best_g[a0:a0 + An]  # contiguous row blocks of the outputs
-            for i, sdf in enumerate(self.sdfs):
-                tf_i = m[i, a0:a0 + An].contiguous()
-                with _lib.on_device(dev):
-                    _lib.check(lib.pvamd_transform_points(_lib.ptr(tf_i), An, _lib.ptr(flat), P, _lib.ptr(x), _lib.stream_ptr()),
-                               "pvamd_transform_points")
-                if order is not None and isinstance(sdf, MeshSDF):
-                    res = sdf.obj_factory.object_frame_closest_point(x, order=order)
-                    v, g = res.distance, res.gradient
-                else:
-                    v, g = sdf(x)
-                v = v.to(device=dev, dtype=torch.float32).reshape(An, P).contiguous()
-                g = g.to(device=dev, dtype=torch.float32).reshape(An, P, 3).contiguous()
-                with _lib.on_device(dev):
-                    _lib.check(lib.pvamd_compose_merge(_lib.ptr(tf_i), An, P, _lib.ptr(v), _lib.ptr(g), i, 1 if i == 0 else 0,
-                                                       _lib.ptr(bv), _lib.ptr(bg), None, _lib.stream_ptr()),
-                               "pvamd_compose_merge")
+                order = _lib.morton_order(flat)  # None for a handful of points: the leaves then sort for themselves
+            if order is not None and A > 1:
+                order = (order.unsqueeze(0) + (torch.arange(A, device=dev, dtype=torch.int32) * P).unsqueeze(1)).reshape(-1)
+        x = torch.empty((A, P, 3), dtype=torch.float32, device=dev)
+        for i, sdf in enumerate(self.sdfs):
+            with _lib.on_device(dev):
+                _lib.check(lib.pvamd_transform_points(_lib.ptr(m[i]), A, _lib.ptr(flat), P, _lib.ptr(x), _lib.stream_ptr()),
+                           "pvamd_transform_points")
+            if order is not None and isinstance(sdf, MeshSDF):
+                res = sdf.obj_factory.object_frame_closest_point(x, order=order)
+                v, g = res.distance, res.gradient
+            else:
+                v, g = sdf(x)
+            v = v.to(device=dev, dtype=torch.float32).reshape(A, P).contiguous()
+            g = g.to(device=dev, dtype=torch.float32).reshape(A, P, 3).contiguous()
+            with _lib.on_device(dev):
+                _lib.check(lib.pvamd_compose_merge(_lib.ptr(m[i]), A, P, _lib.ptr(v), _lib.ptr(g), i, 1 if i == 0 else 0,
+                                                   _lib.ptr(best_v), _lib.ptr(best_g), None, _lib.stream_ptr()),
+                           "pvamd_compose_merge")
         return best_v, best_g
 
 

@@ -2,9 +2,11 @@
 
 Two bounds split a launch in csrc.  stream_grid() (common.h) caps a streaming grid at kNumCU x kMaxBlocksPerCU = 2048 blocks, so with
 256 lanes a lane takes a second item only above H.STREAM_GRID_ITEMS = 524,288 items; and a grid's y dimension holds at most
-H.GRID_Y_MAX = 65,535 rows, so kernels that carry the configuration in y wrap (a += gridDim.y) or their host code walks slabs.
-The first test below ties the two names to the sources.  The audit: every launch that `stream_grid(`, `65535`, `gridDim.y` or
-`kMaxBlocksPerCU` finds in csrc, what its bound counts, and the test whose shape crosses it ("here" = this file, ITEMS =
+H.GRID_Y_MAX = kMaxGridRows (common.h) rows, so kernels that carry the configuration in y wrap (a += gridDim.y) under a grid of
+grid_rows() rows, or their host code walks slabs with for_row_slabs().
+The first test below ties the two names to the sources.  The audit: every launch that `stream_grid(`, `kMaxGridRows`, `grid_rows(`,
+`for_row_slabs(`, `gridDim.y` or `kMaxBlocksPerCU` finds in csrc, what its bound counts, and the test whose shape crosses it
+("here" = this file, ITEMS =
 H.STREAM_GRID_ITEMS, all other tests under tests/).  "not tested" without a reason: reachable in a few seconds (the same items in
 two halves are a reference that needs no launch past the bound), no case yet.
 
@@ -26,13 +28,16 @@ two halves are a reference that needs no launch past the bound), no case yet.
     accumulate_kernel (backward)                             P 3 > ITEMS                  the same hinge test
     mop_backward_kernel, mop scatter (min_over_points)       A Z pairs > ITEMS            not tested: unreachable in a few seconds (more than 524,288 (configuration, leaf) pairs)
     sample_surface_kernel (sample)                           samples > ITEMS              here::test_sample_surface_past_the_streaming_cap
-    transform_points_kernel, compose_merge_kernel (composed) points > ITEMS (A in y,      here::test_transform_points_past_the_streaming_cap,
-                                                             A > 65535 refused)           here::test_mesh_leaves_past_the_streaming_cap_match_the_oracle_and_two_halves
+    transform_points_kernel, compose_merge_kernel (composed) points > ITEMS               here::test_transform_points_past_the_streaming_cap,
+                                                                                          here::test_mesh_leaves_past_the_streaming_cap_match_the_oracle_and_two_halves
+                                                             A in y: for_row_slabs        here::test_transform_points_takes_more_transforms_than_grid_rows,
+                                                                                          here::test_compose_merge_takes_more_configurations_than_grid_rows,
+                                                                                          here::test_generic_leaves_under_more_configurations_than_grid_rows
     chamfer_grid_kernel (chamfer_grid)                       points > ITEMS / B per row;  test_chamfer_gpu::test_chamfer_grid_past_the_slab_and_the_streaming_cap
-                                                             host slabs of 65535 rows
-    chamfer_mesh_kernel (mesh)                               host slabs of 65535 rows     test_chamfer_gpu::test_chamfer_mesh_takes_more_transforms_than_one_grid_dimension_holds
-    mesh part kernels (mesh)                                 parts > 65535                unreachable: a mesh of more than 16.7 M triangles
-    chamfer_normal_eq kernel, reg_finish_kernel (registration) B > 65535; B 29 > ITEMS    test_registration_gpu::test_more_poses_than_one_grid_dimension_holds
+                                                             B in y: for_row_slabs
+    chamfer_mesh_kernel (mesh)                               B in y: for_row_slabs        test_chamfer_gpu::test_chamfer_mesh_takes_more_transforms_than_one_grid_dimension_holds
+    mesh part kernels (mesh)                                 parts > GRID_Y_MAX           unreachable: a mesh of more than 16.7 M triangles
+    chamfer_normal_eq kernel, reg_finish_kernel (registration) B > GRID_Y_MAX; B 29 > ITEMS  test_registration_gpu::test_more_poses_than_one_grid_dimension_holds
     lp_transform_kernel (leaf_pair)                          A K > ITEMS                  not tested
     lp_backward_kernel (leaf_pair)                           A K > ITEMS                  not tested
     lph_pair_vjp_kernel (leaf_pair)                          A K > ITEMS                  not tested
@@ -42,17 +47,17 @@ two halves are a reference that needs no launch past the bound), no case yet.
     cached_ray_cast_backward_kernel (ray_cast_backward)      rays > 2048 kRayBwdBlock     test_ray_cast_backward_gpu::test_cached_with_more_rays_than_the_backward_grid_has_lanes
     ray_reduce_rows_kernel (ray_cast_backward)               R 6 > ITEMS                  not tested
     ray_reduce_tf_kernel (ray_cast_backward)                 S A 16 > ITEMS               not tested
-    mop_partial_kernel (min_over_points)                     A > 65535                    test_min_over_points_gpu::test_more_configurations_than_grid_rows
-    hop_partial_kernel (hinge_over_points)                   A > 65535                    test_hinge_over_points_gpu::test_more_configurations_than_grid_rows
-    composed_ray_cast_kernel (ray_cast)                      A > 65535                    test_ray_cast_gpu::test_more_configurations_than_grid_rows
-    composed_interp_kernel (lane_query)                      A > 65535                    test_interp_gpu::test_composed_forward_with_more_configurations_than_grid_rows
-    composed query kernels, slabs of A (composed)            A > 65535                    test_composed_gpu::test_seventy_thousand_configurations_go_out_in_slabs,
+    mop_partial_kernel (min_over_points)                     A > GRID_Y_MAX               test_min_over_points_gpu::test_more_configurations_than_grid_rows
+    hop_partial_kernel (hinge_over_points)                   A > GRID_Y_MAX               test_hinge_over_points_gpu::test_more_configurations_than_grid_rows
+    composed_ray_cast_kernel (ray_cast)                      A > GRID_Y_MAX               test_ray_cast_gpu::test_more_configurations_than_grid_rows
+    composed_interp_kernel (lane_query)                      A > GRID_Y_MAX               test_interp_gpu::test_composed_forward_with_more_configurations_than_grid_rows
+    composed query kernels, slabs of A (composed)            A > GRID_Y_MAX               test_composed_gpu::test_seventy_thousand_configurations_go_out_in_slabs,
                                                                                           ::test_bucketed_and_packed_paths_take_more_than_65535_configurations
     composed_query_scalar, composed_query_wave (composed)    A x point blocks > 65536     not tested
     composed_query_f64_kernel (lane_query)                   A x point blocks > 65536     not tested
     composed_query_fused, grouped kernels (composed)         A x 4096-point chunks        not tested: more than 268 M (configuration, point) pairs, 4 GB of output
                                                              > 65536
-    pvamd_composed_query_packed (composed)                   tile blocks > 65535          refused (E_SHAPE): more than 67 M points in one call
+    pvamd_composed_query_packed (composed)                   tile blocks > GRID_Y_MAX     refused (E_SHAPE): more than 67 M points in one call
 """
 import ctypes
 import os
@@ -86,10 +91,14 @@ def test_the_bounds_the_tests_are_sized_by_are_the_sources_own():
     assert re.search(r"const int64_t cap = \(int64_t\)kNumCU \* kMaxBlocksPerCU;\s*\n\s*return \(unsigned\)\(need < cap", common)
     assert cus * per_cu * 256 == H.STREAM_GRID_ITEMS  # every stream_grid(n, 256) launch: one item per lane up to here
     assert H.GRID_Y_MAX == 65535
-    # the launches that clamp gridDim.y or walk slabs spell the limit out; each of these files has one
+    assert int(re.search(r"constexpr\s+int\s+kMaxGridRows\s*=\s*(\d+)\s*;", common).group(1)) == H.GRID_Y_MAX
+    # the launches that clamp gridDim.y or walk slabs take the limit from common.h, in one of its three spellings; none has its own
+    # (ray_cast.hip: the one place left is the width of the step counter, `max_steps > ...`, not a grid bound)
     for name in ("min_over_points.hip", "hinge_over_points.hip", "ray_cast.hip", "lane_query.hip", "registration.hip",
-                 "chamfer_grid.hip", "mesh.hip"):
-        assert str(H.GRID_Y_MAX) in source(name), name
+                 "chamfer_grid.hip", "mesh.hip", "composed.hip", "leaf_pair.hip"):
+        text = source(name)
+        assert re.search(r"kMaxGridRows|grid_rows\(|for_row_slabs\(", text), name
+        assert str(H.GRID_Y_MAX) not in re.sub(r"max_steps > \d+", "", text), name
     # the distance transform's z pass: kEdtWaves lines per block of the same capped grid
     edt = source("distance_transform.hip")
     waves = int(re.search(r"constexpr\s+int\s+kEdtWaves\s*=\s*(\d+)\s*;", edt).group(1))
@@ -122,6 +131,79 @@ def test_transform_points_past_the_streaming_cap(A):
                                           _lib.stream_ptr()), "pvamd_transform_points")
     want = oracle.transform_points(tf.numpy(), pts.numpy())
     assert same_bits(x.cpu().numpy(), want)
+
+
+# ---------------------------------------------------------------- GPU: the glue entry points past the grid's rows
+MANY = H.GRID_Y_MAX + 66  # the glue kernels take the configuration from blockIdx.y: rows 65535.. are the entry point's second slab
+EDGE_ROWS = (0, 1, H.GRID_Y_MAX - 1, H.GRID_Y_MAX, H.GRID_Y_MAX + 1, MANY - 1)
+MERGE_SEED = 48  # test_compose_merge_*: both leaves win among the rows of the second slab (asserted there, on the oracle's result)
+
+
+@pytest.mark.gpu
+def test_transform_points_takes_more_transforms_than_grid_rows():
+    """pvamd_transform_points at the C ABI with more transforms than a grid has rows (refused with E_SHAPE before the entry point
+    walked the slabs itself), into an output pre-filled with a value it never writes."""
+    A, P = MANY, 5
+    tf = H.random_rigid(A, seed=46, trans=0.2)
+    pts = H.uniform_points(P, [-0.5] * 3, [0.5] * 3, seed=47)
+    x = torch.full((A, P, 3), -7.0, dtype=torch.float32, device="cuda")
+    _lib.check(_lib.load().pvamd_transform_points(_lib.ptr(tf.cuda().contiguous()), A, _lib.ptr(pts.cuda().contiguous()), P, _lib.ptr(x),
+                                                  _lib.stream_ptr()), "pvamd_transform_points")
+    got, want = x.cpu().numpy(), oracle.transform_points(tf.numpy(), pts.numpy())
+    for a in EDGE_ROWS:  # either side of the slab boundary, by name
+        assert same_bits(got[a], want[a]), a
+    assert same_bits(got, want)
+
+
+@pytest.mark.gpu
+def test_compose_merge_takes_more_configurations_than_grid_rows():
+    """pvamd_compose_merge at the C ABI: two leaves folded (first = 1, then 0) with best_leaf, random values with NaNs in either
+    leaf and in both, more configurations than a grid has rows."""
+    lib = _lib.load()
+    A, P = MANY, 5
+    tf = H.random_rigid(2 * A, seed=MERGE_SEED, trans=0.2).reshape(2, A, 4, 4)
+    rng = np.random.default_rng(MERGE_SEED)
+    leaf_v = rng.standard_normal((2, A, P)).astype(np.float32)
+    leaf_g = rng.standard_normal((2, A, P, 3)).astype(np.float32)
+    leaf_v[0, [3, H.GRID_Y_MAX, MANY - 2], [0, 1, 2]] = np.nan  # NaN against a number, either way round, and against NaN
+    leaf_v[1, [4, H.GRID_Y_MAX + 1, MANY - 2], [0, 1, 2]] = np.nan
+    want_v, want_g = np.full((A, P), -7.0, np.float32), np.full((A, P, 3), -7.0, np.float32)
+    want_leaf = np.full((A, P), -7, np.int32)
+    best_v = torch.full((A, P), -7.0, dtype=torch.float32, device="cuda")
+    best_g = torch.full((A, P, 3), -7.0, dtype=torch.float32, device="cuda")
+    best_leaf = torch.full((A, P), -7, dtype=torch.int32, device="cuda")
+    for s in range(2):
+        oracle.compose_merge(tf[s].numpy(), leaf_v[s], leaf_g[s], s, want_v, want_g, want_leaf)
+        tf_s, v, g = tf[s].cuda().contiguous(), torch.from_numpy(leaf_v[s]).cuda(), torch.from_numpy(leaf_g[s]).cuda()
+        _lib.check(lib.pvamd_compose_merge(_lib.ptr(tf_s), A, P, _lib.ptr(v), _lib.ptr(g), s, 1 if s == 0 else 0, _lib.ptr(best_v),
+                                           _lib.ptr(best_g), _lib.ptr(best_leaf), _lib.stream_ptr()), "pvamd_compose_merge")
+    assert set(np.unique(want_leaf[H.GRID_Y_MAX:])) == {0, 1}  # both leaves win among the rows of the second slab
+    assert np.isnan(want_v[MANY - 2, 2]) and want_leaf[H.GRID_Y_MAX, 1] == 0 and want_leaf[H.GRID_Y_MAX + 1, 1] == 1
+    assert np.array_equal(best_leaf.cpu().numpy(), want_leaf)
+    assert same_bits(best_v.cpu().numpy(), want_v) and same_bits(best_g.cpu().numpy(), want_g)
+
+
+@pytest.mark.gpu
+def test_generic_leaves_under_more_configurations_than_grid_rows():
+    """ComposedSDF over leaves that are no cached grids (pvamd_transform_points -> the leaf -> pvamd_compose_merge) under more
+    configurations than a grid has rows, against the same stack queried as two batches that each stay below that."""
+    A, P = MANY, 3
+    tfm = H.random_rigid(2 * A, seed=49, trans=0.2).reshape(2, A, 4, 4)
+    pts = H.uniform_points(P, [-0.3] * 3, [0.3] * 3, seed=50).cuda()
+
+    def query(rows):
+        comp = pv.ComposedSDF([pv.SphereSDF(0.1), pv.SphereSDF(0.2)], None)
+        comp.set_transforms(tfm[:, rows].reshape(-1, 4, 4).cuda(), batch_dim=(tfm[:, rows].shape[1],))
+        return comp(pts)
+
+    val, grad = query(slice(None))
+    assert val.shape == (A, P) and grad.shape == (A, P, 3)
+    half = A // 2
+    assert half < H.GRID_Y_MAX and A - half < H.GRID_Y_MAX
+    (va, ga), (vb, gb) = query(slice(0, half)), query(slice(half, None))
+    assert same_bits(val.cpu().numpy(), torch.cat((va, vb)).cpu().numpy())
+    assert same_bits(grad.cpu().numpy(), torch.cat((ga, gb)).cpu().numpy())
+    assert len(np.unique(val[H.GRID_Y_MAX:].cpu().numpy())) > 100  # the configurations of the second slab do differ
 
 
 @pytest.mark.gpu

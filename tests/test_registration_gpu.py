@@ -55,10 +55,8 @@ def transformed(Wm, pts):
     """x (B, N, 3) float32 = pvamd_transform_points(W, pts) on the device."""
     B, N = Wm.shape[0], pts.shape[0]
     x = torch.empty((B, N, 3), dtype=torch.float32, device="cuda")
-    for b0 in range(0, B, 65535):
-        nb = min(65535, B - b0)
-        _lib.check(_lib.load().pvamd_transform_points(_lib.ptr(Wm[b0:b0 + nb]), nb, _lib.ptr(pts), N, _lib.ptr(x[b0:b0 + nb]),
-                                                      _lib.stream_ptr()), "pvamd_transform_points")
+    _lib.check(_lib.load().pvamd_transform_points(_lib.ptr(Wm), B, _lib.ptr(pts), N, _lib.ptr(x), _lib.stream_ptr()),
+               "pvamd_transform_points")
     return x
 
 
