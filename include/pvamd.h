@@ -952,6 +952,55 @@ int pvamd_composed_ray_cast_backward_f64(const pvamd_grid_t* grids, int32_t S, c
 int64_t pvamd_distance_transform_scratch_bytes(int32_t nx, int32_t ny, int32_t nz, int32_t is_signed);
 int pvamd_distance_transform(const uint8_t* occupied, int32_t nx, int32_t ny, int32_t nz, float resolution, int32_t is_signed,
                              float* records, int32_t* sites, int32_t* squared, void* scratch, void* stream);
+
+/* ---- Ray integration (occupancy from sensor rays) ----
+ * One pvamd_ray_mark call classifies the voxels of a lattice by one SCAN of R rays, each from an origin o (the sensor) to an
+ * endpoint e (the return), the way OctoMap's insertPointCloud does; pvamd_occupancy_update then moves a log-odds map by that
+ * classification.  Replaces nothing in the reference: its voxel.py stops at the containers, whose only producer is
+ * grid[points] = value.
+ *  1. Marks.  After a scan on zeroed marks a voxel holds PVAMD_MARK_HIT when it is the hit voxel (3.) of at least one ray,
+ *     PVAMD_MARK_FREE when it is no ray's hit voxel and the traversal (6.) of at least one ray visited it, 0 when no ray
+ *     touched it.  A hit takes precedence over any number of traversals, which also makes the result independent of the order of
+ *     the rays.  Marks of two calls accumulate: the traversal writes FREE only where the mark is 0, the hits overwrite.
+ *  2. Lattice.  grid: a finalized descriptor (vox unused, as for the voxel scatter entry points), each axis n_k in [2, 2048].
+ *     s_k(p) = (p_k - fmin_k) / fres_k in float32 (IEEE division); voxel i of axis k is the cell [i - 0.5, i + 0.5) in s.  The
+ *     traversal always uses the float32 fields, whatever index_f64 says.  EVERYTHING below is float32 with every operation
+ *     rounded on its own (no contraction, correctly rounded division and square root).
+ *  3. Hit voxel.  The voxel pvamd_voxel_scatter_* writes for the point e: the flat index of pvamd_voxel_index under the grid's
+ *     own rule and index_f64.  A ray has no hit voxel when e fails that range test, when the ray is ignored (4.) or cut (5.).
+ *  4. Ignored rays.  A ray with a non-finite coordinate in o or e marks nothing.
+ *  5. Range limit.  With v = e - o: len = sqrtf((v_x * v_x + v_y * v_y) + v_z * v_z).  When len > max_range the ray is cut: it
+ *     has no hit voxel and is traversed up to t_end = max_range / len.  Otherwise t_end = 1.  max_range = +INFINITY: no limit.
+ *  6. Traversal.  a = s(o), b = s(e), d = b - a.  Nothing is visited unless every d_k is finite.
+ *     a. Clip to the box, starting from t0 = 0, t1 = t_end.  An axis with d_k == 0: nothing is visited unless
+ *        -0.5 <= a_k < n_k - 0.5.  Any other axis: u = (-0.5 - a_k) / d_k, w = (n_k - 0.5 - a_k) / d_k,
+ *        t0 = fmaxf(t0, fminf(u, w)), t1 = fminf(t1, fmaxf(u, w)).  Nothing is visited unless t0 <= t1.
+ *     b. Start cell: c_k = (int)fminf(fmaxf(floorf((a_k + t0 * d_k) + 0.5f), 0), n_k - 1).
+ *     c. step_k = sign(d_k) (0 for d_k == 0).  tmax_k = (((float)c_k + 0.5f * step_k) - a_k) / d_k, +INFINITY when d_k == 0:
+ *        where the ray leaves cell c along axis k.  It is recomputed from the cell after every step, never accumulated.
+ *     d. At most n_x + n_y + n_z times: visit c; take the axis k with the smallest tmax_k, the lowest axis on a tie; stop unless
+ *        tmax_k < t1; c_k += step_k; stop when that leaves the grid; recompute tmax_k.
+ *     The walk moves by one cell along one axis and never turns back, so it repeats no cell.  It ends in the hit voxel of a
+ *     generic ray that ends inside the grid; where an endpoint or a crossing sits on a cell boundary it may end in a cell next
+ *     to it, which then carries FREE beside the HIT.
+ *  7. Launches: the traversal (one lane per ray; plain byte stores, every writer storing the same value), then the hits in a
+ *     launch of their own, so that the precedence rests on stream order alone and nothing is handed between workgroups inside a
+ *     kernel.  No atomics.
+ *  8. Update, one pass over the voxels, fused with clearing the marks: HIT: L = fminf(fmaxf(L + l_hit, l_min), l_max); FREE: the
+ *     same with l_miss; 0: L keeps its bits.  observed |= (mark != 0) where observed is given.  Every mark is 0 on return.
+ * Argument errors return before any launch: PVAMD_E_SHAPE for R < 0, n < 0 or an axis outside [2, 2048]; PVAMD_E_NULL;
+ * PVAMD_E_MODE for a max_range that is NaN or <= 0, a shared_origin other than 0 / 1, a NaN among l_hit, l_miss, l_min, l_max or
+ * l_min > l_max; PVAMD_E_ALIGN for log_odds not 16-byte, marks (of the update) or observed not 4-byte aligned.
+ * origins: device [1][3] when shared_origin = 1 (one eye for a whole image), else [R][3].  endpoints: device [R][3].
+ * marks: device uint8 [n_x * n_y * n_z] in C order, zero on entry where the caller wants a fresh scan.
+ * log_odds: device float32 [n].  observed: device uint8 [n] (0 / 1) or NULL.
+ * Stream-ordered, no allocation, no device -> host synchronisation: capturable in a graph, and two calls give the same bits. */
+#define PVAMD_MARK_FREE 1
+#define PVAMD_MARK_HIT  2
+int pvamd_ray_mark(const pvamd_grid_t* grid, const float* origins, int32_t shared_origin, const float* endpoints, int64_t R,
+                   float max_range, uint8_t* marks, void* stream);
+int pvamd_occupancy_update(uint8_t* marks, int64_t n, float l_hit, float l_miss, float l_min, float l_max, float* log_odds,
+                           uint8_t* observed, void* stream);
 #ifdef __cplusplus
 }
 #endif

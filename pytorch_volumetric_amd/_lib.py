@@ -239,6 +239,8 @@ RAY_MAX_STEPS = H["PVAMD_RAY_MAX_STEPS"]
 RAY_INVALID = H["PVAMD_RAY_INVALID"]
 RAY_BACKWARD_CHUNK = H["PVAMD_RAY_BACKWARD_CHUNK"]
 EDT_NO_SITE = H["PVAMD_EDT_NO_SITE"]  # DistanceTransform.squared where the site class is empty
+MARK_FREE = H["PVAMD_MARK_FREE"]  # MARK_*: a scan's classification of a voxel (pvamd_ray_mark); 0: no ray touched it
+MARK_HIT = H["PVAMD_MARK_HIT"]
 E_SHAPE = H["PVAMD_E_SHAPE"]
 _ERRORS = {H["PVAMD_E_NULL"]: "a required pointer is NULL", H["PVAMD_E_SHAPE"]: "a size/shape argument is out of range",
            H["PVAMD_E_ALIGN"]: "a pointer is misaligned", H["PVAMD_E_MODE"]: "unknown enum value"}
