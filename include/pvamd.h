@@ -1001,6 +1001,55 @@ int pvamd_ray_mark(const pvamd_grid_t* grid, const float* origins, int32_t share
                    float max_range, uint8_t* marks, void* stream);
 int pvamd_occupancy_update(uint8_t* marks, int64_t n, float l_hit, float l_miss, float l_min, float l_max, float* log_odds,
                            uint8_t* observed, void* stream);
+
+/* ---- TSDF integration (truncated signed distance volumes from depth images) ----
+ * pvamd_tsdf_integrate averages K depth images into a truncated signed distance volume, the integration step of Curless & Levoy
+ * and KinectFusion, in ONE pass over the volume: a voxel's state is read once, taken through the K frames in order in registers
+ * and written once.  pvamd_tsdf_records turns the state into the packed (val, gx, gy, gz) records of a cached voxel grid
+ * (pvamd_grid_t.vox).  Replaces nothing in the reference: its voxel.py stops at the containers.
+ * EVERYTHING below is float32 with every operation rounded on its own (no contraction, correctly rounded division and square
+ * root).
+ *  1. State.  state: device [n][2] float32, (F, W) per voxel in C order (x slowest, z fastest): the running average of the
+ *     truncated signed distance in units of the truncation, F in [-1, 1], and its weight.  A fresh volume is all +0.0.  The state
+ *     of a voxel is read once before the first frame and written once after the last, and only if some frame updated the voxel:
+ *     an untouched voxel keeps its bits, -0.0 included.  One call over K frames gives, bit for bit, what K calls of one frame
+ *     each give in that order.
+ *  2. Lattice.  grid: a finalized descriptor (vox unused), each axis n_j in [2, 2048].  The centre of voxel i = (x, y, z) is
+ *     c_j = fmin_j + (float)i_j * fres_j: always the descriptor's float32 fields, as in "Ray integration" 2.
+ *  Per voxel, for frame k = 0 .. K-1 in order, with T = camera_from_volume[k] (the camera looks along +z, x right, y down):
+ *  3. p_r = ((T[r][0] * c_x + T[r][1] * c_y) + T[r][2] * c_z) + T[r][3] for r = 0, 1, 2.  The frame is skipped unless p_z > 0.
+ *  4. u = fx * (p_x / p_z) + cx, v = fy * (p_y / p_z) + cy.  Pixel (row, col) covers [col - 0.5, col + 0.5) in u.  Skipped unless
+ *     -0.5 <= u < (float)W - 0.5 and -0.5 <= v < (float)H - 0.5: tested in float before any conversion, and NaN fails it.
+ *  5. col = (int)floorf(u + 0.5f), row = (int)floorf(v + 0.5f), each clamped into [0, W - 1] / [0, H - 1] after the conversion
+ *     (the rounded sum can reach W).
+ *  6. d = depth[(k * H + row) * W + col]: z-depth along the optical axis, not range.  Skipped unless d > 0, d is finite and
+ *     d <= max_depth (zero, negative, NaN and infinite depths mean "no return"; max_depth = +INFINITY: no limit).
+ *  7. sdf = d - p_z.  Skipped unless sdf >= -truncation: a voxel further than the band behind the surface is unobserved.
+ *  8. f = fminf(sdf / truncation, 1.0f): free space in front of a surface is evidence too.
+ *  9. With (Fo, Wo) the voxel's state: Wn = Wo + weight, F = ((Wo * Fo) + (weight * f)) / Wn, W = fminf(Wn, max_weight).
+ *  Records, per voxel i (pvamd_tsdf_records):
+ * 10. Known iff W > min_weight.  t = known ? F : unknown_tsdf (+1: unknown space is free, -1: occupied), val = truncation * t.
+ * 11. Per axis j: lo = max(i_j - 1, 0), hi = min(i_j + 1, n_j - 1), g_j = (val(hi) - val(lo)) / ((float)(hi - lo) * resolution),
+ *     val of the neighbours by the same substitution (one-sided at the border).
+ * 12. len = sqrtf((g_x * g_x + g_y * g_y) + g_z * g_z).  The record is (val, g_x / len, g_y / len, g_z / len) when len > 0, else
+ *     (val, 0, 0, 0).  The gradients have unit length, as the mesh and distance-transform records have: consumers use them as
+ *     the surface normal.  Saturated regions, |t| = 1 all round, get zero gradients.  The field is TRUNCATED: |val| never exceeds
+ *     the truncation, which suits sphere tracing, hinge margins up to the truncation and registration, and is wrong for anyone
+ *     who reads far-field distances.
+ * Argument errors return before any launch: PVAMD_E_SHAPE for K < 0, H or W < 1, K * H * W >= 2^31, an axis outside [2, 2048] or
+ * more than 2^31 - 1 voxels; PVAMD_E_NULL; PVAMD_E_MODE for non-finite intrinsics, fx or fy <= 0, a truncation, weight or
+ * resolution that is non-finite or <= 0, a max_weight or max_depth that is NaN or <= 0 (+INFINITY is allowed), a NaN min_weight,
+ * an unknown_tsdf other than +1 / -1; PVAMD_E_ALIGN for state not 8-byte, records not 16-byte aligned.  K = 0 returns 0 without
+ * a launch.
+ * depth: device [K][H][W] float32.  camera_from_volume: device [K][3][4] float32, the rigid inverse of the camera's pose in the
+ * volume's frame.  records: device [n][4] float32.
+ * One launch each.  Stream-ordered, no allocation, no device -> host synchronisation, no atomics: capturable in a graph, and two
+ * calls give the same bits.                                                                                                    */
+int pvamd_tsdf_integrate(const pvamd_grid_t* grid, const float* depth, int32_t K, int32_t H, int32_t W,
+                         const float* camera_from_volume, float fx, float fy, float cx, float cy, float truncation,
+                         float max_depth, float weight, float max_weight, float* state, void* stream);
+int pvamd_tsdf_records(const float* state, int32_t nx, int32_t ny, int32_t nz, float resolution, float truncation,
+                       float min_weight, float unknown_tsdf, float* records, void* stream);
 #ifdef __cplusplus
 }
 #endif

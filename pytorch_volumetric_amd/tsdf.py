@@ -1,0 +1,229 @@
+"""TSDF fusion of depth images: a truncated signed distance volume over a VoxelGrid's lattice that every depth frame is averaged
+into, in the manner of Curless & Levoy and KinectFusion (include/pvamd.h "TSDF integration", csrc/tsdf.hip).
+
+The reference has no counterpart: its voxel.py stops at the containers.  OccupancyMap -> distance_transform puts the surface on
+voxel faces; a TSDFVolume keeps it between the voxels, where the depth images saw it, and hands it to the same consumers:
+ray_cast renders the model depth, refine_poses tracks against it, and integrate() is the step between them.
+"""
+import ctypes
+import math
+import numbers
+
+import torch
+
+from pytorch_volumetric_amd import _lib
+from pytorch_volumetric_amd.occupancy import OccupancySDF
+from pytorch_volumetric_amd.occupancy_map import MAX_AXIS, MIN_AXIS, _check_unknown
+from pytorch_volumetric_amd.sdf import CachedSDF
+from pytorch_volumetric_amd.voxel import RangeView, get_divisible_range_by_resolution
+from pytorch_volumetric_amd.voxel_containers import VoxelGrid
+
+MAX_PIXELS = 2 ** 31  # include/pvamd.h "TSDF integration": K * H * W below this
+
+
+def _positive_finite(name, value):
+    value = float(value)
+    if not (math.isfinite(value) and value > 0):
+        raise ValueError(f"{name} must be finite and positive, got {value}")
+    return value
+
+
+def _positive(name, value):
+    """Positive, +inf allowed (no limit), NaN refused."""
+    value = float(value)
+    if not value > 0:
+        raise ValueError(f"{name} must be positive (inf: no limit), got {value}")
+    return value
+
+
+def _check_min_weight(min_weight):
+    if isinstance(min_weight, bool) or not isinstance(min_weight, numbers.Real):
+        raise TypeError(f"min_weight must be a real number, got {type(min_weight).__name__}")
+    min_weight = float(min_weight)
+    if math.isnan(min_weight):
+        raise ValueError("min_weight must not be NaN")
+    return min_weight
+
+
+def _check_intrinsics(intrinsics):
+    """(fx, fy, cx, cy) as Python floats from four reals or a 3 x 3 matrix (read on the host)."""
+    if torch.is_tensor(intrinsics):
+        intrinsics = intrinsics.detach().cpu().tolist()
+    elif hasattr(intrinsics, "tolist"):
+        intrinsics = intrinsics.tolist()
+    intrinsics = list(intrinsics)
+    if len(intrinsics) == 4 and all(isinstance(v, numbers.Real) for v in intrinsics):
+        fx, fy, cx, cy = (float(v) for v in intrinsics)
+    elif len(intrinsics) == 3 and all(hasattr(row, "__len__") and len(row) == 3 for row in intrinsics):
+        fx, fy, cx, cy = float(intrinsics[0][0]), float(intrinsics[1][1]), float(intrinsics[0][2]), float(intrinsics[1][2])
+    else:
+        raise ValueError("intrinsics must be (fx, fy, cx, cy) or a 3 x 3 matrix")
+    if not all(math.isfinite(v) for v in (fx, fy, cx, cy)) or fx <= 0 or fy <= 0:
+        raise ValueError(f"intrinsics must be finite with fx, fy > 0, got fx={fx} fy={fy} cx={cx} cy={cy}")
+    return fx, fy, cx, cy
+
+
+def camera_from_volume(camera_pose):
+    """(K, 3, 4) float32 on the pose's own device: the rigid inverse (R^T, -R^T t) of (K, 4, 4) or (4, 4) camera poses, worked out
+    in float64 and rounded once.  Elementwise products and sums in a fixed order, so every device gives the same bits.  A pose
+    that is not rigid is the caller's problem: nothing here looks at the values."""
+    pose = camera_pose if torch.is_tensor(camera_pose) else torch.as_tensor(camera_pose)
+    pose = pose.detach().to(torch.float64).reshape(-1, 4, 4)
+    Rt = pose[:, :3, :3].transpose(1, 2)
+    t = pose[:, :3, 3]
+    back = -((Rt[:, :, 0] * t[:, None, 0] + Rt[:, :, 1] * t[:, None, 1]) + Rt[:, :, 2] * t[:, None, 2])
+    return torch.cat((Rt, back[:, :, None]), dim=2).to(torch.float32).contiguous()
+
+
+def _check_frames(depth, intrinsics, camera_pose, max_depth, weight, depth_scale):
+    """The argument errors of integrate, raised before a GPU is asked for."""
+    depth = depth if torch.is_tensor(depth) else torch.as_tensor(depth)
+    pose = camera_pose if torch.is_tensor(camera_pose) else torch.as_tensor(camera_pose)
+    if depth.is_complex():
+        raise TypeError(f"depth must have a real dtype, got {depth.dtype}")
+    if depth.dim() not in (2, 3):
+        raise ValueError(f"depth must be (H, W) or (K, H, W), got {tuple(depth.shape)}")
+    if pose.dim() not in (2, 3) or tuple(pose.shape[-2:]) != (4, 4):
+        raise ValueError(f"camera_pose must be (4, 4) or (K, 4, 4), got {tuple(pose.shape)}")
+    K = 1 if depth.dim() == 2 else depth.shape[0]
+    if (1 if pose.dim() == 2 else pose.shape[0]) != K:
+        raise ValueError(f"depth holds {K} frame(s) and camera_pose {1 if pose.dim() == 2 else pose.shape[0]}: one pose per frame")
+    H, W = depth.shape[-2:]
+    if K and (H < 1 or W < 1):
+        raise ValueError(f"depth images need at least one pixel, got {tuple(depth.shape)}")
+    if K * H * W >= MAX_PIXELS:
+        raise ValueError(f"one call takes fewer than 2^31 pixels, got {tuple(depth.shape)}")
+    fx, fy, cx, cy = _check_intrinsics(intrinsics)
+    return (depth, pose, K, H, W, (fx, fy, cx, cy), _positive("max_depth", max_depth), _positive_finite("weight", weight),
+            float(depth_scale))
+
+
+class TSDFVolume:
+    """A truncated signed distance volume over the lattice of a float32 VoxelGrid(resolution, range_per_dim).
+
+    integrate() averages depth frames into it: per voxel the running mean of min(1, (depth - z) / truncation) over the frames that
+    saw the voxel in front of, or less than the truncation behind, a surface.  The state is one (nx, ny, nz, 2) tensor of
+    (tsdf, weight) pairs; everything stays on the GPU and nothing carries an autograd graph.
+    """
+
+    def __init__(self, resolution, range_per_dim, truncation, device="cuda", max_weight=64.):
+        """
+        :param resolution: side length of a voxel
+        :param range_per_dim: three (low, high) pairs, snapped to whole voxels like a VoxelGrid's
+        :param truncation: the width of the band either side of a surface in which distances are kept, in world units; a few
+            voxels.  Voxels further behind a surface than this are not updated by that frame.
+        :param max_weight: where a voxel's weight stops growing: what bounds how long the volume takes to follow a scene that
+            changed.  inf: a plain mean over every frame.
+        """
+        resolution = _positive_finite("resolution", resolution)
+        if len(range_per_dim) != 3:
+            raise ValueError(f"a TSDFVolume is 3-D: range_per_dim needs three (low, high) pairs, got {len(range_per_dim)}")
+        cells = [round((high - low) / resolution) + 1 for low, high in get_divisible_range_by_resolution(resolution, range_per_dim)]
+        if min(cells) < MIN_AXIS or max(cells) > MAX_AXIS:
+            raise ValueError(f"every axis of a TSDFVolume must have {MIN_AXIS} to {MAX_AXIS} voxels, got {tuple(cells)}")
+        self.truncation = _positive_finite("truncation", truncation)
+        self.max_weight = _positive("max_weight", max_weight)
+        self.resolution, self.range_per_dim = resolution, range_per_dim
+        self.device = torch.device(device)
+        if self.device.type == "cuda":
+            _lib.require_gpu()
+        # the lattice: a VoxelGrid's descriptor.  On the meta device the grid has a shape and no storage; the state below is the volume
+        self._grid = VoxelGrid(resolution, range_per_dim, dtype=torch.float32, device="meta")
+        shape = tuple(self._grid.get_voxel_values().shape)
+        if min(shape) < MIN_AXIS or max(shape) > MAX_AXIS:
+            raise ValueError(f"every axis of a TSDFVolume must have {MIN_AXIS} to {MAX_AXIS} voxels, got {shape}")
+        self._state = torch.zeros(shape + (2,), dtype=torch.float32, device=self.device)
+
+    @property
+    def tsdf(self):
+        """(nx, ny, nz) float32 view of the state: the averaged distance in units of the truncation, in [-1, 1]."""
+        return self._state[..., 0]
+
+    @property
+    def weight(self):
+        """(nx, ny, nz) float32 view of the state: the accumulated weight, 0 where no frame reached."""
+        return self._state[..., 1]
+
+    @property
+    def shape(self):
+        return tuple(self._state.shape[:3])
+
+    def reset(self):
+        """Forget every frame."""
+        self._state.zero_()
+
+    def integrate(self, depth, intrinsics, camera_pose, max_depth=math.inf, weight=1.0, depth_scale=1.0):
+        """Average K depth frames into the volume, in order, in one pass over it: bit for bit what K calls of one frame give.
+
+        :param depth: (H, W) or (K, H, W), any real dtype: z-depth along the optical axis (not range), times `depth_scale` in
+            world units.  Zero, negative, NaN and infinite depths mean "no return".
+        :param intrinsics: (fx, fy, cx, cy) or a 3 x 3 matrix, for every frame of the call; pixel (row, col) is centred on
+            (u, v) = (col, row)
+        :param camera_pose: (4, 4) or (K, 4, 4): the camera's pose in the volume's frame (volume_from_camera); the camera looks
+            along +z, x right, y down.  Inverted rigidly on its own device: poses on the GPU never visit the host.
+        :param max_depth: returns further than this are ignored
+        :param weight: what one frame adds to a voxel's weight
+        No frames: a no-op.  One launch; nothing comes back to the host."""
+        depth, pose, K, H, W, (fx, fy, cx, cy), max_depth, weight, depth_scale = _check_frames(
+            depth, intrinsics, camera_pose, max_depth, weight, depth_scale)
+        if K == 0:
+            return
+        if self.device.type != "cuda":
+            raise _lib.PvamdError(f"TSDF integration runs on the GPU and this volume lives on {self.device}; there is no CPU fallback")
+        depth = depth.detach().to(device=self.device).to(torch.float32)
+        if depth_scale != 1.0:
+            depth = depth * depth_scale
+        depth = depth.contiguous()
+        inverse = camera_from_volume(pose).to(device=self.device)
+        with _lib.on_device(self.device):
+            _lib.check(_lib.load().pvamd_tsdf_integrate(ctypes.byref(self._grid.voxels._grid_desc()), _lib.ptr(depth), K, H, W,
+                                                        _lib.ptr(inverse), fx, fy, cx, cy, self.truncation, max_depth, weight,
+                                                        self.max_weight, _lib.ptr(self._state), _lib.stream_ptr()),
+                       "pvamd_tsdf_integrate")
+
+    def to_sdf(self, name, unknown="free", min_weight=0.0, interpolation="nearest"):
+        """A CachedSDF over the volume's lattice whose records are TSDFField(self, unknown, min_weight)'s, taken as they are and not
+        written to a cache file: a snapshot that can be ray-cast, composed with a robot or used for pose refinement like any mesh
+        cache.  Its values are truncated: never further from zero than the truncation."""
+        field = TSDFField(self, unknown=unknown, min_weight=min_weight)
+        return CachedSDF(name, field.resolution, field.ranges, field, device=self.device, cache_path=None, interpolation=interpolation)
+
+
+class TSDFField(OccupancySDF):
+    """The truncated signed distance field of a TSDFVolume as an ObjectFrameSDF: value truncation * tsdf and a unit gradient by
+    central differences per voxel (include/pvamd.h "TSDF integration" 10-12), worked out once at construction, then answered like a
+    nearest-mode BOUNDING_BOX CachedSDF over the volume's lattice (OccupancySDF's descriptor and kernels).  A snapshot: later
+    frames do not reach it.  A CachedSDF over the same lattice takes its records as they are."""
+
+    def __init__(self, volume, unknown="free", min_weight=0.0):
+        """
+        :param volume: a TSDFVolume
+        :param unknown: what a voxel whose weight is not above `min_weight` counts as: "free" (value +truncation) or "occupied"
+            (-truncation, what a planner that must not enter unseen space wants)
+        :param min_weight: a voxel is known when its weight exceeds this
+        """
+        _check_unknown(unknown)
+        min_weight = _check_min_weight(min_weight)
+        if volume.device.type != "cuda":
+            raise _lib.PvamdError(f"a TSDFField is worked out on the GPU and this volume lives on {volume.device}; there is no CPU fallback")
+        grid = volume._grid
+        self.signed = True
+        self.unknown, self.min_weight, self.truncation = unknown, min_weight, volume.truncation
+        self.resolution = grid.resolution
+        self.ranges = list(grid.voxels._ranges)
+        nx, ny, nz = volume.shape
+        self._view = RangeView(self.ranges, volume.shape, rule=grid.voxels._rule)
+        self._records = torch.empty((nx * ny * nz, 4), dtype=torch.float32, device=volume.device)
+        self._sites = self._squared = None
+        with _lib.on_device(volume.device):
+            _lib.check(_lib.load().pvamd_tsdf_records(_lib.ptr(volume._state), nx, ny, nz, volume.resolution, volume.truncation,
+                                                      min_weight, 1.0 if unknown == "free" else -1.0, _lib.ptr(self._records),
+                                                      _lib.stream_ptr()), "pvamd_tsdf_records")
+        # the one synchronisation: which index box the voxels at or inside the surface fill
+        index = (self._records[:, 0].reshape(volume.shape) <= 0).nonzero()
+        if index.shape[0] == 0:
+            raise ValueError("TSDFField: no voxel of the volume is at or inside a surface (value <= 0)")
+        lo, hi = index.amin(dim=0).cpu().double(), index.amax(dim=0).cpu().double()
+        half = self._view.dres / 2
+        self._box = torch.stack((self._view.dmin + lo * self._view.dres - half, self._view.dmin + hi * self._view.dres + half), dim=1)
+        self._desc = None
