@@ -1035,7 +1035,7 @@ int pvamd_occupancy_update(uint8_t* marks, int64_t n, float l_hit, float l_miss,
  *     (val, 0, 0, 0).  The gradients have unit length, as the mesh and distance-transform records have: consumers use them as
  *     the surface normal.  Saturated regions, |t| = 1 all round, get zero gradients.  The field is TRUNCATED: |val| never exceeds
  *     the truncation, which suits sphere tracing, hinge margins up to the truncation and registration, and is wrong for anyone
- *     who reads far-field distances.
+ *     who reads far-field distances ("Redistancing" below completes it).
  * Argument errors return before any launch: PVAMD_E_SHAPE for K < 0, H or W < 1, K * H * W >= 2^31, an axis outside [2, 2048] or
  * more than 2^31 - 1 voxels; PVAMD_E_NULL; PVAMD_E_MODE for non-finite intrinsics, fx or fy <= 0, a truncation, weight or
  * resolution that is non-finite or <= 0, a max_weight or max_depth that is NaN or <= 0 (+INFINITY is allowed), a NaN min_weight,
@@ -1050,6 +1050,51 @@ int pvamd_tsdf_integrate(const pvamd_grid_t* grid, const float* depth, int32_t K
                          float max_depth, float weight, float max_weight, float* state, void* stream);
 int pvamd_tsdf_records(const float* state, int32_t nx, int32_t ny, int32_t nz, float resolution, float truncation,
                        float min_weight, float unknown_tsdf, float* records, void* stream);
+
+/* ---- Redistancing (full Euclidean distance fields from sampled signed fields) ----
+ * pvamd_redistance measures, from every voxel, the Euclidean distance to the zero set of a signed field sampled on the lattice,
+ * the zero set taken at sub-voxel precision where the samples change sign along the lattice edges: "ESDF from TSDF".  With
+ * band = truncation it completes the records of pvamd_tsdf_records: the band round the surface is kept bit for bit, everything
+ * else becomes a distance with a unit gradient.  Replaces nothing in the reference.
+ * EVERYTHING below is float32 with every operation rounded on its own (no contraction, no fma, correctly rounded division and
+ * square root).  Coordinates are in voxels until statement 7.
+ *  1. Input.  records_in: device [n][4] float32 packed (val, gx, gy, gz) in C order (x slowest, z fastest), n = nx * ny * nz.
+ *     V_i is the val of voxel i.  Only kept voxels (6.) read the gradients.
+ *  2. Crossings.  For axis k and a voxel a with a_k < n_k - 1, b = a + e_k: the lattice edge (a, b) carries a crossing iff V_a and
+ *     V_b are both finite and (V_a < 0) != (V_b < 0).  It lies at a_k + f along k, f = V_a / (V_a - V_b) in [0, 1], and at a's
+ *     integers on the other two axes.  Its family is k.  A NaN or infinite sample gives its edges no crossing.
+ *  3. Cost of a crossing of family k to voxel i.  t = (float)(i_k - a_k) - f.  With p2 > p3 the remaining axes, highest index
+ *     first (x: (z, y); y: (z, x); z: (y, x)) and d_j = i_j - a_j exact in int:
+ *         c1 = t * t,  c2 = c1 + (float)(d_p2 * d_p2),  c3 = c2 + (float)(d_p3 * d_p3).
+ *     Rounding is monotone, so nested line minima give the minimum of c3 over all crossings, and a candidate at offset d along
+ *     the line of a pass costs at least (float)(d * d).
+ *  4. Site.  Defined by the nesting.  Pass 1, along k: per voxel, the crossing on the voxel's own line with the smallest c1, the
+ *     smaller a_k on a tie.  Pass 2, along p2: among the pass-1 results of the voxels of the line, the smallest c2, the smaller
+ *     coordinate along p2 on a tie.  Pass 3, along p3, likewise with c3.  Across the families the smallest c3 wins, the lowest k
+ *     on a tie.  sites[i] = ((a_x * ny + a_y) * nz + a_z) * 4 + k, squared[i] = c3.
+ *  5. Range.  Rv = max_distance / resolution, R2 = Rv * Rv; max_distance = +INFINITY: no limit.  A candidate whose cost exceeds
+ *     R2 at any stage may be dropped: it cannot change a result that 5. does not overwrite.  A voxel without a site, or whose
+ *     c3 > R2, gets sites = -1, squared = +INFINITY, val = max_distance (-max_distance when V_i < 0) and a zero gradient.
+ *  6. Kept voxels.  fabsf(V_i) < band: the output record is the input record bit for bit, sites = PVAMD_REDIST_KEPT, squared =
+ *     +INFINITY.  band = 0 keeps nothing; a NaN V_i is never kept and counts as not negative.
+ *  7. Every other voxel, len = sqrtf(c3): val = resolution * len, negated when V_i < 0.  Gradient: t / len on the site's axis,
+ *     (float)d_j / len on the other two, all three negated when V_i < 0, zeros when c3 == 0.
+ *  8. Three line passes per family, each an outward scan that stops once (float)(d * d) exceeds min(best, R2): in space without
+ *     crossings a scan runs to both ends of its line, and max_distance is what bounds that.  The time grows with the distances
+ *     in the grid, as the distance transform's does.
+ * Argument errors return before any launch, tested in this order: PVAMD_E_SHAPE for an axis outside [2, 2048] or n > 2^29 (the
+ * site code is an int32); PVAMD_E_MODE for a resolution that is non-finite or <= 0, a band that is NaN or < 0, a max_distance that
+ * is NaN or <= 0; PVAMD_E_NULL (sites and squared may be NULL: not wanted); PVAMD_E_ALIGN for records not 16-byte, scratch, sites or
+ * squared not 4-byte aligned.
+ * records_in is never written and must not overlap records_out: device [n][4] float32.  sites: device [n] int32.  squared: device
+ * [n] float32.  scratch: device, pvamd_redistance_scratch_bytes(nx, ny, nz) bytes, 4-byte aligned; that function is the
+ * definition (0 for shapes the entry point refuses) and there is no macro.  Contents on return are unspecified.
+ * Stream-ordered, no allocation, no device -> host synchronisation, no atomics: capturable in a graph, and two calls give the
+ * same bits.                                                                                                                    */
+#define PVAMD_REDIST_KEPT (-2) /* sites[i] of a voxel inside the band */
+int64_t pvamd_redistance_scratch_bytes(int32_t nx, int32_t ny, int32_t nz);
+int pvamd_redistance(const float* records_in, int32_t nx, int32_t ny, int32_t nz, float resolution, float band, float max_distance,
+                     float* records_out, int32_t* sites, float* squared, void* scratch, void* stream);
 #ifdef __cplusplus
 }
 #endif

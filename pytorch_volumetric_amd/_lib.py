@@ -105,6 +105,12 @@ def distance_transform_scratch_bytes(nx, ny, nz, signed):
 
 
 @_remembered
+def redistance_scratch_bytes(nx, ny, nz):
+    """pvamd_redistance_scratch_bytes: the sample column, then one 8-byte state per voxel for pass 1 and for pass 2 of each family."""
+    return load().pvamd_redistance_scratch_bytes(nx, ny, nz)
+
+
+@_remembered
 def composed_query_kernel(A, P, flags):
     """pvamd_composed_query_kernel: the kernel (CO_KERNEL_*) pvamd_composed_query launches for A configurations of P points."""
     return load().pvamd_composed_query_kernel(A, P, flags)
@@ -239,6 +245,7 @@ RAY_MAX_STEPS = H["PVAMD_RAY_MAX_STEPS"]
 RAY_INVALID = H["PVAMD_RAY_INVALID"]
 RAY_BACKWARD_CHUNK = H["PVAMD_RAY_BACKWARD_CHUNK"]
 EDT_NO_SITE = H["PVAMD_EDT_NO_SITE"]  # DistanceTransform.squared where the site class is empty
+REDIST_KEPT = H["PVAMD_REDIST_KEPT"]  # Redistance.sites of a voxel inside the band
 MARK_FREE = H["PVAMD_MARK_FREE"]  # MARK_*: a scan's classification of a voxel (pvamd_ray_mark); 0: no ray touched it
 MARK_HIT = H["PVAMD_MARK_HIT"]
 E_SHAPE = H["PVAMD_E_SHAPE"]

@@ -14,6 +14,7 @@ import torch
 from pytorch_volumetric_amd import _lib
 from pytorch_volumetric_amd.occupancy import OccupancySDF
 from pytorch_volumetric_amd.occupancy_map import MAX_AXIS, MIN_AXIS, _check_unknown
+from pytorch_volumetric_amd.redistance import _check_range, _redistance_records
 from pytorch_volumetric_amd.sdf import CachedSDF
 from pytorch_volumetric_amd.voxel import RangeView, get_divisible_range_by_resolution
 from pytorch_volumetric_amd.voxel_containers import VoxelGrid
@@ -43,6 +44,16 @@ def _check_min_weight(min_weight):
     if math.isnan(min_weight):
         raise ValueError("min_weight must not be NaN")
     return min_weight
+
+
+def _check_far_field(far_field, max_distance):
+    """max_distance as a float; it means something only with far_field=True."""
+    if type(far_field) is not bool:
+        raise TypeError(f"far_field must be a bool, got {type(far_field).__name__}")
+    _, max_distance = _check_range(0.0, max_distance)
+    if not far_field and max_distance != math.inf:
+        raise ValueError("max_distance limits the far field: it needs far_field=True")
+    return max_distance
 
 
 def _check_intrinsics(intrinsics):
@@ -181,11 +192,12 @@ class TSDFVolume:
                                                         self.max_weight, _lib.ptr(self._state), _lib.stream_ptr()),
                        "pvamd_tsdf_integrate")
 
-    def to_sdf(self, name, unknown="free", min_weight=0.0, interpolation="nearest"):
-        """A CachedSDF over the volume's lattice whose records are TSDFField(self, unknown, min_weight)'s, taken as they are and not
-        written to a cache file: a snapshot that can be ray-cast, composed with a robot or used for pose refinement like any mesh
-        cache.  Its values are truncated: never further from zero than the truncation."""
-        field = TSDFField(self, unknown=unknown, min_weight=min_weight)
+    def to_sdf(self, name, unknown="free", min_weight=0.0, interpolation="nearest", far_field=False, max_distance=math.inf):
+        """A CachedSDF over the volume's lattice whose records are TSDFField(self, unknown, min_weight, far_field, max_distance)'s,
+        taken as they are and not written to a cache file: a snapshot that can be ray-cast, composed with a robot or used for pose
+        refinement like any mesh cache.  Without far_field=True its values are truncated: never further from zero than the
+        truncation, with a zero gradient beyond it."""
+        field = TSDFField(self, unknown=unknown, min_weight=min_weight, far_field=far_field, max_distance=max_distance)
         return CachedSDF(name, field.resolution, field.ranges, field, device=self.device, cache_path=None, interpolation=interpolation)
 
 
@@ -193,22 +205,33 @@ class TSDFField(OccupancySDF):
     """The truncated signed distance field of a TSDFVolume as an ObjectFrameSDF: value truncation * tsdf and a unit gradient by
     central differences per voxel (include/pvamd.h "TSDF integration" 10-12), worked out once at construction, then answered like a
     nearest-mode BOUNDING_BOX CachedSDF over the volume's lattice (OccupancySDF's descriptor and kernels).  A snapshot: later
-    frames do not reach it.  A CachedSDF over the same lattice takes its records as they are."""
+    frames do not reach it.  A CachedSDF over the same lattice takes its records as they are.
 
-    def __init__(self, volume, unknown="free", min_weight=0.0):
+    far_field=True redistances those records (include/pvamd.h "Redistancing", band = truncation): a voxel whose |value| is below
+    the truncation keeps its record bit for bit, every other voxel -- unknown space under either rule included -- gets the
+    Euclidean distance to the nearest zero crossing of the values along a lattice edge, with the sign it had and a unit gradient.
+    The two meet at |value| = truncation with a step, up to about a voxel where the surface was seen obliquely: projective
+    distances inside, Euclidean outside (profiles/redistance.md)."""
+
+    def __init__(self, volume, unknown="free", min_weight=0.0, far_field=False, max_distance=math.inf):
         """
         :param volume: a TSDFVolume
         :param unknown: what a voxel whose weight is not above `min_weight` counts as: "free" (value +truncation) or "occupied"
             (-truncation, what a planner that must not enter unseen space wants)
         :param min_weight: a voxel is known when its weight exceeds this
+        :param far_field: False: the truncated field.  True: Euclidean distances beyond the truncation
+        :param max_distance: with far_field=True: voxels further than this from the surface read +/-max_distance with a zero
+            gradient, which also bounds the work in empty space (inf: no limit)
         """
         _check_unknown(unknown)
         min_weight = _check_min_weight(min_weight)
+        max_distance = _check_far_field(far_field, max_distance)
         if volume.device.type != "cuda":
             raise _lib.PvamdError(f"a TSDFField is worked out on the GPU and this volume lives on {volume.device}; there is no CPU fallback")
         grid = volume._grid
         self.signed = True
         self.unknown, self.min_weight, self.truncation = unknown, min_weight, volume.truncation
+        self.far_field, self.max_distance = far_field, max_distance
         self.resolution = grid.resolution
         self.ranges = list(grid.voxels._ranges)
         nx, ny, nz = volume.shape
@@ -219,6 +242,8 @@ class TSDFField(OccupancySDF):
             _lib.check(_lib.load().pvamd_tsdf_records(_lib.ptr(volume._state), nx, ny, nz, volume.resolution, volume.truncation,
                                                       min_weight, 1.0 if unknown == "free" else -1.0, _lib.ptr(self._records),
                                                       _lib.stream_ptr()), "pvamd_tsdf_records")
+        if far_field:
+            self._records, _, _ = _redistance_records(self._records, volume.shape, volume.resolution, volume.truncation, max_distance)
         # the one synchronisation: which index box the voxels at or inside the surface fill
         index = (self._records[:, 0].reshape(volume.shape) <= 0).nonzero()
         if index.shape[0] == 0:

@@ -1,0 +1,119 @@
+"""Restatement of the redistancing contract (include/pvamd.h "Redistancing") for its tests -- TEST INFRASTRUCTURE:
+redistance_ref.c compiled on the fly (the nested separable form, which is the definition, and a brute force over every
+crossing), and the fields the CPU and GPU tests share."""
+import ctypes
+import functools
+import os
+import subprocess
+import tempfile
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+KEPT = -2
+_lib = None
+
+
+def load():
+    global _lib
+    if _lib is None:
+        out = os.path.join(tempfile.mkdtemp(prefix="redistance_ref_"), "redistance_ref.so")
+        subprocess.run(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", os.path.join(HERE, "redistance_ref.c"), "-o", out,
+                        "-lm"], check=True)
+        _lib = ctypes.CDLL(out)
+        _lib.redistance_ref.restype = ctypes.c_int64
+    return _lib
+
+
+def _p(a):
+    return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def as_records(values, gradients=None):
+    """(nx, ny, nz, 4) float32 records from values and optional (nx, ny, nz, 3) gradients (zeros without)."""
+    values = np.asarray(values, np.float32)
+    rec = np.zeros(values.shape + (4,), np.float32)
+    rec[..., 0] = values
+    if gradients is not None:
+        rec[..., 1:] = gradients
+    return rec
+
+
+def redistance(records, resolution=1.0, band=0.0, max_distance=np.inf):
+    """(records (n, 4) float32, sites (n,) int32, squared (n,) float32) of (nx, ny, nz, 4) float32 records: the nested form."""
+    assert records.dtype == np.float32 and records.flags.c_contiguous and records.ndim == 4 and records.shape[3] == 4
+    nx, ny, nz = records.shape[:3]
+    n = nx * ny * nz
+    out = np.empty((n, 4), np.float32)
+    sites = np.empty((n,), np.int32)
+    squared = np.empty((n,), np.float32)
+    f = ctypes.c_float
+    differ = load().redistance_ref(_p(records), ctypes.c_int32(nx), ctypes.c_int32(ny), ctypes.c_int32(nz), f(resolution), f(band),
+                                   f(max_distance), _p(out), _p(sites), _p(squared))
+    assert differ == 0, f"the nested cost differs from statement 3 at its own site at {differ} voxels"
+    return out, sites, squared
+
+
+def brute(records):
+    """(n,) float32: the minimum of c3 over every crossing of the lattice, +inf without one."""
+    assert records.dtype == np.float32 and records.flags.c_contiguous
+    nx, ny, nz = records.shape[:3]
+    squared = np.empty((nx * ny * nz,), np.float32)
+    load().redistance_brute(_p(records), ctypes.c_int32(nx), ctypes.c_int32(ny), ctypes.c_int32(nz), _p(squared))
+    return squared
+
+
+def site_costs(records, sites):
+    """(n,) float32: c3 of the crossing each site names, seen from its voxel; +inf where sites < 0 or the edge has no crossing."""
+    assert records.dtype == np.float32 and records.flags.c_contiguous and sites.dtype == np.int32
+    nx, ny, nz = records.shape[:3]
+    out = np.empty((nx * ny * nz,), np.float32)
+    load().redistance_site_costs(_p(records), ctypes.c_int32(nx), ctypes.c_int32(ny), ctypes.c_int32(nz), _p(sites), _p(out))
+    return out
+
+
+def bits(a):
+    return np.ascontiguousarray(a).view(np.int32)
+
+
+# ---------------------------------------------------------------- the fields the tests share
+@functools.lru_cache(maxsize=None)
+def smooth_field(shape, seed=5):
+    """(nx, ny, nz, 4) float32 records, read-only: a few waves plus noise, many crossings of every family at generic fractions;
+    the gradient columns hold noise of their own, so that a kept record is recognisable."""
+    rng = np.random.default_rng(seed)
+    x, y, z = np.meshgrid(*(np.arange(s, dtype=np.float64) for s in shape), indexing="ij")
+    values = np.sin(0.9 * x + 0.3) * np.cos(0.7 * y) + 0.8 * np.sin(0.23 * z + 0.5 * x) + 0.3 * rng.standard_normal(shape)
+    values -= np.median(values)  # both signs on any lattice, (2, 2, 2) included
+    rec = as_records(values, rng.standard_normal(shape + (3,)))
+    rec.flags.writeable = False
+    return rec
+
+
+@functools.lru_cache(maxsize=None)
+def tie_field(shape):
+    """(nx, ny, nz, 4) float32 records, read-only: the integer-valued x^2 + y^2 + z^2 - c about the lattice's centre (doubled
+    coordinates, so that even axes are centred too): symmetric, so equal costs abound within and across the families."""
+    axes = [2.0 * np.arange(s) - (s - 1) for s in shape]
+    x, y, z = np.meshgrid(*axes, indexing="ij")
+    r2 = x * x + y * y + z * z
+    values = r2 - np.floor(0.35 * r2.max())
+    if not ((values < 0).any() and (values >= 0).any()):
+        values = x + y + z + 1.0  # (2, 2, 2), where every r2 is 3: a plane through the lattice instead
+    rec = as_records(values, np.ones(shape + (3,)))
+    rec.flags.writeable = False
+    return rec
+
+
+FIELDS = {"smooth": smooth_field, "tie": tie_field}
+
+BALL_RADIUS, BALL_RES, BALL_BAND = 0.3, 0.02, 0.06  # the band: 3 voxels
+
+
+def ball_values(centre=(0.0, 0.0, 0.0)):
+    """(values (51, 51, 51) float32 clipped to +/-BALL_BAND, exact signed distance float64) of a ball of BALL_RADIUS about
+    `centre` on the 51^3 lattice over [-0.5, 0.5]^3."""
+    c = np.linspace(-0.5, 0.5, 51)
+    x, y, z = np.meshgrid(c - centre[0], c - centre[1], c - centre[2], indexing="ij")
+    exact = np.sqrt(x * x + y * y + z * z) - BALL_RADIUS
+    return np.clip(exact, -BALL_BAND, BALL_BAND).astype(np.float32), exact
