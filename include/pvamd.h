@@ -919,6 +919,13 @@ int pvamd_composed_ray_cast_backward_f64(const pvamd_grid_t* grids, int32_t S, c
                                          const double* up, double* dorigins, double* ddirections, double* dtf, void* scratch,
                                          void* stream);
 
+/* ---- Volume lattices ----
+ * The four sections below work on a 3-D lattice of nx * ny * nz voxels in C order (x slowest, z fastest): voxel (x, y, z) has the
+ * flat index (x * ny + y) * nz + z, and a record is [4] float32 (val, gx, gy, gz).  No axis is longer than
+ * PVAMD_LATTICE_MAX_AXIS: a coordinate takes 11 bits in the states the line passes hand on.  Each section states its own
+ * shortest axis and its cap on the voxels.                                                                                     */
+#define PVAMD_LATTICE_MAX_AXIS 2048
+
 /* ---- Distance transform (SDF from voxel occupancy) ----
  * The exact Euclidean distance transform of an occupancy grid, fused with the statements that turn it into the packed (val, gx,
  * gy, gz) records of a cached voxel grid (pvamd_grid_t.vox): the producer for scenes that are observed as voxels, not given as
@@ -942,13 +949,16 @@ int pvamd_composed_ray_cast_backward_f64(const pvamd_grid_t* grids, int32_t S, c
  *  5. Three line passes (z, y, x; the last fused with 3.) that keep one int32 per voxel and class in scratch; no sum ever
  *     includes the no-site sentinel.  The line minima are found by an outward scan that stops once the offset alone exceeds the
  *     best cost: the time grows with the distances in the grid, up to the line length per voxel and pass in empty space.
- * Each axis in [1, 2048] and nx * ny * nz <= 2^31 - 1, else PVAMD_E_SHAPE; is_signed other than 0 / 1: PVAMD_E_MODE.
+ * Each axis in [PVAMD_EDT_MIN_AXIS, PVAMD_LATTICE_MAX_AXIS] and nx * ny * nz <= PVAMD_EDT_MAX_VOXELS (sites is an int32), else
+ * PVAMD_E_SHAPE; is_signed other than 0 / 1: PVAMD_E_MODE.
  * records: device [n][4] float32, 16-byte aligned (n = nx * ny * nz).  sites, squared: device [n] int32, or NULL (not wanted).
  * scratch: device, pvamd_distance_transform_scratch_bytes(nx, ny, nz, is_signed) bytes, 4-byte aligned; that function is the
  * definition (0 for arguments the entry point refuses) and there is no macro.  Contents on return are unspecified.
  * Stream-ordered, no allocation, no device -> host synchronisation, no atomics: capturable in a graph, and two calls give the
  * same bits.                                                                                                                    */
 #define PVAMD_EDT_NO_SITE 2147483647  /* INT32_MAX: squared(i) when Q is empty */
+#define PVAMD_EDT_MIN_AXIS 1
+#define PVAMD_EDT_MAX_VOXELS 2147483647 /* 2^31 - 1 */
 int64_t pvamd_distance_transform_scratch_bytes(int32_t nx, int32_t ny, int32_t nz, int32_t is_signed);
 int pvamd_distance_transform(const uint8_t* occupied, int32_t nx, int32_t ny, int32_t nz, float resolution, int32_t is_signed,
                              float* records, int32_t* sites, int32_t* squared, void* scratch, void* stream);
@@ -962,7 +972,8 @@ int pvamd_distance_transform(const uint8_t* occupied, int32_t nx, int32_t ny, in
  *     PVAMD_MARK_FREE when it is no ray's hit voxel and the traversal (6.) of at least one ray visited it, 0 when no ray
  *     touched it.  A hit takes precedence over any number of traversals, which also makes the result independent of the order of
  *     the rays.  Marks of two calls accumulate: the traversal writes FREE only where the mark is 0, the hits overwrite.
- *  2. Lattice.  grid: a finalized descriptor (vox unused, as for the voxel scatter entry points), each axis n_k in [2, 2048].
+ *  2. Lattice.  grid: a finalized descriptor (vox unused, as for the voxel scatter entry points), each axis n_k in
+ *     [PVAMD_RAY_MARK_MIN_AXIS, PVAMD_LATTICE_MAX_AXIS].
  *     s_k(p) = (p_k - fmin_k) / fres_k in float32 (IEEE division); voxel i of axis k is the cell [i - 0.5, i + 0.5) in s.  The
  *     traversal always uses the float32 fields, whatever index_f64 says.  EVERYTHING below is float32 with every operation
  *     rounded on its own (no contraction, correctly rounded division and square root).
@@ -988,7 +999,7 @@ int pvamd_distance_transform(const uint8_t* occupied, int32_t nx, int32_t ny, in
  *     kernel.  No atomics.
  *  8. Update, one pass over the voxels, fused with clearing the marks: HIT: L = fminf(fmaxf(L + l_hit, l_min), l_max); FREE: the
  *     same with l_miss; 0: L keeps its bits.  observed |= (mark != 0) where observed is given.  Every mark is 0 on return.
- * Argument errors return before any launch: PVAMD_E_SHAPE for R < 0, n < 0 or an axis outside [2, 2048]; PVAMD_E_NULL;
+ * Argument errors return before any launch: PVAMD_E_SHAPE for R < 0, n < 0 or an axis outside those limits; PVAMD_E_NULL;
  * PVAMD_E_MODE for a max_range that is NaN or <= 0, a shared_origin other than 0 / 1, a NaN among l_hit, l_miss, l_min, l_max or
  * l_min > l_max; PVAMD_E_ALIGN for log_odds not 16-byte, marks (of the update) or observed not 4-byte aligned.
  * origins: device [1][3] when shared_origin = 1 (one eye for a whole image), else [R][3].  endpoints: device [R][3].
@@ -997,6 +1008,7 @@ int pvamd_distance_transform(const uint8_t* occupied, int32_t nx, int32_t ny, in
  * Stream-ordered, no allocation, no device -> host synchronisation: capturable in a graph, and two calls give the same bits. */
 #define PVAMD_MARK_FREE 1
 #define PVAMD_MARK_HIT  2
+#define PVAMD_RAY_MARK_MIN_AXIS 2
 int pvamd_ray_mark(const pvamd_grid_t* grid, const float* origins, int32_t shared_origin, const float* endpoints, int64_t R,
                    float max_range, uint8_t* marks, void* stream);
 int pvamd_occupancy_update(uint8_t* marks, int64_t n, float l_hit, float l_miss, float l_min, float l_max, float* log_odds,
@@ -1014,7 +1026,8 @@ int pvamd_occupancy_update(uint8_t* marks, int64_t n, float l_hit, float l_miss,
  *     of a voxel is read once before the first frame and written once after the last, and only if some frame updated the voxel:
  *     an untouched voxel keeps its bits, -0.0 included.  One call over K frames gives, bit for bit, what K calls of one frame
  *     each give in that order.
- *  2. Lattice.  grid: a finalized descriptor (vox unused), each axis n_j in [2, 2048].  The centre of voxel i = (x, y, z) is
+ *  2. Lattice.  grid: a finalized descriptor (vox unused), each axis n_j in [PVAMD_TSDF_MIN_AXIS, PVAMD_LATTICE_MAX_AXIS].  The
+ *     centre of voxel i = (x, y, z) is
  *     c_j = fmin_j + (float)i_j * fres_j: always the descriptor's float32 fields, as in "Ray integration" 2.
  *  Per voxel, for frame k = 0 .. K-1 in order, with T = camera_from_volume[k] (the camera looks along +z, x right, y down):
  *  3. p_r = ((T[r][0] * c_x + T[r][1] * c_y) + T[r][2] * c_z) + T[r][3] for r = 0, 1, 2.  The frame is skipped unless p_z > 0.
@@ -1036,15 +1049,18 @@ int pvamd_occupancy_update(uint8_t* marks, int64_t n, float l_hit, float l_miss,
  *     the surface normal.  Saturated regions, |t| = 1 all round, get zero gradients.  The field is TRUNCATED: |val| never exceeds
  *     the truncation, which suits sphere tracing, hinge margins up to the truncation and registration, and is wrong for anyone
  *     who reads far-field distances ("Redistancing" below completes it).
- * Argument errors return before any launch: PVAMD_E_SHAPE for K < 0, H or W < 1, K * H * W >= 2^31, an axis outside [2, 2048] or
- * more than 2^31 - 1 voxels; PVAMD_E_NULL; PVAMD_E_MODE for non-finite intrinsics, fx or fy <= 0, a truncation, weight or
- * resolution that is non-finite or <= 0, a max_weight or max_depth that is NaN or <= 0 (+INFINITY is allowed), a NaN min_weight,
- * an unknown_tsdf other than +1 / -1; PVAMD_E_ALIGN for state not 8-byte, records not 16-byte aligned.  K = 0 returns 0 without
- * a launch.
+ * Argument errors return before any launch: PVAMD_E_SHAPE for K < 0, H or W < 1, K * H * W > PVAMD_TSDF_MAX_PIXELS, an axis
+ * outside those limits or more than PVAMD_TSDF_MAX_VOXELS voxels; PVAMD_E_NULL; PVAMD_E_MODE for non-finite intrinsics, fx or
+ * fy <= 0, a truncation, weight or resolution that is non-finite or <= 0, a max_weight or max_depth that is NaN or <= 0
+ * (+INFINITY is allowed), a NaN min_weight, an unknown_tsdf other than +1 / -1; PVAMD_E_ALIGN for state not 8-byte, records not
+ * 16-byte aligned.  K = 0 returns 0 without a launch.
  * depth: device [K][H][W] float32.  camera_from_volume: device [K][3][4] float32, the rigid inverse of the camera's pose in the
  * volume's frame.  records: device [n][4] float32.
  * One launch each.  Stream-ordered, no allocation, no device -> host synchronisation, no atomics: capturable in a graph, and two
  * calls give the same bits.                                                                                                    */
+#define PVAMD_TSDF_MIN_AXIS 2
+#define PVAMD_TSDF_MAX_VOXELS 2147483647 /* 2^31 - 1 */
+#define PVAMD_TSDF_MAX_PIXELS 2147483647 /* 2^31 - 1 */
 int pvamd_tsdf_integrate(const pvamd_grid_t* grid, const float* depth, int32_t K, int32_t H, int32_t W,
                          const float* camera_from_volume, float fx, float fy, float cx, float cy, float truncation,
                          float max_depth, float weight, float max_weight, float* state, void* stream);
@@ -1082,16 +1098,19 @@ int pvamd_tsdf_records(const float* state, int32_t nx, int32_t ny, int32_t nz, f
  *  8. Three line passes per family, each an outward scan that stops once (float)(d * d) exceeds min(best, R2): in space without
  *     crossings a scan runs to both ends of its line, and max_distance is what bounds that.  The time grows with the distances
  *     in the grid, as the distance transform's does.
- * Argument errors return before any launch, tested in this order: PVAMD_E_SHAPE for an axis outside [2, 2048] or n > 2^29 (the
- * site code is an int32); PVAMD_E_MODE for a resolution that is non-finite or <= 0, a band that is NaN or < 0, a max_distance that
- * is NaN or <= 0; PVAMD_E_NULL (sites and squared may be NULL: not wanted); PVAMD_E_ALIGN for records not 16-byte, scratch, sites or
- * squared not 4-byte aligned.
+ * Argument errors return before any launch, tested in this order: PVAMD_E_SHAPE for an axis outside
+ * [PVAMD_REDIST_MIN_AXIS, PVAMD_LATTICE_MAX_AXIS] or n > PVAMD_REDIST_MAX_VOXELS (sites = flat * 4 + k is an int32);
+ * PVAMD_E_MODE for a resolution that is non-finite or <= 0, a band that is NaN or < 0, a max_distance that is NaN or <= 0;
+ * PVAMD_E_NULL (sites and squared may be NULL: not wanted); PVAMD_E_ALIGN for records not 16-byte, scratch, sites or squared not
+ * 4-byte aligned.
  * records_in is never written and must not overlap records_out: device [n][4] float32.  sites: device [n] int32.  squared: device
  * [n] float32.  scratch: device, pvamd_redistance_scratch_bytes(nx, ny, nz) bytes, 4-byte aligned; that function is the
  * definition (0 for shapes the entry point refuses) and there is no macro.  Contents on return are unspecified.
  * Stream-ordered, no allocation, no device -> host synchronisation, no atomics: capturable in a graph, and two calls give the
  * same bits.                                                                                                                    */
 #define PVAMD_REDIST_KEPT (-2) /* sites[i] of a voxel inside the band */
+#define PVAMD_REDIST_MIN_AXIS 2
+#define PVAMD_REDIST_MAX_VOXELS 536870912 /* 2^29 */
 int64_t pvamd_redistance_scratch_bytes(int32_t nx, int32_t ny, int32_t nz);
 int pvamd_redistance(const float* records_in, int32_t nx, int32_t ny, int32_t nz, float resolution, float band, float max_distance,
                      float* records_out, int32_t* sites, float* squared, void* scratch, void* stream);

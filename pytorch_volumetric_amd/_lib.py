@@ -248,6 +248,15 @@ EDT_NO_SITE = H["PVAMD_EDT_NO_SITE"]  # DistanceTransform.squared where the site
 REDIST_KEPT = H["PVAMD_REDIST_KEPT"]  # Redistance.sites of a voxel inside the band
 MARK_FREE = H["PVAMD_MARK_FREE"]  # MARK_*: a scan's classification of a voxel (pvamd_ray_mark); 0: no ray touched it
 MARK_HIT = H["PVAMD_MARK_HIT"]
+LATTICE_MAX_AXIS = H["PVAMD_LATTICE_MAX_AXIS"]  # the longest axis of a volume lattice; *_MIN_AXIS, *_MAX_VOXELS: per feature
+EDT_MIN_AXIS = H["PVAMD_EDT_MIN_AXIS"]
+EDT_MAX_VOXELS = H["PVAMD_EDT_MAX_VOXELS"]
+RAY_MARK_MIN_AXIS = H["PVAMD_RAY_MARK_MIN_AXIS"]
+TSDF_MIN_AXIS = H["PVAMD_TSDF_MIN_AXIS"]
+TSDF_MAX_VOXELS = H["PVAMD_TSDF_MAX_VOXELS"]
+TSDF_MAX_PIXELS = H["PVAMD_TSDF_MAX_PIXELS"]  # K * H * W of one pvamd_tsdf_integrate call
+REDIST_MIN_AXIS = H["PVAMD_REDIST_MIN_AXIS"]
+REDIST_MAX_VOXELS = H["PVAMD_REDIST_MAX_VOXELS"]
 E_SHAPE = H["PVAMD_E_SHAPE"]
 _ERRORS = {H["PVAMD_E_NULL"]: "a required pointer is NULL", H["PVAMD_E_SHAPE"]: "a size/shape argument is out of range",
            H["PVAMD_E_ALIGN"]: "a pointer is misaligned", H["PVAMD_E_MODE"]: "unknown enum value"}

@@ -80,4 +80,47 @@ static inline int check_grid(const pvamd_grid_t& g, bool need_vox = true) {
     return 0;
 }
 
+// ---- The lattice of the volume entry points (include/pvamd.h "Volume lattices"): distance transform, ray integration, TSDF,
+// redistancing.
+#define PVAMD_DEV __device__ __forceinline__
+
+// a coordinate in the packed states the line passes hand on: (high << kAxisBits) | low, low = packed & kAxisMask
+constexpr int kAxisBits = 11;
+constexpr int kAxisMask = (1 << kAxisBits) - 1;
+static_assert(PVAMD_LATTICE_MAX_AXIS <= (1 << kAxisBits), "a lattice coordinate must fit kAxisBits");
+
+// every axis in [min_axis, PVAMD_LATTICE_MAX_AXIS] and at most `cap` voxels
+static inline bool lattice_shape_ok(int32_t nx, int32_t ny, int32_t nz, int min_axis, int64_t cap) {
+    if (nx < min_axis || ny < min_axis || nz < min_axis) return false;
+    if (nx > PVAMD_LATTICE_MAX_AXIS || ny > PVAMD_LATTICE_MAX_AXIS || nz > PVAMD_LATTICE_MAX_AXIS) return false;
+    return (int64_t)nx * ny * nz <= cap;
+}
+
+// what a kernel reads of a descriptor's lattice: the float32 fields, whatever index_f64 says
+struct Lattice {
+    float fmin[3], fres[3];
+    int n[3];
+};
+
+static inline Lattice lattice_of(const pvamd_grid_t& g) {
+    Lattice L;
+    for (int k = 0; k < 3; ++k) {
+        L.fmin[k] = g.fmin[k];
+        L.fres[k] = g.fres[k];
+        L.n[k] = g.shape[k];
+    }
+    return L;
+}
+
+// voxel (x, y, z) of a flat C-order index; rest = y * nz + z, the index inside the x plane (plane = ny * nz)
+struct Voxel {
+    unsigned x, y, z, rest;
+};
+
+PVAMD_DEV Voxel voxel_of(unsigned flat, unsigned plane, unsigned nz) {
+    const unsigned x = flat / plane, rest = flat - x * plane;
+    const unsigned y = rest / nz, z = rest - y * nz;
+    return {x, y, z, rest};
+}
+
 }  // namespace pvamd

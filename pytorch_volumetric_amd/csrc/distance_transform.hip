@@ -5,8 +5,8 @@
 // Three separable line passes, z then y then x, one lane per voxel in every pass, lanes along z so that every global access
 // is a run of consecutive addresses.  A site class (the occupied voxels; in signed mode also the free ones) keeps ONE int32 per
 // voxel between the passes -- the coordinates of the best site so far along the axes already done, or -1 when there is none:
-//   after z: z' of the nearest site on the voxel's own z line                     (cost (z - z')^2)
-//   after y: (y' << 11) | z' of the nearest site in the voxel's own x plane       (cost (y - y')^2 + (z - z')^2)
+//   after z: z' of the nearest site on the voxel's own z line                      (cost (z - z')^2)
+//   after y: (y' << kAxisBits) | z' of the nearest site in the voxel's own x plane (cost (y - y')^2 + (z - z')^2)
 // and the x pass writes the flat site, the squared distance and the record.  The cost is recomputed from the coordinates where
 // it is compared: a candidate visit is one 4-byte load.  No sum ever includes the no-site sentinel: a candidate without a site
 // is skipped.
@@ -26,14 +26,8 @@
 
 namespace pvamd {
 
-constexpr int kEdtMaxAxis = 2048;           // 11 bits per coordinate in the packed (y', z') state
-constexpr int kEdtWords = kEdtMaxAxis / 64;  // bit-set words of one z line
-constexpr int kEdtWaves = 4;                // z pass: waves (= lines in flight) per workgroup
-
-static inline bool edt_shape_ok(int32_t nx, int32_t ny, int32_t nz) {
-    if (nx < 1 || ny < 1 || nz < 1 || nx > kEdtMaxAxis || ny > kEdtMaxAxis || nz > kEdtMaxAxis) return false;
-    return (int64_t)nx * ny * nz <= (int64_t)INT32_MAX;
-}
+constexpr int kEdtWords = PVAMD_LATTICE_MAX_AXIS / 64;  // bit-set words of one z line
+constexpr int kEdtWaves = 4;                            // z pass: waves (= lines in flight) per workgroup
 
 // nearest set bit of the line's bit set to position z (word w = z / 64, bit b = z % 64), the lower one on equal distance; -1: none
 __device__ __forceinline__ int edt_nearest_bit(const unsigned long long* words, int nw, int w, int b, bool invert,
@@ -108,16 +102,16 @@ __device__ __forceinline__ int edt_scan(int c, int len, int& best, CostOf cost_o
     return at;
 }
 
-// Pass 2.  in: z' per voxel; out: (y' << 11) | z' per voxel.  Both classes of a signed call in one launch.
+// Pass 2.  in: z' per voxel; out: (y' << kAxisBits) | z' per voxel.  Both classes of a signed call in one launch.
 template <bool SIGNED>
 __global__ __launch_bounds__(256) void edt_y_kernel(int64_t n, int ny, int nz, const int* __restrict__ in0, const int* __restrict__ in1,
                                                     int* __restrict__ out0, int* __restrict__ out1) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     const unsigned plane = (unsigned)ny * (unsigned)nz;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const unsigned x = (unsigned)i / plane, rem = (unsigned)i - x * plane;
-        const int y = (int)(rem / (unsigned)nz), z = (int)(rem - (unsigned)y * (unsigned)nz);
-        const int64_t column = (int64_t)x * plane + z;  // + y' * nz: the candidates of this voxel
+        const Voxel v = voxel_of((unsigned)i, plane, (unsigned)nz);
+        const int y = (int)v.y, z = (int)v.z;
+        const int64_t column = (int64_t)v.x * plane + z;  // + y' * nz: the candidates of this voxel
         for (int cls = 0; cls < (SIGNED ? 2 : 1); ++cls) {
             const int* __restrict__ in = cls ? in1 : in0;
             int best, zs = -1;
@@ -128,7 +122,7 @@ __global__ __launch_bounds__(256) void edt_y_kernel(int64_t n, int ny, int nz, c
                 return true;
             });
             if (at >= 0) zs = in[column + (int64_t)at * nz];
-            (cls ? out1 : out0)[i] = at < 0 ? -1 : ((at << 11) | zs);
+            (cls ? out1 : out0)[i] = at < 0 ? -1 : ((at << kAxisBits) | zs);
         }
     }
 }
@@ -142,15 +136,16 @@ __global__ __launch_bounds__(256) void edt_x_kernel(const uint8_t* __restrict__ 
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     const unsigned plane = (unsigned)ny * (unsigned)nz;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const unsigned ux = (unsigned)i / plane, rem = (unsigned)i - ux * plane;
-        const int x = (int)ux, y = (int)(rem / (unsigned)nz), z = (int)(rem - (unsigned)y * (unsigned)nz);
+        const Voxel v = voxel_of((unsigned)i, plane, (unsigned)nz);
+        const unsigned rem = v.rest;
+        const int x = (int)v.x, y = (int)v.y, z = (int)v.z;
         const bool occupied = occ[i] != 0;
         const int* __restrict__ in = (SIGNED && occupied) ? in1 : in0;
         int best;
         const int at = edt_scan(x, nx, best, [&](int k, int& cost) {
             const int s = in[(int64_t)k * plane + rem];
             if (s < 0) return false;
-            const int dy = y - (s >> 11), dz = z - (s & 2047);
+            const int dy = y - (s >> kAxisBits), dz = z - (s & kAxisMask);
             cost = dy * dy + dz * dz;
             return true;
         });
@@ -159,7 +154,7 @@ __global__ __launch_bounds__(256) void edt_x_kernel(const uint8_t* __restrict__ 
         int site = -1;
         if (at >= 0) {
             const int s = in[(int64_t)at * plane + rem];
-            const int sy = s >> 11, sz = s & 2047;
+            const int sy = s >> kAxisBits, sz = s & kAxisMask;
             site = (int)(((unsigned)at * (unsigned)ny + (unsigned)sy) * (unsigned)nz + (unsigned)sz);
             const float root = sqrt_rn((float)best);
             // toward increasing value: away from the site for a free voxel, toward it for an occupied one
@@ -207,14 +202,14 @@ static int edt_launch(const uint8_t* occ, int nx, int ny, int nz, float r, float
 using namespace pvamd;
 
 extern "C" int64_t pvamd_distance_transform_scratch_bytes(int32_t nx, int32_t ny, int32_t nz, int32_t is_signed) {
-    if (!edt_shape_ok(nx, ny, nz) || (is_signed != 0 && is_signed != 1)) return 0;
+    if (!lattice_shape_ok(nx, ny, nz, PVAMD_EDT_MIN_AXIS, PVAMD_EDT_MAX_VOXELS) || (is_signed != 0 && is_signed != 1)) return 0;
     return (int64_t)nx * ny * nz * (is_signed ? 4 : 2) * (int64_t)sizeof(int32_t);
 }
 
 extern "C" int pvamd_distance_transform(const uint8_t* occupied, int32_t nx, int32_t ny, int32_t nz, float resolution,
                                         int32_t is_signed, float* records, int32_t* sites, int32_t* squared, void* scratch,
                                         void* stream) {
-    if (!edt_shape_ok(nx, ny, nz)) return PVAMD_E_SHAPE;
+    if (!lattice_shape_ok(nx, ny, nz, PVAMD_EDT_MIN_AXIS, PVAMD_EDT_MAX_VOXELS)) return PVAMD_E_SHAPE;
     if (is_signed != 0 && is_signed != 1) return PVAMD_E_MODE;
     if (!occupied || !records || !scratch) return PVAMD_E_NULL;
     if (!aligned_to(records, 16) || !aligned_to(scratch, 4) || !aligned_to(sites, 4) || !aligned_to(squared, 4)) return PVAMD_E_ALIGN;

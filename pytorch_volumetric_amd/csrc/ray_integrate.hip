@@ -17,13 +17,6 @@
 
 namespace pvamd {
 
-constexpr int kRayMaxAxis = 2048;
-
-struct RayLattice {
-    float fmin[3], fres[3];
-    int n[3];
-};
-
 PVAMD_DEV bool ray_finite(const float o[3], const float e[3]) {
     const float inf = __builtin_inff();
     return fabsf(o[0]) < inf && fabsf(o[1]) < inf && fabsf(o[2]) < inf && fabsf(e[0]) < inf && fabsf(e[1]) < inf && fabsf(e[2]) < inf;
@@ -41,7 +34,7 @@ PVAMD_DEV float ray_exit(int c, int step, float a, float d) {
 }
 
 template <bool SHARED>
-__global__ __launch_bounds__(256) void ray_walk_kernel(RayLattice L, const float* __restrict__ origins,
+__global__ __launch_bounds__(256) void ray_walk_kernel(Lattice L, const float* __restrict__ origins,
                                                        const float* __restrict__ endpoints, int64_t R, float max_range,
                                                        uint8_t* __restrict__ marks) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -168,20 +161,15 @@ extern "C" int pvamd_ray_mark(const pvamd_grid_t* grid, const float* origins, in
                               int64_t R, float max_range, uint8_t* marks, void* stream) {
     if (R < 0) return PVAMD_E_SHAPE;
     if (!grid) return PVAMD_E_NULL;
-    for (int k = 0; k < 3; ++k) {
-        if (grid->shape[k] < 2 || grid->shape[k] > kRayMaxAxis) return PVAMD_E_SHAPE;
-    }
+    // the cap on the voxels is the descriptor's own, check_grid's
+    const int32_t* shape = grid->shape;
+    if (!lattice_shape_ok(shape[0], shape[1], shape[2], PVAMD_RAY_MARK_MIN_AXIS, INT64_MAX)) return PVAMD_E_SHAPE;
     if (int e = check_grid(*grid, /*need_vox=*/false)) return e;
     if (!(max_range > 0.0f)) return PVAMD_E_MODE;  // NaN included
     if (shared_origin != 0 && shared_origin != 1) return PVAMD_E_MODE;
     if (R == 0) return 0;
     if (!origins || !endpoints || !marks) return PVAMD_E_NULL;
-    RayLattice L;
-    for (int k = 0; k < 3; ++k) {
-        L.fmin[k] = grid->fmin[k];
-        L.fres[k] = grid->fres[k];
-        L.n[k] = grid->shape[k];
-    }
+    const Lattice L = lattice_of(*grid);
     hipStream_t s = (hipStream_t)stream;
     const dim3 gd(stream_grid(R, 256)), block(256);
     if (shared_origin) hipLaunchKernelGGL((ray_walk_kernel<true>), gd, block, 0, s, L, origins, endpoints, R, max_range, marks);

@@ -12,7 +12,7 @@
 //
 // State between the passes: 8 bytes per voxel, (float cost, int32 packed).  packed is -1 without a site (cost +inf), else
 //   after pass 1: a_k                       the edge's lower voxel along k        cost c1
-//   after pass 2: a_k | (a_p2 << 11)                                              cost c2
+//   after pass 2: a_k | (a_p2 << kAxisBits)                                       cost c2
 // and the last pass of all three families is one kernel, which takes the best family (lowest k on a tie) and writes the records,
 // sites and squared.  f, and with it t and the gradient, is recomputed there from the two samples of the winning edge.
 //
@@ -31,16 +31,8 @@
 
 namespace pvamd {
 
-constexpr int kRedistMaxAxis = 2048;  // 11 bits per coordinate in the packed state
-constexpr int64_t kRedistMaxVoxels = (int64_t)1 << 29;  // sites = flat * 4 + k in int32
-
 // the 8-byte state at an address that is only 4-byte aligned (the scratch's contract; gfx950 takes any dword address)
 typedef float state2 __attribute__((ext_vector_type(2), aligned(4)));
-
-static inline bool redist_shape_ok(int32_t nx, int32_t ny, int32_t nz) {
-    if (nx < 2 || ny < 2 || nz < 2 || nx > kRedistMaxAxis || ny > kRedistMaxAxis || nz > kRedistMaxAxis) return false;
-    return (int64_t)nx * ny * nz <= kRedistMaxVoxels;
-}
 
 PVAMD_DEV bool redist_finite(float a) { return sub_rn(a, a) == 0.0f; }
 
@@ -63,7 +55,8 @@ __global__ __launch_bounds__(256) void redist_values_kernel(const f32x4* __restr
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) V[i] = records_in[i].x;
 }
 
-// the coordinate of flat voxel i along `axis`
+// the coordinate of flat voxel i along `axis`.  voxel_of's statements written out: from locals the compiler divides by nz only
+// where axis != 0, from voxel_of's result it divides everywhere (profiles/volume_lattice.md)
 PVAMD_DEV int redist_coordinate(unsigned flat, unsigned ny, unsigned nz, int axis) {
     const unsigned plane = ny * nz;
     const unsigned x = flat / plane, rest = flat - x * plane;
@@ -149,7 +142,7 @@ __global__ __launch_bounds__(256) void redist_line_kernel(const state2* __restri
         float best;
         int packed;
         const int at = redist_scan(in + (i - (int64_t)c * step), step, c, len, R2, best, packed);
-        out[i] = at < 0 ? redist_state(__builtin_inff(), -1) : redist_state(best, packed | (at << 11));
+        out[i] = at < 0 ? redist_state(__builtin_inff(), -1) : redist_state(best, packed | (at << kAxisBits));
     }
 }
 
@@ -164,10 +157,8 @@ __global__ __launch_bounds__(256) void redist_last_kernel(const f32x4* __restric
     const unsigned plane = (unsigned)ny * (unsigned)nz;
     const float inf = __builtin_inff();
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const unsigned flat = (unsigned)i;
-        const unsigned ux = flat / plane, rest = flat - ux * plane;
-        const unsigned uy = rest / (unsigned)nz, uz = rest - uy * (unsigned)nz;
-        const int x = (int)ux, y = (int)uy, z = (int)uz;
+        const Voxel here = voxel_of((unsigned)i, plane, (unsigned)nz);
+        const int x = (int)here.x, y = (int)here.y, z = (int)here.z;
         const float v = V[i];
         if (fabsf(v) < band) {  // NaN: not kept
             records_out[i] = records_in[i];
@@ -188,7 +179,7 @@ __global__ __launch_bounds__(256) void redist_last_kernel(const f32x4* __restric
         int site = -1;
         float c3 = inf;
         if (at >= 0) {
-            const int first = packed & 2047, second = packed >> 11;
+            const int first = packed & kAxisMask, second = packed >> kAxisBits;
             const int ax = k == 0 ? first : at;
             const int ay = k == 0 ? at : (k == 1 ? first : second);
             const int az = k == 2 ? first : second;
@@ -221,14 +212,14 @@ __global__ __launch_bounds__(256) void redist_last_kernel(const f32x4* __restric
 using namespace pvamd;
 
 extern "C" int64_t pvamd_redistance_scratch_bytes(int32_t nx, int32_t ny, int32_t nz) {
-    if (!redist_shape_ok(nx, ny, nz)) return 0;
+    if (!lattice_shape_ok(nx, ny, nz, PVAMD_REDIST_MIN_AXIS, PVAMD_REDIST_MAX_VOXELS)) return 0;
     return (int64_t)nx * ny * nz * 36;
 }
 
 extern "C" int pvamd_redistance(const float* records_in, int32_t nx, int32_t ny, int32_t nz, float resolution, float band,
                                 float max_distance, float* records_out, int32_t* sites, float* squared, void* scratch,
                                 void* stream) {
-    if (!redist_shape_ok(nx, ny, nz)) return PVAMD_E_SHAPE;
+    if (!lattice_shape_ok(nx, ny, nz, PVAMD_REDIST_MIN_AXIS, PVAMD_REDIST_MAX_VOXELS)) return PVAMD_E_SHAPE;
     if (!(resolution > 0.0f && resolution < __builtin_inff()) || !(band >= 0.0f) || !(max_distance > 0.0f)) return PVAMD_E_MODE;
     if (!records_in || !records_out || !scratch) return PVAMD_E_NULL;
     if (!aligned_to(records_in, 16) || !aligned_to(records_out, 16) || !aligned_to(scratch, 4) || !aligned_to(sites, 4) ||

@@ -14,20 +14,13 @@
 
 namespace pvamd {
 
-constexpr int kTsdfMaxAxis = 2048;
-
-struct TsdfLattice {
-    float fmin[3], fres[3];
-    int n[3];
-};
-
 struct TsdfCamera {
     float fx, fy, cx, cy;
     float u_end, v_end;  // (float)W - 0.5f, (float)H - 0.5f
     int H, W;
 };
 
-__global__ __launch_bounds__(256) void tsdf_integrate_kernel(TsdfLattice L, TsdfCamera cam, const float* __restrict__ depth, int K,
+__global__ __launch_bounds__(256) void tsdf_integrate_kernel(Lattice L, TsdfCamera cam, const float* __restrict__ depth, int K,
                                                              const float* __restrict__ camera_from_volume, float truncation,
                                                              float max_depth, float weight, float max_weight,
                                                              f32x2* __restrict__ state, int64_t n) {
@@ -35,12 +28,10 @@ __global__ __launch_bounds__(256) void tsdf_integrate_kernel(TsdfLattice L, Tsdf
     const unsigned plane = (unsigned)L.n[1] * (unsigned)L.n[2];
     const int64_t image = (int64_t)cam.H * cam.W;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const unsigned flat = (unsigned)i;  // n <= 2^31 - 1
-        const unsigned x = flat / plane, rest = flat - x * plane;
-        const unsigned y = rest / (unsigned)L.n[2], z = rest - y * (unsigned)L.n[2];
-        const float c0 = add_rn(L.fmin[0], mul_rn((float)x, L.fres[0]));
-        const float c1 = add_rn(L.fmin[1], mul_rn((float)y, L.fres[1]));
-        const float c2 = add_rn(L.fmin[2], mul_rn((float)z, L.fres[2]));
+        const Voxel at = voxel_of((unsigned)i, plane, (unsigned)L.n[2]);  // n <= PVAMD_TSDF_MAX_VOXELS
+        const float c0 = add_rn(L.fmin[0], mul_rn((float)at.x, L.fres[0]));
+        const float c1 = add_rn(L.fmin[1], mul_rn((float)at.y, L.fres[1]));
+        const float c2 = add_rn(L.fmin[2], mul_rn((float)at.z, L.fres[2]));
         const f32x2 old = state[i];
         float F = old.x, Wt = old.y;
         bool touched = false;
@@ -95,13 +86,11 @@ __global__ __launch_bounds__(256) void tsdf_records_kernel(const f32x2* __restri
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     const unsigned plane = (unsigned)ny * (unsigned)nz;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const unsigned flat = (unsigned)i;  // n <= 2^31 - 1
-        const unsigned x = flat / plane, rest = flat - x * plane;
-        const unsigned y = rest / (unsigned)nz, z = rest - y * (unsigned)nz;
+        const Voxel at = voxel_of((unsigned)i, plane, (unsigned)nz);  // n <= PVAMD_TSDF_MAX_VOXELS
         const float val = tsdf_value(state, i, truncation, min_weight, unknown_tsdf);
-        const float gx = tsdf_slope(state, i, (int)x, nx, (int64_t)plane, resolution, truncation, min_weight, unknown_tsdf);
-        const float gy = tsdf_slope(state, i, (int)y, ny, (int64_t)nz, resolution, truncation, min_weight, unknown_tsdf);
-        const float gz = tsdf_slope(state, i, (int)z, nz, 1, resolution, truncation, min_weight, unknown_tsdf);
+        const float gx = tsdf_slope(state, i, (int)at.x, nx, (int64_t)plane, resolution, truncation, min_weight, unknown_tsdf);
+        const float gy = tsdf_slope(state, i, (int)at.y, ny, (int64_t)nz, resolution, truncation, min_weight, unknown_tsdf);
+        const float gz = tsdf_slope(state, i, (int)at.z, nz, 1, resolution, truncation, min_weight, unknown_tsdf);
         const float len = sqrt_rn(add_rn(add_rn(mul_rn(gx, gx), mul_rn(gy, gy)), mul_rn(gz, gz)));
         f32x4 rec = {val, 0.0f, 0.0f, 0.0f};
         if (len > 0.0f) {
@@ -123,11 +112,10 @@ using namespace pvamd;
 extern "C" int pvamd_tsdf_integrate(const pvamd_grid_t* grid, const float* depth, int32_t K, int32_t H, int32_t W,
                                     const float* camera_from_volume, float fx, float fy, float cx, float cy, float truncation,
                                     float max_depth, float weight, float max_weight, float* state, void* stream) {
-    if (K < 0 || H < 1 || W < 1 || (int64_t)K * H * W > (int64_t)INT32_MAX) return PVAMD_E_SHAPE;
+    if (K < 0 || H < 1 || W < 1 || (int64_t)K * H * W > PVAMD_TSDF_MAX_PIXELS) return PVAMD_E_SHAPE;
     if (!grid) return PVAMD_E_NULL;
-    for (int k = 0; k < 3; ++k) {
-        if (grid->shape[k] < 2 || grid->shape[k] > kTsdfMaxAxis) return PVAMD_E_SHAPE;
-    }
+    const int32_t* shape = grid->shape;
+    if (!lattice_shape_ok(shape[0], shape[1], shape[2], PVAMD_TSDF_MIN_AXIS, PVAMD_TSDF_MAX_VOXELS)) return PVAMD_E_SHAPE;
     if (int e = check_grid(*grid, /*need_vox=*/false)) return e;
     if (!positive_finite(fx) || !positive_finite(fy) || !is_finite(cx) || !is_finite(cy)) return PVAMD_E_MODE;
     if (!positive_finite(truncation) || !positive_finite(weight)) return PVAMD_E_MODE;
@@ -135,12 +123,7 @@ extern "C" int pvamd_tsdf_integrate(const pvamd_grid_t* grid, const float* depth
     if (K == 0) return 0;
     if (!depth || !camera_from_volume || !state) return PVAMD_E_NULL;
     if (!aligned_to(state, 8) || !aligned_to(depth, 4) || !aligned_to(camera_from_volume, 4)) return PVAMD_E_ALIGN;
-    TsdfLattice L;
-    for (int k = 0; k < 3; ++k) {
-        L.fmin[k] = grid->fmin[k];
-        L.fres[k] = grid->fres[k];
-        L.n[k] = grid->shape[k];
-    }
+    const Lattice L = lattice_of(*grid);
     const TsdfCamera cam = {fx, fy, cx, cy, (float)W - 0.5f, (float)H - 0.5f, H, W};
     const int64_t n = (int64_t)L.n[0] * L.n[1] * L.n[2];
     hipLaunchKernelGGL(tsdf_integrate_kernel, dim3(stream_grid(n, 256)), dim3(256), 0, (hipStream_t)stream, L, cam, depth, K,
@@ -150,9 +133,8 @@ extern "C" int pvamd_tsdf_integrate(const pvamd_grid_t* grid, const float* depth
 
 extern "C" int pvamd_tsdf_records(const float* state, int32_t nx, int32_t ny, int32_t nz, float resolution, float truncation,
                                   float min_weight, float unknown_tsdf, float* records, void* stream) {
-    if (nx < 2 || ny < 2 || nz < 2 || nx > kTsdfMaxAxis || ny > kTsdfMaxAxis || nz > kTsdfMaxAxis) return PVAMD_E_SHAPE;
+    if (!lattice_shape_ok(nx, ny, nz, PVAMD_TSDF_MIN_AXIS, PVAMD_TSDF_MAX_VOXELS)) return PVAMD_E_SHAPE;
     const int64_t n = (int64_t)nx * ny * nz;
-    if (n > (int64_t)INT32_MAX) return PVAMD_E_SHAPE;
     if (!positive_finite(resolution) || !positive_finite(truncation) || min_weight != min_weight) return PVAMD_E_MODE;
     if (unknown_tsdf != 1.0f && unknown_tsdf != -1.0f) return PVAMD_E_MODE;
     if (!state || !records) return PVAMD_E_NULL;

@@ -5,16 +5,17 @@ The reference has no counterpart: its VoxelGrid / ExpandingVoxelGrid hold what a
 can query starts from a mesh or a closed form.  With this producer an observed scene is a leaf like any mesh cache.
 """
 import ctypes
-import math
 from typing import NamedTuple
 
 import torch
 
 from pytorch_volumetric_amd import _lib
+from pytorch_volumetric_amd._lattice import positive_finite
 from pytorch_volumetric_amd.sdf import CachedSDF, ObjectFrameSDF, _restore
 from pytorch_volumetric_amd.voxel import RangeView
 
-MAX_AXIS = 2048  # include/pvamd.h "Distance transform": each axis in [1, 2048]
+# include/pvamd.h "Distance transform"
+MIN_AXIS, MAX_AXIS, MAX_VOXELS = _lib.EDT_MIN_AXIS, _lib.LATTICE_MAX_AXIS, _lib.EDT_MAX_VOXELS
 
 
 class DistanceTransform(NamedTuple):
@@ -33,14 +34,11 @@ def _check_arguments(occupied, resolution, signed):
         occupied = torch.as_tensor(occupied)
     if occupied.dim() != 3:
         raise ValueError(f"occupied must be a 3-D tensor, got shape {tuple(occupied.shape)}")
-    if min(occupied.shape) < 1 or max(occupied.shape) > MAX_AXIS:
-        raise ValueError(f"every axis of occupied must be in [1, {MAX_AXIS}], got shape {tuple(occupied.shape)}")
-    if occupied.numel() > 2 ** 31 - 1:
+    if min(occupied.shape) < MIN_AXIS or max(occupied.shape) > MAX_AXIS:
+        raise ValueError(f"every axis of occupied must be in [{MIN_AXIS}, {MAX_AXIS}], got shape {tuple(occupied.shape)}")
+    if occupied.numel() > MAX_VOXELS:
         raise ValueError(f"occupied must have at most 2^31 - 1 voxels, got shape {tuple(occupied.shape)}")
-    resolution = float(resolution)
-    if not (math.isfinite(resolution) and resolution > 0):
-        raise ValueError(f"resolution must be finite and positive, got {resolution}")
-    return occupied, resolution
+    return occupied, positive_finite("resolution", resolution)
 
 
 def _transform(occupied, resolution, signed):
@@ -103,21 +101,28 @@ class OccupancySDF(ObjectFrameSDF):
             raise ValueError(f"OccupancySDF needs a 3-D voxel grid with at least two voxels per axis, got shape {tuple(data.shape)}")
         occupied, resolution = _check_arguments(data != 0 if threshold is None else data > threshold, voxels.resolution, signed)
         self.signed = signed
-        self.resolution = voxels.resolution
-        self.ranges = list(voxels.voxels._ranges)  # the element types decide the dtype of the index arithmetic (voxel.RangeView)
-        self._view = RangeView(self.ranges, data.shape, rule=voxels.voxels._rule)
-        occ, self._records, self._sites, self._squared = _transform(occupied, resolution, signed)
-        # the one synchronisation: how many voxels are occupied and which index box they fill
-        index = occ.nonzero()
-        count = index.shape[0]
-        if count == 0:
-            raise ValueError("OccupancySDF: the grid has no occupied voxel")
+        occ, records, self._sites, self._squared = _transform(occupied, resolution, signed)
+        count = self._set_records(voxels.voxels, voxels.resolution, records, occ, "OccupancySDF: the grid has no occupied voxel")
         if signed and count == occ.numel():
             raise ValueError("OccupancySDF: signed=True needs at least one free voxel, every voxel of the grid is occupied")
+
+    def _set_records(self, view, resolution, records, inside, empty):
+        """What every producer of lattice records ends its __init__ with: the lattice of `view` (a grid's ValueRangeView: ranges,
+        shape, rule), the (n, 4) records over it, and the box of the voxels `inside` (a mask shaped like the lattice) marks as at
+        or inside the surface.  Returns how many those are; none is a ValueError(empty)."""
+        self.resolution = resolution
+        self.ranges = list(view._ranges)  # the element types decide the dtype of the index arithmetic (voxel.RangeView)
+        self._view = RangeView(self.ranges, view.shape, rule=view._rule)
+        self._records = records
+        # the one synchronisation: how many voxels are inside and which index box they fill
+        index = inside.nonzero()
+        if index.shape[0] == 0:
+            raise ValueError(empty)
         lo, hi = index.amin(dim=0).cpu().double(), index.amax(dim=0).cpu().double()
         half = self._view.dres / 2
         self._box = torch.stack((self._view.dmin + lo * self._view.dres - half, self._view.dmin + hi * self._view.dres + half), dim=1)
         self._desc = None
+        return index.shape[0]
 
     def same_lattice(self, resolution, range_per_dim, shape):
         """Whether a grid of `shape` voxels of `resolution` over `range_per_dim` has this field's voxel centres, in the same index

@@ -7,16 +7,15 @@ turns depth images into the occupancy that distance_transform / cached_sdf_from_
 """
 import ctypes
 import math
-import numbers
 
 import torch
 
 from pytorch_volumetric_amd import _lib
+from pytorch_volumetric_amd._lattice import lattice_grid, positive, real
 from pytorch_volumetric_amd.occupancy import cached_sdf_from_voxels
-from pytorch_volumetric_amd.voxel import get_divisible_range_by_resolution
 from pytorch_volumetric_amd.voxel_containers import VoxelGrid
 
-MIN_AXIS, MAX_AXIS = 2, 2048  # include/pvamd.h "Ray integration": each axis in [2, 2048]
+MIN_AXIS, MAX_AXIS = _lib.RAY_MARK_MIN_AXIS, _lib.LATTICE_MAX_AXIS  # include/pvamd.h "Ray integration"
 UNKNOWN = ("free", "occupied")
 
 
@@ -40,10 +39,7 @@ def _check_rays(origins, endpoints, max_range):
         lead = torch.broadcast_shapes(origins.shape[:-1], endpoints.shape[:-1])
     except RuntimeError as e:
         raise ValueError(f"origins {tuple(origins.shape)} and endpoints {tuple(endpoints.shape)} do not broadcast") from e
-    max_range = float(max_range)
-    if not max_range > 0:
-        raise ValueError(f"max_range must be positive (inf: no limit), got {max_range}")
-    return origins, endpoints, max_range, lead
+    return origins, endpoints, positive("max_range", max_range), lead
 
 
 class OccupancyMap:
@@ -64,14 +60,6 @@ class OccupancyMap:
         :param clamp: (lo, hi) probabilities, 0 < lo < 0.5 < hi < 1, that the map never leaves: what bounds the number of scans
             it takes to change its mind
         """
-        resolution = float(resolution)
-        if not (math.isfinite(resolution) and resolution > 0):
-            raise ValueError(f"resolution must be finite and positive, got {resolution}")
-        if len(range_per_dim) != 3:
-            raise ValueError(f"an OccupancyMap is 3-D: range_per_dim needs three (low, high) pairs, got {len(range_per_dim)}")
-        cells = [round((high - low) / resolution) + 1 for low, high in get_divisible_range_by_resolution(resolution, range_per_dim)]
-        if min(cells) < MIN_AXIS or max(cells) > MAX_AXIS:
-            raise ValueError(f"every axis of an OccupancyMap must have {MIN_AXIS} to {MAX_AXIS} voxels, got {tuple(cells)}")
         prob_hit, prob_miss = float(prob_hit), float(prob_miss)
         if not 0.5 < prob_hit < 1.0:
             raise ValueError(f"prob_hit must be in (0.5, 1), got {prob_hit}")
@@ -80,17 +68,12 @@ class OccupancyMap:
         lo, hi = (float(c) for c in clamp)
         if not 0.0 < lo < 0.5 < hi < 1.0:
             raise ValueError(f"clamp must be 0 < lo < 0.5 < hi < 1, got {(lo, hi)}")
-        self.resolution, self.range_per_dim = resolution, range_per_dim
-        self.device = torch.device(device)
         # float64 log, rounded to float32 once: the four numbers the update kernel is handed
         self.l_hit, self.l_miss, self.l_min, self.l_max = (
             torch.tensor(_log_odds(p), dtype=torch.float64).to(torch.float32).item() for p in (prob_hit, prob_miss, lo, hi))
-        if self.device.type == "cuda":
-            _lib.require_gpu()
-        self._grid = VoxelGrid(resolution, range_per_dim, dtype=torch.float32, device=self.device)
+        self._grid = lattice_grid(resolution, range_per_dim, "an OccupancyMap", MIN_AXIS, device)
+        self.resolution, self.range_per_dim, self.device = self._grid.resolution, range_per_dim, self._grid.device
         shape = tuple(self._grid.get_voxel_values().shape)
-        if min(shape) < MIN_AXIS or max(shape) > MAX_AXIS:
-            raise ValueError(f"every axis of an OccupancyMap must have {MIN_AXIS} to {MAX_AXIS} voxels, got {shape}")
         self._observed = torch.zeros(shape, dtype=torch.uint8, device=self.device)
         self._marks = torch.zeros(shape, dtype=torch.uint8, device=self.device)  # zero between scans: the update clears it
 
@@ -116,9 +99,7 @@ class OccupancyMap:
         """(nx, ny, nz) bool: the observed voxels whose probability exceeds `threshold`; with unknown="occupied" also every
         voxel no scan has touched (what a planner that must not enter unseen space wants)."""
         _check_unknown(unknown)
-        if isinstance(threshold, bool) or not isinstance(threshold, numbers.Real):
-            raise TypeError(f"threshold must be a real number, got {type(threshold).__name__}")
-        threshold = float(threshold)
+        threshold = real("threshold", threshold)
         level = -math.inf if threshold <= 0 else (math.inf if threshold >= 1 else _log_odds(threshold))
         seen = self.observed
         occupied = (self.log_odds > level) & seen

@@ -6,15 +6,15 @@ occupancy route (distance_transform) has the far field and a surface on voxel fa
 and the reach from the second: TSDFVolume.to_sdf(far_field=True) is the consumer.
 """
 import math
-import numbers
 from typing import NamedTuple
 
 import torch
 
 from pytorch_volumetric_amd import _lib
+from pytorch_volumetric_amd._lattice import positive, positive_finite, real
 
-MIN_AXIS, MAX_AXIS = 2, 2048  # include/pvamd.h "Redistancing": each axis in [2, 2048]
-MAX_VOXELS = 2 ** 29          # sites = flat index * 4 + axis in an int32
+# include/pvamd.h "Redistancing"; the cap on the voxels: sites = flat index * 4 + axis in an int32
+MIN_AXIS, MAX_AXIS, MAX_VOXELS = _lib.REDIST_MIN_AXIS, _lib.LATTICE_MAX_AXIS, _lib.REDIST_MAX_VOXELS
 
 
 class Redistance(NamedTuple):
@@ -26,20 +26,12 @@ class Redistance(NamedTuple):
     squared: torch.Tensor    # (nx, ny, nz) float32 squared distance to the crossing in voxels; +inf where sites < 0
 
 
-def _real(name, value):
-    if isinstance(value, bool) or not isinstance(value, numbers.Real):
-        raise TypeError(f"{name} must be a real number, got {type(value).__name__}")
-    return float(value)
-
-
 def _check_range(band, max_distance):
     """(band, max_distance) as floats: band >= 0, max_distance > 0 (inf: no limit), neither NaN."""
-    band, max_distance = _real("band", band), _real("max_distance", max_distance)
+    band, max_distance = real("band", band), real("max_distance", max_distance)
     if not band >= 0:
         raise ValueError(f"band must be zero or positive, got {band}")
-    if not max_distance > 0:
-        raise ValueError(f"max_distance must be positive (inf: no limit), got {max_distance}")
-    return band, max_distance
+    return band, positive("max_distance", max_distance)
 
 
 def _check_arguments(values, resolution, band, gradients, max_distance):
@@ -54,9 +46,7 @@ def _check_arguments(values, resolution, band, gradients, max_distance):
         raise ValueError(f"every axis of values must be in [{MIN_AXIS}, {MAX_AXIS}], got shape {tuple(values.shape)}")
     if values.numel() > MAX_VOXELS:
         raise ValueError(f"values must have at most 2^29 voxels, got shape {tuple(values.shape)}")
-    resolution = _real("resolution", resolution)
-    if not (math.isfinite(resolution) and resolution > 0):
-        raise ValueError(f"resolution must be finite and positive, got {resolution}")
+    resolution = positive_finite("resolution", resolution, strict=True)
     band, max_distance = _check_range(band, max_distance)
     if gradients is not None:
         if not torch.is_tensor(gradients):
@@ -92,7 +82,7 @@ def redistance(values, resolution=1.0, band=0.0, gradients=None, max_distance=ma
     (include/pvamd.h "Redistancing").  The zero set is where the samples change sign along the lattice edges, placed by linear
     interpolation between the two samples; the result keeps each voxel's sign.
 
-    :param values: 3-D real tensor (nx, ny, nz), every axis 2 to 2048 voxels: a signed field, for instance truncated.  Only the
+    :param values: 3-D real tensor (nx, ny, nz), every axis MIN_AXIS to MAX_AXIS voxels: a signed field, for instance truncated.  Only the
         signs and the ratios across sign changes matter.  NaN and infinite samples give their edges no crossing.
     :param resolution: side length of a voxel; the values returned are in its units
     :param band: voxels with |value| < band keep their value and gradient as they are (a TSDF's band round the surface)

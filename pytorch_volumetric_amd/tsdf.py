@@ -12,35 +12,18 @@ import numbers
 import torch
 
 from pytorch_volumetric_amd import _lib
+from pytorch_volumetric_amd._lattice import lattice_grid, positive, positive_finite, real
 from pytorch_volumetric_amd.occupancy import OccupancySDF
-from pytorch_volumetric_amd.occupancy_map import MAX_AXIS, MIN_AXIS, _check_unknown
+from pytorch_volumetric_amd.occupancy_map import _check_unknown
 from pytorch_volumetric_amd.redistance import _check_range, _redistance_records
 from pytorch_volumetric_amd.sdf import CachedSDF
-from pytorch_volumetric_amd.voxel import RangeView, get_divisible_range_by_resolution
-from pytorch_volumetric_amd.voxel_containers import VoxelGrid
 
-MAX_PIXELS = 2 ** 31  # include/pvamd.h "TSDF integration": K * H * W below this
-
-
-def _positive_finite(name, value):
-    value = float(value)
-    if not (math.isfinite(value) and value > 0):
-        raise ValueError(f"{name} must be finite and positive, got {value}")
-    return value
-
-
-def _positive(name, value):
-    """Positive, +inf allowed (no limit), NaN refused."""
-    value = float(value)
-    if not value > 0:
-        raise ValueError(f"{name} must be positive (inf: no limit), got {value}")
-    return value
+MIN_AXIS, MAX_AXIS = _lib.TSDF_MIN_AXIS, _lib.LATTICE_MAX_AXIS  # include/pvamd.h "TSDF integration"
+MAX_PIXELS = _lib.TSDF_MAX_PIXELS  # K * H * W of one call
 
 
 def _check_min_weight(min_weight):
-    if isinstance(min_weight, bool) or not isinstance(min_weight, numbers.Real):
-        raise TypeError(f"min_weight must be a real number, got {type(min_weight).__name__}")
-    min_weight = float(min_weight)
+    min_weight = real("min_weight", min_weight)
     if math.isnan(min_weight):
         raise ValueError("min_weight must not be NaN")
     return min_weight
@@ -102,10 +85,10 @@ def _check_frames(depth, intrinsics, camera_pose, max_depth, weight, depth_scale
     H, W = depth.shape[-2:]
     if K and (H < 1 or W < 1):
         raise ValueError(f"depth images need at least one pixel, got {tuple(depth.shape)}")
-    if K * H * W >= MAX_PIXELS:
+    if K * H * W > MAX_PIXELS:
         raise ValueError(f"one call takes fewer than 2^31 pixels, got {tuple(depth.shape)}")
     fx, fy, cx, cy = _check_intrinsics(intrinsics)
-    return (depth, pose, K, H, W, (fx, fy, cx, cy), _positive("max_depth", max_depth), _positive_finite("weight", weight),
+    return (depth, pose, K, H, W, (fx, fy, cx, cy), positive("max_depth", max_depth), positive_finite("weight", weight),
             float(depth_scale))
 
 
@@ -126,24 +109,15 @@ class TSDFVolume:
         :param max_weight: where a voxel's weight stops growing: what bounds how long the volume takes to follow a scene that
             changed.  inf: a plain mean over every frame.
         """
-        resolution = _positive_finite("resolution", resolution)
-        if len(range_per_dim) != 3:
-            raise ValueError(f"a TSDFVolume is 3-D: range_per_dim needs three (low, high) pairs, got {len(range_per_dim)}")
-        cells = [round((high - low) / resolution) + 1 for low, high in get_divisible_range_by_resolution(resolution, range_per_dim)]
-        if min(cells) < MIN_AXIS or max(cells) > MAX_AXIS:
-            raise ValueError(f"every axis of a TSDFVolume must have {MIN_AXIS} to {MAX_AXIS} voxels, got {tuple(cells)}")
-        self.truncation = _positive_finite("truncation", truncation)
-        self.max_weight = _positive("max_weight", max_weight)
-        self.resolution, self.range_per_dim = resolution, range_per_dim
+        # the lattice: a VoxelGrid's descriptor.  On the meta device the grid has a shape and no storage; the state below is the volume
+        self._grid = lattice_grid(resolution, range_per_dim, "a TSDFVolume", MIN_AXIS, "meta")
+        self.truncation = positive_finite("truncation", truncation)
+        self.max_weight = positive("max_weight", max_weight)
+        self.resolution, self.range_per_dim = self._grid.resolution, range_per_dim
         self.device = torch.device(device)
         if self.device.type == "cuda":
             _lib.require_gpu()
-        # the lattice: a VoxelGrid's descriptor.  On the meta device the grid has a shape and no storage; the state below is the volume
-        self._grid = VoxelGrid(resolution, range_per_dim, dtype=torch.float32, device="meta")
-        shape = tuple(self._grid.get_voxel_values().shape)
-        if min(shape) < MIN_AXIS or max(shape) > MAX_AXIS:
-            raise ValueError(f"every axis of a TSDFVolume must have {MIN_AXIS} to {MAX_AXIS} voxels, got {shape}")
-        self._state = torch.zeros(shape + (2,), dtype=torch.float32, device=self.device)
+        self._state = torch.zeros(tuple(self._grid.get_voxel_values().shape) + (2,), dtype=torch.float32, device=self.device)
 
     @property
     def tsdf(self):
@@ -228,27 +202,17 @@ class TSDFField(OccupancySDF):
         max_distance = _check_far_field(far_field, max_distance)
         if volume.device.type != "cuda":
             raise _lib.PvamdError(f"a TSDFField is worked out on the GPU and this volume lives on {volume.device}; there is no CPU fallback")
-        grid = volume._grid
         self.signed = True
         self.unknown, self.min_weight, self.truncation = unknown, min_weight, volume.truncation
         self.far_field, self.max_distance = far_field, max_distance
-        self.resolution = grid.resolution
-        self.ranges = list(grid.voxels._ranges)
         nx, ny, nz = volume.shape
-        self._view = RangeView(self.ranges, volume.shape, rule=grid.voxels._rule)
-        self._records = torch.empty((nx * ny * nz, 4), dtype=torch.float32, device=volume.device)
+        records = torch.empty((nx * ny * nz, 4), dtype=torch.float32, device=volume.device)
         self._sites = self._squared = None
         with _lib.on_device(volume.device):
             _lib.check(_lib.load().pvamd_tsdf_records(_lib.ptr(volume._state), nx, ny, nz, volume.resolution, volume.truncation,
-                                                      min_weight, 1.0 if unknown == "free" else -1.0, _lib.ptr(self._records),
+                                                      min_weight, 1.0 if unknown == "free" else -1.0, _lib.ptr(records),
                                                       _lib.stream_ptr()), "pvamd_tsdf_records")
         if far_field:
-            self._records, _, _ = _redistance_records(self._records, volume.shape, volume.resolution, volume.truncation, max_distance)
-        # the one synchronisation: which index box the voxels at or inside the surface fill
-        index = (self._records[:, 0].reshape(volume.shape) <= 0).nonzero()
-        if index.shape[0] == 0:
-            raise ValueError("TSDFField: no voxel of the volume is at or inside a surface (value <= 0)")
-        lo, hi = index.amin(dim=0).cpu().double(), index.amax(dim=0).cpu().double()
-        half = self._view.dres / 2
-        self._box = torch.stack((self._view.dmin + lo * self._view.dres - half, self._view.dmin + hi * self._view.dres + half), dim=1)
-        self._desc = None
+            records, _, _ = _redistance_records(records, volume.shape, volume.resolution, volume.truncation, max_distance)
+        self._set_records(volume._grid.voxels, volume._grid.resolution, records, records[:, 0].reshape(volume.shape) <= 0,
+                          "TSDFField: no voxel of the volume is at or inside a surface (value <= 0)")

@@ -3,25 +3,16 @@ distance_transform_ref.c compiled on the fly (the O(n * |Q|) brute force with th
 the CPU and GPU tests share."""
 import ctypes
 import functools
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
+from tests import c_ref
+
 NO_SITE = 2 ** 31 - 1
-_lib = None
 
 
 def load():
-    global _lib
-    if _lib is None:
-        out = os.path.join(tempfile.mkdtemp(prefix="distance_transform_ref_"), "distance_transform_ref.so")
-        subprocess.run(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", os.path.join(HERE, "distance_transform_ref.c"),
-                        "-o", out, "-lm"], check=True)
-        _lib = ctypes.CDLL(out)
-    return _lib
+    return c_ref.load("distance_transform_ref")
 
 
 def _p(a):

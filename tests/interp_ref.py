@@ -2,25 +2,15 @@
 INFRASTRUCTURE: interp_ref.c compiled on the fly (bit-exact forward, the forward's cell decisions and blend on their own,
 float64 per-point VJP) and a float64 torch restatement that autograd differentiates given the kernel's decisions."""
 import ctypes
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-_lib = None
+from tests import c_ref
 
 
 def load():
-    global _lib
-    if _lib is None:
-        out = os.path.join(tempfile.mkdtemp(prefix="interp_ref_"), "interp_ref.so")
-        subprocess.run(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", os.path.join(HERE, "interp_ref.c"), "-o", out, "-lm"],
-                       check=True)
-        _lib = ctypes.CDLL(out)
-    return _lib
+    return c_ref.load("interp_ref")
 
 
 def _p(a):

@@ -1,15 +1,12 @@
 """Restatement of the ray-integration contract (include/pvamd.h "Ray integration") for its tests -- TEST INFRASTRUCTURE:
 ray_integrate_ref.c compiled on the fly, the lattices and the ray sets the CPU and GPU tests share."""
 import ctypes
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
+from tests import c_ref
+
 MARK_FREE, MARK_HIT = 1, 2
-_lib = None
 
 
 class Lattice(ctypes.Structure):
@@ -24,14 +21,9 @@ class Lattice(ctypes.Structure):
 
 
 def load():
-    global _lib
-    if _lib is None:
-        out = os.path.join(tempfile.mkdtemp(prefix="ray_integrate_ref_"), "ray_integrate_ref.so")
-        subprocess.run(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", os.path.join(HERE, "ray_integrate_ref.c"),
-                        "-o", out, "-lm"], check=True)
-        _lib = ctypes.CDLL(out)
-        _lib.ray_walk_ref.restype = ctypes.c_int32
-    return _lib
+    lib = c_ref.load("ray_integrate_ref")
+    lib.ray_walk_ref.restype = ctypes.c_int32
+    return lib
 
 
 def _p(a):

@@ -3,26 +3,18 @@ redistance_ref.c compiled on the fly (the nested separable form, which is the de
 crossing), and the fields the CPU and GPU tests share."""
 import ctypes
 import functools
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
+from tests import c_ref
+
 KEPT = -2
-_lib = None
 
 
 def load():
-    global _lib
-    if _lib is None:
-        out = os.path.join(tempfile.mkdtemp(prefix="redistance_ref_"), "redistance_ref.so")
-        subprocess.run(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", os.path.join(HERE, "redistance_ref.c"), "-o", out,
-                        "-lm"], check=True)
-        _lib = ctypes.CDLL(out)
-        _lib.redistance_ref.restype = ctypes.c_int64
-    return _lib
+    lib = c_ref.load("redistance_ref")
+    lib.redistance_ref.restype = ctypes.c_int64
+    return lib
 
 
 def _p(a):

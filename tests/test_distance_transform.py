@@ -11,7 +11,7 @@ import pytest
 import torch
 
 import pytorch_volumetric_amd as pv
-from pytorch_volumetric_amd import _lib
+from pytorch_volumetric_amd import _lib, occupancy
 from tests import distance_transform_ref as ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -37,6 +37,17 @@ def test_exports_header_and_binding():
     lib = _lib.load()
     assert hasattr(lib, "pvamd_distance_transform") and hasattr(lib, "pvamd_distance_transform_scratch_bytes")
     assert os.path.exists(os.path.join(ROOT, "pytorch_volumetric_amd", "csrc", "distance_transform.hip"))
+    # the lattice limits: defined in the header, read by the binding, used by the module and, below, by the library
+    assert _lib.LATTICE_MAX_AXIS == _lib.H["PVAMD_LATTICE_MAX_AXIS"] == occupancy.MAX_AXIS == 2048
+    assert _lib.EDT_MIN_AXIS == _lib.H["PVAMD_EDT_MIN_AXIS"] == occupancy.MIN_AXIS == 1
+    assert _lib.EDT_MAX_VOXELS == _lib.H["PVAMD_EDT_MAX_VOXELS"] == occupancy.MAX_VOXELS == 2 ** 31 - 1
+    for axis in range(3):
+        for n, want in ((occupancy.MAX_AXIS + 1, _lib.E_SHAPE), (occupancy.MIN_AXIS - 1, _lib.E_SHAPE),
+                        (occupancy.MAX_AXIS, _lib.H["PVAMD_E_NULL"])):  # the shape is tested before the pointers: no GPU is touched
+            shape = [occupancy.MIN_AXIS] * 3
+            shape[axis] = n
+            assert lib.pvamd_distance_transform(None, *shape, 1.0, 1, None, None, None, None, None) == want, shape
+            assert (lib.pvamd_distance_transform_scratch_bytes(*shape, 1) > 0) == (want != _lib.E_SHAPE), shape
 
 
 def test_scratch_size_is_the_library_function_and_refuses_what_the_entry_point_refuses():

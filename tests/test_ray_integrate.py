@@ -7,7 +7,7 @@ import pytest
 import torch
 
 import pytorch_volumetric_amd as pv
-from pytorch_volumetric_amd import _lib
+from pytorch_volumetric_amd import _lib, occupancy_map
 from tests import ray_integrate_ref as ref
 
 LATTICES = [(5, 7, 9), (2, 3, 300)]
@@ -22,6 +22,8 @@ def test_header_constants_reach_the_binding():
         assert name in _lib.SIGNATURES
     assert len(_lib.SIGNATURES["pvamd_ray_mark"][1]) == 8 and len(_lib.SIGNATURES["pvamd_occupancy_update"][1]) == 9
     assert pv.OccupancyMap is not None and pv.ray_marks is not None
+    assert _lib.LATTICE_MAX_AXIS == _lib.H["PVAMD_LATTICE_MAX_AXIS"] == occupancy_map.MAX_AXIS == 2048
+    assert _lib.RAY_MARK_MIN_AXIS == _lib.H["PVAMD_RAY_MARK_MIN_AXIS"] == occupancy_map.MIN_AXIS == 2
 
 
 @pytest.mark.parametrize("kwargs", [

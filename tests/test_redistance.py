@@ -25,6 +25,18 @@ def test_the_entry_points_reach_the_binding():
     assert _lib.ABI_VERSION == 16 and _lib.REDIST_KEPT == ref.KEPT == -2
     assert pv.redistance is redistance_module.redistance and pv.Redistance is redistance_module.Redistance
     assert pv.Redistance._fields == ("values", "gradients", "sites", "squared")
+    # the lattice limits: defined in the header, read by the binding, used by the module and, below, by the library
+    MIN, MAX = redistance_module.MIN_AXIS, redistance_module.MAX_AXIS
+    assert _lib.LATTICE_MAX_AXIS == _lib.H["PVAMD_LATTICE_MAX_AXIS"] == MAX == 2048
+    assert _lib.REDIST_MIN_AXIS == _lib.H["PVAMD_REDIST_MIN_AXIS"] == MIN == 2
+    assert _lib.REDIST_MAX_VOXELS == _lib.H["PVAMD_REDIST_MAX_VOXELS"] == redistance_module.MAX_VOXELS == 2 ** 29
+    lib = _lib.load()
+    for axis in range(3):
+        for n, want in ((MAX + 1, _lib.E_SHAPE), (MIN - 1, _lib.E_SHAPE), (MAX, _lib.H["PVAMD_E_NULL"])):
+            shape = [MIN] * 3  # the shape is tested before the pointers: no GPU is touched
+            shape[axis] = n
+            assert lib.pvamd_redistance(None, *shape, 1.0, 0.0, 1.0, None, None, None, None, None) == want, shape
+            assert (lib.pvamd_redistance_scratch_bytes(*shape) > 0) == (want != _lib.E_SHAPE), shape
 
 
 VALUES = torch.ones(3, 4, 5)

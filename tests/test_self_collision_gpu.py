@@ -4,7 +4,6 @@ product; every pair bit-equal to the one-leaf min_over_points under the pair tra
 synthetic arm and on a folded three-link arm; the generic path; autograd to q; reproducibility, graph capture, peak memory."""
 import ctypes
 import os
-import subprocess
 import tempfile
 
 import numpy as np
@@ -14,11 +13,11 @@ import torch
 import pytorch_volumetric_amd as pv
 import workloads as W
 from pytorch_volumetric_amd import mesh_io
+from tests import c_ref
 from tests.test_interp_gpu import build_robot
 from tests.test_min_over_points_gpu import restated_argmin, same_bits
 
 pytestmark = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
 S = 8
 
 
@@ -35,10 +34,7 @@ def robot_tri():
 
 @pytest.fixture(scope="module")
 def ref_lib():
-    out = os.path.join(tempfile.mkdtemp(prefix="leaf_pair_ref_"), "leaf_pair_ref.so")
-    subprocess.run(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", os.path.join(HERE, "leaf_pair_ref.c"), "-o", out, "-lm"],
-                   check=True)
-    return ctypes.CDLL(out)
+    return c_ref.load("leaf_pair_ref")
 
 
 def leaf_sets(sizes, seed):

@@ -22,6 +22,19 @@ def test_the_entry_points_reach_the_binding():
     assert _lib.ABI_VERSION == 16
     assert pv.TSDFVolume is tsdf_module.TSDFVolume and pv.TSDFField is tsdf_module.TSDFField
     assert issubclass(pv.TSDFField, pv.OccupancySDF)  # what CachedSDF takes records from as they are
+    # the lattice limits: defined in the header, read by the binding, used by the module and, below, by the library
+    MIN, MAX = tsdf_module.MIN_AXIS, tsdf_module.MAX_AXIS
+    assert _lib.LATTICE_MAX_AXIS == _lib.H["PVAMD_LATTICE_MAX_AXIS"] == MAX == 2048
+    assert _lib.TSDF_MIN_AXIS == _lib.H["PVAMD_TSDF_MIN_AXIS"] == MIN == 2
+    assert _lib.TSDF_MAX_VOXELS == _lib.H["PVAMD_TSDF_MAX_VOXELS"] == 2 ** 31 - 1
+    assert _lib.TSDF_MAX_PIXELS == _lib.H["PVAMD_TSDF_MAX_PIXELS"] == tsdf_module.MAX_PIXELS == 2 ** 31 - 1
+    lib = _lib.load()
+    for axis in range(3):
+        for n, want in ((MAX + 1, _lib.E_SHAPE), (MIN - 1, _lib.E_SHAPE), (MAX, _lib.H["PVAMD_E_NULL"])):
+            shape = [MIN] * 3  # the shape is tested before the pointers: no GPU is touched
+            shape[axis] = n
+            assert lib.pvamd_tsdf_records(None, *shape, 0.02, 0.06, 0.0, 1.0, None, None) == want, shape
+    assert lib.pvamd_tsdf_records(None, MAX, MAX, MAX, 0.02, 0.06, 0.0, 1.0, None, None) == _lib.E_SHAPE  # too many voxels
 
 
 @pytest.mark.parametrize("kwargs", [

@@ -1,17 +1,14 @@
 """Restatement of the TSDF contract (include/pvamd.h "TSDF integration") for its tests -- TEST INFRASTRUCTURE: tsdf_ref.c compiled
 on the fly, and the scenes the CPU and GPU tests share: analytic depth images of a ball and the camera poses that see it."""
 import ctypes
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
+from tests import c_ref
+
 # the branch counters of tsdf_ref.c, in its enum's order
 HITS = ("behind", "u_low_edge", "u_high_edge", "u_half", "clamped", "no_return", "too_far", "band_edge", "behind_band",
         "saturated_edge", "updated", "outside")
-_lib = None
 
 
 class Lattice(ctypes.Structure):
@@ -24,13 +21,7 @@ class Lattice(ctypes.Structure):
 
 
 def load():
-    global _lib
-    if _lib is None:
-        out = os.path.join(tempfile.mkdtemp(prefix="tsdf_ref_"), "tsdf_ref.so")
-        subprocess.run(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", os.path.join(HERE, "tsdf_ref.c"), "-o", out, "-lm"],
-                       check=True)
-        _lib = ctypes.CDLL(out)
-    return _lib
+    return c_ref.load("tsdf_ref")
 
 
 def _p(a):
