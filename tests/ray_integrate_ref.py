@@ -107,6 +107,31 @@ def generic_rays(lat, count, seed):
     return world(lat, o), world(lat, e)
 
 
+def axis_rays(lat, axis):
+    """(origins (16, 3), endpoints (16, 3)) float32: rays that run the whole length of `axis` -- the four diagonals between the
+    centres of opposite corner voxels, a ray through voxel centres from end to end and one from outside to outside, one on a
+    cell face and one on a cell edge (half-integer lattice coordinates on the other axes), each in both directions."""
+    n = np.array(lat.dims, np.float64)
+    p, q = (axis + 1) % 3, (axis + 2) % 3
+    pairs = []
+    for sp in (0, 1):
+        for sq in (0, 1):  # corner to opposite corner
+            a, b = np.zeros(3), n - 1
+            a[p], b[p] = (b[p], 0.0) if sp else (0.0, b[p])
+            a[q], b[q] = (b[q], 0.0) if sq else (0.0, b[q])
+            pairs.append((a, b))
+    for ends, off_p, off_q in (((0.0, n[axis] - 1), 0.0, 1.0), ((-3.0, n[axis] + 2), 1.0, 0.0),  # through voxel centres
+                               ((-1.25, n[axis] + 0.25), 0.5, 0.0), ((0.0, n[axis] - 1), 0.5, 0.5)):  # on a face, on an edge
+        a, b = np.zeros(3), np.zeros(3)
+        a[axis], b[axis] = ends
+        a[p] = b[p] = off_p
+        a[q] = b[q] = off_q
+        pairs.append((a, b))
+    so = np.array([a for a, b in pairs] + [b for a, b in pairs])
+    se = np.array([b for a, b in pairs] + [a for a, b in pairs])
+    return world(lat, so), world(lat, se)
+
+
 def mixed_rays(lat, R, seed):
     """(origins (R, 3), endpoints (R, 3)) float32: every kind of ray the contract has a statement for, in a seeded shuffle.
     Origins inside and outside the grid, endpoints outside it, rays with one or two zero components, rays through cell corners

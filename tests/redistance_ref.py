@@ -97,7 +97,46 @@ def tie_field(shape):
     return rec
 
 
-FIELDS = {"smooth": smooth_field, "tie": tie_field}
+@functools.lru_cache(maxsize=None)
+def half_field(shape):
+    """(nx, ny, nz, 4) float32 records, read-only: +1 up to the middle of x, -1 beyond it.  The only crossings sit at f = 0.5
+    exactly, so the voxels three slabs to either side of them are exactly 3.5 voxels away, squared == 12.25: whether they keep
+    their site under max_distance = 3.5 * resolution turns on the rounding of max_distance / resolution and of Rv * Rv."""
+    values = np.ones(shape)
+    values[shape[0] // 2 + 1:] = -1.0
+    rec = as_records(values, np.ones(shape + (3,)))
+    rec.flags.writeable = False
+    return rec
+
+
+FIELDS = {"smooth": smooth_field, "tie": tie_field, "half": half_field}
+ROUNDING_RESOLUTIONS = (0.013, 0.02, 0.037)  # max_distance / resolution of 3.5 * resolution: below 3.5 under the first only
+
+TINY = (1e-39, -1e-39, 1.4e-45, -1.4e-45, 0.0, -0.0)  # denormals of either sign, the smallest ones, and both zeros
+
+
+@functools.lru_cache(maxsize=None)
+def tiny_field(shape, seed=9):
+    """((nx, ny, nz, 4) float32 records, (nx, ny, nz) bool: which samples were replaced), read-only: smooth_field with about 1 %
+    of its samples replaced, in a seeded pattern, by TINY: the samples for which f = V_a / (V_a - V_b) has a denormal numerator
+    or denominator, and for which (V_a < 0) == (V_b < 0) turns on the sign of zero."""
+    rec = smooth_field(shape).copy()
+    kind = np.random.default_rng(seed).integers(0, 100 * len(TINY), size=shape)
+    for code, value in enumerate(TINY):
+        rec[..., 0][kind == code] = np.float32(value)
+    rec.flags.writeable = False
+    return rec, kind < len(TINY)
+
+
+@functools.lru_cache(maxsize=None)
+def one_negative_field(shape, far, seed=13):
+    """(nx, ny, nz, 4) float32 records, read-only: positive noise everywhere but one negative voxel, the far corner
+    (n - 1 on every axis) or voxel (0, 0, 0): the lattice's only crossings are on the three edges that leave it."""
+    values = np.random.default_rng(seed).uniform(0.5, 1.5, size=shape)
+    values[tuple(s - 1 for s in shape) if far else (0, 0, 0)] = -0.7
+    rec = as_records(values)
+    rec.flags.writeable = False
+    return rec
 
 BALL_RADIUS, BALL_RES, BALL_BAND = 0.3, 0.02, 0.06  # the band: 3 voxels
 

@@ -104,6 +104,34 @@ def look_at(eye, target, up=(0.0, 0.0, 1.0)):
     return pose
 
 
+def wall_frames(ranges, res, K=3, height=48, width=64, axis=None):
+    """(depth (K, H, W) float32, poses (K, 4, 4) float64), read-only: the frames of tests/test_tsdf_gpu.py for any lattice, its
+    lengths in voxels (at res = 0.25 the same scene): K cameras around and inside the lattice, every one rotated against its
+    axes, looking at a rippled wall through its middle; a tenth of the pixels hold what a sensor reports instead of a return
+    (0, a negative number, NaN, inf) or a depth past any max_depth below 1000.
+    `axis`: the lattice is a line along this axis; the cameras stand beside it, off its middle, and see it obliquely from
+    end to end."""
+    ranges = np.array(ranges, np.float64)
+    centre, reach = ranges.mean(axis=1), np.linalg.norm(ranges[:, 1] - ranges[:, 0]) / 2 + 4.0 * res
+    if axis is None:
+        eyes = [centre + reach * np.array([0.6, -0.5, 0.62]), centre + 0.2 * reach * np.array([-0.3, 0.4, 0.1]),  # the second: inside
+                centre + reach * np.array([-0.45, 0.8, -0.4])]
+    else:
+        along, beside, third = np.eye(3)[axis], np.eye(3)[(axis + 1) % 3], np.eye(3)[(axis + 2) % 3]
+        eyes = [centre + reach * (0.3 * along + 2.6 * beside + 0.3 * third), centre + reach * (-0.25 * along - 2.5 * beside + 0.4 * third)]
+    poses = np.stack([look_at(eyes[k % len(eyes)], centre + 0.4 * res * k) for k in range(K)])
+    rows, cols = np.meshgrid(np.arange(height), np.arange(width), indexing="ij")
+    mean = 1.0 if axis is None else 1.03  # beside a line the wall stands a little behind its middle: parts of either end are in front of it
+    depth = np.stack([np.linalg.norm(eyes[k % len(eyes)] - centre) * (mean + 0.3 * np.sin(0.3 * cols + k) * np.cos(0.2 * rows)) + 0.2 * res
+                      for k in range(K)]).astype(np.float32)
+    rng = np.random.default_rng(7)
+    kind = rng.integers(0, 50, size=depth.shape)
+    for code, value in enumerate((0.0, -1.5, np.nan, np.inf, 1000.0)):
+        depth[kind == code] = value
+    depth.flags.writeable = poses.flags.writeable = False
+    return depth, poses
+
+
 def axis_views(centre, distance):
     """Six poses looking at `centre` from `distance` along -x, +x, -y, +y, -z, +z."""
     centre = np.asarray(centre, np.float64)
