@@ -920,7 +920,7 @@ int pvamd_composed_ray_cast_backward_f64(const pvamd_grid_t* grids, int32_t S, c
                                          void* stream);
 
 /* ---- Volume lattices ----
- * The four sections below work on a 3-D lattice of nx * ny * nz voxels in C order (x slowest, z fastest): voxel (x, y, z) has the
+ * The five sections below work on a 3-D lattice of nx * ny * nz voxels in C order (x slowest, z fastest): voxel (x, y, z) has the
  * flat index (x * ny + y) * nz + z, and a record is [4] float32 (val, gx, gy, gz).  No axis is longer than
  * PVAMD_LATTICE_MAX_AXIS: a coordinate takes 11 bits in the states the line passes hand on.  Each section states its own
  * shortest axis and its cap on the voxels.                                                                                     */
@@ -1114,6 +1114,67 @@ int pvamd_tsdf_records(const float* state, int32_t nx, int32_t ny, int32_t nz, f
 int64_t pvamd_redistance_scratch_bytes(int32_t nx, int32_t ny, int32_t nz);
 int pvamd_redistance(const float* records_in, int32_t nx, int32_t ny, int32_t nz, float resolution, float band, float max_distance,
                      float* records_out, int32_t* sites, float* squared, void* scratch, void* stream);
+
+/* ---- Surface extraction (triangle meshes from sampled signed fields) ----
+ * pvamd_surface_count and pvamd_surface_emit turn the level set of a field sampled on the lattice into an indexed triangle mesh by
+ * naive surface nets (dual contouring without a QEF): one vertex per lattice cell the surface passes through, placed at the mean
+ * of the crossings on the cell's edges, and one quad (two triangles) per lattice edge that carries a crossing.  No case table.
+ * count sizes the result and prepares scratch; emit writes it.  Replaces nothing in the reference.
+ * EVERYTHING below is float32 with every operation rounded on its own (no contraction, no fma, correctly rounded division and
+ * square root).
+ *  1. Samples.  records: device [n][4] float32 packed (val, gx, gy, gz) in C order, V_i the val of voxel i; W_i = V_i - level.
+ *     A sample is usable iff W_i is finite and (valid == NULL or valid[i] != 0); it is negative iff W_i < 0.
+ *  2. Crossings.  For axis k and a voxel a with a_k < n_k - 1, b = a + e_k: the lattice edge (a, b) carries a crossing iff both
+ *     ends are usable and (W_a < 0) != (W_b < 0).  It lies at f = W_a / (W_a - W_b) along k.  With level = 0 and valid = NULL
+ *     these are exactly the crossings of "Redistancing" 2.
+ *  3. Cells.  Cell c, c_j <= n_j - 2 on every axis, has the corners c + {0, 1}^3.  It is active iff all eight corners are usable
+ *     and they are not all negative and not all non-negative.  A cell with an unusable corner emits nothing: no surface between
+ *     seen and unseen space.
+ *  4. Vertex of an active cell.  The twelve edges in this order: the four along x by (dy, dz) = (0,0), (0,1), (1,0), (1,1), then
+ *     the four along y by (dx, dz), then the four along z by (dx, dy), in the same order.  Starting from S = (0, 0, 0) and m = 0,
+ *     each edge that carries a crossing adds its offset inside the cell to S, component by component -- f on the edge's own
+ *     axis, the edge's 0 / 1 on the other two -- and 1 to m.  p_j = (float)c_j + S_j / (float)m in voxels, and the vertex is
+ *     P_j = fmin_j + p_j * fres_j with the lattice of "TSDF integration" 2. (the descriptor's float32 fields): a whole p gives
+ *     the voxel's centre bit for bit.
+ *  5. Normal (normals != NULL).  In the same edge order, from N = (0, 0, 0): N_j = N_j + (g_a,j + f * (g_b,j - g_a,j)) with g the
+ *     gradients of the records at the edge's ends.  len = sqrtf((N_x * N_x + N_y * N_y) + N_z * N_z); the row is N / len when
+ *     len > 0 and finite, else zeros.
+ *  6. Vertex ids.  The active cells, numbered in flat C order of c.  Every active cell has a vertex, also one that no face names
+ *     (on the lattice's border, next to unusable samples).
+ *  7. Faces.  A crossing of family k at a emits one quad iff the four cells round its edge exist and are active: with (p, q) the
+ *     other axes in cyclic order (x: (y, z); y: (z, x); z: (x, y)), C0 = a - e_p - e_q, C1 = a - e_q, C2 = a, C3 = a - e_p.  Its
+ *     vertices are (v0, v1, v2, v3) = ids of (C0, C1, C2, C3) when W_a < 0 and of (C0, C3, C2, C1) otherwise, so that the face
+ *     normals point to the non-negative side; its triangles are (v0, v1, v2) and (v0, v2, v3), in consecutive rows.  Quads are
+ *     ordered by flat(a) * 3 + k.  counts = (number of vertices, number of triangles).
+ *  8. Capacities.  emit writes the vertex (and normal) rows < max_vertices and the face rows < max_faces and not a byte beyond
+ *     them: complete with capacities >= counts, the exact prefix with smaller ones (faces may then name vertices that were not
+ *     written).  A fixed budget makes count + emit capturable in a graph.  scratch as count left it serves any number of emit
+ *     calls while records, valid, level and the shape are unchanged; emit does not write it.
+ *  9. Topology, documented and not promised: a closed field away from the border gives a closed, consistently oriented mesh
+ *     wherever every cell's sign pattern is unambiguous; ambiguous patterns can give an edge four triangles, and an f of
+ *     exactly 0 or 1 can make two vertices of a quad coincide (a degenerate triangle).
+ * grid: a finalized descriptor used as the lattice only (vox unused); each axis in [PVAMD_SURFACE_MIN_AXIS,
+ * PVAMD_LATTICE_MAX_AXIS] and n <= PVAMD_SURFACE_MAX_VOXELS: vertex ids and quad counts (<= 3 n) then fit an int32, and the
+ * triangle counts are int64.  Argument errors return before any launch, tested in this order: PVAMD_E_NULL for grid;
+ * PVAMD_E_SHAPE for those limits or a negative capacity; PVAMD_E_MODE for a descriptor that is not finalized and for a NaN or
+ * infinite level; PVAMD_E_NULL (valid and normals may be NULL; vertices / faces only with a capacity of zero); PVAMD_E_ALIGN for
+ * records not 16-byte, counts not 8-byte, scratch, vertices, normals or faces not 4-byte aligned.
+ * records and valid (device [n] uint8) are never written.  counts: device [2] int64.  vertices, normals: device
+ * [max_vertices][3] float32.  faces: device [max_faces][3] int32.  scratch: device, pvamd_surface_scratch_bytes(nx, ny, nz) bytes,
+ * 4-byte aligned; that function is the definition (0 for shapes the entry points refuse) and there is no macro.  The ids come
+ * from an exclusive scan over blocks of PVAMD_SURFACE_CHUNK consecutive voxels, whose sums one workgroup scans
+ * PVAMD_SURFACE_SCAN_WIDTH at a time; in-wave ranks are popcounts of lower lanes.
+ * Stream-ordered, no allocation, no device -> host synchronisation, no atomics: capturable in a graph, and two calls give the
+ * same bits.                                                                                                                    */
+#define PVAMD_SURFACE_MIN_AXIS 2
+#define PVAMD_SURFACE_MAX_VOXELS 536870912 /* 2^29 */
+#define PVAMD_SURFACE_CHUNK 256
+#define PVAMD_SURFACE_SCAN_WIDTH 1024
+int64_t pvamd_surface_scratch_bytes(int32_t nx, int32_t ny, int32_t nz);
+int pvamd_surface_count(const pvamd_grid_t* grid, const float* records, const uint8_t* valid, float level, void* scratch,
+                        int64_t* counts, void* stream);
+int pvamd_surface_emit(const pvamd_grid_t* grid, const float* records, const uint8_t* valid, float level, const void* scratch,
+                       int64_t max_vertices, int64_t max_faces, float* vertices, float* normals, int32_t* faces, void* stream);
 #ifdef __cplusplus
 }
 #endif

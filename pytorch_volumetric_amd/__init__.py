@@ -19,6 +19,7 @@ from pytorch_volumetric_amd.voxel_containers import (ExpandingVoxelGrid, VoxelGr
 from pytorch_volumetric_amd.occupancy import DistanceTransform, OccupancySDF, cached_sdf_from_voxels, distance_transform
 from pytorch_volumetric_amd.occupancy_map import OccupancyMap, ray_marks
 from pytorch_volumetric_amd.redistance import Redistance, redistance
+from pytorch_volumetric_amd.surface import Surface, extract_surface
 from pytorch_volumetric_amd.tsdf import TSDFField, TSDFVolume
 from pytorch_volumetric_amd.volume import is_inside
 from pytorch_volumetric_amd.visualization import draw_sdf_slice, get_transformed_meshes

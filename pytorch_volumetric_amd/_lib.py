@@ -111,6 +111,12 @@ def redistance_scratch_bytes(nx, ny, nz):
 
 
 @_remembered
+def surface_scratch_bytes(nx, ny, nz):
+    """pvamd_surface_scratch_bytes: the cell -> vertex id map, the scanned chunk sums, then three bytes of classes per voxel."""
+    return load().pvamd_surface_scratch_bytes(nx, ny, nz)
+
+
+@_remembered
 def composed_query_kernel(A, P, flags):
     """pvamd_composed_query_kernel: the kernel (CO_KERNEL_*) pvamd_composed_query launches for A configurations of P points."""
     return load().pvamd_composed_query_kernel(A, P, flags)
@@ -257,6 +263,8 @@ TSDF_MAX_VOXELS = H["PVAMD_TSDF_MAX_VOXELS"]
 TSDF_MAX_PIXELS = H["PVAMD_TSDF_MAX_PIXELS"]  # K * H * W of one pvamd_tsdf_integrate call
 REDIST_MIN_AXIS = H["PVAMD_REDIST_MIN_AXIS"]
 REDIST_MAX_VOXELS = H["PVAMD_REDIST_MAX_VOXELS"]
+SURFACE_MIN_AXIS = H["PVAMD_SURFACE_MIN_AXIS"]
+SURFACE_MAX_VOXELS = H["PVAMD_SURFACE_MAX_VOXELS"]
 E_SHAPE = H["PVAMD_E_SHAPE"]
 _ERRORS = {H["PVAMD_E_NULL"]: "a required pointer is NULL", H["PVAMD_E_SHAPE"]: "a size/shape argument is out of range",
            H["PVAMD_E_ALIGN"]: "a pointer is misaligned", H["PVAMD_E_MODE"]: "unknown enum value"}

@@ -996,6 +996,18 @@ class CachedSDF(ObjectFrameSDF):
                                                   _lib.ptr(d), R, *args, *map(_lib.ptr, out), _lib.stream_ptr()), name)
         return _ray_result(out, lead, self.device), {"o": o, "d": d, "out": out}
 
+    def extract_mesh(self, level=0.0, normals=True):
+        """The surface `value == level` of the cache as a Surface (vertices, faces, normals on the GPU), by naive surface nets over
+        the cache's own records and lattice (surface.extract_surface): whatever filled the cache -- a mesh, an occupancy or TSDF
+        field -- and whatever the interpolation mode and out-of-bounds strategy.  normals=True interpolates unit normals from the
+        cached gradients.  `.to_trimesh()` of the result is what MeshObjectFactory(mesh=...) and mesh_io.save_obj take."""
+        from pytorch_volumetric_amd import surface
+        level, normals = surface.check_level(level), surface.check_normals(normals)
+        if self._dim != 3:
+            raise ValueError("extract_mesh needs a 3-D cache, this one is planar")
+        surface.check_shape(self._view.shape, "the cache")
+        return surface.surface_of_records(self._grid_desc(), self._packed, None, level, normals)
+
     def outside_surface(self, points_in_object_frame, surface_level=0):
         """sdf.py:593-602 (trilinear caches: the interpolated value > surface_level in range, True out of range)"""
         lib = _lib.load()
