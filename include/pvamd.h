@@ -819,6 +819,44 @@ int pvamd_pose_lm_step(int32_t B, const double* sums, int32_t first, double* Wac
                        int32_t* accepted, double* Wtry, float* W_next, double up, double down, double lambda_min,
                        double lambda_max, void* stream);
 
+/* ---- Semantic normal equations (semantic_normal_equations / refine_poses with semantics, targets or huber_delta) ----
+ * "Chamfer normal equations" with a kind and a target distance per point and Huber weights: the cost of a pose that must keep
+ * known-free points outside the object, known-occupied points inside it and surface points on it, robust against outliers.
+ * Steps 1, 2 and 5 of that section hold as they stand (x, (v, n), j, the caller's scaling; N is every point, ignored ones
+ * included); the grid and mode arguments are its.  Per pair (b, i), all in float64:
+ *  1. kind_i = kinds[i] (uint8; PVAMD_POINT_*; any value >= PVAMD_POINT_IGNORE is IGNORE; kinds NULL: every point is SURFACE).
+ *     s_i = targets[i] (float32; targets NULL: 0).  r = (double)v - (double)s_i, rounded once.
+ *  2. The pair is inactive when kind_i is IGNORE, when it is FREE and r >= 0, or when it is OCCUPIED and r <= 0.  An inactive pair
+ *     adds nothing: its terms are skipped, not added as zeros, so a NaN n there reaches no sum.  A NaN r of a SURFACE, FREE or
+ *     OCCUPIED point fails both comparisons: the pair is active and makes its pose's sums NaN.  Accumulators start at +0.0.
+ *  3. An active pair, a = |r|, delta = huber_delta (> 0; +inf: no pair is an outlier):
+ *     inlier (not a > delta): s0 = fma(r, r, s0); s1_k = fma(r, j_k, s1_k); s2_rc = fma(j_r, j_c, s2_rc) -- the statements of
+ *       "Chamfer normal equations" with r for v.
+ *     outlier (a > delta): w = delta / a; s0 = fma(delta, (a + a) - delta, s0); q = w r, s1_k = fma(q, j_k, s1_k); u_r = w j_r,
+ *       s2_rc = fma(u_r, j_c, s2_rc).  Each named product and quotient rounds once.  This is iteratively reweighted least
+ *       squares with the Huber function rho: s0 = sum rho, s1 = sum w r j, s2 = sum w j j^T (rho = r^2 inside delta).
+ *  4. The order of summation is pvamd_chamfer_normal_eq's: per lane in point order over its points of a PVAMD_REG_CHUNK-point
+ *     chunk, a wave butterfly, the four waves in order, the chunks in chunk order.  With kinds NULL or all 0, targets NULL or all
+ *     0 and huber_delta = +inf the 28 sums are those of pvamd_chamfer_normal_eq bit for bit.
+ *  5. out_counts[b][PVAMD_SEM_COUNTS] (int64): the points that pass the range decision of the query (every point, whatever its
+ *     kind: out_counts of pvamd_chamfer_normal_eq); the active pairs of kind SURFACE; of kind FREE; of kind OCCUPIED; the active
+ *     pairs that took the outlier branch.
+ * Bitwise reproducible; no float atomics, no allocation, no device -> host synchronisation; a NaN touches its own pose only.
+ * pvamd_semantic_normal_eq: the argument checks of pvamd_chamfer_normal_eq, and huber_delta NaN or <= 0 is PVAMD_E_MODE; all
+ *   before any launch.  kinds device [N] or NULL, targets device [N] (4-byte aligned) or NULL.  out_sums device [B][28].
+ *   scratch: device, pvamd_semantic_normal_eq_scratch_bytes(B, N) bytes, 8-byte aligned (28 sums and 5 counts per pose and
+ *   chunk); the exported function is the definition of the size.  The sums feed pvamd_pose_lm_step as they are: it accepts on
+ *   s0 alone.                                                                                                                    */
+#define PVAMD_POINT_SURFACE  0 /* penalised on either side: r^2 */
+#define PVAMD_POINT_FREE     1 /* penalised where r < 0 */
+#define PVAMD_POINT_OCCUPIED 2 /* penalised where r > 0 */
+#define PVAMD_POINT_IGNORE   3 /* never penalised; so is every larger value */
+#define PVAMD_SEM_COUNTS 5     /* in range, active SURFACE, active FREE, active OCCUPIED, outliers */
+int64_t pvamd_semantic_normal_eq_scratch_bytes(int32_t B, int64_t N);
+int pvamd_semantic_normal_eq(const pvamd_grid_t* grid, int32_t mode, const float* W, int32_t B, const float* points, int64_t N,
+                             const uint8_t* kinds, const float* targets, double huber_delta, double* out_sums,
+                             int64_t* out_counts, void* scratch, void* stream);
+
 /* ---- Ray casting (CachedSDF.ray_cast / ComposedSDF.ray_cast / RobotSDF.ray_cast) ----
  * Sphere tracing: where the ray o + t d first meets the surface of one cached grid (3-D, BOUNDING_BOX, else PVAMD_E_MODE; either
  * index arithmetic) or of a composition ("Minimum over points": S leaves, A configurations, tf device [S*A][4][4] leaf-major,

@@ -11,8 +11,9 @@ from pytorch_volumetric_amd.sdf import (CachedSDF, ComposedSDF, HingeOverPoints,
 from pytorch_volumetric_amd.model_to_sdf import RobotSDF, aabb_to_ordered_end_points, cache_link_sdf_factory
 from pytorch_volumetric_amd.chamfer import (PlausibleDiversity, batch_chamfer_dist, pairwise_distance,
                                             pairwise_distance_chamfer)
-from pytorch_volumetric_amd.registration import (ChamferNormalEquations, PoseRefinement, chamfer_normal_equations,
-                                                 refine_poses)
+from pytorch_volumetric_amd.registration import (POINT_FREE, POINT_IGNORE, POINT_OCCUPIED, POINT_SURFACE, ChamferNormalEquations,
+                                                 PoseRefinement, SemanticNormalEquations, chamfer_normal_equations,
+                                                 refine_poses, semantic_normal_equations)
 from pytorch_volumetric_amd.voxel import get_coordinates_and_points_in_grid, get_divisible_range_by_resolution
 from pytorch_volumetric_amd.voxel_containers import (ExpandingVoxelGrid, VoxelGrid, VoxelSet, Voxels,
                                                      voxel_down_sample)

@@ -99,6 +99,12 @@ def chamfer_normal_eq_scratch_bytes(B, N):
 
 
 @_remembered
+def semantic_normal_eq_scratch_bytes(B, N):
+    """pvamd_semantic_normal_eq_scratch_bytes: 28 float64 sums and five int64 counts per pose and point chunk."""
+    return load().pvamd_semantic_normal_eq_scratch_bytes(B, N)
+
+
+@_remembered
 def distance_transform_scratch_bytes(nx, ny, nz, signed):
     """pvamd_distance_transform_scratch_bytes: one int32 per voxel, site class and line pass that hands on a state."""
     return load().pvamd_distance_transform_scratch_bytes(nx, ny, nz, int(signed))
@@ -245,6 +251,11 @@ LEAF_MODES = {"nearest": H["PVAMD_LEAF_NEAREST"], "trilinear": H["PVAMD_LEAF_TRI
 MOP_CHUNK = H["PVAMD_MOP_CHUNK"]
 REG_CHUNK = H["PVAMD_REG_CHUNK"]
 REG_SUMS = H["PVAMD_REG_SUMS"]  # the row length of pvamd_chamfer_normal_eq's out_sums
+POINT_SURFACE = H["PVAMD_POINT_SURFACE"]  # POINT_*: the kind of a point of pvamd_semantic_normal_eq
+POINT_FREE = H["PVAMD_POINT_FREE"]
+POINT_OCCUPIED = H["PVAMD_POINT_OCCUPIED"]
+POINT_IGNORE = H["PVAMD_POINT_IGNORE"]  # and every larger value
+SEM_COUNTS = H["PVAMD_SEM_COUNTS"]  # the row length of pvamd_semantic_normal_eq's out_counts
 RAY_MISS = H["PVAMD_RAY_MISS"]  # RAY_*: the status codes of the ray-cast entry points
 RAY_HIT = H["PVAMD_RAY_HIT"]
 RAY_MAX_STEPS = H["PVAMD_RAY_MAX_STEPS"]

@@ -8,6 +8,8 @@
 //                                 row per (chunk, b)
 //   pass 2 (reg_finish_kernel)   one thread per (b, entry): the chunks' rows added in chunk order
 //   pose_lm_step_kernel          one thread per pose, float64: accept / reject, damped Cholesky solve, retraction
+//   sem_partial_kernel, sem_finish_kernel ("Semantic normal equations")  passes 1 and 2 with a kind and a target distance per
+//                                 point and Huber weights, in the same order; five counts per pose beside the 28 sums
 // Every order depends only on (B, N): the result repeats bit for bit.  No float atomics, no host synchronisation.  The (B, N, 3)
 // transformed cloud and the (B, N) field never reach HBM.
 #include "common.h"
@@ -101,6 +103,125 @@ __global__ __launch_bounds__(256) void reg_finish_kernel(int B, int64_t nchunks,
             int64_t n = 0;
             for (int64_t c = 0; c < nchunks; ++c) n += slab_count[c * B + b];
             out_counts[b] = n;
+        }
+    }
+}
+
+// ---- "Semantic normal equations": reg_partial_kernel with a kind and a target per point and Huber weights ----
+// The same workgroup, chunk and lane-to-point assignment, so the same order of summation; per point one byte and one float more
+// are loaded (a NULL kinds / targets is a wave-uniform branch).  An inactive pair skips its 28 statements; an active one enters
+// them as (q, u) = (r, j) or, past delta, (w r, w j): with q = r and u = j they are reg_partial_kernel's own, bit for bit.
+// slab: double [nchunks][B][28], then int64 [nchunks][B][5]
+constexpr int kSemCounts = PVAMD_SEM_COUNTS;
+
+template <bool INTERP>
+__global__ __launch_bounds__(kRegBlock) void sem_partial_kernel(const pvamd_grid_t g, const float* __restrict__ W, int B,
+                                                                const float* __restrict__ pts, int64_t N,
+                                                                const uint8_t* __restrict__ kinds,
+                                                                const float* __restrict__ targets, double delta,
+                                                                double* __restrict__ slab, int64_t* __restrict__ slab_count) {
+    __shared__ double ws[kRegBlock / 64][kRegSums];
+    __shared__ int wc[kRegBlock / 64][kSemCounts];
+    const int64_t chunk = blockIdx.x;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int b = blockIdx.y; b < B; b += gridDim.y) {
+        const float* M = W + 16 * (int64_t)b;  // wave-uniform: scalar loads
+        double acc[kRegSums];
+#pragma unroll
+        for (int e = 0; e < kRegSums; ++e) acc[e] = 0.0;
+        int cnt[kSemCounts];
+#pragma unroll
+        for (int e = 0; e < kSemCounts; ++e) cnt[e] = 0;
+#pragma unroll 1
+        for (int k = 0; k < kRegK; ++k) {
+            const int64_t i = chunk * PVAMD_REG_CHUNK + (int64_t)k * kRegBlock + threadIdx.x;
+            if (i < N) {
+                const float p[3] = {pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]};
+                const int kind = kinds ? (int)kinds[i] : PVAMD_POINT_SURFACE;
+                const float target = targets ? targets[i] : 0.f;
+                float x[3], o[4];
+                LeafOps<float>::xform(M, p, x);
+                MopLeaf<float, INTERP>::eval(g, x, o);
+                cnt[0] += in_range(g, x[0], x[1], x[2]);
+                const double r = (double)o[0] - (double)target;
+                // written as the contract's inactive cases negated: a NaN r fails both comparisons and stays active
+                const bool active = kind == PVAMD_POINT_SURFACE || (kind == PVAMD_POINT_FREE && !(r >= 0.0)) ||
+                                    (kind == PVAMD_POINT_OCCUPIED && !(r <= 0.0));
+                if (active) {
+                    double j[6], u[6];
+                    j[0] = (double)o[1]; j[1] = (double)o[2]; j[2] = (double)o[3];
+                    // x cross n: each product of two float32 values is exact in float64, so each component rounds once
+                    j[3] = (double)x[1] * j[2] - (double)x[2] * j[1];
+                    j[4] = (double)x[2] * j[0] - (double)x[0] * j[2];
+                    j[5] = (double)x[0] * j[1] - (double)x[1] * j[0];
+                    const double a = __builtin_fabs(r);
+                    double q = r;
+#pragma unroll
+                    for (int c = 0; c < 6; ++c) u[c] = j[c];
+                    const bool outlier = a > delta;
+                    if (outlier) {  // per lane: the one float64 division of the pass
+                        const double w = delta / a;
+                        acc[0] = __builtin_fma(delta, (a + a) - delta, acc[0]);
+                        q = w * r;
+#pragma unroll
+                        for (int c = 0; c < 6; ++c) u[c] = w * j[c];
+                    } else {
+                        acc[0] = __builtin_fma(r, r, acc[0]);
+                    }
+                    cnt[1] += kind == PVAMD_POINT_SURFACE;
+                    cnt[2] += kind == PVAMD_POINT_FREE;
+                    cnt[3] += kind == PVAMD_POINT_OCCUPIED;
+                    cnt[4] += outlier;
+                    int e = 7;
+#pragma unroll
+                    for (int rr = 0; rr < 6; ++rr) {
+                        acc[1 + rr] = __builtin_fma(q, j[rr], acc[1 + rr]);
+#pragma unroll
+                        for (int c = rr; c < 6; ++c, ++e) acc[e] = __builtin_fma(u[rr], j[c], acc[e]);
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < kRegSums; ++e) acc[e] = hop_wave_sum<double>(acc[e]);
+#pragma unroll
+        for (int e = 0; e < kSemCounts; ++e) cnt[e] = hop_wave_sum<int>(cnt[e]);
+        if (lane == 0) {
+#pragma unroll
+            for (int e = 0; e < kRegSums; ++e) ws[wave][e] = acc[e];
+#pragma unroll
+            for (int e = 0; e < kSemCounts; ++e) wc[wave][e] = cnt[e];
+        }
+        __syncthreads();
+        if (threadIdx.x < kRegSums) {
+            double s = ws[0][threadIdx.x];
+            for (int w = 1; w < kRegBlock / 64; ++w) s += ws[w][threadIdx.x];
+            slab[(chunk * B + b) * kRegSums + threadIdx.x] = s;
+        } else if (threadIdx.x < kRegSums + kSemCounts) {
+            const int e = threadIdx.x - kRegSums;
+            int c = wc[0][e];
+            for (int w = 1; w < kRegBlock / 64; ++w) c += wc[w][e];
+            slab_count[(chunk * B + b) * kSemCounts + e] = c;
+        }
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(256) void sem_finish_kernel(int B, int64_t nchunks, const double* __restrict__ slab,
+                                                         const int64_t* __restrict__ slab_count, double* __restrict__ out_sums,
+                                                         int64_t* __restrict__ out_counts) {
+    const int64_t per = kRegSums + kSemCounts, total = (int64_t)B * per;
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t b = t / per;
+        const int e = (int)(t - b * per);
+        if (e < kRegSums) {
+            double s = 0.0;
+            for (int64_t c = 0; c < nchunks; ++c) s += slab[(c * B + b) * kRegSums + e];
+            out_sums[b * kRegSums + e] = s;
+        } else {
+            int64_t n = 0;
+            for (int64_t c = 0; c < nchunks; ++c) n += slab_count[(c * B + b) * kSemCounts + (e - kRegSums)];
+            out_counts[b * kSemCounts + (e - kRegSums)] = n;
         }
     }
 }
@@ -246,6 +367,41 @@ extern "C" int pvamd_chamfer_normal_eq(const pvamd_grid_t* grid, int32_t mode, c
                            slab_count);
     hipLaunchKernelGGL(reg_finish_kernel, dim3(stream_grid((int64_t)B * (kRegSums + 1), 256)), dim3(256), 0, st, B, nchunks, slab,
                        slab_count, out_sums, out_counts);
+    return (int)hipGetLastError();
+}
+
+extern "C" int64_t pvamd_semantic_normal_eq_scratch_bytes(int32_t B, int64_t N) {
+    if (B < 1 || N < 1) return 0;
+    return 8 * (int64_t)(kRegSums + kSemCounts) * B * ((N + PVAMD_REG_CHUNK - 1) / PVAMD_REG_CHUNK);
+}
+
+extern "C" int pvamd_semantic_normal_eq(const pvamd_grid_t* grid, int32_t mode, const float* W, int32_t B, const float* points,
+                                        int64_t N, const uint8_t* kinds, const float* targets, double huber_delta,
+                                        double* out_sums, int64_t* out_counts, void* scratch, void* stream) {
+    if (B < 0 || N < 1 || (N + PVAMD_REG_CHUNK - 1) / PVAMD_REG_CHUNK > 0x7fffffff) return PVAMD_E_SHAPE;
+    if (mode != PVAMD_LEAF_NEAREST && mode != PVAMD_LEAF_TRILINEAR) return PVAMD_E_MODE;
+    if (!grid) return PVAMD_E_NULL;
+    if (int e = check_grid(*grid)) return e;
+    if (grid->oob_mode != PVAMD_OOB_BOUNDING_BOX) return PVAMD_E_MODE;
+    if (!(huber_delta > 0.0)) return PVAMD_E_MODE;  // a NaN too
+    if (B == 0) return 0;
+    if (!W || !points || !out_sums || !out_counts || !scratch) return PVAMD_E_NULL;
+    if (!aligned_to(W, 4) || !aligned_to(points, 4) || !aligned_to(targets, 4) || !aligned_to(out_sums, 8) ||
+        !aligned_to(out_counts, 8) || !aligned_to(scratch, 8))
+        return PVAMD_E_ALIGN;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t nchunks = (N + PVAMD_REG_CHUNK - 1) / PVAMD_REG_CHUNK;
+    double* slab = (double*)scratch;
+    int64_t* slab_count = (int64_t*)(slab + nchunks * (int64_t)B * kRegSums);
+    const dim3 grid_dim((unsigned)nchunks, grid_rows(B));
+    if (mode == PVAMD_LEAF_TRILINEAR)
+        hipLaunchKernelGGL((sem_partial_kernel<true>), grid_dim, dim3(kRegBlock), 0, st, *grid, W, B, points, N, kinds, targets,
+                           huber_delta, slab, slab_count);
+    else
+        hipLaunchKernelGGL((sem_partial_kernel<false>), grid_dim, dim3(kRegBlock), 0, st, *grid, W, B, points, N, kinds, targets,
+                           huber_delta, slab, slab_count);
+    hipLaunchKernelGGL(sem_finish_kernel, dim3(stream_grid((int64_t)B * (kRegSums + kSemCounts), 256)), dim3(256), 0, st, B,
+                       nchunks, slab, slab_count, out_sums, out_counts);
     return (int)hipGetLastError();
 }
 

@@ -1,7 +1,10 @@
 """Second-order pose refinement against an SDF: the Gauss-Newton normal equations of the chamfer cost
 sum_i (scale * sdf(W p_i))^2 over a left-multiplied twist of every pose (`chamfer_normal_equations`, one fused pass over the
 (pose, point) pairs) and a Levenberg-Marquardt loop around them whose decisions stay on the device (`refine_poses`).
-The contract is include/pvamd.h "Chamfer normal equations"; the kernels are csrc/registration.hip."""
+`semantic_normal_equations` is the same pass with a kind (surface, free, occupied, ignore) and a target distance per point and
+Huber weights; `refine_poses` runs on it when asked for any of the three.
+The contracts are include/pvamd.h "Chamfer normal equations" and "Semantic normal equations"; the kernels are
+csrc/registration.hip."""
 import ctypes
 import math
 import numbers
@@ -15,6 +18,10 @@ from pytorch_volumetric_amd.sdf import CachedSDF, ObjectFrameSDF, OutOfBoundsStr
 
 LAMBDA_MIN = 1e-12
 LAMBDA_MAX = 1e12
+POINT_SURFACE = _lib.POINT_SURFACE    # penalised on either side of its target distance
+POINT_FREE = _lib.POINT_FREE          # penalised only where the object reaches it: sdf < target
+POINT_OCCUPIED = _lib.POINT_OCCUPIED  # penalised only where the object does not: sdf > target
+POINT_IGNORE = _lib.POINT_IGNORE      # never penalised, like every value outside 0..3
 
 
 class ChamferNormalEquations(NamedTuple):
@@ -22,6 +29,15 @@ class ChamferNormalEquations(NamedTuple):
     gradient: torch.Tensor  # (B, 6) float64: scale^2 / N * sum v j, half of d cost / d xi at xi = 0; xi = (u, w)
     hessian: torch.Tensor   # (B, 6, 6) float64: scale^2 / N * sum j j^T, symmetric
     counts: torch.Tensor    # (B,) int64: points of the pose inside the grid range
+
+
+class SemanticNormalEquations(NamedTuple):
+    cost: torch.Tensor      # (B,) float64: scale^2 / N * sum rho(r), rho the Huber function (r^2 inside huber_delta)
+    gradient: torch.Tensor  # (B, 6) float64: scale^2 / N * sum w r j over the active pairs
+    hessian: torch.Tensor   # (B, 6, 6) float64: scale^2 / N * sum w j j^T over the active pairs, symmetric
+    counts: torch.Tensor    # (B,) int64: points of the pose inside the grid range, whatever their kind
+    active: torch.Tensor    # (B, 3) int64: active pairs of kind POINT_SURFACE, POINT_FREE, POINT_OCCUPIED
+    outliers: torch.Tensor  # (B,) int64: active pairs with |r| > huber_delta
 
 
 class PoseRefinement(NamedTuple):
@@ -119,6 +135,110 @@ class _Evaluator:
         self.counts.fill_(self.N)  # no grid: every point is answered by the object itself
 
 
+def _check_semantic_args(pts, semantics, targets, huber_delta):
+    """(semantics, targets as tensors where given, huber_delta as a float or None); raises before anything touches the device."""
+    lead = tuple(pts.shape[:-1])
+    if semantics is not None:
+        if not torch.is_tensor(semantics):
+            try:
+                semantics = torch.as_tensor(semantics)
+            except (TypeError, ValueError, RuntimeError) as e:
+                raise TypeError(f"semantics must be an integer tensor, got {type(semantics).__name__}") from e
+        if semantics.dtype == torch.bool or semantics.dtype.is_floating_point or semantics.dtype.is_complex:
+            raise TypeError(f"semantics must have an integer dtype, got {semantics.dtype}")
+        if tuple(semantics.shape) != lead:
+            raise ValueError(f"semantics must have the shape of points without its last dimension {lead}, got "
+                             f"{tuple(semantics.shape)}")
+    if targets is not None:
+        if not torch.is_tensor(targets):
+            try:
+                targets = torch.as_tensor(targets)
+            except (TypeError, ValueError, RuntimeError) as e:
+                raise TypeError(f"targets must be a real tensor, got {type(targets).__name__}") from e
+        if targets.dtype == torch.bool or targets.dtype.is_complex:
+            raise TypeError(f"targets must have a real dtype, got {targets.dtype}")
+        if tuple(targets.shape) != lead:
+            raise ValueError(f"targets must have the shape of points without its last dimension {lead}, got "
+                             f"{tuple(targets.shape)}")
+    if huber_delta is not None:
+        if isinstance(huber_delta, bool) or not isinstance(huber_delta, numbers.Real):
+            raise TypeError(f"huber_delta must be a real number, got {huber_delta!r}")
+        if not huber_delta > 0:  # a NaN too; inf switches the weights off
+            raise ValueError(f"huber_delta must be positive, got {huber_delta!r}")
+        huber_delta = float(huber_delta)
+    return semantics, targets, huber_delta
+
+
+def _prepare_semantics(semantics, targets, dev):
+    """(kinds (N,) uint8, targets (N,) float32) on the device, None where not given.  A kind outside 0..3 means POINT_IGNORE:
+    mapped on the device, before the narrowing cast could fold it into range, without a synchronisation."""
+    kinds = None
+    if semantics is not None:
+        s = semantics.detach().reshape(-1).to(device=dev)
+        kinds = torch.where((s >= POINT_SURFACE) & (s <= POINT_IGNORE), s, POINT_IGNORE).to(torch.uint8).contiguous()
+    if targets is not None:
+        targets = targets.detach().reshape(-1).to(device=dev, dtype=torch.float32).contiguous()
+    return kinds, targets
+
+
+class _SemanticEvaluator:
+    """_Evaluator under "Semantic normal equations": the raw sums (B, 28) and the five counts (B, 5).  kinds (N,) uint8 and
+    targets (N,) float32 on the device, or None; delta a float (inf: plain least squares)."""
+
+    def __init__(self, obj_sdf, mode, dev, pts, B, kinds, targets, delta):
+        self.obj_sdf, self.mode, self.dev, self.pts, self.B = obj_sdf, mode, dev, pts, B
+        self.kinds, self.targets, self.delta = kinds, targets, delta
+        self.N = pts.shape[0]
+        self.sums = torch.empty((B, _lib.REG_SUMS), dtype=torch.float64, device=dev)
+        self.counts = torch.empty((B, _lib.SEM_COUNTS), dtype=torch.int64, device=dev)
+        if mode is not None:
+            self.scratch = torch.empty((_lib.semantic_normal_eq_scratch_bytes(B, self.N) // 8,), dtype=torch.int64, device=dev)
+            self.desc = obj_sdf._grid_desc()
+
+    def __call__(self, W32):
+        if self.B == 0:
+            return
+        lib = _lib.load()
+        if self.mode is not None:
+            _lib.check(lib.pvamd_semantic_normal_eq(ctypes.byref(self.desc), self.mode, _lib.ptr(W32), self.B, _lib.ptr(self.pts),
+                                                    self.N, _lib.ptr(self.kinds), _lib.ptr(self.targets), self.delta,
+                                                    _lib.ptr(self.sums), _lib.ptr(self.counts), _lib.ptr(self.scratch),
+                                                    _lib.stream_ptr()), "pvamd_semantic_normal_eq")
+            return
+        # any other object: transform with the kernel's statements, query the object, the contract's statements in float64 in torch
+        x = torch.empty((self.B, self.N, 3), dtype=torch.float32, device=self.dev)
+        _lib.check(lib.pvamd_transform_points(_lib.ptr(W32), self.B, _lib.ptr(self.pts), self.N, _lib.ptr(x), _lib.stream_ptr()),
+                   "pvamd_transform_points")
+        with torch.no_grad():
+            v, n = self.obj_sdf(x)
+        v = v.detach().to(device=self.dev, dtype=torch.float64).reshape(self.B, self.N)
+        n = n.detach().to(device=self.dev, dtype=torch.float64).reshape(self.B, self.N, 3)
+        j = torch.cat((n, torch.linalg.cross(x.to(torch.float64), n, dim=-1)), dim=-1)
+        r = v if self.targets is None else v - self.targets.to(torch.float64)
+        if self.kinds is None:
+            surface = torch.ones_like(r, dtype=torch.bool)
+            free = occupied = torch.zeros_like(surface)
+        else:
+            surface = (self.kinds == POINT_SURFACE).expand(self.B, self.N)
+            free = (self.kinds == POINT_FREE) & ~(r >= 0)
+            occupied = (self.kinds == POINT_OCCUPIED) & ~(r <= 0)
+        active = surface | free | occupied
+        a = r.abs()
+        outlier = active & (a > self.delta)
+        w = torch.where(outlier, self.delta / a, 1.0)  # times one is exact: an inlier enters as (r, j)
+        zero = torch.zeros((), dtype=torch.float64, device=self.dev)
+        # inactive pairs are left out by selection, not by a product with zero: their NaN stays out of the sums
+        self.sums[:, 0] = torch.where(active, torch.where(outlier, self.delta * ((a + a) - self.delta), r * r), zero).sum(-1)
+        self.sums[:, 1:7] = torch.where(active.unsqueeze(-1), (w * r).unsqueeze(-1) * j, zero).sum(-2)
+        rr, cc = torch.triu_indices(6, 6).tolist()
+        self.sums[:, 7:] = torch.where(active.unsqueeze(-1), (w.unsqueeze(-1) * j)[..., rr] * j[..., cc], zero).sum(-2)
+        self.counts[:, 0] = self.N  # no grid: every point is answered by the object itself
+        self.counts[:, 1] = (active & surface).sum(-1)
+        self.counts[:, 2] = free.sum(-1)
+        self.counts[:, 3] = occupied.sum(-1)
+        self.counts[:, 4] = outlier.sum(-1)
+
+
 def _prepare(W, pts, dev):
     pts32 = pts.detach().reshape(-1, 3).to(device=dev, dtype=torch.float32).contiguous()
     W32 = W.detach().to(device=dev, dtype=torch.float32).contiguous()
@@ -153,6 +273,40 @@ def chamfer_normal_equations(world_to_object, points, obj_sdf: ObjectFrameSDF, s
         return ChamferNormalEquations(s[:, 0], s[:, 1:7], s[:, 7:][:, _triangle_index(dev)].reshape(-1, 6, 6), ev.counts)
 
 
+def semantic_normal_equations(world_to_object, points, obj_sdf: ObjectFrameSDF, scale=1000., semantics=None, targets=None,
+                              huber_delta=None):
+    """`chamfer_normal_equations` for points that are not all surface points, with Huber weights: the normal equations of
+    scale^2 / N sum_i rho(r_i), r = sdf(W p_i) - target_i, over the pairs that are active under their point's kind.
+
+    :param semantics: integer tensor of shape points.shape[:-1], the kind of every point: POINT_SURFACE (0) is penalised on
+        either side, POINT_FREE (1) only where r < 0 (the object reaches into known free space), POINT_OCCUPIED (2) only where
+        r > 0, POINT_IGNORE (3) and every value outside 0..3 never.  None: every point is a surface point
+    :param targets: real tensor of the same shape, the distance each point should have (float32 on the device).  None: 0
+    :param huber_delta: a positive number in the units of the SDF (before scale): a pair with |r| > huber_delta enters with the
+        weight w = huber_delta / |r| and the cost huber_delta (2 |r| - huber_delta).  None or inf: w = 1
+    :return: SemanticNormalEquations(cost (B,), gradient (B, 6), hessian (B, 6, 6), counts (B,), active (B, 3), outliers (B,)) on
+        the GPU, float64 / int64: cost = scale^2 / N sum rho, gradient = scale^2 / N sum w r j, hessian = scale^2 / N sum w j j^T
+        with j as in chamfer_normal_equations and N every point, ignored ones included.  An inactive pair adds nothing, whatever
+        the object returns there.  With all three options None the first four fields are chamfer_normal_equations' bit for bit
+        (from another kernel: include/pvamd.h "Semantic normal equations").  Same order, same reproducibility, no autograd
+        graph, no device -> host synchronisation."""
+    scale = _check_scale(scale)
+    W, pts = _check_inputs(world_to_object, points, obj_sdf)
+    semantics, targets, huber_delta = _check_semantic_args(pts, semantics, targets, huber_delta)
+    mode = _fused_mode(obj_sdf)
+    dev = _device_of(obj_sdf, mode)
+    with _lib.on_device(dev):
+        W32, pts32 = _prepare(W, pts, dev)
+        kinds, targets32 = _prepare_semantics(semantics, targets, dev)
+        ev = _SemanticEvaluator(obj_sdf, mode, dev, pts32, W32.shape[0], kinds, targets32,
+                                math.inf if huber_delta is None else huber_delta)
+        ev(W32)
+        k = scale * scale / ev.N
+        s = ev.sums * k
+        return SemanticNormalEquations(s[:, 0], s[:, 1:7], s[:, 7:][:, _triangle_index(dev)].reshape(-1, 6, 6), ev.counts[:, 0],
+                                       ev.counts[:, 1:4], ev.counts[:, 4])
+
+
 def _check_refine_args(iterations, damping, damping_up, damping_down):
     if isinstance(iterations, bool) or not isinstance(iterations, numbers.Integral):
         raise TypeError(f"iterations must be an int, got {iterations!r}")
@@ -171,9 +325,11 @@ def _check_refine_args(iterations, damping, damping_up, damping_down):
 
 
 def refine_poses(world_to_object, points, obj_sdf: ObjectFrameSDF, iterations=10, scale=1000., damping=1e-3, damping_up=10.,
-                 damping_down=0.1):
+                 damping_down=0.1, semantics=None, targets=None, huber_delta=None):
     """Levenberg-Marquardt refinement of B poses against an SDF: minimises the chamfer cost of `chamfer_normal_equations` by
-    damped Gauss-Newton steps, every accept / reject decision taken on the device (pvamd_pose_lm_step).
+    damped Gauss-Newton steps, every accept / reject decision taken on the device (pvamd_pose_lm_step).  With any of semantics,
+    targets and huber_delta given it minimises the cost of `semantic_normal_equations` (their meaning is stated there) by the
+    same loop and step; with all three None it runs the kernels and gives the bits it always did.
 
     :param iterations: normal-equation evaluations after the initial one, an int >= 1
     :param damping: initial Marquardt damping (relative to the Hessian's diagonal), multiplied by damping_down after an
@@ -185,6 +341,8 @@ def refine_poses(world_to_object, points, obj_sdf: ObjectFrameSDF, iterations=10
     scale = _check_scale(scale)
     iterations, damping, up, down = _check_refine_args(iterations, damping, damping_up, damping_down)
     W, pts = _check_inputs(world_to_object, points, obj_sdf)
+    plain = semantics is None and targets is None and huber_delta is None
+    semantics, targets, huber_delta = _check_semantic_args(pts, semantics, targets, huber_delta)
     out_dtype = W.dtype if W.dtype.is_floating_point else torch.float32
     out_device = W.device
     mode = _fused_mode(obj_sdf)
@@ -193,7 +351,11 @@ def refine_poses(world_to_object, points, obj_sdf: ObjectFrameSDF, iterations=10
     with _lib.on_device(dev):
         W32, pts32 = _prepare(W, pts, dev)
         B = W32.shape[0]
-        ev = _Evaluator(obj_sdf, mode, dev, pts32, B)
+        if plain:
+            ev = _Evaluator(obj_sdf, mode, dev, pts32, B)
+        else:
+            kinds, targets32 = _prepare_semantics(semantics, targets, dev)
+            ev = _SemanticEvaluator(obj_sdf, mode, dev, pts32, B, kinds, targets32, math.inf if huber_delta is None else huber_delta)
         # the state of pvamd_pose_lm_step
         w_try = W32[:, :3, :].to(torch.float64).contiguous()
         w_acc = torch.empty_like(w_try)
