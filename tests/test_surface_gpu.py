@@ -39,14 +39,7 @@ def restated(rec, valid=None, level=0.0, normals=True, **capacities):
     return ref.extract(rec, valid, ORIGIN, (RES, RES, RES), level, normals, **capacities)
 
 
-def assert_same(got, want):
-    assert (got.vertices.shape[0], got.faces.shape[0]) == want.counts
-    for name, g, w in (("vertices", got.vertices, want.vertices), ("normals", got.normals, want.normals), ("faces", got.faces, want.faces)):
-        if w is None:
-            assert g is None, name
-            continue
-        g = g.cpu().numpy()
-        assert g.shape == w.shape and np.array_equal(ref.bits(g), ref.bits(w)), (name, int((ref.bits(g) != ref.bits(w)).sum()))
+assert_same = ref.assert_same  # shared with tests/test_surface_edges_gpu.py
 
 
 # Which cases cannot have quads of all three families, by the contract itself (the restatement gives these counts): on (3, 3, 3) a
