@@ -857,6 +857,68 @@ int pvamd_semantic_normal_eq(const pvamd_grid_t* grid, int32_t mode, const float
                              const uint8_t* kinds, const float* targets, double huber_delta, double* out_sums,
                              int64_t* out_counts, void* scratch, void* stream);
 
+/* ---- Joint-space normal equations (joint_normal_equations / refine_joint_configuration) ----
+ * "Semantic normal equations" for a robot: the Gauss-Newton normal equations of scale^2 / N sum_i rho(r_i) over the joint values
+ * q of A configurations of a composition of S leaves ("Minimum over points": grids device [S], stack device [S*A][4][4]
+ * leaf-major, the float32 stack pvamd_configure_chain gives; every grid 3-D, BOUNDING_BOX, either index arithmetic), and the
+ * Levenberg-Marquardt step built on them.  Every point is won by exactly one leaf and a link's twist Jacobian does not depend on
+ * the point, so the joint-space equations factor exactly over the leaves.
+ *  1. Per pair (a, i) the winning leaf s and, in its frame, x = T_s p_i with T_s = stack[s*A + a], (v, n) are those of the fused
+ *     composed forwards (mop_point): the first minimum over the leaves in leaf order, a NaN counting as the minimum; n is the
+ *     leaf's own returned gradient, before it is rotated back into the object frame.
+ *  2. r = v - target; activity, the Huber branch and j = (n, x cross n) in float64 are the statements of "Semantic normal
+ *     equations", unchanged.  The pair's 28 terms go to the sums of leaf s and to no other leaf.
+ *  3. The order of summation is pvamd_semantic_normal_eq's: lane t of chunk c takes points c PVAMD_REG_CHUNK + k 256 + t in k
+ *     order, a wave butterfly, the four waves in order, then the chunks in chunk order.  A point a leaf does not win is skipped for
+ *     that leaf; a wave without a point of a leaf adds +0.0 for it.  So leaf_sums[a][s][28] and leaf_counts[a][s][5] are, bit for
+ *     bit, what pvamd_semantic_normal_eq returns for the pose T_s and the grid of leaf s when the caller's kinds are replaced by
+ *     PVAMD_POINT_IGNORE wherever s does not win -- except leaf_counts[a][s][0], which counts the in-range points s wins.
+ *  4. J[a][s] (6 x M, float64, row-major) carries a joint step into a twist of leaf s's frame.  The records of leaf s's frame and
+ *     its ancestors are walked root first in float64 from the float32 joint values, origins and axes (sin and cos in float64):
+ *     world = world @ origin @ motion, the statements of pvamd_chain_fk.  T_s = offset_inv[s] @ rigid_inverse(world of the leaf's
+ *     frame), in float64.  For a moving joint k on the way, with a = R(world_k) axis_k and o = t(world_k) in the object frame,
+ *     xi_W = (u_W, w_W) = (o cross a, a) for a revolute or continuous joint and (a, 0) for a prismatic one (translation first),
+ *     and with (R, t) = T_s:  J[:, k] = -(R u_W + t cross (R w_W), R w_W).  Every other column is zero.
+ *  5. Assembly, float64, fused multiply-adds, leaves in order s = 0 .. S-1 from +0.0:  cost = sum_s c_s;
+ *     g_k = fma(J_s[r][k], g6_s[r], g_k) for r = 0 .. 5;  H_ij (i <= j) = fma(J_s[r][i], v_r, H_ij) for r = 0 .. 5 with
+ *     v_r = (H6_s J_s)[r][j] = fma(H6_s[r][c], J_s[c][j], v_r) for c = 0 .. 5 from +0.0.  Only the upper triangle is formed: the
+ *     caller mirrors it, so H is exactly symmetric.  sums[a] = (cost, g[M], H upper triangle row-major [M (M + 1) / 2]).
+ *     counts[a][PVAMD_SEM_COUNTS + S] (int64): the five leaf counts summed over s, then per leaf the active pairs it won.
+ *  6. The caller scales by scale^2 / N, N every point, as in "Semantic normal equations".  A NaN sum of a leaf makes every
+ *     entry of its configuration NaN and touches no other configuration.
+ * Bitwise reproducible; no float atomics, no allocation, no device -> host synchronisation.
+ * pvamd_joint_normal_eq: 1 <= S <= PVAMD_JOINT_MAX_LEAVES, 1 <= N, 0 <= A (A = 0 does nothing); mode PVAMD_LEAF_*; huber_delta NaN
+ *   or <= 0 is PVAMD_E_MODE.  kinds device [N] or NULL, targets device [N] or NULL.  scratch: device,
+ *   pvamd_joint_normal_eq_scratch_bytes(A, S, N) bytes, 8-byte aligned: 28 sums and 5 counts per configuration, leaf and chunk
+ *   (264 A S ceil(N / PVAMD_REG_CHUNK) bytes); the exported function is the definition of the size.
+ * pvamd_chain_twists: joints device [F], q device [A][M], offset_inv device [S][4][4] (the arguments of pvamd_configure_chain),
+ *   0 <= M <= PVAMD_JOINT_MAX.  J device [A][S][6][M].
+ * pvamd_joint_assemble: sums device [A][1 + M + M (M + 1) / 2], counts device [A][PVAMD_SEM_COUNTS + S].
+ * pvamd_joint_lm_step: pvamd_pose_lm_step in joint space, one decision per configuration.  sums: the row just assembled at q_try.
+ *   State: q_acc, q_try [A][M] float64, sums_acc (a row of sums each), lambda [A], accepted [A] int32 (the caller zeroes it and
+ *   sets q_try and lambda before the first call).
+ *   a. Accept if first or cost(sums) < cost(sums_acc) (strict: a NaN never accepts): q_acc = q_try, sums_acc = sums,
+ *      lambda = max(lambda down, lambda_min), accepted += 1.  Otherwise lambda = min(lambda up, lambda_max).
+ *   b. Solve (H + lambda D) dq = -g with the accepted sums by Cholesky without pivoting in pvamd_pose_lm_step's loop order, D
+ *      diagonal with D_k = H_kk where that is positive and 1 elsewhere (a joint no point observes gets a zero step).  A pivot that
+ *      is not positive and finite, or a non-finite dq: dq = 0 and lambda = min(lambda up, lambda_max).
+ *   c. q_try = q_acc + dq in float64, then clamped into limits[k] = (lo, hi) (device [M][2] float64, or NULL: no clamp); dq = 0
+ *      copies q_acc bit for bit.  q_next [A][M] = q_try rounded to float32: what the next evaluation reads.
+ *   The checks of up, down, lambda_min, lambda_max and first are pvamd_pose_lm_step's.                                            */
+#define PVAMD_JOINT_MAX 32        /* the most joint values M */
+#define PVAMD_JOINT_MAX_LEAVES 64 /* the most leaves S */
+int64_t pvamd_joint_normal_eq_scratch_bytes(int32_t A, int32_t S, int64_t N);
+int pvamd_joint_normal_eq(const pvamd_grid_t* grids, int32_t S, int32_t mode, const float* stack, int32_t A, const float* points,
+                          int64_t N, const uint8_t* kinds, const float* targets, double huber_delta, double* leaf_sums,
+                          int64_t* leaf_counts, void* scratch, void* stream);
+int pvamd_chain_twists(const pvamd_joint_t* joints, int32_t F, const float* q, int32_t A, int32_t M, const float* offset_inv,
+                       int32_t S, double* J, void* stream);
+int pvamd_joint_assemble(const double* leaf_sums, const int64_t* leaf_counts, const double* J, int32_t A, int32_t S, int32_t M,
+                         double* sums, int64_t* counts, void* stream);
+int pvamd_joint_lm_step(int32_t A, int32_t M, const double* sums, int32_t first, double* q_acc, double* sums_acc, double* lambda,
+                        int32_t* accepted, double* q_try, float* q_next, const double* limits, double up, double down,
+                        double lambda_min, double lambda_max, void* stream);
+
 /* ---- Ray casting (CachedSDF.ray_cast / ComposedSDF.ray_cast / RobotSDF.ray_cast) ----
  * Sphere tracing: where the ray o + t d first meets the surface of one cached grid (3-D, BOUNDING_BOX, else PVAMD_E_MODE; either
  * index arithmetic) or of a composition ("Minimum over points": S leaves, A configurations, tf device [S*A][4][4] leaf-major,

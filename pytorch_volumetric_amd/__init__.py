@@ -14,6 +14,8 @@ from pytorch_volumetric_amd.chamfer import (PlausibleDiversity, batch_chamfer_di
 from pytorch_volumetric_amd.registration import (POINT_FREE, POINT_IGNORE, POINT_OCCUPIED, POINT_SURFACE, ChamferNormalEquations,
                                                  PoseRefinement, SemanticNormalEquations, chamfer_normal_equations,
                                                  refine_poses, semantic_normal_equations)
+from pytorch_volumetric_amd.articulated import (JointNormalEquations, JointRefinement, joint_normal_equations,
+                                                refine_joint_configuration)
 from pytorch_volumetric_amd.voxel import get_coordinates_and_points_in_grid, get_divisible_range_by_resolution
 from pytorch_volumetric_amd.voxel_containers import (ExpandingVoxelGrid, VoxelGrid, VoxelSet, Voxels,
                                                      voxel_down_sample)

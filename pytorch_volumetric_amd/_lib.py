@@ -105,6 +105,12 @@ def semantic_normal_eq_scratch_bytes(B, N):
 
 
 @_remembered
+def joint_normal_eq_scratch_bytes(A, S, N):
+    """pvamd_joint_normal_eq_scratch_bytes: 28 float64 sums and five int64 counts per configuration, leaf and point chunk."""
+    return load().pvamd_joint_normal_eq_scratch_bytes(A, S, N)
+
+
+@_remembered
 def distance_transform_scratch_bytes(nx, ny, nz, signed):
     """pvamd_distance_transform_scratch_bytes: one int32 per voxel, site class and line pass that hands on a state."""
     return load().pvamd_distance_transform_scratch_bytes(nx, ny, nz, int(signed))
@@ -256,6 +262,8 @@ POINT_FREE = H["PVAMD_POINT_FREE"]
 POINT_OCCUPIED = H["PVAMD_POINT_OCCUPIED"]
 POINT_IGNORE = H["PVAMD_POINT_IGNORE"]  # and every larger value
 SEM_COUNTS = H["PVAMD_SEM_COUNTS"]  # the row length of pvamd_semantic_normal_eq's out_counts
+JOINT_MAX = H["PVAMD_JOINT_MAX"]  # the most joint values of pvamd_chain_twists, pvamd_joint_assemble and pvamd_joint_lm_step
+JOINT_MAX_LEAVES = H["PVAMD_JOINT_MAX_LEAVES"]  # the most leaves of pvamd_joint_normal_eq
 RAY_MISS = H["PVAMD_RAY_MISS"]  # RAY_*: the status codes of the ray-cast entry points
 RAY_HIT = H["PVAMD_RAY_HIT"]
 RAY_MAX_STEPS = H["PVAMD_RAY_MAX_STEPS"]
