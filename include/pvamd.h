@@ -1275,6 +1275,52 @@ int pvamd_surface_count(const pvamd_grid_t* grid, const float* records, const ui
                         int64_t* counts, void* stream);
 int pvamd_surface_emit(const pvamd_grid_t* grid, const float* records, const uint8_t* valid, float level, const void* scratch,
                        int64_t max_vertices, int64_t max_faces, float* vertices, float* normals, int32_t* faces, void* stream);
+
+/* ---- Mesh ray casting (the first hit of rays on a triangle mesh) ----
+ * pvamd_mesh_ray_cast finds, for each of B poses and R rays o + t d, the triangle of a prepared mesh the ray meets first: what
+ * the reference's users get from cast_rays on the open3d RaycastingScene every ObjectFactory keeps (sdf.py:115-118).  Exact: the
+ * result is that of the plain loop over all F triangles, not of a march that stops within a tolerance.  An additive entry point:
+ * the ABI version is unchanged.
+ * EVERYTHING below is float32 with every operation rounded on its own: no contraction; fmaf(a, b, c) is one fused, once-rounded
+ * a * b + c exactly where it is written, as in the mesh query's sequences (csrc/mesh_math.h); correctly rounded division.
+ * dot(a, b) = fmaf(a_z, b_z, fmaf(a_y, b_y, a_x * b_x)); cross(a, b) = (fmaf(a_y, b_z, -(a_z * b_y)), fmaf(a_z, b_x, -(a_x * b_z)),
+ * fmaf(a_x, b_y, -(a_y * b_x))).
+ *  1. The ray in the object frame.  poses == NULL: o' = o, d' = d.  With pose b, M = poses[b] row-major, world_to_object:
+ *     o'_i = fmaf(M[4i+2], o_z, fmaf(M[4i+1], o_y, M[4i] * o_x)) + M[4i+3]  -- affine_row, the statement of pvamd_chamfer_mesh and
+ *     the composed queries -- and d'_i = fmaf(M[4i+2], d_z, fmaf(M[4i+1], d_y, M[4i] * d_x)): the same chain without the translation.
+ *     The last row of M is not read.
+ *  2. Candidates.  For a triangle (v0, v1, v2) = the corners (a, b, c) of a face, as float32: e1 = v0 - v1, e2 = v2 - v0,
+ *     Ng = cross(e2, e1), C = v0 - o', Rv = cross(C, d'), den = dot(Ng, d'), absden = |den|, sgn = -1 if den < 0 else 1,
+ *     U = dot(Rv, e2) * sgn, V = dot(Rv, e1) * sgn, T = dot(Ng, C) * sgn -- ray_hits_triangle's sequence of the mesh query's
+ *     parity rays -- and t = T / absden.  The triangle is a candidate iff den != 0, U >= 0, V >= 0, U + V <= absden, t >= t_min and
+ *     t <= t_max.  A NaN fails its comparison (den != 0 alone holds for a NaN den; U >= 0 then fails): a ray with a NaN or
+ *     infinite coordinate, or a zero direction, has no candidate.  Edges and corners are inclusive, both faces of a triangle count.
+ *  3. Result.  Of the candidates, the one with the smallest t; among equal t (-0 equals +0) the one with the smallest ORIGINAL
+ *     face id -- the lexicographic rule of the closest-point query, whatever order the triangles are stored or visited in.
+ *     t_out = its t, face_out = its id, uv_out = (U / absden, V / absden), two more divisions: the hit is
+ *     (1 - u - v) a + u b + v c -- u weights corner b, v corner c -- up to rounding.  normal_out = mesh->normal[face], the
+ *     stored unit face normal, NOT flipped towards the ray; with a pose it is taken back into the rays' frame by the transpose
+ *     of M's 3 x 3 block, n_j = fmaf(M[8+j], n_z, fmaf(M[4+j], n_y, M[j] * n_x)).  Either way each component is written as n_j + 0, so
+ *     that a zero leaves as +0 and the identity pose gives the bits of poses == NULL.  No candidate: t_out = +inf, face_out = -1,
+ *     normal_out and uv_out zeros.
+ *  4. t is the parameter of o + t d for the caller's d, of any length; a pose is affine, so t is the same number in both
+ *     frames.  The normal taken back by the transpose is the normal in the rays' frame for RIGID poses only (orthonormal block);
+ *     nothing checks rigidity.
+ * mesh: host struct (pvamd_mesh_prepare's buffers; of them rec and normal are read, and F).  origins, directions: device [R][3].
+ * poses: NULL (B must be 1) or device [B][16].  t_out: device [B][R] float32; face_out: device [B][R] int32; normal_out: device
+ * [B][R][3] or NULL; uv_out: device [B][R][2] or NULL: the rays are shared by the poses.
+ * Argument errors return before any launch: PVAMD_E_SHAPE for R < 0, B < 0, poses == NULL with B != 1, B * R >= 2^31 or F outside
+ * [0, 2^26]; PVAMD_E_NULL; PVAMD_E_MODE for a NaN t_min or t_max; PVAMD_E_ALIGN for records not 16-byte aligned.
+ * R == 0 or B == 0: nothing is launched or written.  F == 0 or t_min > t_max: every ray misses.
+ * One lane per (pose, ray), rays in caller order; every wave tests its rays against all F records (wave-uniform loads).  Nothing
+ * is culled, although the records carry bounding spheres: for a ray that lies, up to rounding, in a triangle's plane, den, U, V
+ * and T of 2. are all rounding noise and the triangle can be a candidate, with any t, wherever in that plane the line runs -- also
+ * wholly behind the origin or far beside the line.  The statements above are the definition, so no sphere may be skipped.
+ * Stream-ordered, no allocation, no device -> host synchronisation, no atomics: capturable in a graph, and two calls give the
+ * same bits.  mesh->pair_counters is not used.                                                                                  */
+int pvamd_mesh_ray_cast(const pvamd_mesh_t* mesh, const float* origins, const float* directions, int64_t R, const float* poses,
+                        int32_t B, float t_min, float t_max, float* t_out, int32_t* face_out, float* normal_out, float* uv_out,
+                        void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -5,7 +5,7 @@ Every name pytorch_volumetric exports for that path is available here; see INTEG
 from pytorch_volumetric_amd import _lib, mesh_io, voxel
 from pytorch_volumetric_amd._lib import RULE_RES_F64, RULE_ROUND_FLOOR_HALF, RULE_ROUND_HALF_AWAY, RULE_VALID_ON_INDEX
 from pytorch_volumetric_amd.sdf import (CachedSDF, ComposedSDF, HingeOverPoints, LeafPairDistance, LeafPairHinge, MeshObjectFactory,
-                                        MeshSDF, MinOverPoints, ObjectFactory, ObjectFrameSDF, OutOfBoundsStrategy, PreparedPoints,
+                                        MeshRayHits, MeshSDF, MinOverPoints, ObjectFactory, ObjectFrameSDF, OutOfBoundsStrategy, PreparedPoints,
                                         RAY_HIT, RAY_INVALID, RAY_MAX_STEPS, RAY_MISS, RayCast, SDFQuery, SphereSDF,
                                         sample_mesh_points)
 from pytorch_volumetric_amd.model_to_sdf import RobotSDF, aabb_to_ordered_end_points, cache_link_sdf_factory
@@ -23,7 +23,7 @@ from pytorch_volumetric_amd.occupancy import DistanceTransform, OccupancySDF, ca
 from pytorch_volumetric_amd.occupancy_map import OccupancyMap, ray_marks
 from pytorch_volumetric_amd.redistance import Redistance, redistance
 from pytorch_volumetric_amd.surface import Surface, extract_surface
-from pytorch_volumetric_amd.tsdf import TSDFField, TSDFVolume
+from pytorch_volumetric_amd.tsdf import TSDFField, TSDFVolume, camera_rays
 from pytorch_volumetric_amd.volume import is_inside
 from pytorch_volumetric_amd.visualization import draw_sdf_slice, get_transformed_meshes
 # stand-ins for the pytorch_kinematics members the path touches, and the multi-GPU helpers

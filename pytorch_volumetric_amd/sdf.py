@@ -57,6 +57,26 @@ class RayCast(NamedTuple):
 RAY_MISS, RAY_HIT, RAY_MAX_STEPS, RAY_INVALID = _lib.RAY_MISS, _lib.RAY_HIT, _lib.RAY_MAX_STEPS, _lib.RAY_INVALID
 
 
+class MeshRayHits(NamedTuple):
+    """ObjectFactory.cast_rays: per ray the parameter t of the first triangle hit on o + t d (inf: none), that triangle's
+    original face id (int64, -1: none), its stored unit face normal (not flipped towards the ray) and the barycentrics (u, v) of
+    the hit, (1 - u - v) a + u b + v c on the face's corners; zeros on a miss (include/pvamd.h "Mesh ray casting")."""
+    t: torch.Tensor
+    face_ids: torch.Tensor
+    normals: torch.Tensor
+    uv: torch.Tensor
+
+
+def _ray_window(t_min, t_max):
+    """(t_min, t_max) of a mesh ray cast as floats, or the error include/pvamd.h "Mesh ray casting" asks for."""
+    for name, x in (("t_min", t_min), ("t_max", t_max)):
+        if isinstance(x, bool) or not isinstance(x, numbers.Real):
+            raise TypeError(f"{name} must be a Python real number, got {type(x).__name__}")
+    if math.isnan(t_min) or math.isnan(t_max):
+        raise ValueError(f"t_min and t_max must not be NaN, got {t_min!r} and {t_max!r}")
+    return float(t_min), float(t_max)
+
+
 class HingeOverPoints(NamedTuple):
     """ComposedSDF.hinge_over_points / RobotSDF.hinge_over_points: per pair, sum over points of max(margin - v, 0) ** power and
     the number of points with v < margin (include/pvamd.h "Hinge penalty over points")."""
@@ -422,6 +442,79 @@ class ObjectFactory(abc.ABC):
         return SDFQuery(_restore(closest, lead, (3,), dtype, device), _restore(dist, lead, (), dtype, device),
                         _restore(grad, lead, (3,), dtype, device),
                         _restore(normal, lead, (3,), dtype, device) if compute_normal else None)
+
+    def cast_rays(self, origins, directions, t_min=0., t_max=math.inf, world_to_object=None) -> MeshRayHits:
+        """
+        The first triangle every ray o + t d meets, exactly: what cast_rays on the reference's RaycastingScene (sdf.py:115-118)
+        answers, for depth, visibility and occlusion checks.  ONE kernel launch (csrc/mesh_ray.hip; include/pvamd.h "Mesh ray
+        casting" states the arithmetic), computed in float32 and returned in the promoted dtype of the rays on the origins'
+        device; nothing synchronises with the host and nothing carries an autograd graph (inputs that require grad are detached).
+
+        :param origins: [...] x 3, broadcast against `directions`
+        :param directions: [...] x 3, of any length: t is the parameter of the caller's direction.  A zero or NaN direction misses
+        :param t_min: hits with a smaller t are passed over
+        :param t_max: hits with a larger t are passed over
+        :param world_to_object: None (the rays are in the object frame), (4, 4) or (B, 4, 4) matrices that take the rays' frame to
+            the object frame.  A batch prepends B to every output shape: the rays are shared by the poses.  Normals come back in
+            the rays' frame, which is meaningful for rigid poses only
+        :return: MeshRayHits(t, face_ids, normals, uv); t = inf and face_ids = -1 where nothing is hit
+        """
+        t_min, t_max = _ray_window(t_min, t_max)
+        o, d, lead, dtype = _ray_inputs(origins, directions)
+        device = o.device
+        poses, batch = None, ()
+        if world_to_object is not None:
+            poses = world_to_object.get_matrix() if hasattr(world_to_object, "get_matrix") else world_to_object
+            poses = poses if torch.is_tensor(poses) else torch.as_tensor(poses)
+            if poses.dim() not in (2, 3) or tuple(poses.shape[-2:]) != (4, 4):
+                raise ValueError(f"world_to_object must be (4, 4) or (B, 4, 4), got {tuple(poses.shape)}")
+            batch = tuple(poses.shape[:-2])
+        lib = _lib.load()
+        desc = self._mesh_desc()
+        dev = self._rec_dev.device
+        o = o.reshape(-1, 3).to(device=dev, dtype=torch.float32).contiguous()
+        d = d.reshape(-1, 3).to(device=dev, dtype=torch.float32).contiguous()
+        R = o.shape[0]
+        B = 1
+        if poses is not None:
+            poses = poses.detach().reshape(-1, 4, 4).to(device=dev, dtype=torch.float32).contiguous()
+            B = poses.shape[0]
+        t = torch.empty((B, R), dtype=torch.float32, device=dev)
+        face = torch.empty((B, R), dtype=torch.int32, device=dev)
+        normal = torch.empty((B, R, 3), dtype=torch.float32, device=dev)
+        uv = torch.empty((B, R, 2), dtype=torch.float32, device=dev)
+        with _lib.on_device(dev):
+            _lib.check(lib.pvamd_mesh_ray_cast(ctypes.byref(desc), _lib.ptr(o), _lib.ptr(d), R, _lib.ptr(poses), B, t_min, t_max,
+                                               _lib.ptr(t), _lib.ptr(face), _lib.ptr(normal), _lib.ptr(uv), _lib.stream_ptr()),
+                       "pvamd_mesh_ray_cast")
+        shape = batch + lead
+        return MeshRayHits(_restore(t, shape, (), dtype, device), face.reshape(shape).to(device=device, dtype=torch.int64),
+                           _restore(normal, shape, (3,), dtype, device), _restore(uv, shape, (2,), dtype, device))
+
+    def render_depth(self, intrinsics, height, width, camera_pose, max_depth=math.inf):
+        """
+        Depth images of the mesh from pinhole cameras: the image TSDFVolume.integrate and OccupancyMap take.
+
+        :param intrinsics: (fx, fy, cx, cy) or a 3 x 3 matrix; pixel (row, col) is centred on (u, v) = (col, row)
+        :param camera_pose: (4, 4) or (K, 4, 4): the camera's pose in the object frame; it looks along +z, x right, y down
+        :param max_depth: hits deeper than this count as no return
+        :return: (K,) H x W float32 on the GPU: z-depth along the optical axis, t * (direction in the camera frame)_z of
+            camera_rays' unit directions, and exactly 0 -- integrate's "no return" -- where nothing was hit
+        """
+        from pytorch_volumetric_amd import tsdf
+        if isinstance(max_depth, bool) or not isinstance(max_depth, numbers.Real):
+            raise TypeError(f"max_depth must be a Python real number, got {type(max_depth).__name__}")
+        if not max_depth > 0:
+            raise ValueError(f"max_depth must be positive, got {max_depth!r}")
+        pose = camera_pose if torch.is_tensor(camera_pose) else torch.as_tensor(camera_pose)
+        if pose.dim() not in (2, 3) or tuple(pose.shape[-2:]) != (4, 4):
+            raise ValueError(f"camera_pose must be (4, 4) or (K, 4, 4), got {tuple(pose.shape)}")
+        tsdf._check_intrinsics(intrinsics)  # before a GPU is asked for
+        dev = _lib.require_gpu()
+        origins, directions, local = tsdf._pinhole(intrinsics, height, width, pose.detach().to(device=dev, dtype=torch.float32))
+        hits = self.cast_rays(origins, directions)
+        depth = hits.t * local[..., 2]
+        return torch.where((hits.face_ids >= 0) & (depth <= float(max_depth)), depth, torch.zeros_like(depth))
 
 
 class MeshObjectFactory(ObjectFactory):

@@ -69,6 +69,48 @@ def camera_from_volume(camera_pose):
     return torch.cat((Rt, back[:, :, None]), dim=2).to(torch.float32).contiguous()
 
 
+def camera_rays(intrinsics, height, width, camera_pose=None):
+    """(origins, directions) of a pinhole camera's pixel rays in the convention integrate() fixes: pixel (row, col) is centred on
+    (u, v) = (col, row) and the camera looks along +z with x right and y down, so the ray of a pixel points along
+    ((u - cx) / fx, (v - cy) / fy, 1), normalised.
+
+    :param intrinsics: (fx, fy, cx, cy) or a 3 x 3 matrix
+    :param camera_pose: None (the rays stay in the camera frame), (4, 4) or (K, 4, 4): the camera's pose in the target frame
+    :return: directions (K,) H x W x 3 of unit length and origins (K,) 1 x 1 x 3 that broadcast against them (zeros without a
+        pose), in the pose's floating dtype on the pose's device (float32 on the CPU without one).  Plain torch: elementwise
+        products and sums in a fixed order, so every device gives the same bits."""
+    origins, directions, _ = _pinhole(intrinsics, height, width, camera_pose)
+    return origins, directions
+
+
+def _pinhole(intrinsics, height, width, camera_pose):
+    """camera_rays' (origins, directions) and the unit directions in the camera frame, (H, W, 3), that they were turned from."""
+    fx, fy, cx, cy = _check_intrinsics(intrinsics)
+    for name, n in (("height", height), ("width", width)):
+        if isinstance(n, bool) or not isinstance(n, numbers.Integral) or n < 1:
+            raise ValueError(f"{name} must be a positive integer, got {n!r}")
+    pose = None
+    if camera_pose is not None:
+        pose = camera_pose if torch.is_tensor(camera_pose) else torch.as_tensor(camera_pose)
+        if pose.dim() not in (2, 3) or tuple(pose.shape[-2:]) != (4, 4):
+            raise ValueError(f"camera_pose must be (4, 4) or (K, 4, 4), got {tuple(pose.shape)}")
+        pose = pose.detach()
+        if not pose.dtype.is_floating_point:
+            pose = pose.to(torch.float32)
+    dtype, device = (torch.float32, torch.device("cpu")) if pose is None else (pose.dtype, pose.device)
+    x = ((torch.arange(width, dtype=dtype, device=device) - cx) / fx)[None, :].expand(height, width)
+    y = ((torch.arange(height, dtype=dtype, device=device) - cy) / fy)[:, None].expand(height, width)
+    length = torch.sqrt((x * x + y * y) + 1.0)
+    local = torch.stack((x / length, y / length, 1.0 / length), dim=-1)
+    if pose is None:
+        return torch.zeros((1, 1, 3), dtype=dtype, device=device), local, local
+    lx, ly, lz = local[..., 0], local[..., 1], local[..., 2]
+    rot = pose[..., :3, :3, None, None]  # (K,) 3 x 3 x 1 x 1
+    directions = torch.stack([(rot[..., i, 0, :, :] * lx + rot[..., i, 1, :, :] * ly) + rot[..., i, 2, :, :] * lz for i in range(3)],
+                             dim=-1)
+    return pose[..., None, None, :3, 3], directions, local
+
+
 def _check_frames(depth, intrinsics, camera_pose, max_depth, weight, depth_scale):
     """The argument errors of integrate, raised before a GPU is asked for."""
     depth = depth if torch.is_tensor(depth) else torch.as_tensor(depth)

@@ -17,7 +17,7 @@ for o in $C/*.o; do
   if { [ "$base" = "$n" ] || [ "${base#${n}_}" != "$base" ]; } && [ ${#n} -gt ${#which} ]; then which=$n; fi
 done
 [ -n "$which" ] || { echo "$src: no object of csrc/Makefile to replace" >&2; exit 1; }
-extra=""; { [ "$which" = composed ] || [ "$which" = mesh ]; } && extra="-fno-slp-vectorize"   # as csrc/Makefile (FLAGS_*)
+extra=""; { [ "$which" = composed ] || [ "$which" = mesh ] || [ "$which" = mesh_ray ]; } && extra="-fno-slp-vectorize"   # as csrc/Makefile (FLAGS_*)
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -fno-fast-math -ffp-contract=off -Wno-unused-value -Werror=unused-parameter -I$C -Iinclude $extra "-DPVAMD_VARIANT=\"$name: $*\"" "$@" -c "$src" -o tools/variants/${which}_$name.o
 objs=""
 for o in $C/*.o; do   # every object the Makefile built, except the one being replaced
