@@ -73,15 +73,6 @@ def _check_config(joint_config, M, names):
     return q.reshape(1, M) if q.dim() == 1 else q
 
 
-def _check_points(points):
-    pts = points if torch.is_tensor(points) else torch.as_tensor(points)
-    if pts.dim() < 1 or pts.shape[-1] != 3:
-        raise ValueError(f"points must have last dimension 3, got {tuple(pts.shape)}")
-    if pts.numel() == 0:
-        raise ValueError("points must hold at least one point (the cost is a mean over them)")
-    return pts
-
-
 def _check_limits(joint_limits, M):
     """joint_limits as an (M, 2) float64 array whose bounds are float32 values inside the caller's, or None.  The step clamps in
     float64 and the result is rounded to float32: bounds that are float32 values keep the rounded result inside them."""
@@ -101,22 +92,6 @@ def _check_limits(joint_limits, M):
     if not (lo <= hi).all():
         raise ValueError("joint_limits leave no float32 value between the lower and the upper bound of some joint")
     return np.stack((lo, hi), axis=-1)
-
-
-_TRIANGLE = {}
-
-
-def _triangle_index(dev, M):
-    """(M * M,) index into the packed upper triangle, cached per (device, M) (creating it copies from the host)."""
-    idx = _TRIANGLE.get((dev, M))
-    if idx is None:
-        rows, e = [[0] * M for _ in range(M)], 0
-        for r in range(M):
-            for c in range(r, M):
-                rows[r][c] = rows[c][r] = e
-                e += 1
-        idx = _TRIANGLE[(dev, M)] = torch.tensor(rows, dtype=torch.int64, device=dev).reshape(-1)
-    return idx
 
 
 class _Evaluator:
@@ -159,15 +134,13 @@ def _prepare(robot, joint_config, points, semantics, targets, huber_delta):
     """The argument checks of both entry points, all on the host: (S, M, mode, q (A, M), points, semantics, targets, delta)."""
     S, M, mode = _check_robot(robot)
     q = _check_config(joint_config, M, robot.joint_names)
-    pts = _check_points(points)
+    pts = reg._check_points(points)
     semantics, targets, huber_delta = reg._check_semantic_args(pts, semantics, targets, huber_delta)
     return S, M, mode, q, pts, semantics, targets, math.inf if huber_delta is None else huber_delta
 
 
-def _evaluator(robot, S, M, mode, q, pts, semantics, targets, delta):
-    dev = robot.sdf._owner_device()
-    pts32 = pts.detach().reshape(-1, 3).to(device=dev, dtype=torch.float32).contiguous()
-    q32 = q.detach().to(device=dev, dtype=torch.float32).contiguous()
+def _evaluator(robot, dev, S, M, mode, q, pts, semantics, targets, delta):
+    q32, pts32 = reg._prepare(q, pts, dev)
     kinds, targets32 = reg._prepare_semantics(semantics, targets, dev)
     return _Evaluator(robot, S, M, mode, dev, pts32, q32.shape[0], kinds, targets32, delta), q32
 
@@ -192,11 +165,11 @@ def joint_normal_equations(robot: RobotSDF, joint_config, points, scale=1000., s
     S, M, mode, q, pts, semantics, targets, delta = _prepare(robot, joint_config, points, semantics, targets, huber_delta)
     dev = robot.sdf._owner_device()
     with _lib.on_device(dev):
-        ev, q32 = _evaluator(robot, S, M, mode, q, pts, semantics, targets, delta)
+        ev, q32 = _evaluator(robot, dev, S, M, mode, q, pts, semantics, targets, delta)
         ev(q32)
         s = ev.sums * (scale * scale / ev.N)
         C = _lib.SEM_COUNTS
-        return JointNormalEquations(s[:, 0], s[:, 1:1 + M], s[:, 1 + M:][:, _triangle_index(dev, M)].reshape(ev.A, M, M),
+        return JointNormalEquations(s[:, 0], s[:, 1:1 + M], s[:, 1 + M:][:, reg._triangle_index(dev, M)].reshape(ev.A, M, M),
                                     ev.counts[:, 0], ev.counts[:, 1:4], ev.counts[:, 4], ev.counts[:, C:])
 
 
@@ -223,7 +196,7 @@ def refine_joint_configuration(robot: RobotSDF, joint_config, points, iterations
     dev = robot.sdf._owner_device()
     lib = _lib.load()
     with _lib.on_device(dev):
-        ev, q32 = _evaluator(robot, S, M, mode, q, pts, semantics, targets, delta)
+        ev, q32 = _evaluator(robot, dev, S, M, mode, q, pts, semantics, targets, delta)
         A = ev.A
         lim = None
         if limits is not None and M > 0:

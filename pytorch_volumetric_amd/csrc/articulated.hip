@@ -5,10 +5,10 @@
 // with (c_s, g6_s, H6_s) the 28 sums of "Semantic normal equations" over the points leaf s wins, in leaf s's frame.
 //
 //   joint_partial_kernel   workgroup (chunk, a): per point one composed walk (mop_point's statements) that keeps the winner and
-//                          its record; then, per leaf that won a point of the wave, sem_partial_kernel's 28 statements over the
+//                          its record; then, per leaf that won a point of the wave, the 28 statements of pair_sums over the
 //                          lane's points of that leaf in point order, a wave butterfly, the four waves in order; one slab row
 //                          per (chunk, a, leaf).  A wave without a point of leaf s adds +0.0 and skips that leaf's butterflies
-//   joint_finish_kernel    one thread per (a, leaf, entry): the chunks' rows added in chunk order
+//   normal_eq_finish_kernel (normal_eq.h)  one thread per (a, leaf, entry): the chunks' rows added in chunk order
 //   chain_twists_kernel    lane = configuration, blockIdx.y = leaf: the float64 chain walk and the 6 x M twist Jacobian J[a][s]
 //   joint_assemble_kernel  one thread per (a, entry of cost | gradient | upper triangle): the leaves in order, fused multiply-adds
 //   joint_lm_step_kernel   one wave per configuration, the damped matrix in LDS: pose_lm_step_kernel's decisions in joint space
@@ -16,14 +16,15 @@
 // (A, N) buffer reaches HBM.
 #include "common.h"
 #include "composed_point.h"
+#include "normal_eq.h"
 
 namespace pvamd {
 
 constexpr int kJntBlock = 256;
 constexpr int kJntK = PVAMD_REG_CHUNK / kJntBlock;  // points per lane per chunk
 static_assert(kJntK * kJntBlock == PVAMD_REG_CHUNK, "whole lanes per chunk");
-constexpr int kJntSums = PVAMD_REG_SUMS;
-constexpr int kJntCounts = PVAMD_SEM_COUNTS;
+constexpr int kJntSums = kNeSums;
+constexpr int kJntCounts = kSemCounts;
 constexpr int kJntWaves = kJntBlock / 64;
 static_assert(PVAMD_JOINT_MAX_LEAVES <= 64, "the leaves a wave saw are one 64-bit mask");
 static_assert(PVAMD_JOINT_MAX_LEAVES < 255, "winner and range bit share one register");
@@ -68,9 +69,7 @@ PVAMD_DEV void walk_points(const pvamd_grid_t* __restrict__ grids, int S, const 
     }
 }
 
-// slab: double [nchunks][A][S][28], then int64 [nchunks][A][S][5].  LDS: double ws[4][S][28], then int wc[4][S][5].
-// The per-pair statements are sem_partial_kernel's (registration.hip), copied and not shared: that kernel's bits and time are
-// pinned by tests and profiles of their own, and this file is compiled apart from it.
+// slab: double [nchunks][A][S][28], then int64 [nchunks][A][S][5].  LDS: double ws[4][S][28], then int wc[4][S][5]
 template <bool INTERP>
 __global__ __launch_bounds__(kJntBlock) void joint_partial_kernel(const pvamd_grid_t* __restrict__ grids, int S,
                                                                   const float* __restrict__ tf, int A,
@@ -143,43 +142,7 @@ __global__ __launch_bounds__(kJntBlock) void joint_partial_kernel(const pvamd_gr
                     // of all eight points' records is hoisted out of the leaf loop, 64 registers held across it
                     float v = bv[k], n0 = lg[k][0], n1 = lg[k][1], n2 = lg[k][2];
                     asm volatile("" : "+v"(v), "+v"(n0), "+v"(n1), "+v"(n2));
-                    const double r = (double)v - (double)target;
-                    // written as the contract's inactive cases negated: a NaN r fails both comparisons and stays active
-                    const bool active = kind == PVAMD_POINT_SURFACE || (kind == PVAMD_POINT_FREE && !(r >= 0.0)) ||
-                                        (kind == PVAMD_POINT_OCCUPIED && !(r <= 0.0));
-                    if (active) {
-                        double j[6], u[6];
-                        j[0] = (double)n0; j[1] = (double)n1; j[2] = (double)n2;
-                        // x cross n: each product of two float32 values is exact in float64, so each component rounds once
-                        j[3] = (double)x[1] * j[2] - (double)x[2] * j[1];
-                        j[4] = (double)x[2] * j[0] - (double)x[0] * j[2];
-                        j[5] = (double)x[0] * j[1] - (double)x[1] * j[0];
-                        const double ab = __builtin_fabs(r);
-                        double q = r;
-#pragma unroll
-                        for (int c = 0; c < 6; ++c) u[c] = j[c];
-                        const bool outlier = ab > delta;
-                        if (outlier) {
-                            const double w = delta / ab;
-                            acc[0] = __builtin_fma(delta, (ab + ab) - delta, acc[0]);
-                            q = w * r;
-#pragma unroll
-                            for (int c = 0; c < 6; ++c) u[c] = w * j[c];
-                        } else {
-                            acc[0] = __builtin_fma(r, r, acc[0]);
-                        }
-                        cnt[1] += kind == PVAMD_POINT_SURFACE;
-                        cnt[2] += kind == PVAMD_POINT_FREE;
-                        cnt[3] += kind == PVAMD_POINT_OCCUPIED;
-                        cnt[4] += outlier;
-                        int e = 7;
-#pragma unroll
-                        for (int rr = 0; rr < 6; ++rr) {
-                            acc[1 + rr] = __builtin_fma(q, j[rr], acc[1 + rr]);
-#pragma unroll
-                            for (int c = rr; c < 6; ++c, ++e) acc[e] = __builtin_fma(u[rr], j[c], acc[e]);
-                        }
-                    }
+                    pair_sums<true>(kind, (double)v - (double)target, x, n0, n1, n2, delta, acc, cnt);
                 }
             }
 #pragma unroll
@@ -206,26 +169,6 @@ __global__ __launch_bounds__(kJntBlock) void joint_partial_kernel(const pvamd_gr
             slab_count[row * kJntCounts + t] = c;
         }
         __syncthreads();
-    }
-}
-
-// rows = A * S (configuration, leaf) pairs
-__global__ __launch_bounds__(256) void joint_finish_kernel(int64_t rows, int64_t nchunks, const double* __restrict__ slab,
-                                                           const int64_t* __restrict__ slab_count,
-                                                           double* __restrict__ leaf_sums, int64_t* __restrict__ leaf_counts) {
-    const int64_t per = kJntSums + kJntCounts, total = rows * per;
-    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t b = t / per;
-        const int e = (int)(t - b * per);
-        if (e < kJntSums) {
-            double s = 0.0;
-            for (int64_t c = 0; c < nchunks; ++c) s += slab[(c * rows + b) * kJntSums + e];
-            leaf_sums[b * kJntSums + e] = s;
-        } else {
-            int64_t n = 0;
-            for (int64_t c = 0; c < nchunks; ++c) n += slab_count[(c * rows + b) * kJntCounts + (e - kJntSums)];
-            leaf_counts[b * kJntCounts + (e - kJntSums)] = n;
-        }
     }
 }
 
@@ -520,17 +463,14 @@ __global__ __launch_bounds__(64) void joint_lm_step_kernel(int M, const double* 
 
 using namespace pvamd;
 
-static inline int64_t joint_chunks(int64_t N) { return (N + PVAMD_REG_CHUNK - 1) / PVAMD_REG_CHUNK; }
-
 extern "C" int64_t pvamd_joint_normal_eq_scratch_bytes(int32_t A, int32_t S, int64_t N) {
-    if (A < 1 || S < 1 || N < 1) return 0;
-    return 8 * (int64_t)(kJntSums + kJntCounts) * A * S * joint_chunks(N);
+    return A < 1 || S < 1 || N < 1 ? 0 : normal_eq_slab_bytes((int64_t)A * S, kJntCounts, N);
 }
 
 extern "C" int pvamd_joint_normal_eq(const pvamd_grid_t* grids, int32_t S, int32_t mode, const float* stack, int32_t A,
                                      const float* points, int64_t N, const uint8_t* kinds, const float* targets,
                                      double huber_delta, double* leaf_sums, int64_t* leaf_counts, void* scratch, void* stream) {
-    if (A < 0 || S < 1 || S > PVAMD_JOINT_MAX_LEAVES || N < 1 || joint_chunks(N) > 0x7fffffff) return PVAMD_E_SHAPE;
+    if (A < 0 || S < 1 || S > PVAMD_JOINT_MAX_LEAVES || N < 1 || normal_eq_chunks(N) > 0x7fffffff) return PVAMD_E_SHAPE;
     if (mode != PVAMD_LEAF_NEAREST && mode != PVAMD_LEAF_TRILINEAR) return PVAMD_E_MODE;
     if (!(huber_delta > 0.0)) return PVAMD_E_MODE;  // a NaN too
     if (A == 0) return 0;
@@ -539,10 +479,10 @@ extern "C" int pvamd_joint_normal_eq(const pvamd_grid_t* grids, int32_t S, int32
         !aligned_to(leaf_sums, 8) || !aligned_to(leaf_counts, 8) || !aligned_to(scratch, 8))
         return PVAMD_E_ALIGN;
     hipStream_t st = (hipStream_t)stream;
-    const int64_t nchunks = joint_chunks(N), rows = (int64_t)A * S;
+    const int64_t rows = (int64_t)A * S;
     double* slab = (double*)scratch;
-    int64_t* slab_count = (int64_t*)(slab + nchunks * rows * kJntSums);
-    const dim3 grid_dim((unsigned)nchunks, grid_rows(A));
+    int64_t* slab_count = normal_eq_slab_counts(scratch, rows, N);
+    const dim3 grid_dim((unsigned)normal_eq_chunks(N), grid_rows(A));
     const size_t lds = (size_t)kJntWaves * S * (kJntSums * sizeof(double) + kJntCounts * sizeof(int));
     if (mode == PVAMD_LEAF_TRILINEAR)
         hipLaunchKernelGGL((joint_partial_kernel<true>), grid_dim, dim3(kJntBlock), lds, st, grids, S, stack, A, points, N, kinds,
@@ -550,8 +490,7 @@ extern "C" int pvamd_joint_normal_eq(const pvamd_grid_t* grids, int32_t S, int32
     else
         hipLaunchKernelGGL((joint_partial_kernel<false>), grid_dim, dim3(kJntBlock), lds, st, grids, S, stack, A, points, N, kinds,
                            targets, huber_delta, slab, slab_count);
-    hipLaunchKernelGGL(joint_finish_kernel, dim3(stream_grid(rows * (kJntSums + kJntCounts), 256)), dim3(256), 0, st, rows, nchunks,
-                       slab, slab_count, leaf_sums, leaf_counts);
+    launch_normal_eq_finish<kJntCounts>(rows, N, scratch, leaf_sums, leaf_counts, st);
     return (int)hipGetLastError();
 }
 
@@ -584,9 +523,7 @@ extern "C" int pvamd_joint_lm_step(int32_t A, int32_t M, const double* sums, int
                                    double* lambda, int32_t* accepted, double* q_try, float* q_next, const double* limits,
                                    double up, double down, double lambda_min, double lambda_max, void* stream) {
     if (A < 0 || M < 0 || M > PVAMD_JOINT_MAX) return PVAMD_E_SHAPE;
-    if ((first != 0 && first != 1) || !(up > 1.0) || !(down > 0.0 && down <= 1.0) || !(lambda_min > 0.0) ||
-        !(lambda_max >= lambda_min) || !(lambda_max < __builtin_inf()))
-        return PVAMD_E_MODE;
+    if (!lm_args_ok(first, up, down, lambda_min, lambda_max)) return PVAMD_E_MODE;
     if (A == 0) return 0;
     if (!sums || !sums_acc || !lambda || !accepted) return PVAMD_E_NULL;
     if (M > 0 && (!q_acc || !q_try || !q_next)) return PVAMD_E_NULL;

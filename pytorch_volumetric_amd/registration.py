@@ -55,6 +55,15 @@ def _check_scale(scale):
     return float(scale)
 
 
+def _check_points(points):
+    pts = points if torch.is_tensor(points) else torch.as_tensor(points)
+    if pts.dim() < 1 or pts.shape[-1] != 3:
+        raise ValueError(f"points must have last dimension 3, got {tuple(pts.shape)}")
+    if pts.numel() == 0:
+        raise ValueError("points must hold at least one point (the cost is a mean over them)")
+    return pts
+
+
 def _check_inputs(world_to_object, points, obj_sdf):
     """(W (B, 4, 4) as given, points as a tensor); raises before anything touches the device."""
     if not isinstance(obj_sdf, ObjectFrameSDF):
@@ -62,12 +71,7 @@ def _check_inputs(world_to_object, points, obj_sdf):
     W = tf.as_matrix(world_to_object)
     if W.dim() != 3 or tuple(W.shape[1:]) != (4, 4):
         raise ValueError(f"world_to_object must be (B, 4, 4), got {tuple(W.shape)}")
-    pts = points if torch.is_tensor(points) else torch.as_tensor(points)
-    if pts.dim() < 1 or pts.shape[-1] != 3:
-        raise ValueError(f"points must have last dimension 3, got {tuple(pts.shape)}")
-    if pts.numel() == 0:
-        raise ValueError("points must hold at least one point (the cost is a mean over them)")
-    return W, pts
+    return W, _check_points(points)
 
 
 def _fused_mode(obj_sdf):
@@ -85,81 +89,39 @@ def _device_of(obj_sdf, mode):
 _TRIANGLE = {}
 
 
-def _triangle_index(dev):
-    """(6, 6) index into the 21 packed upper-triangle entries, cached per device (creating it copies from the host)."""
-    idx = _TRIANGLE.get(dev)
+def _triangle_index(dev, M):
+    """(M * M,) index into the packed upper triangle, cached per (device, M) (creating it copies from the host)."""
+    idx = _TRIANGLE.get((dev, M))
     if idx is None:
-        rows, e = [[0] * 6 for _ in range(6)], 0
-        for r in range(6):
-            for c in range(r, 6):
+        rows, e = [[0] * M for _ in range(M)], 0
+        for r in range(M):
+            for c in range(r, M):
                 rows[r][c] = rows[c][r] = e
                 e += 1
-        idx = _TRIANGLE[dev] = torch.tensor(rows, dtype=torch.int64, device=dev).reshape(-1)
+        idx = _TRIANGLE[(dev, M)] = torch.tensor(rows, dtype=torch.int64, device=dev).reshape(-1)
     return idx
-
-
-class _Evaluator:
-    """The raw sums (B, 28) and counts (B,) at float32 poses (B, 4, 4) on the device; buffers allocated once."""
-
-    def __init__(self, obj_sdf, mode, dev, pts, B):
-        self.obj_sdf, self.mode, self.dev, self.pts, self.B = obj_sdf, mode, dev, pts, B
-        self.N = pts.shape[0]
-        self.sums = torch.empty((B, _lib.REG_SUMS), dtype=torch.float64, device=dev)
-        self.counts = torch.empty((B,), dtype=torch.int64, device=dev)
-        if mode is not None:
-            self.scratch = torch.empty((_lib.chamfer_normal_eq_scratch_bytes(B, self.N) // 8,), dtype=torch.int64, device=dev)
-            self.desc = obj_sdf._grid_desc()
-
-    def __call__(self, W32):
-        if self.B == 0:
-            return
-        lib = _lib.load()
-        if self.mode is not None:
-            _lib.check(lib.pvamd_chamfer_normal_eq(ctypes.byref(self.desc), self.mode, _lib.ptr(W32), self.B, _lib.ptr(self.pts),
-                                                   self.N, _lib.ptr(self.sums), _lib.ptr(self.counts), _lib.ptr(self.scratch),
-                                                   _lib.stream_ptr()), "pvamd_chamfer_normal_eq")
-            return
-        # any other object: transform with the kernel's statements, query the object, the same sums in float64 in torch
-        x = torch.empty((self.B, self.N, 3), dtype=torch.float32, device=self.dev)
-        _lib.check(lib.pvamd_transform_points(_lib.ptr(W32), self.B, _lib.ptr(self.pts), self.N, _lib.ptr(x), _lib.stream_ptr()),
-                   "pvamd_transform_points")
-        with torch.no_grad():
-            v, n = self.obj_sdf(x)
-        v = v.detach().to(device=self.dev, dtype=torch.float64).reshape(self.B, self.N)
-        n = n.detach().to(device=self.dev, dtype=torch.float64).reshape(self.B, self.N, 3)
-        j = torch.cat((n, torch.linalg.cross(x.to(torch.float64), n, dim=-1)), dim=-1)
-        self.sums[:, 0] = (v * v).sum(-1)
-        self.sums[:, 1:7] = (v.unsqueeze(-1) * j).sum(-2)
-        r, c = torch.triu_indices(6, 6).tolist()
-        self.sums[:, 7:] = (j[..., r] * j[..., c]).sum(-2)
-        self.counts.fill_(self.N)  # no grid: every point is answered by the object itself
 
 
 def _check_semantic_args(pts, semantics, targets, huber_delta):
     """(semantics, targets as tensors where given, huber_delta as a float or None); raises before anything touches the device."""
     lead = tuple(pts.shape[:-1])
-    if semantics is not None:
-        if not torch.is_tensor(semantics):
+
+    def per_point(name, val, what, floating_ok):
+        if val is None:
+            return None
+        if not torch.is_tensor(val):
             try:
-                semantics = torch.as_tensor(semantics)
+                val = torch.as_tensor(val)
             except (TypeError, ValueError, RuntimeError) as e:
-                raise TypeError(f"semantics must be an integer tensor, got {type(semantics).__name__}") from e
-        if semantics.dtype == torch.bool or semantics.dtype.is_floating_point or semantics.dtype.is_complex:
-            raise TypeError(f"semantics must have an integer dtype, got {semantics.dtype}")
-        if tuple(semantics.shape) != lead:
-            raise ValueError(f"semantics must have the shape of points without its last dimension {lead}, got "
-                             f"{tuple(semantics.shape)}")
-    if targets is not None:
-        if not torch.is_tensor(targets):
-            try:
-                targets = torch.as_tensor(targets)
-            except (TypeError, ValueError, RuntimeError) as e:
-                raise TypeError(f"targets must be a real tensor, got {type(targets).__name__}") from e
-        if targets.dtype == torch.bool or targets.dtype.is_complex:
-            raise TypeError(f"targets must have a real dtype, got {targets.dtype}")
-        if tuple(targets.shape) != lead:
-            raise ValueError(f"targets must have the shape of points without its last dimension {lead}, got "
-                             f"{tuple(targets.shape)}")
+                raise TypeError(f"{name} must be {what} tensor, got {type(val).__name__}") from e
+        if val.dtype == torch.bool or val.dtype.is_complex or (val.dtype.is_floating_point and not floating_ok):
+            raise TypeError(f"{name} must have {what} dtype, got {val.dtype}")
+        if tuple(val.shape) != lead:
+            raise ValueError(f"{name} must have the shape of points without its last dimension {lead}, got {tuple(val.shape)}")
+        return val
+
+    semantics = per_point("semantics", semantics, "an integer", False)
+    targets = per_point("targets", targets, "a real", True)
     if huber_delta is not None:
         if isinstance(huber_delta, bool) or not isinstance(huber_delta, numbers.Real):
             raise TypeError(f"huber_delta must be a real number, got {huber_delta!r}")
@@ -181,18 +143,20 @@ def _prepare_semantics(semantics, targets, dev):
     return kinds, targets
 
 
-class _SemanticEvaluator:
-    """_Evaluator under "Semantic normal equations": the raw sums (B, 28) and the five counts (B, 5).  kinds (N,) uint8 and
-    targets (N,) float32 on the device, or None; delta a float (inf: plain least squares)."""
+class _Evaluator:
+    """The raw sums (B, 28) and counts at float32 poses (B, 4, 4) on the device; buffers allocated once.  plain: "Chamfer normal
+    equations", counts (B,).  Otherwise "Semantic normal equations", the five counts (B, 5): kinds (N,) uint8 and targets (N,)
+    float32 on the device, or None; delta a float (inf: plain least squares)."""
 
-    def __init__(self, obj_sdf, mode, dev, pts, B, kinds, targets, delta):
+    def __init__(self, obj_sdf, mode, dev, pts, B, kinds=None, targets=None, delta=math.inf, plain=False):
         self.obj_sdf, self.mode, self.dev, self.pts, self.B = obj_sdf, mode, dev, pts, B
-        self.kinds, self.targets, self.delta = kinds, targets, delta
+        self.kinds, self.targets, self.delta, self.plain = kinds, targets, delta, plain
         self.N = pts.shape[0]
         self.sums = torch.empty((B, _lib.REG_SUMS), dtype=torch.float64, device=dev)
-        self.counts = torch.empty((B, _lib.SEM_COUNTS), dtype=torch.int64, device=dev)
+        self.counts = torch.empty((B,) if plain else (B, _lib.SEM_COUNTS), dtype=torch.int64, device=dev)
         if mode is not None:
-            self.scratch = torch.empty((_lib.semantic_normal_eq_scratch_bytes(B, self.N) // 8,), dtype=torch.int64, device=dev)
+            size = _lib.chamfer_normal_eq_scratch_bytes if plain else _lib.semantic_normal_eq_scratch_bytes
+            self.scratch = torch.empty((size(B, self.N) // 8,), dtype=torch.int64, device=dev)
             self.desc = obj_sdf._grid_desc()
 
     def __call__(self, W32):
@@ -200,12 +164,17 @@ class _SemanticEvaluator:
             return
         lib = _lib.load()
         if self.mode is not None:
-            _lib.check(lib.pvamd_semantic_normal_eq(ctypes.byref(self.desc), self.mode, _lib.ptr(W32), self.B, _lib.ptr(self.pts),
-                                                    self.N, _lib.ptr(self.kinds), _lib.ptr(self.targets), self.delta,
-                                                    _lib.ptr(self.sums), _lib.ptr(self.counts), _lib.ptr(self.scratch),
-                                                    _lib.stream_ptr()), "pvamd_semantic_normal_eq")
+            head = (ctypes.byref(self.desc), self.mode, _lib.ptr(W32), self.B, _lib.ptr(self.pts), self.N)
+            tail = (_lib.ptr(self.sums), _lib.ptr(self.counts), _lib.ptr(self.scratch), _lib.stream_ptr())
+            if self.plain:
+                _lib.check(lib.pvamd_chamfer_normal_eq(*head, *tail), "pvamd_chamfer_normal_eq")
+            else:
+                _lib.check(lib.pvamd_semantic_normal_eq(*head, _lib.ptr(self.kinds), _lib.ptr(self.targets), self.delta, *tail),
+                           "pvamd_semantic_normal_eq")
             return
-        # any other object: transform with the kernel's statements, query the object, the contract's statements in float64 in torch
+        # any other object: transform with the kernel's statements, query the object, the contract's statements in float64 in torch.
+        # One block serves the plain form too: without kinds and targets and with delta = inf every pair is active and none an
+        # outlier, and a `where` on an all-true mask, a product with 1.0 and `a > inf` change no bit of v v, v j and j j^T
         x = torch.empty((self.B, self.N, 3), dtype=torch.float32, device=self.dev)
         _lib.check(lib.pvamd_transform_points(_lib.ptr(W32), self.B, _lib.ptr(self.pts), self.N, _lib.ptr(x), _lib.stream_ptr()),
                    "pvamd_transform_points")
@@ -232,7 +201,10 @@ class _SemanticEvaluator:
         self.sums[:, 1:7] = torch.where(active.unsqueeze(-1), (w * r).unsqueeze(-1) * j, zero).sum(-2)
         rr, cc = torch.triu_indices(6, 6).tolist()
         self.sums[:, 7:] = torch.where(active.unsqueeze(-1), (w.unsqueeze(-1) * j)[..., rr] * j[..., cc], zero).sum(-2)
-        self.counts[:, 0] = self.N  # no grid: every point is answered by the object itself
+        if self.plain:
+            self.counts.fill_(self.N)  # no grid: every point is answered by the object itself
+            return
+        self.counts[:, 0] = self.N
         self.counts[:, 1] = (active & surface).sum(-1)
         self.counts[:, 2] = free.sum(-1)
         self.counts[:, 3] = occupied.sum(-1)
@@ -266,11 +238,11 @@ def chamfer_normal_equations(world_to_object, points, obj_sdf: ObjectFrameSDF, s
     dev = _device_of(obj_sdf, mode)
     with _lib.on_device(dev):
         W32, pts32 = _prepare(W, pts, dev)
-        ev = _Evaluator(obj_sdf, mode, dev, pts32, W32.shape[0])
+        ev = _Evaluator(obj_sdf, mode, dev, pts32, W32.shape[0], plain=True)
         ev(W32)
         k = scale * scale / ev.N
         s = ev.sums * k
-        return ChamferNormalEquations(s[:, 0], s[:, 1:7], s[:, 7:][:, _triangle_index(dev)].reshape(-1, 6, 6), ev.counts)
+        return ChamferNormalEquations(s[:, 0], s[:, 1:7], s[:, 7:][:, _triangle_index(dev, 6)].reshape(-1, 6, 6), ev.counts)
 
 
 def semantic_normal_equations(world_to_object, points, obj_sdf: ObjectFrameSDF, scale=1000., semantics=None, targets=None,
@@ -298,12 +270,11 @@ def semantic_normal_equations(world_to_object, points, obj_sdf: ObjectFrameSDF, 
     with _lib.on_device(dev):
         W32, pts32 = _prepare(W, pts, dev)
         kinds, targets32 = _prepare_semantics(semantics, targets, dev)
-        ev = _SemanticEvaluator(obj_sdf, mode, dev, pts32, W32.shape[0], kinds, targets32,
-                                math.inf if huber_delta is None else huber_delta)
+        ev = _Evaluator(obj_sdf, mode, dev, pts32, W32.shape[0], kinds, targets32, math.inf if huber_delta is None else huber_delta)
         ev(W32)
         k = scale * scale / ev.N
         s = ev.sums * k
-        return SemanticNormalEquations(s[:, 0], s[:, 1:7], s[:, 7:][:, _triangle_index(dev)].reshape(-1, 6, 6), ev.counts[:, 0],
+        return SemanticNormalEquations(s[:, 0], s[:, 1:7], s[:, 7:][:, _triangle_index(dev, 6)].reshape(-1, 6, 6), ev.counts[:, 0],
                                        ev.counts[:, 1:4], ev.counts[:, 4])
 
 
@@ -351,11 +322,8 @@ def refine_poses(world_to_object, points, obj_sdf: ObjectFrameSDF, iterations=10
     with _lib.on_device(dev):
         W32, pts32 = _prepare(W, pts, dev)
         B = W32.shape[0]
-        if plain:
-            ev = _Evaluator(obj_sdf, mode, dev, pts32, B)
-        else:
-            kinds, targets32 = _prepare_semantics(semantics, targets, dev)
-            ev = _SemanticEvaluator(obj_sdf, mode, dev, pts32, B, kinds, targets32, math.inf if huber_delta is None else huber_delta)
+        kinds, targets32 = _prepare_semantics(semantics, targets, dev)
+        ev = _Evaluator(obj_sdf, mode, dev, pts32, B, kinds, targets32, math.inf if huber_delta is None else huber_delta, plain)
         # the state of pvamd_pose_lm_step
         w_try = W32[:, :3, :].to(torch.float64).contiguous()
         w_acc = torch.empty_like(w_try)

@@ -37,7 +37,7 @@ two halves are a reference that needs no launch past the bound), no case yet.
                                                              B in y: for_row_slabs
     chamfer_mesh_kernel (mesh)                               B in y: for_row_slabs        test_chamfer_gpu::test_chamfer_mesh_takes_more_transforms_than_one_grid_dimension_holds
     mesh part kernels (mesh)                                 parts > GRID_Y_MAX           unreachable: a mesh of more than 16.7 M triangles
-    chamfer_normal_eq kernel, reg_finish_kernel (registration) B > GRID_Y_MAX; B 29 > ITEMS  test_registration_gpu::test_more_poses_than_one_grid_dimension_holds
+    reg_partial_kernel, normal_eq_finish_kernel (registration) B > GRID_Y_MAX; B 29 > ITEMS  test_registration_gpu::test_more_poses_than_one_grid_dimension_holds
     lp_transform_kernel (leaf_pair)                          A K > ITEMS                  not tested
     lp_backward_kernel (leaf_pair)                           A K > ITEMS                  not tested
     lph_pair_vjp_kernel (leaf_pair)                          A K > ITEMS                  not tested

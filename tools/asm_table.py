@@ -5,8 +5,10 @@ profiles/composed_prune.md and profiles/argument_prune.md.
 Per `.amdhsa_kernel` entry: the text from the kernel's label to its .Lfunc_end, comments and blank lines dropped, every
 mangled name replaced by one token and every .LBBn_m label by its order of appearance, hashed (SHA-256, 16 hex digits);
 instructions = the lines of that text that are neither labels nor directives; VGPR / SGPR / scratch / LDS from
-.amdhsa_next_free_vgpr, .amdhsa_next_free_sgpr, .amdhsa_private_segment_fixed_size, .amdhsa_group_segment_fixed_size."""
-import hashlib, re, subprocess, sys
+.amdhsa_next_free_vgpr, .amdhsa_next_free_sgpr, .amdhsa_private_segment_fixed_size, .amdhsa_group_segment_fixed_size.
+Below the table, for every kernel whose hash changed: the mnemonics whose count differs (parent -> new).  A kernel that is not
+listed there but changed its hash holds the same instructions in another order or with other registers."""
+import collections, hashlib, re, subprocess, sys
 
 FIELDS = ("next_free_vgpr", "next_free_sgpr", "private_segment_fixed_size", "group_segment_fixed_size")
 
@@ -27,7 +29,8 @@ def kernels(path):
         lines = [re.sub(r"\.LBB\d+_\d+", lambda m: labels[m.group(0)], l) for l in lines]
         insts = sum(1 for l in lines if not l.endswith(":") and not l.startswith("."))
         res = tuple(int(re.search(r"\.amdhsa_%s (\d+)" % f, block.group(2)).group(1)) for f in FIELDS)
-        out[name] = (hashlib.sha256("\n".join(lines).encode()).hexdigest()[:16], insts) + res
+        ops = collections.Counter(l.split()[0] for l in lines if not l.endswith(":") and not l.startswith("."))
+        out[name] = (hashlib.sha256("\n".join(lines).encode()).hexdigest()[:16], insts) + res + (ops,)
     return out
 
 
@@ -45,6 +48,11 @@ def main():
         print("| `%s` | %s | %s | %s |" % (n, o[0] if o else "absent", w[0] if w else "gone", " | ".join(cell(i) for i in range(1, 6))))
     same = sum(1 for n in old if n in new and old[n][0] == new[n][0])
     print("\n%d kernels in parent, %d in new, %d with the same hash" % (len(old), len(new), same))
+    for n in sorted(set(old) & set(new)):
+        a, b = old[n][6], new[n][6]
+        moved = ["%s %d -> %d" % (m, a[m], b[m]) for m in sorted(set(a) | set(b)) if a[m] != b[m]]
+        if moved:
+            print("\n`%s`: %s" % (n, ", ".join(moved)))
 
 
 if __name__ == "__main__":

@@ -9,12 +9,18 @@ for A in {1, 64} configurations and N in {15,251, 262,144} points sampled from t
              then one semantic_normal_equations call per (configuration, leaf) on the masked kinds and a float64 torch assembly
              with the twist Jacobians (taken from pvamd_chain_twists here, so their cost is not in the figure); timed eagerly
 
+Every --parent-lib (the option repeats) names another build of the library, a parent commit's say: one evaluation through its
+entry points, called by address through a handle of their own in the same process into buffers of their own, is timed in regions
+that alternate with this build's (eval_parent_ms) and its sums compared bit for bit (parent_bits_equal).  Two builds of one source
+give the spread a difference has to exceed.  --eval-only leaves refine10 and the baseline out.
+
 HIP-event timings after a warm-up, median of --regions regions.  Prints one JSON line per row and writes the markdown table to
 --out.
 
-  python tools/bench_articulated.py [--regions 11] [--iters 3] [--out table.md]
+  python tools/bench_articulated.py [--regions 11] [--iters 3] [--parent-lib libpvamd.so]... [--eval-only] [--out table.md]
 """
 import argparse
+import ctypes
 import json
 import math
 import os
@@ -33,6 +39,7 @@ from pytorch_volumetric_amd import _lib  # noqa: E402
 from pytorch_volumetric_amd import articulated as art  # noqa: E402
 from pytorch_volumetric_amd import registration as reg  # noqa: E402
 from pytorch_volumetric_amd import transforms as tf  # noqa: E402
+from bench_min_over_points import alternate  # noqa: E402
 from bench_registration import graphed, median_ms  # noqa: E402
 
 CONFIGS = (1, 64)
@@ -99,12 +106,38 @@ def baseline(robot, q32, pts, kinds, targets, delta, J, scale=1000.):
     return cost, g, H
 
 
+def parent_library(path):
+    lib = ctypes.CDLL(path)
+    for name in ("pvamd_configure_chain", "pvamd_joint_normal_eq", "pvamd_chain_twists", "pvamd_joint_assemble"):
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = _lib.SIGNATURES[name]
+    return lib
+
+
+def parent_evaluation(lib, ev, q32):
+    """art._Evaluator.__call__ through another build's entry points, on ev's buffers."""
+    def run():
+        stream = _lib.stream_ptr()
+        ev.robot._configure(lib, ev.dev, q32, ev.A, ev.M, ev.S, ev.offset_inv, stack=ev.stack)
+        _lib.check(lib.pvamd_joint_normal_eq(_lib.ptr(ev.grids), ev.S, ev.mode, _lib.ptr(ev.stack), ev.A, _lib.ptr(ev.pts), ev.N,
+                                             _lib.ptr(ev.kinds), _lib.ptr(ev.targets), ev.delta, _lib.ptr(ev.leaf_sums),
+                                             _lib.ptr(ev.leaf_counts), _lib.ptr(ev.scratch), stream), "pvamd_joint_normal_eq (parent)")
+        _lib.check(lib.pvamd_chain_twists(_lib.ptr(ev.joints), ev.F, _lib.ptr(q32), ev.A, ev.M, _lib.ptr(ev.offset_inv), ev.S,
+                                          _lib.ptr(ev.J), stream), "pvamd_chain_twists (parent)")
+        _lib.check(lib.pvamd_joint_assemble(_lib.ptr(ev.leaf_sums), _lib.ptr(ev.leaf_counts), _lib.ptr(ev.J), ev.A, ev.S, ev.M,
+                                            _lib.ptr(ev.sums), _lib.ptr(ev.counts), stream), "pvamd_joint_assemble (parent)")
+    return run
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--regions", type=int, default=11)
     ap.add_argument("--iters", type=int, default=3)
+    ap.add_argument("--parent-lib", action="append", default=[], help="another build of libpvamd.so to time side by side (repeats)")
+    ap.add_argument("--eval-only", action="store_true", help="leave refine10 and the baseline out")
     ap.add_argument("--out", default=None, help="also write the markdown table here (profiles/articulated.md quotes it)")
     args = ap.parse_args()
+    parent_libs = [parent_library(path) for path in args.parent_lib]
     torch.cuda.set_device(0)
     dev = torch.device("cuda", 0)
     rows = []
@@ -125,14 +158,21 @@ def main():
                         k8 = reg._prepare_semantics(kinds, None, dev)[0]
                         ev = art._Evaluator(robot, S, M, leaf_mode, dev, pts, A, k8, targets, DELTA)
                         kw = dict(semantics=kinds, targets=targets, huber_delta=DELTA)
-                        row = {"robot": name, "S": S, "M": M, "mode": mode, "A": A, "N": N,
-                               "slab_bytes": _lib.joint_normal_eq_scratch_bytes(A, S, N),
-                               "eval_ms": median_ms(graphed(lambda: ev(q32)), args.regions, args.iters),
-                               "refine10_ms": median_ms(graphed(lambda: pv.refine_joint_configuration(robot, q32, pts, iterations=10,
-                                                                                                        **kw)), args.regions, 1)}
+                        parents = [art._Evaluator(robot, S, M, leaf_mode, dev, pts, A, k8, targets, DELTA) for _ in parent_libs]
+                        ms = alternate({"this": graphed(lambda: ev(q32)),
+                                        **{i: graphed(parent_evaluation(lib, p, q32)) for i, (lib, p) in enumerate(zip(parent_libs, parents))}},
+                                       args.regions, args.iters)
                         torch.cuda.synchronize()
-                        row["leaves_observed"] = int((ev.counts[0, _lib.SEM_COUNTS:] > 0).sum())
-                        if mode == "nearest":
+                        row = {"robot": name, "S": S, "M": M, "mode": mode, "A": A, "N": N,
+                               "slab_bytes": _lib.joint_normal_eq_scratch_bytes(A, S, N), "eval_ms": ms["this"],
+                               "eval_parent_ms": [ms[i] for i in range(len(parents))],
+                               "parent_bits_equal": [bool(torch.equal(p.sums, ev.sums) and torch.equal(p.leaf_sums, ev.leaf_sums)
+                                                          and torch.equal(p.counts, ev.counts)) for p in parents],
+                               "leaves_observed": int((ev.counts[0, _lib.SEM_COUNTS:] > 0).sum())}
+                        if not args.eval_only:
+                            row["refine10_ms"] = median_ms(graphed(lambda: pv.refine_joint_configuration(robot, q32, pts, iterations=10,
+                                                                                                          **kw)), args.regions, 1)
+                        if mode == "nearest" and not args.eval_only:
                             ne = pv.joint_normal_equations(robot, q32, pts, **kw)
                             row["baseline_ms"] = median_ms(lambda: baseline(robot, q32, pts, kinds, targets, DELTA, ev.J), 3, 1)
                             cost, gq, Hq = baseline(robot, q32, pts, kinds, targets, DELTA, ev.J)
@@ -140,12 +180,14 @@ def main():
                             row["baseline_hessian_rel_diff"] = float((Hq - ne.hessian).abs().max() / ne.hessian.abs().max())
                         rows.append(row)
                         print(json.dumps(row), flush=True)
-    lines = ["| robot | mode | A x N | eval ms | refine10 ms | baseline eval ms | baseline / eval | slab MB | leaves observed |",
-             "|---|---|---|---|---|---|---|---|---|"]
+    lines = ["| robot | mode | A x N | eval ms" + "".join(f" / {path}" for path in args.parent_lib) + " | refine10 ms | "
+             "baseline eval ms | baseline / eval | slab MB | leaves observed |", "|---|---|---|---|---|---|---|---|---|"]
     for r in rows:
         b = r.get("baseline_ms", math.nan)
-        lines.append(f"| {r['robot']} (S {r['S']}, M {r['M']}) | {r['mode']} | {r['A']} x {r['N']:,} | {r['eval_ms']:.4f} | "
-                     f"{r['refine10_ms']:.3f} | {b:.3f} | {b / r['eval_ms']:.0f} | {r['slab_bytes'] / 1e6:.2f} | {r['leaves_observed']} |")
+        lines.append(f"| {r['robot']} (S {r['S']}, M {r['M']}) | {r['mode']} | {r['A']} x {r['N']:,} | "
+                     + " / ".join(f"{v:.4f}" for v in [r["eval_ms"]] + r["eval_parent_ms"])
+                     + f" | {r.get('refine10_ms', math.nan):.3f} | {b:.3f} | {b / r['eval_ms']:.0f} | {r['slab_bytes'] / 1e6:.2f} | "
+                     f"{r['leaves_observed']} |")
     table = "\n".join(lines)
     print(table)
     if args.out:

@@ -5,15 +5,18 @@ B x N in {64 x 16,384, 1 x 2^20} -- the shapes of profiles/registration.md -- in
   mixed        kinds uniform in 0..3, targets uniform in +-0.02, delta = inf
   outliers     the same kinds and targets, delta at the 80th percentile of |r| over the first pose's active pairs
 
-each next to two baselines: pvamd_chamfer_normal_eq (of this build, and of the library given with --parent-lib, a build of the
-commit before the semantic kernels, called by address through its own handle), and the same sums written in torch ops on (B, N)
-tensors (the package's generic path, run on the cache's own query).  HIP-event timings of graph replays after a warm-up, median
-of --regions regions; one replay is the two launches of an evaluation into buffers allocated once.  The torch baseline is
-timed eagerly between the same events (its index tensors are built from host lists, which a capture refuses): some thirty
-launches over (B, N) float64 tensors, whose device time is what the figure mostly holds at these sizes.
+each next to two baselines: pvamd_chamfer_normal_eq of this build, and the same sums written in torch ops on (B, N) tensors (the
+package's generic path, run on the cache's own query; --skip-torch leaves it out).  Every --parent-lib (the option repeats) names
+another build of the library, a parent commit's say: its pvamd_chamfer_normal_eq and its pvamd_semantic_normal_eq in the three
+configurations are called by address through a handle of their own in the same process, timed in regions that alternate with
+this build's, and their sums compared bit for bit (parent_bits_equal).  Two builds of one source give the spread a difference has
+to exceed.  HIP-event timings of graph replays after a warm-up, median of --regions regions; one replay is the two launches of an
+evaluation into buffers allocated once.  The torch baseline is timed eagerly between the same events (its index tensors are
+built from host lists, which a capture refuses): some thirty launches over (B, N) float64 tensors, whose device time is what
+the figure mostly holds at these sizes.
 Prints one JSON line per row and writes the markdown table to --out.
 
-  python tools/bench_semantic_registration.py [--regions 21] [--iters 5] [--parent-lib libpvamd.so] [--out table.md]
+  python tools/bench_semantic_registration.py [--regions 21] [--iters 5] [--parent-lib libpvamd.so]... [--skip-torch] [--out table.md]
 """
 import argparse
 import ctypes
@@ -31,36 +34,50 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 import workloads as W  # noqa: E402
 from pytorch_volumetric_amd import _lib  # noqa: E402
 from pytorch_volumetric_amd import registration as reg  # noqa: E402
+from bench_min_over_points import alternate  # noqa: E402
 from bench_registration import graphed, median_ms  # noqa: E402
 
 CASES = ((64, 16384), (1, 1 << 20))
 
 
-def parent_evaluator(path, c, mode, W32, pts):
-    """pvamd_chamfer_normal_eq of another build of the library, through a handle of its own."""
+def parent_evaluator(path, c, mode, W32, pts, config=None):
+    """pvamd_chamfer_normal_eq, or with config = (kinds, targets, delta) pvamd_semantic_normal_eq, of another build of the
+    library, through a handle of its own."""
+    name = "pvamd_chamfer_normal_eq" if config is None else "pvamd_semantic_normal_eq"
     lib = ctypes.CDLL(path)
-    fn = lib.pvamd_chamfer_normal_eq
-    fn.restype, fn.argtypes = _lib.SIGNATURES["pvamd_chamfer_normal_eq"]
-    size = lib.pvamd_chamfer_normal_eq_scratch_bytes
-    size.restype, size.argtypes = _lib.SIGNATURES["pvamd_chamfer_normal_eq_scratch_bytes"]
+    fn, size = getattr(lib, name), getattr(lib, name + "_scratch_bytes")
+    fn.restype, fn.argtypes = _lib.SIGNATURES[name]
+    size.restype, size.argtypes = _lib.SIGNATURES[name + "_scratch_bytes"]
     B, N = W32.shape[0], pts.shape[0]
     sums = torch.empty((B, _lib.REG_SUMS), dtype=torch.float64, device=pts.device)
-    counts = torch.empty((B,), dtype=torch.int64, device=pts.device)
+    counts = torch.empty((B,) if config is None else (B, _lib.SEM_COUNTS), dtype=torch.int64, device=pts.device)
     scratch = _lib.scratch_buffer(size(B, N), pts.device)
     desc = c._grid_desc()
+    extra = () if config is None else (_lib.ptr(config[0]), _lib.ptr(config[1]), config[2])
 
     def run():
-        _lib.check(fn(ctypes.byref(desc), mode, _lib.ptr(W32), B, _lib.ptr(pts), N, _lib.ptr(sums), _lib.ptr(counts),
-                      _lib.ptr(scratch), _lib.stream_ptr()), "pvamd_chamfer_normal_eq (parent)")
+        _lib.check(fn(ctypes.byref(desc), mode, _lib.ptr(W32), B, _lib.ptr(pts), N, *extra, _lib.ptr(sums), _lib.ptr(counts),
+                      _lib.ptr(scratch), _lib.stream_ptr()), name + " (parent)")
     run.sums = sums
     return run
+
+
+def against_parents(ev, parents, Wm, regions, iters):
+    """(ms of ev, [ms of every parent], [its sums equal ev's bit for bit]), the regions of all of them alternating."""
+    ms = alternate({"this": graphed(lambda: ev(Wm)), **{i: graphed(p) for i, p in enumerate(parents)}}, regions, iters)
+    ev(Wm)
+    for p in parents:
+        p()
+    torch.cuda.synchronize()
+    return ms["this"], [ms[i] for i in range(len(parents))], [bool(torch.equal(p.sums, ev.sums)) for p in parents]
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--regions", type=int, default=21)
     ap.add_argument("--iters", type=int, default=5)
-    ap.add_argument("--parent-lib", default=None, help="libpvamd.so built from the commit before the semantic kernels")
+    ap.add_argument("--parent-lib", action="append", default=[], help="another build of libpvamd.so to time side by side (repeats)")
+    ap.add_argument("--skip-torch", action="store_true", help="leave the torch-ops baseline out")
     ap.add_argument("--out", default=None, help="also write the markdown table here (profiles/semantic_registration.md quotes it)")
     args = ap.parse_args()
     torch.cuda.set_device(0)
@@ -87,41 +104,39 @@ def main():
             delta = float(torch.quantile(r[active].abs()[:1 << 20], 0.8))
             configs = {"degenerate": (None, None, math.inf), "mixed": (kinds, targets, math.inf),
                        "outliers": (kinds, targets, delta)}
-            old = reg._Evaluator(c, mode, dev, pts, B)
-            row = {"B": B, "N": N, "mode": mode_name, "delta": delta,
-                   "chamfer_ms": median_ms(graphed(lambda: old(Wm)), args.regions, args.iters)}
-            if args.parent_lib:
-                parent = parent_evaluator(args.parent_lib, c, mode, Wm, pts)
-                row["chamfer_parent_ms"] = median_ms(graphed(parent), args.regions, args.iters)
-                old(Wm)
-                torch.cuda.synchronize()
-                row["parent_bits_equal"] = bool(torch.equal(parent.sums, old.sums))
+            old = reg._Evaluator(c, mode, dev, pts, B, plain=True)
+            parents = [parent_evaluator(path, c, mode, Wm, pts) for path in args.parent_lib]
+            row = {"B": B, "N": N, "mode": mode_name, "delta": delta}
+            row["chamfer_ms"], row["chamfer_parent_ms"], row["parent_bits_equal"] = against_parents(old, parents, Wm, args.regions,
+                                                                                                    args.iters)
             for name, (k, t, d) in configs.items():
-                ev = reg._SemanticEvaluator(c, mode, dev, pts, B, k, t, d)
-                ms = median_ms(graphed(lambda: ev(Wm)), args.regions, args.iters)
-                torch.cuda.synchronize()
+                ev = reg._Evaluator(c, mode, dev, pts, B, k, t, d)
+                parents = [parent_evaluator(path, c, mode, Wm, pts, (k, t, d)) for path in args.parent_lib]
+                ms, parent_ms, equal = against_parents(ev, parents, Wm, args.regions, args.iters)
                 counts = ev.counts.sum(0).tolist()
-                generic = reg._SemanticEvaluator(c, None, dev, pts, B, k, t, d)
-                torch_ms = median_ms(lambda: generic(Wm), args.regions, max(1, args.iters // 2))
-                row[name] = {"ms": ms, "torch_ms": torch_ms, "active": sum(counts[1:4]), "outliers": counts[4],
-                             "outlier_share_of_active": counts[4] / max(1, sum(counts[1:4]))}
+                row[name] = {"ms": ms, "parent_ms": parent_ms, "parent_bits_equal": equal, "active": sum(counts[1:4]),
+                             "outliers": counts[4], "outlier_share_of_active": counts[4] / max(1, sum(counts[1:4]))}
+                if not args.skip_torch:
+                    generic = reg._Evaluator(c, None, dev, pts, B, k, t, d)
+                    row[name]["torch_ms"] = median_ms(lambda: generic(Wm), args.regions, max(1, args.iters // 2))
                 if name == "degenerate":
                     old(Wm)
                     torch.cuda.synchronize()
                     row["degenerate_bits_equal"] = bool(torch.equal(ev.sums, old.sums))
             rows.append(row)
-            print(json.dumps(row))
-    head = "| B x N | mode | chamfer ms |" + (" chamfer (parent build) ms |" if args.parent_lib else "")
-    lines = [head + " degenerate ms | mixed ms | outliers ms | outlier share | x chamfer: degenerate / mixed / outliers | "
-             "torch ops ms: degenerate / mixed / outliers |", "|---" * (head.count("|") - 1 + 6) + "|"]
+            print(json.dumps(row), flush=True)
+    cell = lambda ms, parent_ms: " / ".join(f"{v:.4f}" for v in [ms] + parent_ms)
+    lines = ["| B x N | mode | chamfer ms | degenerate ms | mixed ms | outliers ms | outlier share | x chamfer: degenerate / mixed / "
+             "outliers | torch ops ms: degenerate / mixed / outliers |", "|---" * 9 + "|"]
+    if args.parent_lib:
+        lines.insert(0, f"(every ms cell: this build / {' / '.join(args.parent_lib)})\n")
     for r in rows:
         d, m, o = r["degenerate"], r["mixed"], r["outliers"]
         base = r["chamfer_ms"]
-        lines.append(f"| {r['B']:,} x {r['N']:,} | {r['mode']} | {base:.4f} |"
-                     + (f" {r['chamfer_parent_ms']:.4f} |" if args.parent_lib else "")
-                     + f" {d['ms']:.4f} | {m['ms']:.4f} | {o['ms']:.4f} | {o['outlier_share_of_active']:.3f} | "
-                     f"{d['ms'] / base:.2f} / {m['ms'] / base:.2f} / {o['ms'] / base:.2f} | "
-                     f"{d['torch_ms']:.3f} / {m['torch_ms']:.3f} / {o['torch_ms']:.3f} |")
+        lines.append(f"| {r['B']:,} x {r['N']:,} | {r['mode']} | {cell(base, r['chamfer_parent_ms'])} | "
+                     + " | ".join(cell(v["ms"], v["parent_ms"]) for v in (d, m, o))
+                     + f" | {o['outlier_share_of_active']:.3f} | {d['ms'] / base:.2f} / {m['ms'] / base:.2f} / {o['ms'] / base:.2f} | "
+                     + " / ".join(f"{v.get('torch_ms', math.nan):.3f}" for v in (d, m, o)) + " |")
     table = "\n".join(lines)
     print(table)
     if args.out:
