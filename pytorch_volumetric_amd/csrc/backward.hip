@@ -11,17 +11,17 @@
 //   dp = L^T dx,   dL[r][j] += dx_r p_j,   dt_r = dx_r
 // Every sum is a fixed-order reduction (no float atomics): dpoints over configurations in registers (configuration order) and,
 // when the configurations are split over workgroups, over the splits in split order; dtf over the points of a workgroup by
-// wave butterflies + per-wave LDS slots, then over the workgroups' slab rows in chunk order.  Results are bitwise
-// reproducible from run to run (float atomics would make the sums depend on arrival order).
+// wave butterflies + per-wave LDS slots, then over the workgroups' slab rows in chunk order (tf_reduce.h, which the ray-cast and
+// the leaf-pair hinge backward share).  Results are bitwise reproducible from run to run (float atomics would make the sums
+// depend on arrival order).
 #include "common.h"
 #include "grid_lookup.h"
 #include "interp.h"
 #include "leaf_vjp.h"
 #include "composed_point.h"
+#include "tf_reduce.h"
 
 namespace pvamd {
-
-constexpr int kBwdMaxLeaves = 64;                  // per-wave LDS slots (and the presence mask) hold up to 64 leaves
 
 // ---- CachedSDF.__call__ backward: one point per lane, no reduction ----
 template <typename T, bool HAS_V, bool HAS_G, bool INTERP>
@@ -47,19 +47,11 @@ __global__ __launch_bounds__(256) void cached_backward_kernel(const pvamd_grid_t
     }
 }
 
-template <typename T>
-PVAMD_DEV T wave_sum(T v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;  // a butterfly: every lane holds the same bits (float addition is commutative)
-}
-
 // ---- ComposedSDF.__call__ / grid chamfer backward ----
 // Workgroup (chunk, split): points [chunk * kBwdChunk, +kBwdChunk) x configurations [split * aper, +aper).  Each lane keeps the
 // dpoints of its kBwdK points in registers over the configurations; per configuration the 12 dtf partials of every
-// (configuration, leaf) are reduced wave by wave (one butterfly per leaf present in the wave) into a per-wave LDS slot, the
-// four waves' slots are added in wave order and leave as one slab row [chunk][s*A + a][12] (every row written, zeros for
-// absent leaves: the slab needs no clearing).
+// (configuration, leaf) go through tf_wave_reduce and tf_block_store (tf_reduce.h) and leave as one slab row
+// [chunk][s*A + a][12].
 // CHAMFER: one leaf (the grid g0), tf = the B world->object matrices, dv = dsum[a] * d(scale v)^2/dv = dsum[a] 2 scale^2 v.
 // HINGE (the upstream policy of hinge_over_points): no leaf ids and no (A, P) upstream.  Per pair the composed value v and the
 // winning leaf are recomputed with the forward's statements (mop_point, the same bits), and dv is torch's VJP of
@@ -71,8 +63,8 @@ __global__ __launch_bounds__(kBwdBlock) void composed_backward_kernel(
     const T* __restrict__ pts, int64_t P, const int32_t* __restrict__ leaf, const T* __restrict__ dval,
     const T* __restrict__ dgrad, T scale, int aper, T* __restrict__ dp_out, T* __restrict__ slab,
     const T* __restrict__ up = nullptr, int64_t up_stride = 0, T margin = T(0), int power = 0) {
-    __shared__ T part[kBwdBlock / 64][kBwdMaxLeaves][12];
-    __shared__ uint64_t present[kBwdBlock / 64];
+    __shared__ T part[kTfWaves][kTfMaxLeaves][12];
+    __shared__ uint64_t present[kTfWaves];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int64_t chunk = blockIdx.x;
     const int split = blockIdx.y;
@@ -152,36 +144,9 @@ __global__ __launch_bounds__(kBwdBlock) void composed_backward_kernel(
                     }
                 }
             }
-            if (WANT_TF) {
-                uint64_t todo = __builtin_amdgcn_ballot_w64(s >= 0);
-                while (todo) {  // wave-uniform: one butterfly per leaf that wins somewhere in the wave
-                    const int first = __builtin_ctzll(todo);
-                    const int sl = __builtin_amdgcn_readlane(s, first);
-                    const bool mine = s == sl;
-                    todo &= ~__builtin_amdgcn_ballot_w64(mine);
-                    const bool seen = (present[wave] >> sl) & 1ull;
-#pragma unroll
-                    for (int j = 0; j < 12; ++j) {
-                        const T v = wave_sum<T>(mine ? c[j] : T(0));
-                        if (lane == 0) part[wave][sl][j] = seen ? part[wave][sl][j] + v : v;
-                    }
-                    if (lane == 0) present[wave] |= 1ull << sl;
-                    PVAMD_WAVE_SYNC();
-                }
-            }
+            if (WANT_TF) tf_wave_reduce(s, c, part, present, wave, lane);
         }
-        if (WANT_TF) {
-            __syncthreads();
-            for (int e = threadIdx.x; e < S * 12; e += kBwdBlock) {
-                const int s = e / 12, j = e - 12 * (e / 12);
-                T v = T(0);
-#pragma unroll
-                for (int w = 0; w < kBwdBlock / 64; ++w)
-                    if ((present[w] >> s) & 1ull) v += part[w][s][j];
-                slab[(chunk * ((int64_t)S * A) + (int64_t)s * A + a) * 12 + j] = v;
-            }
-            __syncthreads();
-        }
+        if (WANT_TF) tf_block_store(S, part, present, slab + (chunk * ((int64_t)S * A) + a) * 12, (int64_t)A * 12);
     }
     if (dp_out) {
         T* out = dp_out + (int64_t)split * P * 3;
@@ -192,21 +157,6 @@ __global__ __launch_bounds__(kBwdBlock) void composed_backward_kernel(
                 out[3 * idx[k] + 1] = dp[k][1];
                 out[3 * idx[k] + 2] = dp[k][2];
             }
-    }
-}
-
-// dtf[sa][r][c] = sum over chunks, in chunk order, of slab[chunk][sa][4r + c] (row 3: zeros)
-template <typename T>
-__global__ __launch_bounds__(256) void reduce_tf_kernel(const T* __restrict__ slab, int64_t nchunks, int64_t SA, T* __restrict__ dtf) {
-    const int64_t n = SA * 16;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += stride) {
-        const int64_t sa = e >> 4;
-        const int rc = (int)(e & 15);
-        T v = T(0);
-        if (rc < 12)
-            for (int64_t ch = 0; ch < nchunks; ++ch) v += slab[(ch * SA + sa) * 12 + rc];
-        dtf[e] = v;
     }
 }
 
@@ -223,9 +173,8 @@ __global__ __launch_bounds__(256) void reduce_splits_kernel(const T* __restrict_
 
 // The launch geometry and the scratch layout of one composed backward pass.  The size functions report `bytes` (the per-leaf
 // hinge: `leaf_off` plus its leaf term) and the launch code carves at the same offsets: the slab at 0, the split rows, the leaf term.
-struct BwdPlan {
+struct BwdPlan : TfSplit {
     int64_t nchunks;
-    int nsplit, aper;
     int64_t split_off;  // bytes: past the slab [nchunks][S*A][12]; the dpoints rows [nsplit][P][3] when nsplit > 1
     int64_t bytes;      // slab and split rows
     int64_t leaf_off;   // bytes: past both; the per-leaf hinge's one [P][3] leaf term
@@ -235,12 +184,8 @@ static BwdPlan bwd_plan(int S, int A, int64_t P, size_t elem) {
     BwdPlan b;
     b.nchunks = (P + kBwdChunk - 1) / kBwdChunk;
     if (b.nchunks < 1) b.nchunks = 1;
-    int64_t want = (kBwdTargetBlocks + b.nchunks - 1) / b.nchunks;
-    if (want > A) want = A;
-    if (want < 1) want = 1;
-    b.aper = (int)((A + want - 1) / want);
-    b.nsplit = (A + b.aper - 1) / b.aper;
-    b.split_off = round256(b.nchunks * (int64_t)S * A * 12 * (int64_t)elem);
+    static_cast<TfSplit&>(b) = tf_split_plan(b.nchunks, A);
+    b.split_off = tf_slab_bytes(b.nchunks * (int64_t)S * A, elem);
     b.bytes = b.split_off + (b.nsplit > 1 ? (int64_t)b.nsplit * P * 3 * (int64_t)elem : 0);
     b.leaf_off = round256(b.bytes);
     return b;
@@ -265,7 +210,7 @@ template <typename T, bool INTERP = false>
 static int composed_backward(const pvamd_grid_t* grids, const pvamd_grid_t* g0, int32_t S, const T* tf, int32_t A, const T* points,
                              int64_t P, const int32_t* leaf, const T* dval, const T* dgrad, T scale, T* dpoints, T* dtf,
                              void* scratch, void* stream, bool chamfer) {
-    if (S < 1 || S > kBwdMaxLeaves || A < 1 || P < 0) return PVAMD_E_SHAPE;
+    if (S < 1 || S > kTfMaxLeaves || A < 1 || P < 0) return PVAMD_E_SHAPE;
     if (!dpoints && !dtf) return 0;
     hipStream_t st = (hipStream_t)stream;
     const int64_t SA = (int64_t)S * A;
@@ -297,8 +242,7 @@ static int composed_backward(const pvamd_grid_t* grids, const pvamd_grid_t* g0, 
     else
         launch_composed_backward<T, false, true, false, INTERP>(b, st, grids, gz, S, tf, A, points, P, leaf, nullptr, dgrad, scale, dp_out,
                                                         slab, dtf != nullptr);
-    if (dtf)
-        hipLaunchKernelGGL(reduce_tf_kernel<T>, dim3(stream_grid(SA * 16, 256)), dim3(256), 0, st, slab, b.nchunks, SA, dtf);
+    if (dtf) launch_reduce_tf<T, T>(slab, b.nchunks, SA, dtf, st);
     if (dpoints && b.nsplit > 1)
         hipLaunchKernelGGL(reduce_splits_kernel<T>, dim3(stream_grid(P * 3, 256)), dim3(256), 0, st, split_part, b.nsplit, P * 3,
                            dpoints);
@@ -331,7 +275,7 @@ static void launch_hinge_backward(const BwdPlan& b, hipStream_t st, const pvamd_
 template <typename T>
 static int hinge_backward(const pvamd_grid_t* grids, int32_t S, const T* tf, int32_t A, const T* points, int64_t P, int32_t mode,
                           int32_t per_leaf, T margin, int32_t power, const T* up, T* dpoints, T* dtf, void* scratch, void* stream) {
-    if (S < 1 || S > kBwdMaxLeaves || A < 1 || P < 1) return PVAMD_E_SHAPE;
+    if (S < 1 || S > kTfMaxLeaves || A < 1 || P < 1) return PVAMD_E_SHAPE;
     if ((mode != PVAMD_LEAF_NEAREST && mode != PVAMD_LEAF_TRILINEAR) || (per_leaf != 0 && per_leaf != 1) ||
         (power != 1 && power != 2))
         return PVAMD_E_MODE;
@@ -360,9 +304,7 @@ static int hinge_backward(const pvamd_grid_t* grids, int32_t S, const T* tf, int
             if (dtf) launch_hinge_backward<T, true, false>(b, st, gz, Sg, tz, A, points, P, up + z, Z, margin, power, dp_out, slab);
             else launch_hinge_backward<T, false, false>(b, st, gz, Sg, tz, A, points, P, up + z, Z, margin, power, dp_out, slab);
         }
-        if (dtf)
-            hipLaunchKernelGGL(reduce_tf_kernel<T>, dim3(stream_grid(SgA * 16, 256)), dim3(256), 0, st, slab, b.nchunks, SgA,
-                               dtf + (per_leaf ? (int64_t)z * A * 16 : 0));
+        if (dtf) launch_reduce_tf<T, T>(slab, b.nchunks, SgA, dtf + (per_leaf ? (int64_t)z * A * 16 : 0), st);
         if (dpoints && b.nsplit > 1)
             hipLaunchKernelGGL(reduce_splits_kernel<T>, dim3(stream_grid(P * 3, 256)), dim3(256), 0, st, split_part, b.nsplit, P * 3,
                                target);

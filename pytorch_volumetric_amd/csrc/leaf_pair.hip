@@ -23,6 +23,7 @@
 #include "interp.h"
 #include "leaf_vjp.h"
 #include "composed_point.h"
+#include "tf_reduce.h"
 
 namespace pvamd {
 
@@ -306,11 +307,10 @@ __global__ __launch_bounds__(256) void lp_accumulate_kernel(const T* __restrict_
 // The scratch of the leaf-pair entry points: the size functions report `bytes`, the launch code carves at the same offsets.
 //   forward (distance and hinge): one 16-byte partial per (k, a, chunk) at 0 when a set holds more than one chunk, else nothing
 //   distance backward:            dM [K][A][24] at 0
-//   hinge backward:               the dC slab [K][A][nchunks][12] at 0, then dM; configurations split over workgroups until
-//                                 about kBwdTargetBlocks exist (the split does not change any sum)
-struct LpPlan {
+//   hinge backward:               the dC slab [K][A][nchunks][12] at 0, then dM; configurations split over workgroups by
+//                                 tf_split_plan (the split does not change any sum)
+struct LpPlan : TfSplit {  // hinge backward: configurations per workgroup, workgroups per (chunk, k)
     int64_t nchunks;  // chunks of the largest set: PVAMD_MOP_CHUNK points forward, kBwdChunk points in the hinge backward
-    int aper, nsplit; // hinge backward: configurations per workgroup, workgroups per (chunk, k)
     int64_t dM_off;   // backward, bytes
     int64_t bytes;
 };
@@ -324,12 +324,8 @@ static LpPlan lp_plan(int K, int A, int64_t max_points, size_t elem, bool hinge,
     }
     if (hinge) {
         p.nchunks = (max_points + kBwdChunk - 1) / kBwdChunk;
-        int64_t want = (kBwdTargetBlocks + (int64_t)K * p.nchunks - 1) / ((int64_t)K * p.nchunks);
-        if (want > A) want = A;
-        if (want < 1) want = 1;
-        p.aper = (int)((A + want - 1) / want);
-        p.nsplit = (A + p.aper - 1) / p.aper;
-        p.dM_off = round256(p.nchunks * K * A * 12 * (int64_t)elem);
+        static_cast<TfSplit&>(p) = tf_split_plan((int64_t)K * p.nchunks, A);
+        p.dM_off = tf_slab_bytes(p.nchunks * K * A, elem);
     }
     p.bytes = p.dM_off + PVAMD_LEAF_PAIR_SCRATCH_BYTES(K, A, max_points, elem, 1);
     return p;
@@ -401,7 +397,7 @@ template <typename T>
 static int leaf_pair_distance_backward(const pvamd_grid_t* grids, int32_t S, const T* tf, const T* C, int32_t A, const T* points,
                                        int64_t npoints, const int64_t* table, int32_t K, int32_t mode, const int64_t* index,
                                        const T* dval, const T* dgrad, T* dtf, void* scratch, void* stream) {
-    if (S > 64) return PVAMD_E_SHAPE;  // the limit of every composed backward
+    if (S > kTfMaxLeaves) return PVAMD_E_SHAPE;  // the limit of every composed backward
     if (int e = lp_check<T>(grids, S, C, A, points, npoints, table, K, mode)) return e;
     if (!dtf) return 0;
     if (!tf || (K > 0 && (!index || !scratch))) return PVAMD_E_NULL;
@@ -432,8 +428,8 @@ static int leaf_pair_distance_backward(const pvamd_grid_t* grids, int32_t S, con
 //                             rounded as hop_finish_kernel rounds it; else one HopPart per (k, a, chunk)
 //   lph_finish_kernel         (sets above one chunk) one wave per (a, k): hop_finish_kernel over the pair's own chunks
 //   lph_backward_kernel       workgroup (1024-chunk, a-split, k): composed_backward_kernel's HINGE statements for the one-leaf
-//                             composition, its per-wave slots and wave order -> dC slab [k][a][chunk][12]
-//   lph_pair_vjp_kernel       one lane per (a, k): the slab's chunks in chunk order (reduce_tf_kernel), then lp_pair_vjp -> dM
+//                             composition, then the same reduction (tf_reduce.h) -> dC slab [k][a][chunk][12]
+//   lph_pair_vjp_kernel       one lane per (a, k): the slab's chunks in chunk order (tf_chunk_sum), then lp_pair_vjp -> dM
 //   lp_accumulate_kernel      as for the leaf-pair distance
 template <typename T, bool INTERP, bool FINISH>
 __global__ __launch_bounds__(kHopBlock) void lph_partial_kernel(const pvamd_grid_t* __restrict__ grids, int S, const T* __restrict__ C,
@@ -530,8 +526,8 @@ __global__ __launch_bounds__(kBwdBlock) void lph_backward_kernel(const pvamd_gri
                                                                  int64_t npoints, const int64_t* __restrict__ table, int K, T margin,
                                                                  int power, const T* __restrict__ up, int aper, int64_t nchunks,
                                                                  T* __restrict__ slab) {
-    __shared__ T part[kBwdBlock / 64][12];
-    __shared__ int present[kBwdBlock / 64];
+    __shared__ T part[kTfWaves][1][12];  // one leaf
+    __shared__ int present[kTfWaves];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int64_t chunk = blockIdx.x;
     const int k = blockIdx.z;
@@ -587,28 +583,9 @@ __global__ __launch_bounds__(kBwdBlock) void lph_backward_kernel(const pvamd_gri
                     }
                 }
             }
-            if (__builtin_amdgcn_ballot_w64(s >= 0)) {  // wave-uniform: the one leaf wins somewhere in the wave
-                const bool mine = s == 0;
-                const bool seen = present[wave] != 0;
-#pragma unroll
-                for (int j = 0; j < 12; ++j) {
-                    const T v = hop_wave_sum<T>(mine ? c[j] : T(0));
-                    if (lane == 0) part[wave][j] = seen ? part[wave][j] + v : v;
-                }
-                if (lane == 0) present[wave] = 1;
-                PVAMD_WAVE_SYNC();
-            }
+            tf_wave_reduce(s, c, part, present, wave, lane);
         }
-        __syncthreads();
-        if (threadIdx.x < 12) {
-            const int j = threadIdx.x;
-            T v = T(0);
-#pragma unroll
-            for (int w = 0; w < kBwdBlock / 64; ++w)
-                if (present[w]) v += part[w][j];
-            slab[(((int64_t)k * A + a) * nchunks + chunk) * 12 + j] = v;
-        }
-        __syncthreads();
+        tf_block_store(1, part, present, slab + (((int64_t)k * A + a) * nchunks + chunk) * 12, 0);
     }
 }
 
@@ -628,11 +605,7 @@ __global__ __launch_bounds__(256) void lph_pair_vjp_kernel(int S, const T* __res
         const T* row = slab + ((int64_t)k * A + a) * nchunks * 12;
         T dC[12];
 #pragma unroll
-        for (int e = 0; e < 12; ++e) {
-            T v = T(0);
-            for (int64_t ch = 0; ch < nc; ++ch) v += row[ch * 12 + e];
-            dC[e] = v;
-        }
+        for (int e = 0; e < 12; ++e) dC[e] = tf_chunk_sum<T>(row + e, nc, 12);
         T dMs[12], dMt[12];
 #pragma unroll
         for (int e = 0; e < 12; ++e) { dMs[e] = T(0); dMt[e] = T(0); }
@@ -693,7 +666,7 @@ template <typename T>
 static int leaf_pair_hinge_backward(const pvamd_grid_t* grids, int32_t S, const T* tf, const T* C, int32_t A, const T* points,
                                     int64_t npoints, const int64_t* table, int32_t K, int64_t max_points, int32_t mode, T margin,
                                     int32_t power, const T* up, T* dtf, void* scratch, void* stream) {
-    if (S > 64) return PVAMD_E_SHAPE;  // the limit of every composed backward
+    if (S > kTfMaxLeaves) return PVAMD_E_SHAPE;  // the limit of every composed backward
     if (int e = lph_check<T>(grids, S, C, A, points, npoints, table, K, max_points, mode, power)) return e;
     if (!dtf) return 0;
     if (!tf || (K > 0 && (!up || !scratch))) return PVAMD_E_NULL;

@@ -9,18 +9,18 @@
 //   dM[r][j] += (w gamma_r) x_j,  dM[r][3] += w gamma_r,  x_j = o_j + t d_j in float64
 // One grid: elementwise, a lane per ray, no lookup (n is the saved gradient).  A composition: a lane per (configuration, ray) in
 // the forward's geometry; (v, n, s) are recomputed at the forward's own p (mul_rn / add_rn in T) with mop_point unchanged, so n is
-// the forward's bits and no leaf ids are stored.  Sums follow composed_backward_kernel (backward.hip) in float64:
-// do / dd in registers in configuration order, configuration splits added in split order; the 12 entries of dM[s, a] by one wave
-// butterfly per leaf that wins somewhere in the wave, per-wave LDS slots added in wave order, one slab row per (ray chunk,
-// s*A + a), the rows added in chunk order.  Each sum is rounded once to T.  No float atomics, no device -> host synchronisation.
+// the forward's bits and no leaf ids are stored.  Sums are composed_backward_kernel's (backward.hip) in float64:
+// do / dd in registers in configuration order, configuration splits added in split order; the 12 entries of dM[s, a] by the
+// stack-gradient reduction of tf_reduce.h (a butterfly per winning leaf, the waves in order, one slab row per (ray chunk,
+// s*A + a): restated in the kernel below; the rows in chunk order: the header's reduce_tf_kernel).  Each sum is rounded once to T.  No float atomics, no device -> host synchronisation.
 #include "common.h"
 #include "composed_point.h"
+#include "tf_reduce.h"
 
 namespace pvamd {
 
 constexpr int kRayBwdBlock = PVAMD_RAY_BACKWARD_CHUNK;  // one ray per lane, four waves
-constexpr int kRayBwdMaxLeaves = 64;                    // per-wave LDS slots (and the presence mask) hold up to 64 leaves
-static_assert(kRayBwdBlock == 256, "four waves per workgroup");
+static_assert(kRayBwdBlock == kTfWaves * 64, "four waves per workgroup");
 
 // the forward's separately rounded product and sum in float64 (ray_cast.hip; exact_math.h states the float32 ones)
 #pragma clang fp contract(off)
@@ -73,8 +73,8 @@ __global__ __launch_bounds__(kRayBwdBlock) void composed_ray_cast_backward_kerne
     const T* __restrict__ directions, int64_t R, const T* __restrict__ t, const uint8_t* __restrict__ status,
     const T* __restrict__ up, int aper, T* __restrict__ dorigins, T* __restrict__ ddirections, double* __restrict__ rows,
     double* __restrict__ slab) {
-    __shared__ double part[kRayBwdBlock / 64][kRayBwdMaxLeaves][12];
-    __shared__ uint64_t present[kRayBwdBlock / 64];
+    __shared__ double part[kTfWaves][kTfMaxLeaves][12];
+    __shared__ uint64_t present[kTfWaves];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int64_t chunk = blockIdx.x;
     const int split = blockIdx.y;
@@ -132,6 +132,9 @@ __global__ __launch_bounds__(kRayBwdBlock) void composed_ray_cast_backward_kerne
             }
         }
         if (WANT_TF) {
+            // This kernel keeps its own copy of tf_reduce.h's tf_wave_reduce (a wave meets a leaf once per configuration, so
+            // the slot rule only assigns) and tf_block_store: through the shared functions its rows did not stay inside the
+            // parent's own spread (profiles/tf_reduce_shared.md).  The statements below must equal those two functions.
             uint64_t todo = __builtin_amdgcn_ballot_w64(s >= 0);
             while (todo) {  // wave-uniform: one butterfly per leaf that wins somewhere in the wave
                 const int first = __builtin_ctzll(todo);
@@ -141,7 +144,7 @@ __global__ __launch_bounds__(kRayBwdBlock) void composed_ray_cast_backward_kerne
 #pragma unroll
                 for (int j = 0; j < 12; ++j) {
                     const double v = hop_wave_sum<double>(mine ? c12[j] : 0.0);
-                    if (lane == 0) part[wave][sl][j] = v;  // one configuration per pass: a leaf is met once per wave
+                    if (lane == 0) part[wave][sl][j] = v;
                 }
                 if (lane == 0) present[wave] |= 1ull << sl;
                 PVAMD_WAVE_SYNC();
@@ -151,7 +154,7 @@ __global__ __launch_bounds__(kRayBwdBlock) void composed_ray_cast_backward_kerne
                 const int sl = e / 12, j = e - 12 * (e / 12);
                 double v = 0.0;
 #pragma unroll
-                for (int w = 0; w < kRayBwdBlock / 64; ++w)
+                for (int w = 0; w < kTfWaves; ++w)
                     if ((present[w] >> sl) & 1ull) v += part[w][sl][j];
                 slab[(chunk * ((int64_t)S * A) + (int64_t)sl * A + a) * 12 + j] = v;
             }
@@ -176,22 +179,6 @@ __global__ __launch_bounds__(kRayBwdBlock) void composed_ray_cast_backward_kerne
     }
 }
 
-// dtf[sa][r][c] = T(sum over chunks, in chunk order, of slab[chunk][sa][4r + c]) (row 3: zeros)
-template <typename T>
-__global__ __launch_bounds__(256) void ray_reduce_tf_kernel(const double* __restrict__ slab, int64_t nchunks, int64_t SA,
-                                                            T* __restrict__ dtf) {
-    const int64_t n = SA * 16;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += stride) {
-        const int64_t sa = e >> 4;
-        const int rc = (int)(e & 15);
-        double v = 0.0;
-        if (rc < 12)
-            for (int64_t ch = 0; ch < nchunks; ++ch) v += slab[(ch * SA + sa) * 12 + rc];
-        dtf[e] = (T)v;
-    }
-}
-
 // do / dd [i][j] = T(sum over splits, in split order, of rows[split][i][j] / rows[split][i][3 + j])
 template <typename T>
 __global__ __launch_bounds__(256) void ray_reduce_rows_kernel(const double* __restrict__ rows, int nsplit, int64_t R,
@@ -213,9 +200,8 @@ __global__ __launch_bounds__(256) void ray_reduce_rows_kernel(const double* __re
 
 // The launch geometry and the scratch layout of one composed pass (every partial is float64 whatever T).  The size function
 // reports `bytes` and the launch code carves at the same offsets: the slab at 0, then the split rows.
-struct RayBwdPlan {
+struct RayBwdPlan : TfSplit {
     int64_t nchunks;
-    int nsplit, aper;
     int64_t rows_off;  // bytes: past the slab [nchunks][S*A][12]; the rows [nsplit][R][6] when nsplit > 1
     int64_t bytes;
 };
@@ -224,12 +210,8 @@ static RayBwdPlan ray_bwd_plan(int S, int A, int64_t R) {
     RayBwdPlan b;
     b.nchunks = (R + kRayBwdBlock - 1) / kRayBwdBlock;
     if (b.nchunks < 1) b.nchunks = 1;
-    int64_t want = (kBwdTargetBlocks + b.nchunks - 1) / b.nchunks;
-    if (want > A) want = A;
-    if (want < 1) want = 1;
-    b.aper = (int)((A + want - 1) / want);
-    b.nsplit = (A + b.aper - 1) / b.aper;
-    b.rows_off = round256(b.nchunks * (int64_t)S * A * 12 * (int64_t)sizeof(double));
+    static_cast<TfSplit&>(b) = tf_split_plan(b.nchunks, A);
+    b.rows_off = tf_slab_bytes(b.nchunks * (int64_t)S * A, sizeof(double));
     b.bytes = b.rows_off + (b.nsplit > 1 ? (int64_t)b.nsplit * R * 6 * (int64_t)sizeof(double) : 0);
     return b;
 }
@@ -273,7 +255,7 @@ template <typename T>
 static int composed_ray_cast_backward(const pvamd_grid_t* grids, int32_t S, const T* tf, int32_t A, const T* origins,
                                       const T* directions, int64_t R, int32_t mode, const T* t, const uint8_t* status, const T* up,
                                       T* dorigins, T* ddirections, T* dtf, void* scratch, void* stream) {
-    if (S < 1 || S > kRayBwdMaxLeaves || A < 0 || R < 0) return PVAMD_E_SHAPE;
+    if (S < 1 || S > kTfMaxLeaves || A < 0 || R < 0) return PVAMD_E_SHAPE;
     if (mode != PVAMD_LEAF_NEAREST && mode != PVAMD_LEAF_TRILINEAR) return PVAMD_E_MODE;
     if (!dorigins && !ddirections && !dtf) return 0;
     if ((dorigins && !aligned_to(dorigins, sizeof(T))) || (ddirections && !aligned_to(ddirections, sizeof(T))) ||
@@ -297,9 +279,7 @@ static int composed_ray_cast_backward(const pvamd_grid_t* grids, int32_t S, cons
     else
         launch_composed_ray_backward<T, false>(b, st, grids, S, tf, A, origins, directions, R, t, status, up, dorigins, ddirections, rows,
                                                slab);
-    if (dtf)
-        hipLaunchKernelGGL(ray_reduce_tf_kernel<T>, dim3(stream_grid((int64_t)S * A * 16, 256)), dim3(256), 0, st, slab, b.nchunks,
-                           (int64_t)S * A, dtf);
+    if (dtf) launch_reduce_tf<double, T>(slab, b.nchunks, (int64_t)S * A, dtf, st);
     if (want_rows)
         hipLaunchKernelGGL(ray_reduce_rows_kernel<T>, dim3(stream_grid(R * 6, 256)), dim3(256), 0, st, rows, b.nsplit, R, dorigins,
                            ddirections);

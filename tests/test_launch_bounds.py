@@ -22,7 +22,8 @@ two halves are a reference that needs no launch past the bound), no case yet.
     cached_outside_kernel, voxel_index_kernel (cached)       points > ITEMS               here::test_outside_surface_and_index_keys_past_the_streaming_cap (float32 range)
     cached_outside_f64_kernel, voxel_index_f64_kernel        points > ITEMS               not tested
     cached_backward_kernel (backward)                        points > ITEMS               not tested
-    reduce_tf_kernel (backward)                              S A 16 > ITEMS               not tested
+    reduce_tf_kernel (tf_reduce.h: backward,                 S A 16 > ITEMS               here::test_composed_stack_gradient_past_the_streaming_cap (<float, float>),
+    ray_cast_backward)                                                                    here::test_ray_cast_stack_gradient_past_the_streaming_cap (<double, float>)
     reduce_splits_kernel (backward)                          P 3 > ITEMS                  test_autograd_edges_gpu::test_composed_uneven_splits_300k (composed),
                                                                                           test_hinge_over_points_gpu::test_per_leaf_dpoints_of_more_points_than_the_reduction_grids_have_lanes
     accumulate_kernel (backward)                             P 3 > ITEMS                  the same hinge test
@@ -46,7 +47,6 @@ two halves are a reference that needs no launch past the bound), no case yet.
                                                              4096 / (K chunks) rows       test_leaf_pair_hinge_gpu::test_bit_equal_to_one_leaf_hinge[200-*]: 56 pairs, 25 or 74 rows for 200
     cached_ray_cast_backward_kernel (ray_cast_backward)      rays > 2048 kRayBwdBlock     test_ray_cast_backward_gpu::test_cached_with_more_rays_than_the_backward_grid_has_lanes
     ray_reduce_rows_kernel (ray_cast_backward)               R 6 > ITEMS                  not tested
-    ray_reduce_tf_kernel (ray_cast_backward)                 S A 16 > ITEMS               not tested
     mop_partial_kernel (min_over_points)                     A > GRID_Y_MAX               test_min_over_points_gpu::test_more_configurations_than_grid_rows
     hop_partial_kernel (hinge_over_points)                   A > GRID_Y_MAX               test_hinge_over_points_gpu::test_more_configurations_than_grid_rows
     composed_ray_cast_kernel (ray_cast)                      A > GRID_Y_MAX               test_ray_cast_gpu::test_more_configurations_than_grid_rows
@@ -234,6 +234,73 @@ def test_mesh_leaves_past_the_streaming_cap_match_the_oracle_and_two_halves():
         oracle.compose_merge(tf_s, d.reshape(1, P), g.reshape(1, P, 3), s, best_v, best_g, best_leaf)
     assert same_bits(val.cpu().numpy(), best_v) and same_bits(grad.cpu().numpy(), best_g)
     assert len(np.unique(best_leaf[0, H.STREAM_GRID_ITEMS:])) == 2  # both leaves win among the points of the second turn
+
+
+# ---------------------------------------------------------------- GPU: the stack gradient's finish kernel past the cap
+TF_A = 16_400  # two leaves: S A 16 = 524,800 entries of dtf, 512 past the cap; each half of the configurations stays below it
+TF_POINTS = 64
+
+
+@pytest.fixture(scope="module")
+def two_leaves_and_a_stack():
+    """Two small analytic caches under TF_A rigid configurations, leaf-major (2, TF_A, 4, 4)."""
+    S = 2
+    assert S * TF_A * 16 > H.STREAM_GRID_ITEMS >= S * (TF_A // 2) * 16 and TF_A % 2 == 0
+    return [analytic_cache(False, 0.02) for _ in range(S)], H.random_rigid(S * TF_A, seed=51, trans=0.05).reshape(S, TF_A, 4, 4)
+
+
+def stack_gradient_whole_and_in_halves(stack, gradient_of):
+    """gradient_of(rows) -> the (S, len(rows), 4, 4) gradient w.r.t. the stack of the configurations `rows` alone.  A row
+    dtf[s, a] is a sum over the points or rays of configuration a only, so the halves are a reference for the whole."""
+    S, A, half = stack.shape[0], stack.shape[1], stack.shape[1] // 2
+    whole = gradient_of(slice(None))
+    halves = torch.cat((gradient_of(slice(0, half)), gradient_of(slice(half, None))), dim=1)
+    assert whole.shape == halves.shape == (S, A, 4, 4)
+    second_turn = whole.reshape(-1)[H.STREAM_GRID_ITEMS:]  # the entries a lane of reduce_tf_kernel takes second
+    assert second_turn.numel() == S * A * 16 - H.STREAM_GRID_ITEMS and bool((second_turn != 0).any())
+    share = float((whole[:, :, :3] != 0).any(dim=3).any(dim=2).float().mean())  # (leaf, configuration) rows that receive a term
+    print(f"rows of dtf with a term: {share:.3f}, non-zero entries of the second turn: {int((second_turn != 0).sum())}")
+    assert bool((whole[:, :, 3] == 0).all()) and share > 0.25
+    assert same_bits(whole.cpu().numpy(), halves.cpu().numpy())
+
+
+@pytest.mark.gpu
+def test_composed_stack_gradient_past_the_streaming_cap(two_leaves_and_a_stack):
+    """reduce_tf_kernel<float, float> (csrc/tf_reduce.h) behind the composed backward: a value-only upstream, float32."""
+    leaves, stack = two_leaves_and_a_stack
+    pts = spread_points(TF_POINTS, seed=52, margin=0.1).cuda()
+    up = torch.randn((TF_A, TF_POINTS), generator=torch.Generator().manual_seed(53)).cuda()
+
+    def gradient_of(rows):
+        m = stack[:, rows].reshape(-1, 4, 4).cuda().requires_grad_()
+        comp = pv.ComposedSDF(leaves, None)
+        comp.set_transforms(m, batch_dim=(m.shape[0] // 2,))
+        val, _ = comp(pts)
+        return torch.autograd.grad((val * up[rows]).sum(), m)[0].reshape(2, -1, 4, 4)
+
+    stack_gradient_whole_and_in_halves(stack, gradient_of)
+
+
+@pytest.mark.gpu
+def test_ray_cast_stack_gradient_past_the_streaming_cap(two_leaves_and_a_stack):
+    """reduce_tf_kernel<double, float> behind the ray-cast backward: 64 rays from a sphere around the leaves towards them."""
+    leaves, stack = two_leaves_and_a_stack
+    rng = np.random.default_rng(54)
+    o = rng.normal(size=(TF_POINTS, 3))
+    o = 0.8 * o / np.linalg.norm(o, axis=-1, keepdims=True)
+    d = rng.uniform(-0.08, 0.08, size=(TF_POINTS, 3)) - o
+    d /= np.linalg.norm(d, axis=-1, keepdims=True)
+    o, d = torch.from_numpy(o).float().cuda(), torch.from_numpy(d).float().cuda()
+    up = (torch.rand((TF_A, TF_POINTS), generator=torch.Generator().manual_seed(55)) + 0.5).cuda()
+
+    def gradient_of(rows):
+        m = stack[:, rows].reshape(-1, 4, 4).cuda().requires_grad_()
+        comp = pv.ComposedSDF(leaves, None)
+        comp.set_transforms(m, batch_dim=(m.shape[0] // 2,))
+        res = comp.ray_cast(o, d, differentiable=True, t_max=2.0, max_steps=32)
+        return torch.autograd.grad((res.t * up[rows]).sum(), m)[0].reshape(2, -1, 4, 4)
+
+    stack_gradient_whole_and_in_halves(stack, gradient_of)
 
 
 @pytest.mark.gpu

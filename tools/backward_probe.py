@@ -2,7 +2,13 @@
 the saved leaf ids, and (C4) torch autograd through the reference's op sequence (oracle.torch_opforop.ComposedOpForOp) on the
 same GPU.  Prints one JSON object; `--out FILE` also writes it.
 
+With --parent-lib (the option repeats; another build of the library, a parent commit's say) it times instead
+pvamd_composed_query_backward / pvamd_composed_query_interp_backward alone at the same two sizes, nearest and trilinear, for a
+value-only and a full upstream, with and without dtf, this build and every parent's in alternating regions on the same buffers
+(bench_min_over_points.against_parents), and prints one JSON line per row with parent_bits_equal.
+
   python tools/backward_probe.py [--reps 20] [--out profiles/backward_probe.json]
+  python tools/backward_probe.py --parent-lib A/libpvamd.so --parent-lib B/libpvamd.so [--regions 11] [--iters 3]
 """
 import argparse
 import json
@@ -12,8 +18,11 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import workloads as Wk  # noqa: E402
 from pytorch_volumetric_amd import _lib  # noqa: E402
+from pytorch_volumetric_amd import autograd as ag  # noqa: E402
+from bench_min_over_points import against_parents, parent_library  # noqa: E402
 
 
 def timed(fn, reps):
@@ -80,13 +89,56 @@ def measure(comp, pts, reps):
     return out
 
 
+def rows_against_parents(case, comp, pts, mode, parents, regions, iters):
+    """The composed backward of `comp` at `pts` alone (C ABI, the forward's leaf ids kept), this build against `parents`."""
+    dev = pts.device
+    with torch.no_grad():
+        _, _, leaf, flat, tfd = comp._fused_forward(pts, mode, want_leaf=True)
+    S, A, P = len(comp.sdfs), leaf.shape[0], flat.shape[0]
+    grids = comp._leaf_grids(dev)
+    entry = ag._BACKWARD[mode].format("composed")
+    dval = torch.randn((A, P), device=dev)
+    dgrad = torch.randn((A, P, 3), device=dev)
+    dpoints = torch.empty((P, 3), device=dev)
+    dtf = torch.empty((S * A, 4, 4), device=dev)
+    scratch = ag._scratch(S, A, P, False, dev)
+    for upstream, dg in (("val-only", None), ("full", dgrad)):
+        for want_dtf in (True, False):
+            def run(dg=dg, want_dtf=want_dtf):
+                _lib.check(getattr(_lib.load(), entry)(_lib.ptr(grids), S, _lib.ptr(tfd), A, _lib.ptr(flat), P, _lib.ptr(leaf),
+                                                       _lib.ptr(dval), _lib.ptr(dg), _lib.ptr(dpoints),
+                                                       _lib.ptr(dtf if want_dtf else None), _lib.ptr(scratch), _lib.stream_ptr()), entry)
+                return (dpoints, dtf) if want_dtf else (dpoints,)
+            row = {"case": case, "mode": mode, "S": S, "A": A, "P": P, "upstream": upstream, "dtf": want_dtf}
+            row.update(against_parents(run, parents, regions, iters))
+            print(json.dumps(row), flush=True)
+
+
+def main_against_parents(args):
+    parents = [parent_library(path) for path in args.parent_lib]
+    for mode in ("nearest", "trilinear"):
+        cached = Wk.build_c2_cache()
+        cached.interpolation = mode
+        rows_against_parents("C3", Wk.build_c3(cached), Wk.c3_points(1 << 22, seed=0), mode, parents, args.regions, args.iters)
+        robot = Wk.build_c4()
+        for leaf in robot.sdf.sdfs:
+            leaf.interpolation = mode
+        robot.set_joint_configuration(Wk.c4_joint_configs(200).cuda())
+        rows_against_parents("C4", robot.sdf, Wk.c4_points(262144), mode, parents, args.regions, args.iters)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--parent-lib", action="append", default=[], help="another build of libpvamd.so to time side by side (repeats)")
+    ap.add_argument("--regions", type=int, default=11, help="with --parent-lib: alternating regions per library")
+    ap.add_argument("--iters", type=int, default=3, help="with --parent-lib: calls per region")
     ap.add_argument("--out", default=None)
     ap.add_argument("--no-torch", action="store_true", help="skip the torch-autograd restatement at C4 size")
     args = ap.parse_args()
     torch.cuda.set_device(0)
+    if args.parent_lib:
+        return main_against_parents(args)
     res = {}
     cached = Wk.build_c2_cache()
     c3 = Wk.build_c3(cached)

@@ -20,7 +20,6 @@ HIP-event timings after a warm-up, median of --regions regions.  Prints one JSON
   python tools/bench_articulated.py [--regions 11] [--iters 3] [--parent-lib libpvamd.so]... [--eval-only] [--out table.md]
 """
 import argparse
-import ctypes
 import json
 import math
 import os
@@ -39,7 +38,7 @@ from pytorch_volumetric_amd import _lib  # noqa: E402
 from pytorch_volumetric_amd import articulated as art  # noqa: E402
 from pytorch_volumetric_amd import registration as reg  # noqa: E402
 from pytorch_volumetric_amd import transforms as tf  # noqa: E402
-from bench_min_over_points import alternate  # noqa: E402
+from bench_min_over_points import alternate, parent_library  # noqa: E402
 from bench_registration import graphed, median_ms  # noqa: E402
 
 CONFIGS = (1, 64)
@@ -106,12 +105,7 @@ def baseline(robot, q32, pts, kinds, targets, delta, J, scale=1000.):
     return cost, g, H
 
 
-def parent_library(path):
-    lib = ctypes.CDLL(path)
-    for name in ("pvamd_configure_chain", "pvamd_joint_normal_eq", "pvamd_chain_twists", "pvamd_joint_assemble"):
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = _lib.SIGNATURES[name]
-    return lib
+PARENT_ENTRIES = ("pvamd_configure_chain", "pvamd_joint_normal_eq", "pvamd_chain_twists", "pvamd_joint_assemble")
 
 
 def parent_evaluation(lib, ev, q32):
@@ -137,7 +131,7 @@ def main():
     ap.add_argument("--eval-only", action="store_true", help="leave refine10 and the baseline out")
     ap.add_argument("--out", default=None, help="also write the markdown table here (profiles/articulated.md quotes it)")
     args = ap.parse_args()
-    parent_libs = [parent_library(path) for path in args.parent_lib]
+    parent_libs = [parent_library(path, PARENT_ENTRIES) for path in args.parent_lib]
     torch.cuda.set_device(0)
     dev = torch.device("cuda", 0)
     rows = []

@@ -5,7 +5,11 @@ median of --regions regions, the variants alternated in one process on the same 
 and forward + backward to q (C4) or to the transforms (C3) of (a) against (b).  Prints one JSON line per case and writes the
 markdown table to --out.
 
-  python tools/bench_hinge_over_points.py [--regions 15] [--iters 10] [--out table.md]
+With --parent-lib (the option repeats; another build of the library, a parent commit's say) it times instead the backward of (b)
+alone -- torch.autograd.grad of the kept forward w.r.t. the transform stack -- through this build and through every parent's
+entry points in alternating regions (bench_min_over_points.against_parents), one JSON line per case with parent_bits_equal.
+
+  python tools/bench_hinge_over_points.py [--regions 15] [--iters 10] [--out table.md] [--parent-lib libpvamd.so]...
 """
 import argparse
 import json
@@ -20,7 +24,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import workloads as W  # noqa: E402
 import pytorch_volumetric_amd as pv  # noqa: E402
-from bench_min_over_points import alternate  # noqa: E402
+from bench_min_over_points import against_parents, alternate, parent_library  # noqa: E402
 
 MARGIN = 0.02
 
@@ -45,8 +49,17 @@ def fwd_bwd(set_input, call, pts):
     return {"a_call_expr": fb_a, "b_fused": fb_b}
 
 
+def backward_against_parents(case, mode, comp, stack, pts, parents, regions, iters):
+    """comp's stack requires grad: the backward of hinge_over_points to it alone, this build against `parents`."""
+    out = comp.hinge_over_points(pts, MARGIN).values.sum()
+    row = {"case": case, "mode": mode, "stack_rows": stack.shape[0], "points": pts.shape[0]}
+    row.update(against_parents(lambda: torch.autograd.grad(out, stack, retain_graph=True), parents, regions, iters))
+    print(json.dumps(row), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--parent-lib", action="append", default=[], help="another build of libpvamd.so to time the backward against (repeats)")
     ap.add_argument("--regions", type=int, default=15)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--out", default=None, help="also write the markdown table here (profiles/hinge_over_points.md quotes it)")
@@ -62,7 +75,12 @@ def main():
     A, P = 200, 262_144
     q = W.c4_joint_configs(A, seed=0).cuda()
     pts = W.c4_points(P, seed=1)
+    parents = [parent_library(path) for path in args.parent_lib]
     for mode, r in robots.items():
+        if parents:
+            r.set_joint_configuration(q.clone().requires_grad_())
+            backward_against_parents("C4", mode, r, r.sdf._tf_matrix, pts, parents, args.regions, args.iters)
+            continue
         r.set_joint_configuration(q)
         t = alternate(variants(r, pts), args.regions, args.iters)
 
@@ -79,6 +97,11 @@ def main():
     pts3 = W.c3_points(P3, seed=0)
     for mode, c in caches.items():
         comp = W.build_c3(c)
+        if parents:
+            stack = comp._tf_matrix.detach().clone().requires_grad_()
+            comp.set_transforms(stack, batch_dim=comp.tsf_batch, known_rigid=True)
+            backward_against_parents("C3", mode, comp, stack, pts3, parents, args.regions, args.iters)
+            continue
         t = alternate(variants(comp, pts3), args.regions, args.iters)
         tfm = comp._tf_matrix.detach().clone()
         batch = comp.tsf_batch
@@ -90,6 +113,8 @@ def main():
         comp.set_transforms(tfm, batch_dim=batch, known_rigid=True)
         rows.append({"case": "C3", "mode": mode, "configs": 1, "points": P3, "leaves": 8, "fwd_ms": t, "fwd_bwd_ms": fb})
 
+    if parents:
+        return
     for row in rows:
         print(json.dumps(row))
     lines = ["| case | leaves | (a) call + expr ms | (b) fused ms | (c) fused per leaf ms | b / a | fwd+bwd (a) ms | "

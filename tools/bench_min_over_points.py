@@ -8,6 +8,8 @@ and, on C4, forward + backward to q of (a) against (b).  Prints one JSON line pe
   python tools/bench_min_over_points.py [--regions 15] [--iters 10] [--out profiles/min_over_points.md]
 """
 import argparse
+import contextlib
+import ctypes
 import json
 import os
 import statistics
@@ -20,6 +22,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import workloads as W  # noqa: E402
 import pytorch_volumetric_amd as pv  # noqa: E402
+from pytorch_volumetric_amd import _lib  # noqa: E402
 
 
 def region_ms(fn, iters):
@@ -42,6 +45,55 @@ def alternate(fns, regions, iters):
         for k, fn in fns.items():
             times[k].append(region_ms(fn, iters))
     return {k: statistics.median(v) for k, v in times.items()}
+
+
+def parent_library(path, names=None):
+    """Another build of libpvamd.so, a parent commit's say, through a handle of its own (so with code objects of its own in
+    memory), its entry points `names` (default: all of include/pvamd.h) given the binding's signatures."""
+    lib = ctypes.CDLL(path)
+    for name in _lib.SIGNATURES if names is None else names:
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = _lib.SIGNATURES[name]
+    return lib
+
+
+@contextlib.contextmanager
+def through(lib):
+    """Inside the block the package's own calls (_lib.load().pvamd_...) go to `lib`, a parent_library with all entry points."""
+    saved, _lib._lib = _lib.load(), lib
+    try:
+        yield
+    finally:
+        _lib._lib = saved
+
+
+def same_bits(a, b):
+    ints = {4: torch.int32, 8: torch.int64}
+    return a.shape == b.shape and a.dtype == b.dtype and bool(torch.equal(a.view(ints[a.element_size()]), b.view(ints[b.element_size()])))
+
+
+def against_parents(fn, parents, regions, iters):
+    """fn() -> a tuple of tensors, computed through the package.  Timed as it is and with the package's library calls going to
+    each of `parents` (parent_library handles), the regions of all of them alternating: the row's
+    {"ms", "parent_ms": [...], "parent_bits_equal": [...]}, the last comparing every output of fn bit for bit.  Two builds of one
+    parent give the spread a difference has to exceed."""
+    def under(lib):
+        def run():
+            with through(lib):
+                return fn()
+        return run
+    fns = {"this": under(_lib.load()), **{i: under(lib) for i, lib in enumerate(parents)}}  # the same host path for all of them
+    ms = alternate(fns, regions, iters)
+    outs = fns["this"]()
+    mine = [t.clone() for t in outs]
+    equal = []
+    for i in range(len(parents)):
+        for t in outs:  # where fn writes into buffers of its own, a parent that wrote nothing must not pass on this build's bits
+            t.fill_(float("nan"))
+        outs = theirs = fns[i]()
+        equal.append(len(theirs) == len(mine) and all(same_bits(a, b) for a, b in zip(mine, theirs)))
+    torch.cuda.synchronize()
+    return {"ms": ms["this"], "parent_ms": [ms[i] for i in range(len(parents))], "parent_bits_equal": equal}
 
 
 def one_leaf_compositions(comp):

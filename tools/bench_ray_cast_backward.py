@@ -11,7 +11,12 @@ gradient w.r.t. the shared eye and the directions; 160 x 120 rays at the C4 robo
 gradient w.r.t. the eye, the directions and the transform stack.  Prints one JSON line per case and the markdown table of
 profiles/ray_cast_backward.md (--out FILE writes the table there too).
 
-  python tools/bench_ray_cast_backward.py [--regions 9] [--iters 3] [--out FILE]
+With --parent-lib (the option repeats; another build of the library, a parent commit's say) it times instead the fused backward
+of the C4 robot alone at the table's size and at A = 200 under 640 x 480 rays, nearest and trilinear -- torch.autograd.grad of the kept forward w.r.t. the eye, the directions and
+the stack, and w.r.t. the first two only -- through this build and through every parent's entry points in alternating regions
+(bench_min_over_points.against_parents), one JSON line per row with parent_bits_equal.
+
+  python tools/bench_ray_cast_backward.py [--regions 9] [--iters 3] [--out FILE] [--parent-lib libpvamd.so]...
 """
 import argparse
 import json
@@ -27,6 +32,7 @@ import workloads as W  # noqa: E402
 import pytorch_volumetric_amd as pv  # noqa: E402
 from pytorch_volumetric_amd.sdf import first_argmin  # noqa: E402
 from bench_ray_cast import alternate, pinhole  # noqa: E402
+from bench_min_over_points import against_parents, parent_library  # noqa: E402
 
 T_MAX, TOL, MAX_STEPS = 3.0, 1e-3, 128
 KW = dict(t_max=T_MAX, hit_tolerance=TOL, max_steps=MAX_STEPS)
@@ -81,11 +87,35 @@ def fused(sdf, eye, dirs, dz, depth, stack):
     return torch.autograd.grad(res.t, (e, dd) + ((stack,) if stack is not None else ()), grad_outputs=up)
 
 
+def against_parent_builds(robot, args):
+    """The fused backward of the C4 robot alone (the forward kept), this build against every --parent-lib: the case of the table
+    (A = 20, 160 x 120 rays), where the call is launch-bound, and A = 200 under 640 x 480 rays, where the kernel is the time."""
+    parents = [parent_library(path) for path in args.parent_lib]
+    for A, (w, h) in ((20, (160, 120)), (200, (640, 480))):
+        robot.set_joint_configuration(W.c4_joint_configs(A, seed=0).cuda().requires_grad_())
+        stack = robot.sdf._tf_matrix
+        eye, dirs = pinhole(w, h, [1.2, 0.5, 0.8], [0.0, 0.0, 0.6], 70.0)
+        for mode in ("nearest", "trilinear"):
+            for leaf in robot.sdf.sdfs:
+                leaf.interpolation = mode
+            e, dd = eye.detach().requires_grad_(), dirs.detach().requires_grad_()
+            res = robot.ray_cast(e, dd, differentiable=True, **KW)
+            up = loss_upstream(res, dirs[..., 2], (res.t * dirs[..., 2] + 0.01).detach()).detach()
+            for wrt in ((e, dd, stack), (e, dd)):  # without the stack: the kernel without the slab, for the session's spread
+                row = {"case": f"C4 robot, {mode}", "configs": A, "rays": dirs.numel() // 3, "stack": len(wrt) == 3,
+                       "hit_fraction": float((res.status == pv.RAY_HIT).float().mean())}
+                row.update(against_parents(lambda: torch.autograd.grad(res.t, wrt, grad_outputs=up, retain_graph=True), parents,
+                                           args.regions, args.iters))
+                print(json.dumps(row), flush=True)
+            del res, up
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--regions", type=int, default=9)
     ap.add_argument("--iters", type=int, default=3)
     ap.add_argument("--out", default=None, help="also write the table to this file (profiles/ray_cast_backward.md holds it with its notes)")
+    ap.add_argument("--parent-lib", action="append", default=[], help="another build of libpvamd.so to time the backward against (repeats)")
     args = ap.parse_args()
     torch.cuda.set_device(0)
     rows = []
@@ -107,7 +137,7 @@ def main():
                      "fused_ms": t["fused"], "fused_over_restated": t["fused"] / t["restated"],
                      "hit_fraction": float((plain.status == pv.RAY_HIT).float().mean()), "max_rel_difference": worst})
 
-    for mode in ("nearest", "trilinear"):
+    for mode in () if args.parent_lib else ("nearest", "trilinear"):
         c = W.build_c2_cache()
         c.interpolation = mode
         centre = [(r[0] + r[1]) / 2 for r in c.ranges]
@@ -115,6 +145,8 @@ def main():
         case(f"drill cache 0.01 m, {mode}", c, None, eye, dirs, None)
 
     robot = W.build_c4()
+    if args.parent_lib:
+        return against_parent_builds(robot, args)
     A = 20
     q = W.c4_joint_configs(A, seed=0).cuda().requires_grad_()
     robot.set_joint_configuration(q)

@@ -9,7 +9,11 @@ and forward + backward to q of the same three.  "bwd" times the new backward alo
 a composition stack that requires grad (no chain), forward included, next to the forward alone on that composition.  Prints
 one JSON line per case and writes the markdown table to --out.
 
-  python tools/bench_self_collision_hinge.py [--regions 7] [--iters 3] [--out table.md]
+With --parent-lib (the option repeats; another build of the library, a parent commit's say) it times instead that backward
+alone -- torch.autograd.grad of the kept forward w.r.t. the stack -- through this build and through every parent's entry points
+in alternating regions (bench_min_over_points.against_parents), one JSON line per case with parent_bits_equal.
+
+  python tools/bench_self_collision_hinge.py [--regions 7] [--iters 3] [--out table.md] [--parent-lib libpvamd.so]...
 """
 import argparse
 import json
@@ -24,7 +28,7 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 import workloads as W  # noqa: E402
 import pytorch_volumetric_amd as pv  # noqa: E402
 from pytorch_volumetric_amd import transforms as tf  # noqa: E402
-from bench_min_over_points import alternate  # noqa: E402
+from bench_min_over_points import against_parents, alternate, parent_library  # noqa: E402
 from bench_self_collision import build  # noqa: E402
 
 MARGIN, POWER = 0.2, 2
@@ -86,13 +90,25 @@ def stack_only(r, pairs):
     return {"stack_fwd": fwd, "stack_fwd_bwd": fb}
 
 
+def backward_against_parents(r, pairs, parents, regions, iters):
+    """stack_only's backward without its forward, this build against `parents`."""
+    A = r.sdf._tf_matrix.shape[0] // len(r.sdf.sdfs)
+    tfm = r.sdf._tf_matrix.detach().clone().requires_grad_()
+    comp = pv.ComposedSDF(list(r.sdf.sdfs), None)
+    comp.set_transforms(tfm, batch_dim=(A,), known_rigid=True)
+    out = comp.leaf_pair_hinge(r._sc_points, pairs, MARGIN, POWER).values.sum()
+    return against_parents(lambda: torch.autograd.grad(out, tfm, retain_graph=True), parents, regions, iters)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--parent-lib", action="append", default=[], help="another build of libpvamd.so to time the backward against (repeats)")
     ap.add_argument("--regions", type=int, default=7)
     ap.add_argument("--iters", type=int, default=3)
     ap.add_argument("--out", default=None, help="also write the markdown table here (profiles/self_collision_hinge.md quotes it)")
     args = ap.parse_args()
     torch.cuda.set_device(0)
+    parents = [parent_library(path) for path in args.parent_lib]
     rows = []
     for grid, padding in (("C4", 0.1), ("README", 1.0)):
         for mode in ("nearest", "trilinear"):
@@ -103,6 +119,11 @@ def main():
                 for A in (1, 200, 1000):
                     q = W.c4_joint_configs(A, seed=0).cuda()
                     r.set_joint_configuration(q)
+                    if parents:
+                        row = {"grid": grid, "mode": mode, "points": npts, "configs": A, "pairs": int(pairs.shape[0])}
+                        row.update(backward_against_parents(r, pairs, parents, args.regions, args.iters))
+                        print(json.dumps(row), flush=True)
+                        continue
                     # the fused and generic paths agree bit for bit, the recipe within float32 rounding of the terms
                     a = r.self_collision_hinge(MARGIN, POWER, pairs).values
                     b = r.sdf._leaf_pair_hinge_generic(r.sdf._leaf_pair_plan(r._sc_points, pairs), MARGIN, POWER).values
@@ -117,6 +138,8 @@ def main():
                     print(json.dumps(rows[-1]), flush=True)
             del r
             torch.cuda.empty_cache()
+    if parents:
+        return
     lines = ["| grid | leaves | pts/link | A | (a) fused ms | (b) per-pair ms | (c) torch ms | b / a | c / a | "
              "fwd+bwd to q (a) ms | (b) ms | (c) ms | stack fwd ms | stack fwd+bwd ms | bwd alone ms |",
              "|---|---|---|---|---|---|---|---|---|---|---|---|---|---|---|"]

@@ -34,7 +34,7 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 import workloads as W  # noqa: E402
 from pytorch_volumetric_amd import _lib  # noqa: E402
 from pytorch_volumetric_amd import registration as reg  # noqa: E402
-from bench_min_over_points import alternate  # noqa: E402
+from bench_min_over_points import alternate, parent_library  # noqa: E402
 from bench_registration import graphed, median_ms  # noqa: E402
 
 CASES = ((64, 16384), (1, 1 << 20))
@@ -44,10 +44,8 @@ def parent_evaluator(path, c, mode, W32, pts, config=None):
     """pvamd_chamfer_normal_eq, or with config = (kinds, targets, delta) pvamd_semantic_normal_eq, of another build of the
     library, through a handle of its own."""
     name = "pvamd_chamfer_normal_eq" if config is None else "pvamd_semantic_normal_eq"
-    lib = ctypes.CDLL(path)
+    lib = parent_library(path, (name, name + "_scratch_bytes"))
     fn, size = getattr(lib, name), getattr(lib, name + "_scratch_bytes")
-    fn.restype, fn.argtypes = _lib.SIGNATURES[name]
-    size.restype, size.argtypes = _lib.SIGNATURES[name + "_scratch_bytes"]
     B, N = W32.shape[0], pts.shape[0]
     sums = torch.empty((B, _lib.REG_SUMS), dtype=torch.float64, device=pts.device)
     counts = torch.empty((B,) if config is None else (B, _lib.SEM_COUNTS), dtype=torch.int64, device=pts.device)
