@@ -6,6 +6,7 @@ fails loudly if the shared object is missing, and every query raises if no MI355
 import ctypes
 import functools
 import os
+import re
 
 import torch
 
@@ -193,14 +194,14 @@ class MeshPlan(ctypes.Structure):
 def mesh_query_plan(P, F, has_scratch, unordered=False):
     """pvamd_mesh_query_plan as a MeshPlan."""
     plan = MeshPlan()
-    check(load().pvamd_mesh_query_plan(P, F, int(has_scratch), int(unordered), ctypes.byref(plan)), "pvamd_mesh_query_plan")
+    call("pvamd_mesh_query_plan", P, F, has_scratch, unordered, plan)
     return plan
 
 
 def chamfer_mesh_plan(N, rows, F, has_scratch):
     """pvamd_chamfer_mesh_plan as a MeshPlan."""
     plan = MeshPlan()
-    check(load().pvamd_chamfer_mesh_plan(N, rows, F, int(has_scratch), ctypes.byref(plan)), "pvamd_chamfer_mesh_plan")
+    call("pvamd_chamfer_mesh_plan", N, rows, F, has_scratch, plan)
     return plan
 
 
@@ -218,10 +219,13 @@ class PvamdError(RuntimeError):
 # The binding is read from include/pvamd.h, the one definition of the C ABI (_header.py states the rules).  SIGNATURES: name ->
 # (restype, argtypes) of every declaration; scalars map to their ctypes scalar and pointers to c_void_p, except the host structs
 # passed with byref -- `pvamd_grid_t* grid`, `pvamd_mesh_t* mesh`, `pvamd_mesh_plan_t* plan_out` -- which map to POINTER of the
-# mirror above.  H: the header's integer #defines.  The test-suite checks that every entry is exported by the .so and that
-# the mirrors have the header's layout.
+# mirror above.  H: the header's integer #defines.  PARAMETERS: name -> [(parameter name, base type, is a pointer, is const)],
+# the element types that argtypes drops and call() checks tensors against.  The test-suite checks that every entry is exported
+# by the .so and that the mirrors have the header's layout.
+_MIRRORS = {"GridDesc": GridDesc, "MeshDesc": MeshDesc, "MeshPlan": MeshPlan}
 try:
-    SIGNATURES, H = _header.read({"GridDesc": GridDesc, "MeshDesc": MeshDesc, "MeshPlan": MeshPlan})
+    SIGNATURES, H = _header.read(_MIRRORS)
+    PARAMETERS = _header.read_parameters()
 except OSError as e:
     raise PvamdError(f"{_header.HEADER_PATH} cannot be read ({e}): the binding of libpvamd.so is read from the header that "
                      f"the library was built from, and there is no second copy of it") from e
@@ -423,6 +427,129 @@ def ptr(t):
     return ctypes.c_void_p(t.data_ptr())
 
 
+_ELEMENTS = {"float": torch.float32, "double": torch.float64, "int32_t": torch.int32, "int64_t": torch.int64,
+             "uint8_t": torch.uint8}
+_TYPED, _UNTYPED, _SCALAR, _STRUCT = range(4)
+_plans = {}
+
+
+def _plan(name):
+    """[kinds, wants, names, whether the stream is appended, the bound function once it has been called] of a declared entry
+    point, made once per name.  Per parameter the caller passes: its kind, the dtype of a typed data pointer / the mirror of a
+    host struct / None, and its name in the header."""
+    params = PARAMETERS.get(name)
+    if params is None:
+        raise PvamdError(f"{name} is not declared in include/pvamd.h")
+    stream = bool(params) and params[-1] == ("stream", "void", True, False)
+    kinds, wants = [], []
+    for pname, ctype, pointer, _ in params[:-1] if stream else params:
+        if not pointer:
+            kind, want = _SCALAR, None
+        elif (ctype, pname) in _header.HOST_STRUCTS:
+            kind, want = _STRUCT, _MIRRORS[_header.HOST_STRUCTS[ctype, pname]]
+        elif ctype in _ELEMENTS:
+            kind, want = _TYPED, _ELEMENTS[ctype]
+        else:  # void* and the device arrays of structs take any dtype
+            kind, want = _UNTYPED, None
+        kinds.append(kind)
+        wants.append(want)
+    plan = _plans[name] = [tuple(kinds), tuple(wants), tuple(p[0] for p in params), stream, None]
+    return plan
+
+
+def _takes(arg, kind, want, dev):
+    """Whether call() takes `arg` for a parameter of `kind`: THE statement of the rule.  call()'s loop is this function written
+    out per kind (a call per argument would cost what the checks cost); tests/test_binding_call.py holds the two together."""
+    if kind == _SCALAR:
+        return True
+    if kind == _STRUCT:
+        return isinstance(arg, want)
+    return arg is None or (torch.is_tensor(arg) and (kind == _UNTYPED or arg.dtype is want) and arg.is_contiguous()
+                           and arg.get_device() == dev)
+
+
+def _refusal(name, plan, args, dev):
+    """The PvamdError for the first argument _takes() refuses, worked out off call()'s loop."""
+    for arg, kind, want, pname in zip(args, *plan[:3]):
+        if _takes(arg, kind, want, dev):
+            continue
+        if kind == _STRUCT:
+            return PvamdError(f"{name}: `{pname}` takes a {want.__name__}, given {type(arg).__name__}")
+        expected = f"a contiguous GPU tensor{'' if want is None else ' of ' + str(want)} or None"
+        if not torch.is_tensor(arg):
+            return PvamdError(f"{name}: `{pname}` takes {expected}, given {type(arg).__name__}")
+        if arg.is_cuda and arg.is_contiguous() and (want is None or arg.dtype is want):
+            return PvamdError(f"{name}: `{pname}` is on GPU {arg.get_device()} and the current device is GPU {dev}, whose stream "
+                              f"the call would take (wrap it in `with _lib.on_device(dev):`)")
+        return PvamdError(f"{name}: `{pname}` takes {expected}, given a "
+                          f"{'contiguous' if arg.is_contiguous() else 'non-contiguous'} {arg.dtype} tensor on {arg.device}")
+    raise AssertionError(f"{name}: call() refused arguments that _takes() accepts: the two have drifted apart")
+
+
+def call(name, *args, f64=False):
+    """The one way the package calls a status-returning entry point: `name` (+ "_f64" with f64=True) with every argument
+    checked against its parameter in include/pvamd.h, the current stream appended where the declaration ends in `void* stream`,
+    and the status through check().  A typed data pointer takes None (NULL) or a contiguous GPU tensor of the element type's
+    dtype -- a tensor of another dtype on purpose says so with .view(dtype); void* and the device arrays of structs a contiguous
+    GPU tensor of any dtype; a host struct pointer the ctypes mirror itself; scalars pass through.  Every tensor is on the
+    current device, whose stream it is (get_device() is its index there and -1 off a GPU).  A refused argument raises PvamdError
+    naming the parameter, and nothing is launched.  Per tensor: four reads and no object built -- the address goes as an int,
+    which c_void_p takes."""
+    if f64:
+        name += "_f64"
+    plan = _plans.get(name) or _plan(name)
+    kinds, wants, names, stream, fn = plan
+    if len(args) != len(kinds):
+        raise PvamdError(f"{name} takes {len(kinds)} arguments{' before the stream' if stream else ''} "
+                         f"({', '.join(names[:len(kinds)])}), given {len(args)}")
+    try:
+        dev = current_device_index()
+    except RuntimeError:  # no GPU: no tensor is on it, and each is refused by name
+        dev = -2
+    out = []
+    append = out.append
+    try:
+        for arg, kind, want in zip(args, kinds, wants):
+            if kind == _TYPED:
+                if arg is None:
+                    append(None)
+                elif arg.dtype is want and arg.is_contiguous() and arg.get_device() == dev:
+                    append(arg.data_ptr())
+                else:
+                    raise AttributeError
+            elif kind == _SCALAR:
+                append(arg)
+            elif kind == _UNTYPED:
+                if arg is None:
+                    append(None)
+                elif arg.is_contiguous() and arg.get_device() == dev:
+                    append(arg.data_ptr())
+                else:
+                    raise AttributeError
+            elif isinstance(arg, want):
+                append(ctypes.byref(arg))
+            else:
+                raise AttributeError
+    except AttributeError:  # raised above, or by something that is no tensor
+        raise _refusal(name, plan, args, dev) from None
+    if stream:
+        if dev < 0 or not _gpu_checked:
+            dev = require_gpu().index
+        append(current_raw_stream(dev))
+    if fn is None:
+        fn = plan[4] = getattr(load(), name)
+    try:
+        code = fn(*out)
+    except ctypes.ArgumentError as e:  # a scalar that ctypes could not convert; its text is "argument N: ..."
+        number = re.match(r"argument (\d+):", str(e))
+        at = int(number.group(1)) - 1 if number else len(args)
+        if at < len(args):
+            raise PvamdError(f"{name}: `{names[at]}` takes a {PARAMETERS[name][at][1]}, given {type(args[at]).__name__}") from None
+        raise PvamdError(f"{name}: {e}") from None
+    if code:
+        check(code, name)
+
+
 def as_query_points(points, device=None, keep_f64=False):
     """[..., 3] any float dtype / device  ->  (contiguous fp32 [P,3] on the GPU, leading shape, dtype, device).
 
@@ -468,10 +595,9 @@ def whole_tiles(P):
 
 def group_points(flat):
     """pvamd_group_points over contiguous fp32 (P, 3) GPU points: the scratch (uint8 tensor) pvamd_composed_query_grouped reads."""
-    lib = load()
     P = flat.shape[0]
-    scratch = scratch_buffer(int(lib.pvamd_group_scratch_bytes(P)), flat.device)
-    check(lib.pvamd_group_points(ptr(flat), P, ptr(scratch), stream_ptr()), "pvamd_group_points")
+    scratch = scratch_buffer(int(load().pvamd_group_scratch_bytes(P)), flat.device)
+    call("pvamd_group_points", flat, P, scratch)
     return scratch
 
 
@@ -488,6 +614,5 @@ def morton_order(points, min_points=2048, want_inverse=False, want_sorted=False)
     inv = torch.empty((P,), dtype=torch.int32, device=dev) if want_inverse else None
     spts = torch.empty((P, 3), dtype=torch.float32, device=dev) if want_sorted else None
     scratch = scratch_buffer(morton_order_scratch_bytes(P), dev)
-    check(load().pvamd_morton_order(ptr(points), P, ptr(order), ptr(inv), ptr(spts), ptr(scratch), stream_ptr()),
-          "pvamd_morton_order")
+    call("pvamd_morton_order", points, P, order, inv, spts, scratch)
     return (order, inv, spts) if (want_inverse or want_sorted) else order

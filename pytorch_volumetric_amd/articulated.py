@@ -118,16 +118,11 @@ class _Evaluator:
     def __call__(self, q32):
         if self.A == 0:
             return
-        lib, stream = _lib.load(), _lib.stream_ptr()
-        self.robot._configure(lib, self.dev, q32, self.A, self.M, self.S, self.offset_inv, stack=self.stack)
-        _lib.check(lib.pvamd_joint_normal_eq(_lib.ptr(self.grids), self.S, self.mode, _lib.ptr(self.stack), self.A,
-                                             _lib.ptr(self.pts), self.N, _lib.ptr(self.kinds), _lib.ptr(self.targets), self.delta,
-                                             _lib.ptr(self.leaf_sums), _lib.ptr(self.leaf_counts), _lib.ptr(self.scratch), stream),
-                   "pvamd_joint_normal_eq")
-        _lib.check(lib.pvamd_chain_twists(_lib.ptr(self.joints), self.F, _lib.ptr(q32), self.A, self.M, _lib.ptr(self.offset_inv),
-                                          self.S, _lib.ptr(self.J), stream), "pvamd_chain_twists")
-        _lib.check(lib.pvamd_joint_assemble(_lib.ptr(self.leaf_sums), _lib.ptr(self.leaf_counts), _lib.ptr(self.J), self.A, self.S,
-                                            self.M, _lib.ptr(self.sums), _lib.ptr(self.counts), stream), "pvamd_joint_assemble")
+        self.robot._configure(_lib.load(), self.dev, q32, self.A, self.M, self.S, self.offset_inv, stack=self.stack)
+        _lib.call("pvamd_joint_normal_eq", self.grids, self.S, self.mode, self.stack, self.A, self.pts, self.N, self.kinds,
+                  self.targets, self.delta, self.leaf_sums, self.leaf_counts, self.scratch)
+        _lib.call("pvamd_chain_twists", self.joints, self.F, q32, self.A, self.M, self.offset_inv, self.S, self.J)
+        _lib.call("pvamd_joint_assemble", self.leaf_sums, self.leaf_counts, self.J, self.A, self.S, self.M, self.sums, self.counts)
 
 
 def _prepare(robot, joint_config, points, semantics, targets, huber_delta):
@@ -194,7 +189,6 @@ def refine_joint_configuration(robot: RobotSDF, joint_config, points, iterations
     out_dtype = q.dtype if q.dtype.is_floating_point else torch.float32
     out_device = q.device
     dev = robot.sdf._owner_device()
-    lib = _lib.load()
     with _lib.on_device(dev):
         ev, q32 = _evaluator(robot, dev, S, M, mode, q, pts, semantics, targets, delta)
         A = ev.A
@@ -214,8 +208,7 @@ def refine_joint_configuration(robot: RobotSDF, joint_config, points, iterations
             ev(q_next)
             if it == 0:
                 initial = ev.sums[:, 0].clone()
-            _lib.check(lib.pvamd_joint_lm_step(A, M, _lib.ptr(ev.sums), int(it == 0), _lib.ptr(q_acc), _lib.ptr(sums_acc),
-                                               _lib.ptr(lam), _lib.ptr(accepted), _lib.ptr(q_try), _lib.ptr(q_next), _lib.ptr(lim),
-                                               up, down, reg.LAMBDA_MIN, reg.LAMBDA_MAX, _lib.stream_ptr()), "pvamd_joint_lm_step")
+            _lib.call("pvamd_joint_lm_step", A, M, ev.sums, it == 0, q_acc, sums_acc, lam, accepted, q_try, q_next, lim,
+                      up, down, reg.LAMBDA_MIN, reg.LAMBDA_MAX)
         k = scale * scale / ev.N
         return JointRefinement(q_acc.to(out_dtype).to(out_device), sums_acc[:, 0] * k, initial * k, accepted.to(torch.int64))

@@ -8,7 +8,6 @@ chamfer_partial_sums) route here only when grad mode is on and an input requires
 
 Double backward is not supported: every backward is once_differentiable, so create_graph=True raises.
 """
-import ctypes
 
 import torch
 from torch.autograd.function import once_differentiable
@@ -63,12 +62,9 @@ class CachedQuery(torch.autograd.Function):
         dv = _upstream(dval, dev, dt, (P,))
         dg = _upstream(dgrad, dev, dt, (P, 3))
         out = torch.empty((P, 3), dtype=dt, device=dev)
-        lib = _lib.load()
-        entry = getattr(lib, ctx.backward_entry + "_f64" if dt == torch.float64 else ctx.backward_entry)
         desc = cached._grid_desc()
         with _lib.on_device(dev):
-            _lib.check(entry(ctypes.byref(desc), _lib.ptr(flat), P, _lib.ptr(dv), _lib.ptr(dg), _lib.ptr(out), _lib.stream_ptr()),
-                       ctx.backward_entry)
+            _lib.call(ctx.backward_entry, desc, flat, P, dv, dg, out, f64=dt == torch.float64)
         return None, out.reshape(ctx.pshape).to(device=ctx.pdevice, dtype=ctx.pdtype)
 
 
@@ -108,14 +104,10 @@ class ComposedQuery(torch.autograd.Function):
         dg = _upstream(dgrad, dev, dt, (A, P, 3))
         dpoints = torch.empty((P, 3), dtype=dt, device=dev) if need_p else None
         dtf = torch.empty((S * A, 4, 4), dtype=dt, device=dev) if need_tf else None
-        lib = _lib.load()
         f64 = dt == torch.float64
-        entry = getattr(lib, ctx.backward_entry + "_f64" if f64 else ctx.backward_entry)
         with _lib.on_device(dev):
             scratch = _scratch(S, A, P, f64, dev)
-            _lib.check(entry(_lib.ptr(ctx.grids), S, _lib.ptr(tfd), A, _lib.ptr(flat), P, _lib.ptr(ctx.leaf), _lib.ptr(dv), _lib.ptr(dg),
-                             _lib.ptr(dpoints), _lib.ptr(dtf), _lib.ptr(scratch), _lib.stream_ptr()),
-                       ctx.backward_entry)
+            _lib.call(ctx.backward_entry, ctx.grids, S, tfd, A, flat, P, ctx.leaf, dv, dg, dpoints, dtf, scratch, f64=f64)
         gp = dpoints.reshape(ctx.pshape).to(device=ctx.pdevice, dtype=ctx.pdtype) if need_p else None
         gt = dtf.to(device=ctx.tdevice, dtype=ctx.tdtype) if need_tf else None
         return None, gp, gt, None
@@ -160,13 +152,10 @@ class MinOverPointsQuery(torch.autograd.Function):
         dg = _upstream(dgrad, dev, dt, (A, Z, 3))
         dpoints = torch.empty((P, 3), dtype=dt, device=dev) if need_p else None
         dtf = torch.empty((S * A, 4, 4), dtype=dt, device=dev) if need_tf else None
-        name = "pvamd_composed_min_over_points_backward" + ("_f64" if dt == torch.float64 else "")
         with _lib.on_device(dev):
             scratch = _lib.scratch_buffer(max(_lib.min_over_points_backward_scratch_bytes(S, A, ctx.per_leaf), 16), dev)
-            _lib.check(getattr(_lib.load(), name)(_lib.ptr(ctx.grids), S, _lib.ptr(tfd), A, _lib.ptr(flat), P,
-                                                  _lib.LEAF_MODES[ctx.mode], int(ctx.per_leaf), _lib.ptr(ctx.idx),
-                                                  _lib.ptr(ctx.leaf), _lib.ptr(dv), _lib.ptr(dg), _lib.ptr(dpoints), _lib.ptr(dtf),
-                                                  _lib.ptr(scratch), _lib.stream_ptr()), name)
+            _lib.call("pvamd_composed_min_over_points_backward", ctx.grids, S, tfd, A, flat, P, _lib.LEAF_MODES[ctx.mode],
+                      ctx.per_leaf, ctx.idx, ctx.leaf, dv, dg, dpoints, dtf, scratch, f64=dt == torch.float64)
         gp = dpoints.reshape(ctx.pshape).to(device=ctx.pdevice, dtype=ctx.pdtype) if need_p else None
         gt = dtf.to(device=ctx.tdevice, dtype=ctx.tdtype) if need_tf else None
         return None, gp, gt, None, None
@@ -213,13 +202,10 @@ class HingeOverPointsQuery(torch.autograd.Function):
         dpoints = torch.empty((P, 3), dtype=dt, device=dev) if need_p else None
         dtf = torch.empty((S * A, 4, 4), dtype=dt, device=dev) if need_tf else None
         f64 = dt == torch.float64
-        name = "pvamd_composed_hinge_over_points_backward" + ("_f64" if f64 else "")
         with _lib.on_device(dev):
             scratch = _lib.scratch_buffer(max(_lib.hinge_over_points_backward_scratch_bytes(S, A, P, ctx.per_leaf, f64), 16), dev)
-            _lib.check(getattr(_lib.load(), name)(_lib.ptr(ctx.grids), S, _lib.ptr(tfd), A, _lib.ptr(flat), P,
-                                                  _lib.LEAF_MODES[ctx.mode], int(ctx.per_leaf), ctx.margin, ctx.power,
-                                                  _lib.ptr(up), _lib.ptr(dpoints), _lib.ptr(dtf), _lib.ptr(scratch),
-                                                  _lib.stream_ptr()), name)
+            _lib.call("pvamd_composed_hinge_over_points_backward", ctx.grids, S, tfd, A, flat, P, _lib.LEAF_MODES[ctx.mode],
+                      ctx.per_leaf, ctx.margin, ctx.power, up, dpoints, dtf, scratch, f64=f64)
         gp = dpoints.reshape(ctx.pshape).to(device=ctx.pdevice, dtype=ctx.pdtype) if need_p else None
         gt = dtf.to(device=ctx.tdevice, dtype=ctx.tdtype) if need_tf else None
         return None, gp, gt, None, None, None, None
@@ -261,13 +247,10 @@ class LeafPairQuery(torch.autograd.Function):
         dg = _upstream(dgrad, dev, dt, (A, K, 3))
         dtf = torch.empty((S * A, 4, 4), dtype=dt, device=dev)
         f64 = dt == torch.float64
-        name = "pvamd_leaf_pair_distance_backward" + ("_f64" if f64 else "")
         with _lib.on_device(dev):
             scratch = _lib.scratch_buffer(_lib.leaf_pair_scratch_bytes(K, A, plan["max_points"], f64, True), dev)
-            _lib.check(getattr(_lib.load(), name)(_lib.ptr(ctx.grids), S, _lib.ptr(ctx.tfd), _lib.ptr(ctx.C), A,
-                                                  _lib.ptr(plan["packed"]), plan["npoints"], _lib.ptr(plan["table"]), K,
-                                                  _lib.LEAF_MODES[ctx.mode], _lib.ptr(ctx.idx), _lib.ptr(dv), _lib.ptr(dg),
-                                                  _lib.ptr(dtf), _lib.ptr(scratch), _lib.stream_ptr()), name)
+            _lib.call("pvamd_leaf_pair_distance_backward", ctx.grids, S, ctx.tfd, ctx.C, A, plan["packed"], plan["npoints"],
+                      plan["table"], K, _lib.LEAF_MODES[ctx.mode], ctx.idx, dv, dg, dtf, scratch, f64=f64)
         return None, dtf.to(device=ctx.tdevice, dtype=ctx.tdtype), None, None
 
 
@@ -308,13 +291,11 @@ class LeafPairHingeQuery(torch.autograd.Function):
             return None, None, None, None, None, None
         dtf = torch.empty((S * A, 4, 4), dtype=dt, device=dev)
         f64 = dt == torch.float64
-        name = "pvamd_leaf_pair_hinge_backward" + ("_f64" if f64 else "")
         with _lib.on_device(dev):
             scratch = _lib.scratch_buffer(_lib.leaf_pair_hinge_scratch_bytes(K, A, plan["max_points"], f64, True), dev)
-            _lib.check(getattr(_lib.load(), name)(_lib.ptr(ctx.grids), S, _lib.ptr(ctx.tfd), _lib.ptr(ctx.C), A,
-                                                  _lib.ptr(plan["packed"]), plan["npoints"], _lib.ptr(plan["table"]), K,
-                                                  plan["max_points"], _lib.LEAF_MODES[ctx.mode], ctx.margin, ctx.power, _lib.ptr(up),
-                                                  _lib.ptr(dtf), _lib.ptr(scratch), _lib.stream_ptr()), name)
+            _lib.call("pvamd_leaf_pair_hinge_backward", ctx.grids, S, ctx.tfd, ctx.C, A, plan["packed"], plan["npoints"],
+                      plan["table"], K, plan["max_points"], _lib.LEAF_MODES[ctx.mode], ctx.margin, ctx.power, up, dtf, scratch,
+                      f64=f64)
         return None, dtf.to(device=ctx.tdevice, dtype=ctx.tdtype), None, None, None, None
 
 
@@ -396,21 +377,16 @@ class RayCastQuery(torch.autograd.Function):
         gtf = None
         if "tfd" not in kept:
             up = _upstream(dt, dev, dtype, (R,))
-            name = "pvamd_cached_ray_cast_backward" + ("_f64" if f64 else "")
             with _lib.on_device(dev):
-                _lib.check(getattr(_lib.load(), name)(_lib.ptr(d), R, _lib.ptr(t), _lib.ptr(status), _lib.ptr(grad), _lib.ptr(up),
-                                                      _lib.ptr(go), _lib.ptr(gd), _lib.stream_ptr()), name)
+                _lib.call("pvamd_cached_ray_cast_backward", d, R, t, status, grad, up, go, gd, f64=f64)
         else:
             S, A = kept["S"], kept["A"]
             up = _upstream(dt, dev, dtype, (A, R))
             gtf = torch.empty((S * A, 4, 4), dtype=dtype, device=dev) if need_tf else None
-            name = "pvamd_composed_ray_cast_backward" + ("_f64" if f64 else "")
             with _lib.on_device(dev):
                 scratch = _lib.scratch_buffer(max(_lib.ray_cast_backward_scratch_bytes(S, A, R, f64), 16), dev)
-                _lib.check(getattr(_lib.load(), name)(_lib.ptr(kept["grids"]), S, _lib.ptr(kept["tfd"]), A, _lib.ptr(o), _lib.ptr(d), R,
-                                                      _lib.LEAF_MODES[kept["mode"]], _lib.ptr(t), _lib.ptr(status), _lib.ptr(up),
-                                                      _lib.ptr(go), _lib.ptr(gd), _lib.ptr(gtf), _lib.ptr(scratch),
-                                                      _lib.stream_ptr()), name)
+                _lib.call("pvamd_composed_ray_cast_backward", kept["grids"], S, kept["tfd"], A, o, d, R,
+                          _lib.LEAF_MODES[kept["mode"]], t, status, up, go, gd, gtf, scratch, f64=f64)
         return (None,
                 go.reshape(*ctx.lead, 3).to(device=origins.device, dtype=origins.dtype) if need_o else None,
                 gd.reshape(*ctx.lead, 3).to(device=directions.device, dtype=directions.dtype) if need_d else None,
@@ -534,15 +510,13 @@ class GridChamfer(torch.autograd.Function):
     def forward(ctx, cached, W, points, scale):
         ctx.set_materialize_grads(False)
         dev = _lib.require_gpu()
-        lib = _lib.load()
         pts = torch.as_tensor(points).detach().reshape(-1, 3).to(device=dev, dtype=torch.float32).contiguous()
         Wd = W.detach().to(device=dev, dtype=torch.float32).contiguous()
         B, N = Wd.shape[0], pts.shape[0]
         sums = torch.empty((B,), dtype=torch.float64, device=dev)
         desc = cached._grid_desc()
         with _lib.on_device(dev):
-            _lib.check(lib.pvamd_chamfer_grid(ctypes.byref(desc), _lib.ptr(Wd), B, _lib.ptr(pts), N, float(scale), _lib.ptr(sums),
-                                              _lib.stream_ptr()), "pvamd_chamfer_grid")
+            _lib.call("pvamd_chamfer_grid", desc, Wd, B, pts, N, float(scale), sums)
         ctx.cached, ctx.Wd, ctx.pts, ctx.scale = cached, Wd, pts, float(scale)
         # Wd / pts may alias W / points: torch's version check then raises on an in-place write before backward, as it does for
         # the reference's matmul (chamfer.py:82)
@@ -566,9 +540,7 @@ class GridChamfer(torch.autograd.Function):
         desc = ctx.cached._grid_desc()
         with _lib.on_device(dev):
             scratch = _scratch(1, B, N, False, dev)
-            _lib.check(_lib.load().pvamd_chamfer_grid_backward(ctypes.byref(desc), _lib.ptr(Wd), B, _lib.ptr(pts), N, ctx.scale,
-                                                               _lib.ptr(dsum), _lib.ptr(dW), _lib.ptr(dp), _lib.ptr(scratch),
-                                                               _lib.stream_ptr()), "pvamd_chamfer_grid_backward")
+            _lib.call("pvamd_chamfer_grid_backward", desc, Wd, B, pts, N, ctx.scale, dsum, dW, dp, scratch)
         gw = dW.to(device=ctx.wdevice, dtype=ctx.wdtype) if need_w else None
         gp = dp.reshape(ctx.pshape).to(device=ctx.pdevice, dtype=ctx.pdtype) if need_p else None
         return None, gw, gp, None

@@ -3,7 +3,6 @@
 reduction); the callers stay thin Python like the reference's."""
 from typing import NamedTuple
 
-import ctypes
 import torch
 
 from pytorch_volumetric_amd import _lib
@@ -67,7 +66,6 @@ def chamfer_partial_sums(W, points, obj_factory, obj_sdf, scale):
     """The per-rank half of batch_chamfer_dist: sum over THESE points of (scale * d)^2 per transform, float64 on the GPU, and
     the number of points -- what a run sharded over the points all-reduces (dist.sharded_chamfer).  W: (B, 4, 4)."""
     B = W.shape[0]
-    lib = _lib.load()
     dev = _lib.require_gpu()
     pts = torch.as_tensor(points).detach().reshape(-1, 3).to(device=dev, dtype=torch.float32)
     pts = pts.contiguous()
@@ -95,8 +93,7 @@ def chamfer_partial_sums(W, points, obj_factory, obj_sdf, scale):
     with _lib.on_device(dev):
         if fused_grid:
             desc = obj_sdf._grid_desc()
-            _lib.check(lib.pvamd_chamfer_grid(ctypes.byref(desc), _lib.ptr(Wd), B, _lib.ptr(pts), N, float(scale),
-                                              _lib.ptr(sums), _lib.stream_ptr()), "pvamd_chamfer_grid")
+            _lib.call("pvamd_chamfer_grid", desc, Wd, B, pts, N, float(scale), sums)
         elif obj_sdf is not None:
             # arbitrary SDF object: transform on device, query it, reduce
             x = pts.unsqueeze(0) @ Wd[:, :3, :3].transpose(-1, -2) + Wd[:, None, :3, 3]
@@ -109,21 +106,16 @@ def chamfer_partial_sums(W, points, obj_factory, obj_sdf, scale):
                 # B * N points once, walk them in ONE spatial order (the 64 points of a wave are then neighbours in space,
                 # whichever transform they came from) and let every point add to its own transform's sum
                 x = torch.empty((B, N, 3), dtype=torch.float32, device=dev)
-                _lib.check(lib.pvamd_transform_points(_lib.ptr(Wd), B, _lib.ptr(pts), N, _lib.ptr(x), _lib.stream_ptr()),
-                           "pvamd_transform_points")
+                _lib.call("pvamd_transform_points", Wd, B, pts, N, x)
                 flat = x.view(-1, 3)
                 order = _lib.morton_order(flat)
                 scratch = _lib.scratch_buffer(_lib.mesh_scratch_bytes(B * N), dev)
-                _lib.check(lib.pvamd_chamfer_mesh_flat(ctypes.byref(desc), B, _lib.ptr(flat), _lib.ptr(order), N, float(scale),
-                                                       _lib.ptr(sums), _lib.ptr(scratch), _lib.stream_ptr()),
-                           "pvamd_chamfer_mesh_flat")
+                _lib.call("pvamd_chamfer_mesh_flat", desc, B, flat, order, N, float(scale), sums, scratch)
             else:
                 order = _lib.morton_order(pts)
                 # slots for the point groups the kernel hands over (those about equidistant to much of the mesh)
                 scratch = _lib.scratch_buffer(_lib.mesh_scratch_bytes(N), dev)
-                _lib.check(lib.pvamd_chamfer_mesh(ctypes.byref(desc), _lib.ptr(Wd), B, _lib.ptr(pts), _lib.ptr(order), N,
-                                                  float(scale), _lib.ptr(sums), _lib.ptr(scratch), _lib.stream_ptr()),
-                           "pvamd_chamfer_mesh")
+                _lib.call("pvamd_chamfer_mesh", desc, Wd, B, pts, order, N, float(scale), sums, scratch)
     return sums, N
 
 
@@ -174,9 +166,7 @@ def reduce_pairwise_errors(errors):
     row_idx, col_idx = torch.empty((B,), dtype=torch.int64, device=dev), torch.empty((P,), dtype=torch.int64, device=dev)
     means = torch.empty((2,), dtype=torch.float64, device=dev)
     with _lib.on_device(dev):
-        _lib.check(_lib.load().pvamd_pairwise_min_reduce(_lib.ptr(E), 1 if E.dtype == torch.float64 else 0, B, P, _lib.ptr(row_val),
-                                                         _lib.ptr(row_idx), _lib.ptr(col_val), _lib.ptr(col_idx), _lib.ptr(means),
-                                                         _lib.stream_ptr()), "pvamd_pairwise_min_reduce")
+        _lib.call("pvamd_pairwise_min_reduce", E, E.dtype == torch.float64, B, P, row_val, row_idx, col_val, col_idx, means)
     means = means.to(E.dtype)
     return PlausibleDiversityReturn(means[0], means[1], MinOverAxis(row_val, row_idx), MinOverAxis(col_val, col_idx))
 

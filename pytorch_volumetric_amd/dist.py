@@ -160,8 +160,7 @@ class ShardedSDF:
         val = torch.empty((A, P), dtype=torch.float32, device=dev)
         grad = torch.empty((A, P, 3), dtype=torch.float32, device=dev)
         with _lib.on_device(dev):
-            _lib.check(_lib.load().pvamd_unpack_records(_lib.ptr(gathered), _lib.ptr(index), P, Pp, A, _lib.ptr(val),
-                                                        _lib.ptr(grad), _lib.stream_ptr()), "pvamd_unpack_records")
+            _lib.call("pvamd_unpack_records", gathered, index, P, Pp, A, val, grad)
         return val, grad
 
     def _packed_call(self, flat, lead, world, start, stop, chunk):

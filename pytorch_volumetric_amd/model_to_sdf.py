@@ -133,8 +133,7 @@ class RobotSDF(sdf.ObjectFrameSDF):
                 def contract(lw):
                     # object_to_link[s*A+a] = offset[s]^-1 @ world_T_link[s,a]^-1 on the matrix cores
                     out = torch.empty_like(lw)
-                    _lib.check(lib.pvamd_transform_stack(_lib.ptr(offset_inv), _lib.ptr(lw), S, A,
-                                                         _lib.ptr(out), _lib.stream_ptr()), "pvamd_transform_stack")
+                    _lib.call("pvamd_transform_stack", offset_inv, lw, S, A, out)
                     return out
 
                 if link_world_d.requires_grad and torch.is_grad_enabled():

@@ -4,7 +4,6 @@ csrc/distance_transform.hip) and the ObjectFrameSDF over a VoxelGrid that it fil
 The reference has no counterpart: its VoxelGrid / ExpandingVoxelGrid hold what a sensor saw (voxel.py:42-103) and every SDF it
 can query starts from a mesh or a closed form.  With this producer an observed scene is a leaf like any mesh cache.
 """
-import ctypes
 from typing import NamedTuple
 
 import torch
@@ -56,9 +55,7 @@ def _transform(occupied, resolution, signed):
     squared = torch.empty((n,), dtype=torch.int32, device=dev)
     with _lib.on_device(dev):
         scratch = _lib.scratch_buffer(_lib.distance_transform_scratch_bytes(nx, ny, nz, signed), dev)
-        _lib.check(_lib.load().pvamd_distance_transform(_lib.ptr(occ), nx, ny, nz, resolution, int(signed), _lib.ptr(records),
-                                                        _lib.ptr(sites), _lib.ptr(squared), _lib.ptr(scratch), _lib.stream_ptr()),
-                   "pvamd_distance_transform")
+        _lib.call("pvamd_distance_transform", occ, nx, ny, nz, resolution, signed, records, sites, squared, scratch)
     return occ, records, sites, squared
 
 
@@ -152,7 +149,7 @@ class OccupancySDF(ObjectFrameSDF):
                 desc.bb_min[d], desc.bb_max[d] = bb[d, 0].item(), bb[d, 1].item()
                 desc.dbb_min[d], desc.dbb_max[d] = self._box[d, 0].item(), self._box[d, 1].item()
             desc.oob_mode = _lib.OOB_BOUNDING_BOX
-            _lib.check(_lib.load().pvamd_grid_finalize(ctypes.byref(desc)), "pvamd_grid_finalize")
+            _lib.call("pvamd_grid_finalize", desc)
             self._desc = desc
         return self._desc
 
@@ -163,11 +160,8 @@ class OccupancySDF(ObjectFrameSDF):
         P = flat.shape[0]
         val = torch.empty((P,), dtype=flat.dtype, device=flat.device)
         grad = torch.empty((P, 3), dtype=flat.dtype, device=flat.device)
-        lib = _lib.load()
-        entry = lib.pvamd_cached_query_f64 if flat.dtype == torch.float64 else lib.pvamd_cached_query
         with _lib.on_device(flat.device):
-            _lib.check(entry(ctypes.byref(self._grid_desc()), _lib.ptr(flat), P, _lib.ptr(val), _lib.ptr(grad), None,
-                             _lib.stream_ptr()), "pvamd_cached_query")
+            _lib.call("pvamd_cached_query", self._grid_desc(), flat, P, val, grad, None, f64=flat.dtype == torch.float64)
         return _restore(val, lead, (), dtype, device), _restore(grad, lead, (3,), dtype, device)
 
 

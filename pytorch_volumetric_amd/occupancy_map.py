@@ -5,7 +5,6 @@ The reference has no counterpart: its containers are written with grid[points] =
 voxel a sensor once reported stays occupied and free space is never told from space nobody looked at.  An OccupancyMap is what
 turns depth images into the occupancy that distance_transform / cached_sdf_from_voxels make a CachedSDF of.
 """
-import ctypes
 import math
 
 import torch
@@ -124,9 +123,7 @@ class OccupancyMap:
         origins = (origins.reshape(1, 3) if shared else origins.expand(*lead, 3).reshape(-1, 3)).contiguous()
         R = endpoints.shape[0]
         with _lib.on_device(self.device):
-            _lib.check(_lib.load().pvamd_ray_mark(ctypes.byref(self._grid.voxels._grid_desc()), _lib.ptr(origins), int(shared),
-                                                  _lib.ptr(endpoints), R, max_range, _lib.ptr(marks), _lib.stream_ptr()),
-                       "pvamd_ray_mark")
+            _lib.call("pvamd_ray_mark", self._grid.voxels._grid_desc(), origins, shared, endpoints, R, max_range, marks)
         return True
 
     def integrate(self, origins, endpoints, max_range=math.inf):
@@ -136,9 +133,8 @@ class OccupancyMap:
         if not self._mark(origins, endpoints, max_range, self._marks):
             return
         with _lib.on_device(self.device):
-            _lib.check(_lib.load().pvamd_occupancy_update(_lib.ptr(self._marks), self._marks.numel(), self.l_hit, self.l_miss,
-                                                          self.l_min, self.l_max, _lib.ptr(self.log_odds), _lib.ptr(self._observed),
-                                                          _lib.stream_ptr()), "pvamd_occupancy_update")
+            _lib.call("pvamd_occupancy_update", self._marks, self._marks.numel(), self.l_hit, self.l_miss, self.l_min, self.l_max,
+                      self.log_odds, self._observed)
 
     def to_sdf(self, name, signed=True, unknown="free", interpolation="nearest", threshold=0.5):
         """A CachedSDF of occupied(threshold, unknown) over the map's lattice (cached_sdf_from_voxels): a snapshot that can be

@@ -71,9 +71,7 @@ def _redistance_records(records, shape, resolution, band, max_distance):
     squared = torch.empty((n,), dtype=torch.float32, device=dev)
     with _lib.on_device(dev):
         scratch = _lib.scratch_buffer(_lib.redistance_scratch_bytes(nx, ny, nz), dev)
-        _lib.check(_lib.load().pvamd_redistance(_lib.ptr(records), nx, ny, nz, resolution, band, max_distance, _lib.ptr(out),
-                                                _lib.ptr(sites), _lib.ptr(squared), _lib.ptr(scratch), _lib.stream_ptr()),
-                   "pvamd_redistance")
+        _lib.call("pvamd_redistance", records, nx, ny, nz, resolution, band, max_distance, out, sites, squared, scratch)
     return out, sites, squared
 
 

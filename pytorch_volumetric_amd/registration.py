@@ -5,7 +5,6 @@ sum_i (scale * sdf(W p_i))^2 over a left-multiplied twist of every pose (`chamfe
 Huber weights; `refine_poses` runs on it when asked for any of the three.
 The contracts are include/pvamd.h "Chamfer normal equations" and "Semantic normal equations"; the kernels are
 csrc/registration.hip."""
-import ctypes
 import math
 import numbers
 from typing import NamedTuple
@@ -162,22 +161,19 @@ class _Evaluator:
     def __call__(self, W32):
         if self.B == 0:
             return
-        lib = _lib.load()
         if self.mode is not None:
-            head = (ctypes.byref(self.desc), self.mode, _lib.ptr(W32), self.B, _lib.ptr(self.pts), self.N)
-            tail = (_lib.ptr(self.sums), _lib.ptr(self.counts), _lib.ptr(self.scratch), _lib.stream_ptr())
+            head = (self.desc, self.mode, W32, self.B, self.pts, self.N)
+            tail = (self.sums, self.counts, self.scratch)
             if self.plain:
-                _lib.check(lib.pvamd_chamfer_normal_eq(*head, *tail), "pvamd_chamfer_normal_eq")
+                _lib.call("pvamd_chamfer_normal_eq", *head, *tail)
             else:
-                _lib.check(lib.pvamd_semantic_normal_eq(*head, _lib.ptr(self.kinds), _lib.ptr(self.targets), self.delta, *tail),
-                           "pvamd_semantic_normal_eq")
+                _lib.call("pvamd_semantic_normal_eq", *head, self.kinds, self.targets, self.delta, *tail)
             return
         # any other object: transform with the kernel's statements, query the object, the contract's statements in float64 in torch.
         # One block serves the plain form too: without kinds and targets and with delta = inf every pair is active and none an
         # outlier, and a `where` on an all-true mask, a product with 1.0 and `a > inf` change no bit of v v, v j and j j^T
         x = torch.empty((self.B, self.N, 3), dtype=torch.float32, device=self.dev)
-        _lib.check(lib.pvamd_transform_points(_lib.ptr(W32), self.B, _lib.ptr(self.pts), self.N, _lib.ptr(x), _lib.stream_ptr()),
-                   "pvamd_transform_points")
+        _lib.call("pvamd_transform_points", W32, self.B, self.pts, self.N, x)
         with torch.no_grad():
             v, n = self.obj_sdf(x)
         v = v.detach().to(device=self.dev, dtype=torch.float64).reshape(self.B, self.N)
@@ -318,7 +314,6 @@ def refine_poses(world_to_object, points, obj_sdf: ObjectFrameSDF, iterations=10
     out_device = W.device
     mode = _fused_mode(obj_sdf)
     dev = _device_of(obj_sdf, mode)
-    lib = _lib.load()
     with _lib.on_device(dev):
         W32, pts32 = _prepare(W, pts, dev)
         B = W32.shape[0]
@@ -336,9 +331,8 @@ def refine_poses(world_to_object, points, obj_sdf: ObjectFrameSDF, iterations=10
             ev(w_next)
             if it == 0:
                 initial = ev.sums[:, 0].clone()
-            _lib.check(lib.pvamd_pose_lm_step(B, _lib.ptr(ev.sums), int(it == 0), _lib.ptr(w_acc), _lib.ptr(sums_acc), _lib.ptr(lam),
-                                              _lib.ptr(accepted), _lib.ptr(w_try), _lib.ptr(w_next), up, down, LAMBDA_MIN,
-                                              LAMBDA_MAX, _lib.stream_ptr()), "pvamd_pose_lm_step")
+            _lib.call("pvamd_pose_lm_step", B, ev.sums, it == 0, w_acc, sums_acc, lam, accepted, w_try, w_next, up, down,
+                      LAMBDA_MIN, LAMBDA_MAX)
         k = scale * scale / ev.N
         out = torch.zeros((B, 4, 4), dtype=out_dtype, device=dev)
         out[:, :3, :] = w_acc.to(out_dtype)

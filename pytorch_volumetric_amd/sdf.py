@@ -315,7 +315,6 @@ class ObjectFactory(abc.ABC):
         the kernels' group and tile spheres tight), per-triangle records, tile spheres, face-id map."""
         dev = _lib.require_gpu()
         if self._tri_dev is None or self._tri_dev.device != dev:
-            lib = _lib.load()
             soup = self._mesh.triangle_soup().astype(np.float32)  # the scene stores float32 vertices
             order = mesh_io.patch_order(soup.mean(axis=1))
             F = soup.shape[0]
@@ -329,10 +328,8 @@ class ObjectFactory(abc.ABC):
             lo, hi = self._mesh.aabb()
             abs_margin = 1e-6 * float(np.abs(self._mesh.vertices).max() + np.linalg.norm(hi - lo)) if F else 0.0
             with _lib.on_device(dev):
-                _lib.check(lib.pvamd_mesh_prepare(_lib.ptr(self._tri_dev), _lib.ptr(face_id), F, abs_margin,
-                                                  _lib.ptr(self._rec_dev), _lib.ptr(self._tiles_dev),
-                                                  _lib.ptr(self._rec_of_face_dev), _lib.stream_ptr()),
-                           "pvamd_mesh_prepare")
+                _lib.call("pvamd_mesh_prepare", self._tri_dev, face_id, F, abs_margin, self._rec_dev, self._tiles_dev,
+                          self._rec_of_face_dev)
         if getattr(self, "_mesh_desc_cache", None) is not None and self._mesh_desc_cache.rec == self._rec_dev.data_ptr():
             return self._mesh_desc_cache
         desc = _lib.MeshDesc()
@@ -363,7 +360,6 @@ class ObjectFactory(abc.ABC):
     def sample_surface(self, n, seed):
         """n area-uniform surface points (float64, on the GPU), the index of the prepared triangle each came from and a
         random key per sample; the draw of sample_mesh_points (sdf.py:643-650)."""
-        lib = _lib.load()
         self._mesh_desc()
         dev = self._tri_dev.device
         if getattr(self, "_area_cdf_dev", None) is None or self._area_cdf_dev.device != dev:
@@ -378,10 +374,8 @@ class ObjectFactory(abc.ABC):
         face = torch.empty((n,), dtype=torch.int32, device=dev)
         keys = torch.empty((n,), dtype=torch.int64, device=dev)
         with _lib.on_device(dev):
-            _lib.check(lib.pvamd_sample_surface(_lib.ptr(self._tri_dev), _lib.ptr(self._area_cdf_dev),
-                                                int(self._tri_dev.shape[0]), n, ctypes.c_uint64(int(seed) & (2 ** 64 - 1)),
-                                                _lib.ptr(pts), _lib.ptr(face), _lib.ptr(keys), _lib.stream_ptr()),
-                       "pvamd_sample_surface")
+            _lib.call("pvamd_sample_surface", self._tri_dev, self._area_cdf_dev, int(self._tri_dev.shape[0]), n,
+                      ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), pts, face, keys)
         return pts, face, keys
 
     @property
@@ -404,7 +398,6 @@ class ObjectFactory(abc.ABC):
         :param order: int32 processing order of the flattened points (a permutation that keeps neighbours in space together),
             when the caller already has one; results do not depend on it
         """
-        lib = _lib.load()
         if not torch.is_tensor(points_in_object_frame):
             points_in_object_frame = torch.as_tensor(np.asarray(points_in_object_frame), dtype=torch.float)
         flat, lead, dtype, device = _lib.as_query_points(points_in_object_frame)
@@ -425,19 +418,13 @@ class ObjectFactory(abc.ABC):
             if order is None and 0 < P <= _lib.mesh_small_points() and scratch is not None:
                 # few points: the processing order is worked out inside the query's first launch (one workgroup of it)
                 order_scratch = torch.empty((P,), dtype=torch.int32, device=dev)
-                _lib.check(lib.pvamd_mesh_query_unordered(ctypes.byref(desc), _lib.ptr(flat), P,
-                                                          ctypes.c_uint64(self.jitter_seed), int(index_base),
-                                                          _lib.ptr(closest), _lib.ptr(dist), _lib.ptr(grad), _lib.ptr(face),
-                                                          _lib.ptr(normal), _lib.ptr(order_scratch), _lib.ptr(scratch),
-                                                          _lib.stream_ptr()), "pvamd_mesh_query_unordered")
+                _lib.call("pvamd_mesh_query_unordered", desc, flat, P, ctypes.c_uint64(self.jitter_seed), int(index_base),
+                          closest, dist, grad, face, normal, order_scratch, scratch)
             else:
                 if order is None:
                     order = _lib.morton_order(flat)
-                _lib.check(lib.pvamd_mesh_query(ctypes.byref(desc), _lib.ptr(flat), _lib.ptr(order), P,
-                                                ctypes.c_uint64(self.jitter_seed),
-                                                int(index_base), _lib.ptr(closest), _lib.ptr(dist), _lib.ptr(grad),
-                                                _lib.ptr(face), _lib.ptr(normal), _lib.ptr(scratch), _lib.stream_ptr()),
-                           "pvamd_mesh_query")
+                _lib.call("pvamd_mesh_query", desc, flat, order, P, ctypes.c_uint64(self.jitter_seed), int(index_base),
+                          closest, dist, grad, face, normal, scratch)
         self._last_face_ids = face
         return SDFQuery(_restore(closest, lead, (3,), dtype, device), _restore(dist, lead, (), dtype, device),
                         _restore(grad, lead, (3,), dtype, device),
@@ -469,7 +456,6 @@ class ObjectFactory(abc.ABC):
             if poses.dim() not in (2, 3) or tuple(poses.shape[-2:]) != (4, 4):
                 raise ValueError(f"world_to_object must be (4, 4) or (B, 4, 4), got {tuple(poses.shape)}")
             batch = tuple(poses.shape[:-2])
-        lib = _lib.load()
         desc = self._mesh_desc()
         dev = self._rec_dev.device
         o = o.reshape(-1, 3).to(device=dev, dtype=torch.float32).contiguous()
@@ -484,9 +470,7 @@ class ObjectFactory(abc.ABC):
         normal = torch.empty((B, R, 3), dtype=torch.float32, device=dev)
         uv = torch.empty((B, R, 2), dtype=torch.float32, device=dev)
         with _lib.on_device(dev):
-            _lib.check(lib.pvamd_mesh_ray_cast(ctypes.byref(desc), _lib.ptr(o), _lib.ptr(d), R, _lib.ptr(poses), B, t_min, t_max,
-                                               _lib.ptr(t), _lib.ptr(face), _lib.ptr(normal), _lib.ptr(uv), _lib.stream_ptr()),
-                       "pvamd_mesh_ray_cast")
+            _lib.call("pvamd_mesh_ray_cast", desc, o, d, R, poses, B, t_min, t_max, t, face, normal, uv)
         shape = batch + lead
         return MeshRayHits(_restore(t, shape, (), dtype, device), face.reshape(shape).to(device=device, dtype=torch.int64),
                            _restore(normal, shape, (3,), dtype, device), _restore(uv, shape, (2,), dtype, device))
@@ -677,17 +661,14 @@ class VoxelView:
         return self._owner._packed[:, 0]
 
     def _index(self, points, want_key=False, want_flat=False, want_valid=False):
-        lib = _lib.load()
         flat, lead, _, device = _lib.as_query_points(self._owner._lift(points), self._owner._packed.device, keep_f64=True)
         P = flat.shape[0]
         key = torch.empty((P, 3), dtype=torch.int64, device=flat.device) if want_key else None
         ravel = torch.empty((P,), dtype=torch.int64, device=flat.device) if want_flat else None
         valid = torch.empty((P,), dtype=torch.uint8, device=flat.device) if want_valid else None
         desc = self._owner._grid_desc()
-        entry = lib.pvamd_voxel_index_f64 if flat.dtype == torch.float64 else lib.pvamd_voxel_index
         with _lib.on_device(flat.device):
-            _lib.check(entry(ctypes.byref(desc), _lib.ptr(flat), P, _lib.ptr(key), _lib.ptr(ravel),
-                             _lib.ptr(valid), _lib.stream_ptr()), "pvamd_voxel_index")
+            _lib.call("pvamd_voxel_index", desc, flat, P, key, ravel, valid, f64=flat.dtype == torch.float64)
         d = self._owner._dim
         return (key.reshape(*lead, 3)[..., :d] if want_key else None, ravel.reshape(*lead) if want_flat else None,
                 valid.reshape(*lead).bool() if want_valid else None)
@@ -819,7 +800,6 @@ class CachedSDF(ObjectFrameSDF):
             grad = torch.stack((g3, g3), dim=1).reshape(-1, 3)
         self._view = RangeView(view_ranges, val.shape)
         dev = _lib.require_gpu()
-        lib = _lib.load()
         if built is not None and self._dim == 3 and built.device == dev:
             self._packed = built  # the mesh kernel wrote the records themselves
         else:
@@ -827,8 +807,7 @@ class CachedSDF(ObjectFrameSDF):
             grad_d = grad.to(device=dev, dtype=torch.float32).contiguous().reshape(-1, 3)
             self._packed = torch.empty((val_d.shape[0], 4), dtype=torch.float32, device=dev)
             with _lib.on_device(dev):
-                _lib.check(lib.pvamd_pack_grid(_lib.ptr(val_d), _lib.ptr(grad_d), val_d.shape[0], _lib.ptr(self._packed),
-                                               _lib.stream_ptr()), "pvamd_pack_grid")
+                _lib.call("pvamd_pack_grid", val_d, grad_d, val_d.shape[0], self._packed)
         self.voxels = VoxelView(self)
         self.voxels_grad = self._packed[:, 1:]
         self.bb = self.surface_bounding_box().to(device=dev)
@@ -853,7 +832,6 @@ class CachedSDF(ObjectFrameSDF):
         n = shape[0] * shape[1] * shape[2]
         if n == 0 or n > 2 ** 31 - 1:
             return None
-        lib = _lib.load()
         with _lib.on_device(dev):
             desc = obj._mesh_desc()
             if obj._rec_dev.device != dev:
@@ -866,9 +844,8 @@ class CachedSDF(ObjectFrameSDF):
             order = torch.empty((n,), dtype=torch.int32, device=dev)
             scratch = _lib.scratch_buffer(_lib.mesh_scratch_bytes(n), dev) \
                 if getattr(obj, "tile_split", True) else None
-            _lib.check(lib.pvamd_cache_build(ctypes.byref(desc), _lib.ptr(cx), _lib.ptr(cy), _lib.ptr(cz), shape[0], shape[1], shape[2],
-                                             ctypes.c_uint64(obj.jitter_seed), _lib.ptr(packed), _lib.ptr(pts), _lib.ptr(order),
-                                             _lib.ptr(scratch), _lib.stream_ptr()), "pvamd_cache_build")
+            _lib.call("pvamd_cache_build", desc, cx, cy, cz, shape[0], shape[1], shape[2], ctypes.c_uint64(obj.jitter_seed),
+                      packed, pts, order, scratch)
         return packed
 
     @staticmethod
@@ -940,7 +917,7 @@ class CachedSDF(ObjectFrameSDF):
             desc.dbb_min[d], desc.dbb_max[d] = bb64[d, 0].item(), bb64[d, 1].item()
         mode = self.out_of_bounds_strategy if oob_mode is None else oob_mode
         desc.oob_mode = _lib.OOB_BOUNDING_BOX if mode == OutOfBoundsStrategy.BOUNDING_BOX else _lib.OOB_LOOKUP_GT_SDF
-        _lib.check(_lib.load().pvamd_grid_finalize(ctypes.byref(desc)), "pvamd_grid_finalize")
+        _lib.call("pvamd_grid_finalize", desc)
         cache[mode_key] = desc
         return desc
 
@@ -1031,9 +1008,7 @@ class CachedSDF(ObjectFrameSDF):
             raise ValueError("query_into needs contiguous fp32 outputs of shape (P,) and (P,3)")
         desc = self._grid_desc()  # cached per mode and cache pointer, dropped by __setattr__ when `bb` / the cache change
         with _lib.on_device(points.device):
-            _lib.check(_lib.load().pvamd_cached_query(ctypes.byref(desc), _lib.ptr(points), P,
-                                                      _lib.ptr(out_val), _lib.ptr(out_grad), None, _lib.stream_ptr()),
-                       "pvamd_cached_query")
+            _lib.call("pvamd_cached_query", desc, points, P, out_val, out_grad, None)
 
     def _forward(self, flat, want_oob):
         """(val, grad, oob) of contiguous (P, 3) points on the grid's GPU (float64 stays float64) by this cache's interpolation:
@@ -1043,11 +1018,9 @@ class CachedSDF(ObjectFrameSDF):
         grad = torch.empty((P, 3), dtype=flat.dtype, device=flat.device)
         oob = torch.empty((P,), dtype=torch.uint8, device=flat.device) if want_oob else None
         desc = self._grid_desc()
-        name = "pvamd_cached_query" if self.interpolation == "nearest" else "pvamd_cached_query_interp"
-        entry = getattr(_lib.load(), name + "_f64" if flat.dtype == torch.float64 else name)
         with _lib.on_device(flat.device):
-            _lib.check(entry(ctypes.byref(desc), _lib.ptr(flat), P, _lib.ptr(val), _lib.ptr(grad), _lib.ptr(oob), _lib.stream_ptr()),
-                       name)
+            _lib.call("pvamd_cached_query" if self.interpolation == "nearest" else "pvamd_cached_query_interp",
+                      desc, flat, P, val, grad, oob, f64=flat.dtype == torch.float64)
         return val, grad, oob
 
     def ray_cast(self, origins, directions, t_min=0., t_max=math.inf, hit_tolerance=1e-3, step_scale=1., max_steps=128,
@@ -1083,10 +1056,9 @@ class CachedSDF(ObjectFrameSDF):
         d = d.reshape(-1, 3).to(device=dev, dtype=dtype).contiguous()
         R = o.shape[0]
         out = _ray_outputs((R,), dtype, dev)
-        name = "pvamd_cached_ray_cast" + ("_f64" if dtype == torch.float64 else "")
         with _lib.on_device(dev):
-            _lib.check(getattr(_lib.load(), name)(ctypes.byref(self._grid_desc()), _lib.LEAF_MODES[self.interpolation], _lib.ptr(o),
-                                                  _lib.ptr(d), R, *args, *map(_lib.ptr, out), _lib.stream_ptr()), name)
+            _lib.call("pvamd_cached_ray_cast", self._grid_desc(), _lib.LEAF_MODES[self.interpolation], o, d, R, *args, *out,
+                      f64=dtype == torch.float64)
         return _ray_result(out, lead, self.device), {"o": o, "d": d, "out": out}
 
     def extract_mesh(self, level=0.0, normals=True):
@@ -1103,18 +1075,14 @@ class CachedSDF(ObjectFrameSDF):
 
     def outside_surface(self, points_in_object_frame, surface_level=0):
         """sdf.py:593-602 (trilinear caches: the interpolated value > surface_level in range, True out of range)"""
-        lib = _lib.load()
         flat, lead, _, _ = _lib.as_query_points(self._lift(points_in_object_frame), self._packed.device, keep_f64=True)
         if self.interpolation == "trilinear":
             val, _, oob = self._forward(flat, want_oob=True)
             return ((oob != 0) | (val > surface_level)).reshape(*lead).to(device=self.device)
         out = torch.empty((flat.shape[0],), dtype=torch.uint8, device=flat.device)
         desc = self._grid_desc()
-        entry = lib.pvamd_cached_outside_f64 if flat.dtype == torch.float64 else lib.pvamd_cached_outside
         with _lib.on_device(flat.device):
-            _lib.check(entry(ctypes.byref(desc), _lib.ptr(flat), flat.shape[0],
-                             float(surface_level), _lib.ptr(out), _lib.stream_ptr()),
-                       "pvamd_cached_outside")
+            _lib.call("pvamd_cached_outside", desc, flat, flat.shape[0], float(surface_level), out, f64=flat.dtype == torch.float64)
         return out.reshape(*lead).bool().to(device=self.device)
 
     def _fallback_sdf_value_func(self, *args, **kwargs):
@@ -1355,8 +1323,7 @@ class ComposedSDF(ObjectFrameSDF):
         a fresh point tensor every step gets the same address back from the caching allocator, so no cheap key tells a new
         query from the last one."""
         box = torch.empty((2, 3), dtype=torch.float32, device=flat.device)
-        _lib.check(_lib.load().pvamd_points_aabb(_lib.ptr(flat), flat.shape[0], _lib.ptr(box), _lib.stream_ptr()),
-                   "pvamd_points_aabb")
+        _lib.call("pvamd_points_aabb", flat, flat.shape[0], box)
         lo, hi = box.cpu().double().unbind(0)
         extent = (hi - lo).clamp_min(0.0)
         res = min(float(s._view.dres.min()) for s in self.sdfs)
@@ -1491,7 +1458,6 @@ class ComposedSDF(ObjectFrameSDF):
         P = flat.shape[0]
         dev = flat.device
         if fused:
-            lib = _lib.load()
             out_device = self.sdfs[0].device  # leaves return on their own device (sdf.py:546)
             val = torch.empty((A, P), dtype=torch.float32, device=dev)
             grad = torch.empty((A, P, 3), dtype=torch.float32, device=dev)
@@ -1505,20 +1471,15 @@ class ComposedSDF(ObjectFrameSDF):
                     if Pp != P:  # whole tiles: pad with copies of the last point (never read back)
                         spts = torch.cat((spts, spts[-1:].expand(Pp - P, 3))).contiguous()
                     scratch = torch.empty((A, Pp, 4), dtype=torch.float32, device=dev)
-                    _lib.check(lib.pvamd_composed_query_bucketed(_lib.ptr(grids), S, _lib.ptr(self._tf_device(dev)), A,
-                                                                 _lib.ptr(spts), _lib.ptr(inv), P, Pp, _lib.ptr(scratch),
-                                                                 _lib.ptr(val), _lib.ptr(grad), self._query_flags,
-                                                                 _lib.stream_ptr()), "pvamd_composed_query_bucketed")
+                    _lib.call("pvamd_composed_query_bucketed", grids, S, self._tf_device(dev), A, spts, inv, P, Pp, scratch,
+                              val, grad, self._query_flags)
                 elif self._grouping_pays(A, P, self._query_flags):
                     scratch = _lib.group_points(flat)
-                    _lib.check(lib.pvamd_composed_query_grouped(_lib.ptr(grids), S, _lib.ptr(self._tf_device(dev)), A,
-                                                                _lib.ptr(scratch), P, _lib.ptr(val), _lib.ptr(grad), None,
-                                                                self._query_flags, _lib.stream_ptr()),
-                               "pvamd_composed_query_grouped")
+                    _lib.call("pvamd_composed_query_grouped", grids, S, self._tf_device(dev), A, scratch, P, val, grad, None,
+                              self._query_flags)
                 else:
-                    _lib.check(lib.pvamd_composed_query(_lib.ptr(grids), S, _lib.ptr(self._tf_device(dev)),
-                                                        A, _lib.ptr(flat), P, _lib.ptr(val), _lib.ptr(grad), None,
-                                                        self._direct_flags(), _lib.stream_ptr()), "pvamd_composed_query")
+                    _lib.call("pvamd_composed_query", grids, S, self._tf_device(dev), A, flat, P, val, grad, None,
+                              self._direct_flags())
         else:
             val, grad = self._generic(flat, S, A)
         if self.tsf_batch is not None:
@@ -1527,9 +1488,6 @@ class ComposedSDF(ObjectFrameSDF):
         else:
             val, grad = val.reshape(-1), grad.reshape(-1, 3)
         return val.to(device=out_device, dtype=dtype), grad.to(device=out_device, dtype=dtype)
-
-    _FUSED_ENTRIES = {("nearest", False): "pvamd_composed_query", ("nearest", True): "pvamd_composed_query_f64",
-                      ("trilinear", False): "pvamd_composed_query_interp", ("trilinear", True): "pvamd_composed_query_interp_f64"}
 
     def _fused_forward(self, points, mode, want_leaf=False, configs=None):
         """One launch of the fused kernel of leaf mode `mode` over all the points, without sorting or regrouping them: float64
@@ -1549,12 +1507,11 @@ class ComposedSDF(ObjectFrameSDF):
         grad = torch.empty((A, P, 3), dtype=flat.dtype, device=dev)
         leaf = torch.empty((A, P), dtype=torch.int32, device=dev) if want_leaf else None
         if P > 0:
-            name = self._FUSED_ENTRIES[mode, f64]
             with _lib.on_device(dev):
                 grids = self._leaf_grids(dev)
-                flags = (self._direct_flags(),) if name == "pvamd_composed_query" else ()
-                _lib.check(getattr(_lib.load(), name)(_lib.ptr(grids), S, _lib.ptr(tfd), A, _lib.ptr(flat), P, _lib.ptr(val),
-                                                      _lib.ptr(grad), _lib.ptr(leaf), *flags, _lib.stream_ptr()), name)
+                flags = (self._direct_flags(),) if mode == "nearest" and not f64 else ()  # pvamd_composed_query alone takes them
+                _lib.call("pvamd_composed_query" if mode == "nearest" else "pvamd_composed_query_interp",
+                          grids, S, tfd, A, flat, P, val, grad, leaf, *flags, f64=f64)
         if configs is not None:
             return val, grad, leaf, flat, tfd
         if self.tsf_batch is not None:
@@ -1625,13 +1582,11 @@ class ComposedSDF(ObjectFrameSDF):
         grad = torch.empty((A, Z, 3), dtype=flat.dtype, device=dev)
         idx = torch.empty((A, Z), dtype=torch.int64, device=dev)
         leaf = torch.empty((A, Z), dtype=torch.int32, device=dev)
-        name = "pvamd_composed_min_over_points" + ("_f64" if flat.dtype == torch.float64 else "")
         with _lib.on_device(dev):
             grids = self._leaf_grids(dev)
             scratch = _lib.scratch_buffer(_lib.min_over_points_scratch_bytes(S, A, P, per_leaf), dev)
-            _lib.check(getattr(_lib.load(), name)(_lib.ptr(grids), S, _lib.ptr(tfd), A, _lib.ptr(flat), P, _lib.LEAF_MODES[mode],
-                                                  int(per_leaf), _lib.ptr(val), _lib.ptr(grad), _lib.ptr(idx), _lib.ptr(leaf),
-                                                  _lib.ptr(scratch), _lib.stream_ptr()), name)
+            _lib.call("pvamd_composed_min_over_points", grids, S, tfd, A, flat, P, _lib.LEAF_MODES[mode], per_leaf,
+                      val, grad, idx, leaf, scratch, f64=flat.dtype == torch.float64)
         shape = batch + ((S,) if per_leaf else ())
         out_device = self.sdfs[0].device  # leaves return on their own device (sdf.py:546)
         return (val.reshape(shape).to(device=out_device, dtype=dtype), idx.reshape(shape).to(device=out_device),
@@ -1707,11 +1662,10 @@ class ComposedSDF(ObjectFrameSDF):
         _, tfd, _ = self._fused_inputs(o, dev)
         R = o.shape[0]
         out = _ray_outputs((A, R), dtype, dev)
-        name = "pvamd_composed_ray_cast" + ("_f64" if dtype == torch.float64 else "")
         with _lib.on_device(dev):
             grids = self._leaf_grids(dev)
-            _lib.check(getattr(_lib.load(), name)(_lib.ptr(grids), S, _lib.ptr(tfd), A, _lib.ptr(o), _lib.ptr(d), R,
-                                                  _lib.LEAF_MODES[mode], *args, *map(_lib.ptr, out), _lib.stream_ptr()), name)
+            _lib.call("pvamd_composed_ray_cast", grids, S, tfd, A, o, d, R, _lib.LEAF_MODES[mode], *args, *out,
+                      f64=dtype == torch.float64)
         # leaves return on their own device (sdf.py:546)
         return _ray_result(out, batch + lead, self.sdfs[0].device), {"o": o, "d": d, "out": out, "tfd": tfd, "grids": grids,
                                                                       "S": S, "A": A, "mode": mode}
@@ -1801,13 +1755,11 @@ class ComposedSDF(ObjectFrameSDF):
         P, Z = flat.shape[0], S if per_leaf else 1
         val = torch.empty((A, Z), dtype=flat.dtype, device=dev)
         cnt = torch.empty((A, Z), dtype=torch.int64, device=dev)
-        name = "pvamd_composed_hinge_over_points" + ("_f64" if flat.dtype == torch.float64 else "")
         with _lib.on_device(dev):
             grids = self._leaf_grids(dev)
             scratch = _lib.scratch_buffer(_lib.hinge_over_points_scratch_bytes(S, A, P, per_leaf), dev)
-            _lib.check(getattr(_lib.load(), name)(_lib.ptr(grids), S, _lib.ptr(tfd), A, _lib.ptr(flat), P, _lib.LEAF_MODES[mode],
-                                                  int(per_leaf), margin, power, _lib.ptr(val), _lib.ptr(cnt), _lib.ptr(scratch),
-                                                  _lib.stream_ptr()), name)
+            _lib.call("pvamd_composed_hinge_over_points", grids, S, tfd, A, flat, P, _lib.LEAF_MODES[mode], per_leaf, margin, power,
+                      val, cnt, scratch, f64=flat.dtype == torch.float64)
         shape = batch + ((S,) if per_leaf else ())
         out_device = self.sdfs[0].device  # leaves return on their own device (sdf.py:546)
         return val.reshape(shape).to(device=out_device, dtype=dtype), cnt.reshape(shape).to(device=out_device), flat, tfd
@@ -1909,9 +1861,8 @@ class ComposedSDF(ObjectFrameSDF):
         tfd = self._stack_for(dtype, dev)
         C = torch.empty((K, A, 4, 4), dtype=dtype, device=dev)
         if K:
-            name = "pvamd_leaf_pair_transforms" + ("_f64" if dtype == torch.float64 else "")
             with _lib.on_device(dev):
-                _lib.check(getattr(_lib.load(), name)(_lib.ptr(tfd), S, A, _lib.ptr(table), K, _lib.ptr(C), _lib.stream_ptr()), name)
+                _lib.call("pvamd_leaf_pair_transforms", tfd, S, A, table, K, C, f64=dtype == torch.float64)
         return C, tfd
 
     def leaf_pair_transforms(self, pairs, dtype=torch.float32):
@@ -1992,14 +1943,12 @@ class ComposedSDF(ObjectFrameSDF):
         grad = torch.empty((A, K, 3), dtype=dt, device=dev)
         idx = torch.empty((A, K), dtype=torch.int64, device=dev)
         f64 = dt == torch.float64
-        name = "pvamd_leaf_pair_distance" + ("_f64" if f64 else "")
         with _lib.on_device(dev):
             grids = self._leaf_grids(dev)
             n = _lib.leaf_pair_scratch_bytes(K, A, plan["max_points"], f64, False)
             scratch = _lib.scratch_buffer(n, dev) if n else None
-            _lib.check(getattr(_lib.load(), name)(_lib.ptr(grids), S, _lib.ptr(C), A, _lib.ptr(plan["packed"]), plan["npoints"],
-                                                  _lib.ptr(table), K, plan["max_points"], _lib.LEAF_MODES[mode], _lib.ptr(val),
-                                                  _lib.ptr(grad), _lib.ptr(idx), _lib.ptr(scratch), _lib.stream_ptr()), name)
+            _lib.call("pvamd_leaf_pair_distance", grids, S, C, A, plan["packed"], plan["npoints"], table, K, plan["max_points"],
+                      _lib.LEAF_MODES[mode], val, grad, idx, scratch, f64=f64)
         return val.reshape(*batch, K), idx.reshape(*batch, K), grad.reshape(*batch, K, 3), idx, C, tfd
 
     def _leaf_pair_generic(self, plan):
@@ -2073,14 +2022,12 @@ class ComposedSDF(ObjectFrameSDF):
         val = torch.empty((A, K), dtype=dt, device=dev)
         cnt = torch.empty((A, K), dtype=torch.int64, device=dev)
         f64 = dt == torch.float64
-        name = "pvamd_leaf_pair_hinge" + ("_f64" if f64 else "")
         with _lib.on_device(dev):
             grids = self._leaf_grids(dev)
             n = _lib.leaf_pair_hinge_scratch_bytes(K, A, plan["max_points"], f64, False)
             scratch = _lib.scratch_buffer(n, dev) if n else None
-            _lib.check(getattr(_lib.load(), name)(_lib.ptr(grids), S, _lib.ptr(C), A, _lib.ptr(plan["packed"]), plan["npoints"],
-                                                  _lib.ptr(table), K, plan["max_points"], _lib.LEAF_MODES[mode], margin, power,
-                                                  _lib.ptr(val), _lib.ptr(cnt), _lib.ptr(scratch), _lib.stream_ptr()), name)
+            _lib.call("pvamd_leaf_pair_hinge", grids, S, C, A, plan["packed"], plan["npoints"], table, K, plan["max_points"],
+                      _lib.LEAF_MODES[mode], margin, power, val, cnt, scratch, f64=f64)
         return val.reshape(*batch, K), cnt.reshape(*batch, K), C, tfd
 
     def _leaf_pair_hinge_generic(self, plan, margin, power):
@@ -2144,7 +2091,6 @@ class ComposedSDF(ObjectFrameSDF):
         if prepared.points.device != dev:
             raise _lib.PvamdError(f"query_prepared: the leaf grids live on {dev}; the prepared points are on {prepared.points.device}")
         P = prepared.points.shape[0]
-        lib = _lib.load()
         val = torch.empty((A, P), dtype=torch.float32, device=dev)
         grad = torch.empty((A, P, 3), dtype=torch.float32, device=dev)
         with _lib.on_device(dev):
@@ -2152,17 +2098,13 @@ class ComposedSDF(ObjectFrameSDF):
             tfd = self._tf_device(dev)
             if order == "sorted":
                 # (already sorted along the Hilbert curve: regrouping inside chunks would only cost its sort)
-                _lib.check(lib.pvamd_composed_query(_lib.ptr(grids), S, _lib.ptr(tfd), A, _lib.ptr(prepared.sorted_points), P,
-                                                    _lib.ptr(val), _lib.ptr(grad), None, self._query_flags | _lib.COMPOSED_NO_GROUPING,
-                                                    _lib.stream_ptr()),
-                           "pvamd_composed_query")
+                _lib.call("pvamd_composed_query", grids, S, tfd, A, prepared.sorted_points, P, val, grad, None,
+                          self._query_flags | _lib.COMPOSED_NO_GROUPING)
             else:
                 Pp = prepared.padded_points.shape[0]
                 scratch = torch.empty((A, Pp, 4), dtype=torch.float32, device=dev)
-                _lib.check(lib.pvamd_composed_query_bucketed(_lib.ptr(grids), S, _lib.ptr(tfd), A, _lib.ptr(prepared.padded_points),
-                                                             _lib.ptr(prepared.inverse), P, Pp, _lib.ptr(scratch), _lib.ptr(val),
-                                                             _lib.ptr(grad), self._query_flags, _lib.stream_ptr()),
-                           "pvamd_composed_query_bucketed")
+                _lib.call("pvamd_composed_query_bucketed", grids, S, tfd, A, prepared.padded_points, prepared.inverse, P, Pp,
+                          scratch, val, grad, self._query_flags)
         lead = (P,) if order == "sorted" else prepared.lead
         out_device = self.sdfs[0].device
         if self.tsf_batch is not None:
@@ -2192,14 +2134,11 @@ class ComposedSDF(ObjectFrameSDF):
             grids = self._leaf_grids(dev)
             if self._grouping_pays(A, P, self._query_flags):
                 scratch = _lib.group_points(points)
-                _lib.check(_lib.load().pvamd_composed_query_grouped(_lib.ptr(grids), len(self.sdfs), _lib.ptr(self._tf_device(dev)), A,
-                                                                    _lib.ptr(scratch), P, _lib.ptr(out), None, None,
-                                                                    self._query_flags | _lib.COMPOSED_OUT_PACKED, _lib.stream_ptr()),
-                           "pvamd_composed_query_grouped")
+                _lib.call("pvamd_composed_query_grouped", grids, len(self.sdfs), self._tf_device(dev), A, scratch, P, out, None, None,
+                          self._query_flags | _lib.COMPOSED_OUT_PACKED)
                 return out
-            _lib.check(_lib.load().pvamd_composed_query_packed(_lib.ptr(grids), len(self.sdfs), _lib.ptr(self._tf_device(dev)),
-                                                               A, _lib.ptr(points), P, _lib.ptr(out), self._query_flags,
-                                                               _lib.stream_ptr()), "pvamd_composed_query_packed")
+            _lib.call("pvamd_composed_query_packed", grids, len(self.sdfs), self._tf_device(dev), A, points, P, out,
+                      self._query_flags)
         return out
 
     def query_configs(self, points, first, count):
@@ -2223,9 +2162,7 @@ class ComposedSDF(ObjectFrameSDF):
         grad = torch.empty((count, P, 3), dtype=torch.float32, device=dev)
         with _lib.on_device(dev):
             grids = self._leaf_grids(dev)
-            _lib.check(_lib.load().pvamd_composed_query(_lib.ptr(grids), S, _lib.ptr(sub), count, _lib.ptr(flat), P,
-                                                        _lib.ptr(val), _lib.ptr(grad), None, self._direct_flags(),
-                                                        _lib.stream_ptr()), "pvamd_composed_query")
+            _lib.call("pvamd_composed_query", grids, S, sub, count, flat, P, val, grad, None, self._direct_flags())
         return val, grad
 
     def query_into(self, points, out_val, out_grad):
@@ -2252,8 +2189,7 @@ class ComposedSDF(ObjectFrameSDF):
             if self._grouping_pays(A, P, self._query_flags):
                 # two launches (the chunk sort, the query) over a scratch buffer this object keeps per point count: nothing is
                 # allocated after the first call of a size, so a captured graph replays both
-                lib = _lib.load()
-                need = int(lib.pvamd_group_scratch_bytes(P))
+                need = int(_lib.load().pvamd_group_scratch_bytes(P))
                 # one buffer per (point count, device, stream): two streams querying the same object never share a scratch.
                 # At most 8 are remembered -- except those a stream capture has seen: a captured graph replays with the
                 # buffer's address, so such a buffer lives as long as this object
@@ -2268,17 +2204,12 @@ class ComposedSDF(ObjectFrameSDF):
                 if not entry[1] and torch.cuda.is_current_stream_capturing():
                     entry[1] = True
                 scratch = entry[0]
-                _lib.check(lib.pvamd_group_points(_lib.ptr(points), P, _lib.ptr(scratch), _lib.stream_ptr()), "pvamd_group_points")
-                _lib.check(lib.pvamd_composed_query_grouped(_lib.ptr(grids), len(self.sdfs), _lib.ptr(self._tf_device(dev)), A,
-                                                            _lib.ptr(scratch), P, _lib.ptr(out_val), _lib.ptr(out_grad), None,
-                                                            self._query_flags, _lib.stream_ptr()),
-                           "pvamd_composed_query_grouped")
+                _lib.call("pvamd_group_points", points, P, scratch)
+                _lib.call("pvamd_composed_query_grouped", grids, len(self.sdfs), self._tf_device(dev), A, scratch, P,
+                          out_val, out_grad, None, self._query_flags)
                 return
-            _lib.check(_lib.load().pvamd_composed_query(_lib.ptr(grids), len(self.sdfs),
-                                                        _lib.ptr(self._tf_device(dev)), A, _lib.ptr(points), P,
-                                                        _lib.ptr(out_val), _lib.ptr(out_grad), None, self._direct_flags(),
-                                                        _lib.stream_ptr()),
-                       "pvamd_composed_query")
+            _lib.call("pvamd_composed_query", grids, len(self.sdfs), self._tf_device(dev), A, points, P, out_val, out_grad, None,
+                      self._direct_flags())
 
     def _generic_f64(self, points, S, A):
         """float64 query points over leaves that are not cached grids: sdf.py:395-431 runs transform_points, transform_normals
@@ -2319,7 +2250,6 @@ class ComposedSDF(ObjectFrameSDF):
         """Leaves that are not cached grids (MeshSDF -- the reference's own tests/test_sdf.py:61-80 -- SphereSDF, nested
         compositions): per leaf one transform kernel, the leaf's own query, one merge kernel (pvamd_transform_points /
         pvamd_compose_merge: the fused kernel's arithmetic, valid for any affine transform)."""
-        lib = _lib.load()
         dev = flat.device
         P = flat.shape[0]
         m = self._tf_device(dev).reshape(S, A, 4, 4)
@@ -2336,8 +2266,7 @@ class ComposedSDF(ObjectFrameSDF):
         x = torch.empty((A, P, 3), dtype=torch.float32, device=dev)
         for i, sdf in enumerate(self.sdfs):
             with _lib.on_device(dev):
-                _lib.check(lib.pvamd_transform_points(_lib.ptr(m[i]), A, _lib.ptr(flat), P, _lib.ptr(x), _lib.stream_ptr()),
-                           "pvamd_transform_points")
+                _lib.call("pvamd_transform_points", m[i], A, flat, P, x)
             if order is not None and isinstance(sdf, MeshSDF):
                 res = sdf.obj_factory.object_frame_closest_point(x, order=order)
                 v, g = res.distance, res.gradient
@@ -2346,9 +2275,7 @@ class ComposedSDF(ObjectFrameSDF):
             v = v.to(device=dev, dtype=torch.float32).reshape(A, P).contiguous()
             g = g.to(device=dev, dtype=torch.float32).reshape(A, P, 3).contiguous()
             with _lib.on_device(dev):
-                _lib.check(lib.pvamd_compose_merge(_lib.ptr(m[i]), A, P, _lib.ptr(v), _lib.ptr(g), i, 1 if i == 0 else 0,
-                                                   _lib.ptr(best_v), _lib.ptr(best_g), None, _lib.stream_ptr()),
-                           "pvamd_compose_merge")
+                _lib.call("pvamd_compose_merge", m[i], A, P, v, g, i, i == 0, best_v, best_g, None)
         return best_v, best_g
 
 

@@ -5,7 +5,6 @@ The reference has no counterpart.  A TSDFVolume, an occupancy map taken through 
 records on a lattice; extract_surface / CachedSDF.extract_mesh / TSDFVolume.extract_mesh hand the surface in them to everything
 here that starts from a mesh: MeshObjectFactory(mesh=...), MeshSDF, sample_mesh_points, mesh_io.save_obj.
 """
-import ctypes
 import math
 from typing import NamedTuple, Optional
 
@@ -99,7 +98,7 @@ def lattice_desc(shape, resolution, origin):
     desc.index_f64 = 0
     desc.rule = voxel.INDEX_RULE
     desc.oob_mode = _lib.OOB_BOUNDING_BOX
-    _lib.check(_lib.load().pvamd_grid_finalize(ctypes.byref(desc)), "pvamd_grid_finalize")
+    _lib.call("pvamd_grid_finalize", desc)
     return desc
 
 
@@ -108,20 +107,16 @@ def surface_of_records(desc, records, valid, level, want_normals):
     size, on the current stream.  records: contiguous float32 (n, 4) on the GPU; valid: contiguous uint8 (n,) there, or None."""
     dev = records.device
     nx, ny, nz = desc.shape
-    lib = _lib.load()
     with _lib.on_device(dev):
         scratch = _lib.scratch_buffer(_lib.surface_scratch_bytes(nx, ny, nz), dev)
         counts = torch.empty((2,), dtype=torch.int64, device=dev)
-        _lib.check(lib.pvamd_surface_count(ctypes.byref(desc), _lib.ptr(records), _lib.ptr(valid), level, _lib.ptr(scratch),
-                                           _lib.ptr(counts), _lib.stream_ptr()), "pvamd_surface_count")
+        _lib.call("pvamd_surface_count", desc, records, valid, level, scratch, counts)
         nv, nf = counts.tolist()
         vertices = torch.empty((nv, 3), dtype=torch.float32, device=dev)
         normals = torch.empty((nv, 3), dtype=torch.float32, device=dev) if want_normals else None
         faces = torch.empty((nf, 3), dtype=torch.int32, device=dev)
         if nv:
-            _lib.check(lib.pvamd_surface_emit(ctypes.byref(desc), _lib.ptr(records), _lib.ptr(valid), level, _lib.ptr(scratch), nv, nf,
-                                              _lib.ptr(vertices), _lib.ptr(normals), _lib.ptr(faces), _lib.stream_ptr()),
-                       "pvamd_surface_emit")
+            _lib.call("pvamd_surface_emit", desc, records, valid, level, scratch, nv, nf, vertices, normals, faces)
     return Surface(vertices, faces, normals)
 
 

@@ -5,7 +5,6 @@ The reference has no counterpart: its voxel.py stops at the containers.  Occupan
 voxel faces; a TSDFVolume keeps it between the voxels, where the depth images saw it, and hands it to the same consumers:
 ray_cast renders the model depth, refine_poses tracks against it, and integrate() is the step between them.
 """
-import ctypes
 import math
 import numbers
 
@@ -203,10 +202,8 @@ class TSDFVolume:
         depth = depth.contiguous()
         inverse = camera_from_volume(pose).to(device=self.device)
         with _lib.on_device(self.device):
-            _lib.check(_lib.load().pvamd_tsdf_integrate(ctypes.byref(self._grid.voxels._grid_desc()), _lib.ptr(depth), K, H, W,
-                                                        _lib.ptr(inverse), fx, fy, cx, cy, self.truncation, max_depth, weight,
-                                                        self.max_weight, _lib.ptr(self._state), _lib.stream_ptr()),
-                       "pvamd_tsdf_integrate")
+            _lib.call("pvamd_tsdf_integrate", self._grid.voxels._grid_desc(), depth, K, H, W, inverse, fx, fy, cx, cy,
+                      self.truncation, max_depth, weight, self.max_weight, self._state)
 
     def to_sdf(self, name, unknown="free", min_weight=0.0, interpolation="nearest", far_field=False, max_distance=math.inf):
         """A CachedSDF over the volume's lattice whose records are TSDFField(self, unknown, min_weight, far_field, max_distance)'s,
@@ -229,8 +226,7 @@ class TSDFVolume:
         nx, ny, nz = self.shape
         records = torch.empty((nx * ny * nz, 4), dtype=torch.float32, device=self.device)
         with _lib.on_device(self.device):
-            _lib.check(_lib.load().pvamd_tsdf_records(_lib.ptr(self._state), nx, ny, nz, self.resolution, self.truncation, min_weight,
-                                                      1.0, _lib.ptr(records), _lib.stream_ptr()), "pvamd_tsdf_records")
+            _lib.call("pvamd_tsdf_records", self._state, nx, ny, nz, self.resolution, self.truncation, min_weight, 1.0, records)
             valid = (self.weight > min_weight).to(torch.uint8).contiguous().reshape(-1)
             return surface.surface_of_records(self._grid.voxels._grid_desc(), records, valid, level, normals)
 
@@ -269,9 +265,8 @@ class TSDFField(OccupancySDF):
         records = torch.empty((nx * ny * nz, 4), dtype=torch.float32, device=volume.device)
         self._sites = self._squared = None
         with _lib.on_device(volume.device):
-            _lib.check(_lib.load().pvamd_tsdf_records(_lib.ptr(volume._state), nx, ny, nz, volume.resolution, volume.truncation,
-                                                      min_weight, 1.0 if unknown == "free" else -1.0, _lib.ptr(records),
-                                                      _lib.stream_ptr()), "pvamd_tsdf_records")
+            _lib.call("pvamd_tsdf_records", volume._state, nx, ny, nz, volume.resolution, volume.truncation, min_weight,
+                      1.0 if unknown == "free" else -1.0, records)
         if far_field:
             records, _, _ = _redistance_records(records, volume.shape, volume.resolution, volume.truncation, max_distance)
         self._set_records(volume._grid.voxels, volume._grid.resolution, records, records[:, 0].reshape(volume.shape) <= 0,

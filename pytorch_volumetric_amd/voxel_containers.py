@@ -8,7 +8,6 @@ tensors -- is plain torch over the same value-range indexing rule (index = round
 iff min <= p <= max); that generic path is container bookkeeping, not an SDF query, and nothing on the query path uses it.
 """
 import abc
-import ctypes
 
 import numpy as np
 import torch
@@ -50,28 +49,24 @@ class ValueRangeView:
             desc = _lib.GridDesc()
             RangeView(self._ranges, self.shape, rule=self._rule).fill(desc)  # same dtype inference as the torch tensors above
             desc.oob_mode = _lib.OOB_BOUNDING_BOX
-            _lib.check(_lib.load().pvamd_grid_finalize(ctypes.byref(desc)), "pvamd_grid_finalize")
+            _lib.call("pvamd_grid_finalize", desc)
             self._desc = desc
         return self._desc
 
     def _device_get(self, pts):
-        lib = _lib.load()
         flat = pts.reshape(-1, 3).contiguous()
         P = flat.shape[0]
         as_bytes = self.dtype == torch.bool
         store = self.raw_data.view(torch.uint8) if as_bytes else self.raw_data
         out = torch.empty((P,), dtype=store.dtype, device=flat.device)
         invalid = self.invalid_value
-        fn = lib.pvamd_voxel_gather_u8 if as_bytes else lib.pvamd_voxel_gather_f32
         with _lib.on_device(flat.device):
-            _lib.check(fn(ctypes.byref(self._grid_desc()), _lib.ptr(store), _lib.ptr(flat), P,
-                          int(bool(invalid)) if as_bytes else float(invalid), _lib.ptr(out), _lib.stream_ptr()),
-                       "pvamd_voxel_gather")
+            _lib.call("pvamd_voxel_gather_u8" if as_bytes else "pvamd_voxel_gather_f32", self._grid_desc(), store, flat, P,
+                      int(bool(invalid)) if as_bytes else float(invalid), out)
         out = out.view(torch.bool) if as_bytes else out
         return out.reshape(pts.shape[:-1])
 
     def _device_set(self, pts, value):
-        lib = _lib.load()
         flat = pts.reshape(-1, 3).contiguous()
         P = flat.shape[0]
         if P == 0:
@@ -86,11 +81,9 @@ class ValueRangeView:
             owner = torch.empty((self.raw_data.numel(),), dtype=torch.int32, device=flat.device)
         else:
             scalar = value.item() if torch.is_tensor(value) else value
-        fn = lib.pvamd_voxel_scatter_u8 if as_bytes else lib.pvamd_voxel_scatter_f32
         with _lib.on_device(flat.device):
-            _lib.check(fn(ctypes.byref(self._grid_desc()), _lib.ptr(store), _lib.ptr(flat), _lib.ptr(values),
-                          int(bool(scalar)) if as_bytes else float(scalar), P, _lib.ptr(owner), _lib.stream_ptr()),
-                       "pvamd_voxel_scatter")
+            _lib.call("pvamd_voxel_scatter_u8" if as_bytes else "pvamd_voxel_scatter_f32", self._grid_desc(), store, flat, values,
+                      int(bool(scalar)) if as_bytes else float(scalar), P, owner)
 
     def _rounded(self, key):
         q = (key - self._min) / self._resolution
@@ -257,8 +250,7 @@ def _point_bounds(points):
         flat = points.contiguous()
         box = torch.empty((2, 3), dtype=torch.float32, device=points.device)
         with _lib.on_device(points.device):
-            _lib.check(_lib.load().pvamd_points_aabb(_lib.ptr(flat), flat.shape[0], _lib.ptr(box), _lib.stream_ptr()),
-                       "pvamd_points_aabb")
+            _lib.call("pvamd_points_aabb", flat, flat.shape[0], box)
         box = box.cpu().numpy()
         if np.isfinite(box).all():  # a cloud with non-finite coordinates takes the plain reductions below
             return box[0], box[1]

@@ -26,7 +26,6 @@ def warm_up(device=None, freeze_gc=True):
     import pytorch_volumetric_amd as pv
     from pytorch_volumetric_amd import _lib, mesh_io
     from pytorch_volumetric_amd import transforms as tf
-    lib = _lib.load()
     dev = _lib.require_gpu() if device is None else torch.device(device)
     with _lib.on_device(dev):
         obj = pv.MeshObjectFactory(mesh=mesh_io.uv_sphere_mesh(0.1, 12, 6))
@@ -49,9 +48,7 @@ def warm_up(device=None, freeze_gc=True):
         val = torch.empty((3, many.shape[0]), dtype=torch.float32, device=dev)
         grad = torch.empty((3, many.shape[0], 3), dtype=torch.float32, device=dev)
         for flags in (4, 4 | 1):                              # the wave-tile kernel's two leaf loops
-            _lib.check(lib.pvamd_composed_query(_lib.ptr(grids), 2, _lib.ptr(comp._tf_device(dev)), 3, _lib.ptr(many),
-                                                many.shape[0], _lib.ptr(val), _lib.ptr(grad), None, flags, _lib.stream_ptr()),
-                       "pvamd_composed_query")
+            _lib.call("pvamd_composed_query", grids, 2, comp._tf_device(dev), 3, many, many.shape[0], val, grad, None, flags)
         comp.bucket_points = True
         comp(many)                                            # packed records + un-permute, spatial order
         comp(few.double())                                    # float64 entry
@@ -74,10 +71,8 @@ def warm_up(device=None, freeze_gc=True):
         scratch = torch.empty((1, 12, 4), dtype=torch.float32, device=dev)
         lw = torch.empty((4, 4, 4), dtype=torch.float32, device=dev)
         stack = torch.empty((4, 4, 4), dtype=torch.float32, device=dev)
-        _lib.check(lib.pvamd_configure_chain(_lib.ptr(table), 1, _lib.ptr(q), 4, 1, _lib.ptr(off), 1, None, _lib.ptr(scratch),
-                                             _lib.ptr(lw), _lib.ptr(stack), _lib.stream_ptr()), "pvamd_configure_chain")
-        _lib.check(lib.pvamd_transform_stack(_lib.ptr(off), _lib.ptr(lw), 1, 4, _lib.ptr(stack), _lib.stream_ptr()),
-                   "pvamd_transform_stack")
+        _lib.call("pvamd_configure_chain", table, 1, q, 4, 1, off, 1, None, scratch, lw, stack)
+        _lib.call("pvamd_transform_stack", off, lw, 1, 4, stack)
         torch.cuda.synchronize(dev)
     if freeze_gc:
         gc.collect()
