@@ -1321,6 +1321,58 @@ int pvamd_surface_emit(const pvamd_grid_t* grid, const float* records, const uin
 int pvamd_mesh_ray_cast(const pvamd_mesh_t* mesh, const float* origins, const float* directions, int64_t R, const float* poses,
                         int32_t B, float t_min, float t_max, float* t_out, int32_t* face_out, float* normal_out, float* uv_out,
                         void* stream);
+
+/* ---- Mesh ray casting, culled (the same call with the bounding spheres of the prepared mesh as part of the definition) ----
+ * pvamd_mesh_ray_cast_culled has the signature of pvamd_mesh_ray_cast and a second, opt-in contract, stated as strictly as the
+ * first: a triangle is a candidate only if, in addition, the ray (sphere_ok) and the candidate's own point o' + t d'
+ * (point_ok) pass the float32 tests below against the two bounding spheres pvamd_mesh_prepare wrote for the triangle's record
+ * -- that of its tile (PVAMD_TRI_TILE records) and that of its group (PVAMD_TRI_GROUP records).  It exists because the plain contract cannot be culled (the end of "Mesh ray casting"), and costs
+ * rays x triangles.  An additive entry point: the ABI version is unchanged.
+ * The rules of "Mesh ray casting" hold: float32, every operation rounded on its own, fmaf exactly where it is written, the same
+ * dot and cross; sqrt is correctly rounded.  Steps 1, 3 and 4 apply unchanged.  Step 2 gains two conditions: with j =
+ * rec_of_face[f] the position of the triangle's record and T = ceil(F / PVAMD_TRI_TILE), the ray passes sphere_ok, and the t of
+ * step 2 passes point_ok, for the tile sphere tiles[4 (j / PVAMD_TRI_TILE) ...] AND for the group sphere
+ * tiles[4 T + 4 (j / PVAMD_TRI_GROUP) ...].  Both spheres are required: that the group's sphere lies inside the tile's is not
+ * provable in float32, so neither test stands for the other.
+ *   per ray, after the pose:   dd = dot(d', d');   len = sqrt(dd)
+ *   per sphere (c, r):         w = c - o';   q = cross(w, d');   qq = dot(q, q);   ww = dot(w, w);   wd = dot(w, d')
+ *                              rs = fmaf(4e-7f, sqrt(ww), r * 1.00001f)
+ *   sphere_ok  :=  qq <= (rs * rs) * dd                  the line meets the inflated sphere
+ *              and fmaf( rs, len, wd) >= t_min * dd      the sphere is not wholly before t_min
+ *              and fmaf(-rs, len, wd) <= t_max * dd      the sphere is not wholly beyond t_max
+ *   point_ok   :=  dot(v, v) <= rs * rs,  v_i = fmaf(t, d'_i, -w_i)     the point o' + t d' lies in the inflated sphere
+ * sphere_ok does not know t, so whole tiles and groups can be skipped by it; point_ok is what ties the t of a candidate to its
+ * spheres.  Without it a ray in a triangle's rounded plane whose line does pass the sphere keeps its noise candidate, with
+ * any t: of 30,000 such rays at a rotated box one kept a hit 3.88 from the centre of a sphere of radius 2.6.
+ * A NaN fails its comparison and inf * 0 is NaN: a ray with a NaN or infinite coordinate, or a zero direction, has no candidate, as in the plain
+ * mode (a zero direction under a finite window passes the spheres and fails den != 0).
+ * The slack.  4e-7 |w| covers the float32 evaluation of q and wd for a line that meets the stored sphere in real arithmetic
+ * (|w x d'| <= r |d'|): w carries a relative error of 2^-24 per component (the sphere moved by at most 2^-24 |w|); each
+ * component of q adds the rounding of one product and of the fmaf, together at most 2^-24 (|w||d'| + |q|) as a vector; wd adds
+ * three roundings of terms bounded by |w||d'|.  To first order |q - w x d'| and |wd - w . d'| are both at most
+ * 4 * 2^-24 |w||d'| = 2.4e-7 |w||d'| < 4e-7 |w||d'| (tests/test_mesh_ray_cull.py measures it).  The factor 1.00001 covers what is
+ * relative to r: the roundings of qq, ww, dd, len, rs and the products of the comparison, under 16 * 2^-24 = 1e-6 together.  This
+ * holds while nothing under- or overflows.  v of point_ok carries the error of w and one rounding, 2^-24 (|w| + |v|), inside
+ * the same slack.  All of this bounds the evaluation of the tests, not t: the t of a candidate is the float32 t of step 2, whose
+ * own error is not covered -- a triangle met at a grazing angle at the very rim of its sphere may be inside by its corners and
+ * outside by its t.
+ * No candidate is dropped because of a hit already held: "the sphere begins beyond the best t so far" would depend on the order
+ * of the records, and is not part of this contract.
+ * Consequences.  Every culled result is a candidate of the plain loop, and its point lies in the inflated spheres of its
+ * triangle.  The two modes differ only where the plain winner is a candidate that fails sphere_ok or point_ok of its own
+ * triangle: in practice the rays of "Mesh ray casting" that lie, up to rounding, in a triangle's plane, whose t is noise.  Which tile and group a triangle
+ * sits in follows the order given to pvamd_mesh_prepare, so the results on such rays may depend on that order; the plain mode's
+ * never do.  Groups that begin at or past F have no sphere and are never read as a test.
+ * mesh: as for pvamd_mesh_ray_cast, and `tiles` is read as well.  All other arguments, the outputs, the error codes, R == 0 or
+ * B == 0 and the miss path for F == 0 or t_min > t_max are those of pvamd_mesh_ray_cast; in addition PVAMD_E_NULL for F > 0 without
+ * `tiles`.
+ * One lane per (pose, ray), rays in caller order.  A wave skips a tile, and in a tile a group, whose sphere none of its 64 rays
+ * passes, so it executes the exact tests of the union of its rays' surviving groups: rays that are neighbours in space should
+ * be neighbours in the call.  Stream-ordered, no allocation, no device -> host synchronisation, no atomics: capturable in a
+ * graph, and two calls give the same bits.  mesh->pair_counters is not used.                                                  */
+int pvamd_mesh_ray_cast_culled(const pvamd_mesh_t* mesh, const float* origins, const float* directions, int64_t R,
+                               const float* poses, int32_t B, float t_min, float t_max, float* t_out, int32_t* face_out,
+                               float* normal_out, float* uv_out, void* stream);
 #ifdef __cplusplus
 }
 #endif

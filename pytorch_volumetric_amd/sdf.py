@@ -430,7 +430,7 @@ class ObjectFactory(abc.ABC):
                         _restore(grad, lead, (3,), dtype, device),
                         _restore(normal, lead, (3,), dtype, device) if compute_normal else None)
 
-    def cast_rays(self, origins, directions, t_min=0., t_max=math.inf, world_to_object=None) -> MeshRayHits:
+    def cast_rays(self, origins, directions, t_min=0., t_max=math.inf, world_to_object=None, cull=False) -> MeshRayHits:
         """
         The first triangle every ray o + t d meets, exactly: what cast_rays on the reference's RaycastingScene (sdf.py:115-118)
         answers, for depth, visibility and occlusion checks.  ONE kernel launch (csrc/mesh_ray.hip; include/pvamd.h "Mesh ray
@@ -444,8 +444,15 @@ class ObjectFactory(abc.ABC):
         :param world_to_object: None (the rays are in the object frame), (4, 4) or (B, 4, 4) matrices that take the rays' frame to
             the object frame.  A batch prepends B to every output shape: the rays are shared by the poses.  Normals come back in
             the rays' frame, which is meaningful for rigid poses only
+        :param cull: False: every ray is tested against every triangle.  True: the culled contract (include/pvamd.h "Mesh ray
+            casting, culled"): a triangle counts only if the ray also passes a float32 test against the bounding spheres of the
+            triangle's tile and group of the prepared mesh and the hit's point lies in them, and whole tiles and groups are skipped -- the same bits on rays in
+            general position at a fraction of the cost, and next to none of the plain mode's rounding-noise hits for rays that
+            lie in a triangle's plane; on such rays the result may depend on how the mesh was sorted
         :return: MeshRayHits(t, face_ids, normals, uv); t = inf and face_ids = -1 where nothing is hit
         """
+        if not isinstance(cull, bool):
+            raise TypeError(f"cull must be a bool, got {type(cull).__name__}")
         t_min, t_max = _ray_window(t_min, t_max)
         o, d, lead, dtype = _ray_inputs(origins, directions)
         device = o.device
@@ -470,22 +477,26 @@ class ObjectFactory(abc.ABC):
         normal = torch.empty((B, R, 3), dtype=torch.float32, device=dev)
         uv = torch.empty((B, R, 2), dtype=torch.float32, device=dev)
         with _lib.on_device(dev):
-            _lib.call("pvamd_mesh_ray_cast", desc, o, d, R, poses, B, t_min, t_max, t, face, normal, uv)
+            _lib.call("pvamd_mesh_ray_cast_culled" if cull else "pvamd_mesh_ray_cast", desc, o, d, R, poses, B, t_min, t_max, t, face,
+                      normal, uv)
         shape = batch + lead
         return MeshRayHits(_restore(t, shape, (), dtype, device), face.reshape(shape).to(device=device, dtype=torch.int64),
                            _restore(normal, shape, (3,), dtype, device), _restore(uv, shape, (2,), dtype, device))
 
-    def render_depth(self, intrinsics, height, width, camera_pose, max_depth=math.inf):
+    def render_depth(self, intrinsics, height, width, camera_pose, max_depth=math.inf, cull=False):
         """
         Depth images of the mesh from pinhole cameras: the image TSDFVolume.integrate and OccupancyMap take.
 
         :param intrinsics: (fx, fy, cx, cy) or a 3 x 3 matrix; pixel (row, col) is centred on (u, v) = (col, row)
         :param camera_pose: (4, 4) or (K, 4, 4): the camera's pose in the object frame; it looks along +z, x right, y down
         :param max_depth: hits deeper than this count as no return
+        :param cull: cast_rays' `cull`: True renders under the culled contract
         :return: (K,) H x W float32 on the GPU: z-depth along the optical axis, t * (direction in the camera frame)_z of
             camera_rays' unit directions, and exactly 0 -- integrate's "no return" -- where nothing was hit
         """
         from pytorch_volumetric_amd import tsdf
+        if not isinstance(cull, bool):
+            raise TypeError(f"cull must be a bool, got {type(cull).__name__}")
         if isinstance(max_depth, bool) or not isinstance(max_depth, numbers.Real):
             raise TypeError(f"max_depth must be a Python real number, got {type(max_depth).__name__}")
         if not max_depth > 0:
@@ -496,7 +507,7 @@ class ObjectFactory(abc.ABC):
         tsdf._check_intrinsics(intrinsics)  # before a GPU is asked for
         dev = _lib.require_gpu()
         origins, directions, local = tsdf._pinhole(intrinsics, height, width, pose.detach().to(device=dev, dtype=torch.float32))
-        hits = self.cast_rays(origins, directions)
+        hits = self.cast_rays(origins, directions, cull=cull)
         depth = hits.t * local[..., 2]
         return torch.where((hits.face_ids >= 0) & (depth <= float(max_depth)), depth, torch.zeros_like(depth))
 
